@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- EKF visual updates/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4] [--dump-outputs DIR] [--full]
 
 One process per GPU.  N > 1: either a launcher started the ranks (torch.distributed.run -- RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment) or the plain command `python bench.py --gpus N` starts them itself by
@@ -13,9 +13,11 @@ the agents exchange their SimpleState payloads (state + full covariance) with
 one RCCL all-gather and fuse the shared tracks against them on the device
 (config 4); --config 5 runs the reference's request/response protocol instead,
 every 6 updates: binary-VLAD request, the responder's best keyframe back.
-value = (N * K updates) / max-over-ranks wall time.
+value = (N * K updates) / max-over-ranks wall time; ms_per_step = that wall time / K.
+--dump-outputs DIR writes what the last timed step computed (posterior P, correction, inlier masks, gamma) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      fp64 roofline of the dominant stage (CAQR kernels), timed with
                 HIP events on the engine's stream: achieved TFLOP/s from the rows
                 actually stacked, against the spec peak AND the ceiling measured
@@ -406,6 +408,140 @@ def other_configs(engine, synth, with_cpu=True):
     return out
 
 
+def full_legs(args, engine, synth, eng, sc, sigma, dev, world, dt):
+    """--full: what the benchmark measures and checks beyond the headline -- fp64 roofline of the dominant stage (per-stage
+    HIP events, the fp64 ceiling probe, the PMC file of this round), whole frames through the C++ mirror, BASELINE configs 2
+    and 3, the nominal-rows and small-frames legs, the single-core CPU baseline and the parity check against the C oracle
+    (rank 0, after the timed steps).  Returns the fields they fill: those of the line's `config` block, those of the line."""
+    N, K, M = eng.N, eng.K, eng.M
+    # per-stage HIP-event timing of the same staged update (untimed region)
+    tm = eng.bench_staged(sigma, 2, min(20, max(5, args.steps)))
+    rows = tm["rows_stacked"]                          # gated-out tracks leave zero rows: they do no algorithmic work
+    f_feat, f_qr, f_upd = alg_flops(N, K, M, rows=rows)
+    f_alg = f_feat + f_qr + f_upd
+    st = tm["stages"]
+    qr_keys = [k for k in st if k.startswith("xk_caqr")]
+    qr_ms = sum(st[k]["ms"] for k in qr_keys)
+    dom = max(st.items(), key=lambda kv: kv[1]["ms"])
+    pmc, pmc_state = pmc_of_this_round(args.config)
+    try:                                # (the probe kernels live in the lab build of the library, include/xk_lab.h)
+        pe = engine.LabEngine(2, 0, 1, device=dev)
+        ceil_fma, ceil_mfma = pe.probe_fp64_peak(False), pe.probe_fp64_peak(True)
+        pe.close()
+    except Exception:
+        ceil_fma = ceil_mfma = None
+    # the Kalman update rides INSIDE the compression launch where the geometry allows it (xk_pipe_kalman): the dominant launch then
+    # does the QR's and the update's algorithmic flops, and there is no Kalman stage behind it
+    kal_fused = st.get("xk_kalman_update", {}).get("launches", 1) == 0
+    f_dom = f_qr + (f_upd if kal_fused else 0.0)
+    ach = f_dom / (qr_ms * 1e-3) / 1e12
+    per_kernel = None
+    if pmc:
+        per_kernel = {k: {a: v for a, v in e.items() if a in ("avg_us", "l2_fabric_GBps", "mfma_util_pct", "wait_any_pct_of_wave_cycles", "l2_hit_pct")}
+                      for k, e in pmc["per_kernel"].items()}
+    roof = {"bound": "fp64-valu/latency",
+            "bound_note": "compute-side roofline (the compulsory HBM traffic of an update is < 1 MB); the QR kernels are Householder "
+                          "steps on the vector pipe -- fp64 vector and matrix peaks are the same 78.6 TFLOP/s on MI355X -- and what "
+                          "binds them is the dependent chain of reflector steps and the hand-offs between merge levels (launch boundaries in "
+                          "the multi-launch schedule), not flops or bytes",
+            "achieved": ach, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP64_PEAK_TFLOPS,
+            "measured_ceiling": {"v_fma_f64": ceil_fma, "v_mfma_f64_16x16x4": ceil_mfma,
+                                 "frac_of_fma_ceiling": (ach / ceil_fma) if ceil_fma else None},
+            "traffic": pmc["qr_bytes_per_update"] if pmc else None,
+            "traffic_note": "bytes between the L2s and the fabric per update, QR kernels, PMC FETCH_SIZE (x2, gfx950) + WRITE_SIZE from "
+                            f"profiles/{ROUND_TAG}_pmc_traffic.json; Infinity-Cache hits are included (no counter separates them)",
+            "pmc_file": pmc_state, "per_kernel": per_kernel,
+            "kernel": ("xk_caqr_pipe (Householder QR compression of the stacked [H|res]: ONE launch, the row stack resident in "
+                       "registers, the three levels of the CAQR tree pipelined on workgroups of their own"
+                       + ("; the Kalman update -- gain, P = (I - K H) P, correction -- applied block by block inside the same launch as "
+                          "the panels' rows of R become final, on the one workgroup the tree does not need" if kal_fused else "")
+                       + "; stage keys " + "+".join(qr_keys) + ")") if tm.get("n_levels") == 1 else
+                      "+".join(qr_keys) + " (Householder QR compression of the stacked [H|res], multi-launch CAQR)",
+            "alg_flops_per_update": f_dom, "alg_flops_qr": f_qr, "alg_flops_kalman_in_the_launch": (f_upd if kal_fused else 0.0),
+            "kalman_update_inside_the_launch": kal_fused, "rows_stacked": rows, "stage_ms": qr_ms,
+            "launches_per_update": sum(st[k]["launches"] for k in qr_keys),
+            "dominant_kernel_by_time": dom[0], "dominant_kernel_ms": dom[1]["ms"],
+            "dominant_kernel_launches": dom[1]["launches"],
+            "whole_update": {"alg_flops": f_alg, "ms": tm["total_ms"],
+                             "achieved": f_alg / (tm["total_ms"] * 1e-3) / 1e12,
+                             "frac": f_alg / (tm["total_ms"] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS},
+            "stages_ms": {k: v["ms"] for k, v in st.items() if v["launches"]},
+            "dtype_peak_note": "fp64 dense peak, vector = matrix = 78.6 TFLOP/s (AMD public MI355X spec)"}
+    # what the device path computes on these inputs (untimed; checked against the CPU baseline's result below)
+    gpu_res = None
+    if world == 1 and not args.no_cpu:
+        eng.stage(sc)
+        gpu_res = eng.visual_update_staged(sigma)
+        gpu_res["P"] = eng.download_P()
+    fl = None
+    if world == 1 and not args.no_frame_loop and args.config in (1, 3, 4):
+        eng.close()                       # the mirror creates its own handle
+        fl = frame_loop(sc)
+        if fl and "ms_per_frame" in fl:
+            fl["ratio_to_replay"] = fl["ms_per_frame"] / (1e3 * dt / args.steps)
+    others = None
+    if world == 1 and args.config == 4 and not args.no_other_configs:
+        try:
+            eng.close()
+        except Exception:
+            pass
+        others = other_configs(engine, synth, with_cpu=not args.no_cpu)
+    nominal = None
+    if world == 1 and args.config in (4, 5) and not args.no_other_configs:
+        try:
+            nominal = nominal_rows(engine, synth, args.config, dev, max(100, min(args.steps, 1000)), with_cpu=not args.no_cpu,
+                                   with_frame_loop=not args.no_frame_loop)
+            # (VERDICT round 5, next #7: the nominal-rows scenario is the one to read against BASELINE.md's F_alg = 2.008 GFLOP)
+            roof["frac_at_nominal_rows"] = nominal.get("roofline_frac_dominant_launch")
+            roof["achieved_at_nominal_rows"] = (nominal["roofline_frac_dominant_launch"] * FP64_PEAK_TFLOPS
+                                                if nominal.get("roofline_frac_dominant_launch") is not None else None)
+        except Exception as ex:      # an extra must not take the headline line down
+            nominal = {"error": repr(ex)[:300]}
+    small = None
+    if world == 1 and args.config in (4, 5) and not args.no_other_configs:
+        try:
+            small = small_frames(engine, synth, dev, with_frame_loop=not args.no_frame_loop)
+        except Exception as ex:
+            small = {"error": repr(ex)[:200]}
+    cpu = None
+    parity = None
+    if world == 1 and not args.no_cpu:
+        cpu = cpu_baseline(sc)
+        ref = cpu.pop("_ref", None)
+        if ref is not None and gpu_res is not None:
+            def _rel(a, b):
+                nb = float(np.linalg.norm(b))
+                return float(np.linalg.norm(np.asarray(a) - np.asarray(b)) / nb) if nb > 0 else float(np.linalg.norm(a))
+            parity = {"rel_dP_fro": _rel(gpu_res["P"], ref["P"]), "rel_dcorrection": _rel(gpu_res["correction"], ref["correction"]),
+                      "inlier_masks_identical": bool(np.array_equal(gpu_res["inlier"], ref["inlier"])),
+                      "inliers": int(np.sum(ref["inlier"])), "bar_rel_dP": 1e-6,
+                      "checker": "oracle/xk_oracle.c on the same inputs (the cpu_baseline leg's result; parity unpinned, DESIGN 5)"}
+    value = world * args.steps / dt
+    return ({"tracks_passing_the_gate_rank0": (int(np.sum(gpu_res["inlier"])) if gpu_res is not None else None), "rows_stacked_rank0": rows},
+            {"value_at_nominal_rows": (nominal.get("value") if nominal else None), "nominal_rows": nominal,
+             "roofline": roof, "frame_loop": fl, "other_configs": others, "small_frames": small, "parity": parity, "cpu_baseline": cpu,
+             "speedup_vs_cpu_1core": (value / world / cpu["value"]) if cpu else None})
+
+
+def last_step_outputs(eng, sigma):
+    """What the timed path computed in its last step: the posterior covariance, the correction and the gates' results.  Every timed
+    step recomputes the same update from the staged prior (xk_run_steps leaves the prior resident; a CI round restores it), so one
+    more such update, untimed, hands them out; the staged prior is restored on the device afterwards."""
+    got = eng.visual_update_staged(sigma)
+    got["P"] = eng.download_P()
+    eng.snapshot_P(restore=True)
+    return got
+
+
+def dump_outputs(d, got):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (inlier masks as 0 / 1); arrays a config does not have are left out."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in got.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size:
+            np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-run this command line under torch.distributed.run with N ranks on
     this node (rendezvous on 127.0.0.1, a free port), pass rank 0's JSON line through and return the launcher's exit code."""
@@ -431,10 +567,14 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)     # ~0.65 s of timed work at the headline size
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=4)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-frame-loop", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, the legs it does not need (full_legs): roofline, frame loop, "
+                    "other configs, nominal rows, small frames, CPU baseline, parity against the C oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and the parity checks")
+    ap.add_argument("--no-frame-loop", action="store_true", help="--full without the frame loops through the C++ mirror")
     ap.add_argument("--no-clock-ramp", action="store_true", help="skip the untimed 0.2 s clock ramp in front of the warm-up steps (profiling runs: tools/profile_round.sh counts launches)")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without configs 2 / 3, nominal rows and small frames")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 / the dry-run rank: write what the timed path computed in "
+                    "its last step as DIR/<name>.npy (float64)")
     # First-contact insurance for the multi-GPU run (no multi-GPU node is available to the builder): ONE process walks rank
     # --dry-run-rank of a fleet of --dry-run-ranks agents -- rank-indexed scenario, payload sizes, ring pattern, device-side
     # pack into the RCCL send buffer, the collective itself on a ONE-RANK nccl communicator (its own slot really travels
@@ -444,6 +584,8 @@ def main():
     ap.add_argument("--dry-run-rank", type=int, default=0)
     ap.add_argument("--dump-posterior", default=None, help="rank 0 / the dry-run rank: save the covariance the last CI round fused (no round: the resident one) as .npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     dry = args.dry_run_ranks >= 2
@@ -685,6 +827,8 @@ def main():
 
     if args.dump_posterior and (dry or rank == 0):
         np.save(args.dump_posterior, ci_stats["P"] if "P" in ci_stats else eng.download_P())
+    if args.dump_outputs and (dry or rank == 0):
+        dump_outputs(args.dump_outputs, last_step_outputs(eng, sigma))
     if dry:
         rep = {"dry_run": True, "fleet": world, "rank": rank, "config": args.config, "backend": backend,
                "real_ranks_in_the_communicator": real_world, "steps": args.steps, "ms_per_step": 1e3 * dt / args.steps,
@@ -697,108 +841,7 @@ def main():
         dist.destroy_process_group()
         return
     if rank == 0:
-        # per-stage HIP-event timing of the same staged update (untimed region)
-        tm = eng.bench_staged(sigma, 2, min(20, max(5, args.steps)))
-        rows = tm["rows_stacked"]                          # gated-out tracks leave zero rows: they do no algorithmic work
-        f_feat, f_qr, f_upd = alg_flops(N, K, M, rows=rows)
-        f_alg = f_feat + f_qr + f_upd
-        st = tm["stages"]
-        qr_keys = [k for k in st if k.startswith("xk_caqr")]
-        qr_ms = sum(st[k]["ms"] for k in qr_keys)
-        dom = max(st.items(), key=lambda kv: kv[1]["ms"])
-        pmc, pmc_state = pmc_of_this_round(args.config)
-        try:                                # (the probe kernels live in the lab build of the library, include/xk_lab.h)
-            pe = engine.LabEngine(2, 0, 1, device=dev)
-            ceil_fma, ceil_mfma = pe.probe_fp64_peak(False), pe.probe_fp64_peak(True)
-            pe.close()
-        except Exception:
-            ceil_fma = ceil_mfma = None
-        # the Kalman update rides INSIDE the compression launch where the geometry allows it (xk_pipe_kalman): the dominant launch then
-        # does the QR's and the update's algorithmic flops, and there is no Kalman stage behind it
-        kal_fused = st.get("xk_kalman_update", {}).get("launches", 1) == 0
-        f_dom = f_qr + (f_upd if kal_fused else 0.0)
-        ach = f_dom / (qr_ms * 1e-3) / 1e12
-        per_kernel = None
-        if pmc:
-            per_kernel = {k: {a: v for a, v in e.items() if a in ("avg_us", "l2_fabric_GBps", "mfma_util_pct", "wait_any_pct_of_wave_cycles", "l2_hit_pct")}
-                          for k, e in pmc["per_kernel"].items()}
-        roof = {"bound": "fp64-valu/latency",
-                "bound_note": "compute-side roofline (the compulsory HBM traffic of an update is < 1 MB); the QR kernels are Householder "
-                              "steps on the vector pipe -- fp64 vector and matrix peaks are the same 78.6 TFLOP/s on MI355X -- and what "
-                              "binds them is the dependent chain of reflector steps and the hand-offs between merge levels (launch boundaries in "
-                              "the multi-launch schedule), not flops or bytes",
-                "achieved": ach, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / FP64_PEAK_TFLOPS,
-                "measured_ceiling": {"v_fma_f64": ceil_fma, "v_mfma_f64_16x16x4": ceil_mfma,
-                                     "frac_of_fma_ceiling": (ach / ceil_fma) if ceil_fma else None},
-                "traffic": pmc["qr_bytes_per_update"] if pmc else None,
-                "traffic_note": "bytes between the L2s and the fabric per update, QR kernels, PMC FETCH_SIZE (x2, gfx950) + WRITE_SIZE from "
-                                f"profiles/{ROUND_TAG}_pmc_traffic.json; Infinity-Cache hits are included (no counter separates them)",
-                "pmc_file": pmc_state, "per_kernel": per_kernel,
-                "kernel": ("xk_caqr_pipe (Householder QR compression of the stacked [H|res]: ONE launch, the row stack resident in "
-                           "registers, the three levels of the CAQR tree pipelined on workgroups of their own"
-                           + ("; the Kalman update -- gain, P = (I - K H) P, correction -- applied block by block inside the same launch as "
-                              "the panels' rows of R become final, on the one workgroup the tree does not need" if kal_fused else "")
-                           + "; stage keys " + "+".join(qr_keys) + ")") if tm.get("n_levels") == 1 else
-                          "+".join(qr_keys) + " (Householder QR compression of the stacked [H|res], multi-launch CAQR)",
-                "alg_flops_per_update": f_dom, "alg_flops_qr": f_qr, "alg_flops_kalman_in_the_launch": (f_upd if kal_fused else 0.0),
-                "kalman_update_inside_the_launch": kal_fused, "rows_stacked": rows, "stage_ms": qr_ms,
-                "launches_per_update": sum(st[k]["launches"] for k in qr_keys),
-                "dominant_kernel_by_time": dom[0], "dominant_kernel_ms": dom[1]["ms"],
-                "dominant_kernel_launches": dom[1]["launches"],
-                "whole_update": {"alg_flops": f_alg, "ms": tm["total_ms"],
-                                 "achieved": f_alg / (tm["total_ms"] * 1e-3) / 1e12,
-                                 "frac": f_alg / (tm["total_ms"] * 1e-3) / 1e12 / FP64_PEAK_TFLOPS},
-                "stages_ms": {k: v["ms"] for k, v in st.items() if v["launches"]},
-                "dtype_peak_note": "fp64 dense peak, vector = matrix = 78.6 TFLOP/s (AMD public MI355X spec)"}
-        # what the device path computes on these inputs (untimed; checked against the CPU baseline's result below)
-        gpu_res = None
-        if world == 1 and not args.no_cpu:
-            eng.stage(sc)
-            gpu_res = eng.visual_update_staged(sigma)
-            gpu_res["P"] = eng.download_P()
-        fl = None
-        if world == 1 and not args.no_frame_loop and args.config in (1, 3, 4):
-            eng.close()                       # the mirror creates its own handle
-            fl = frame_loop(sc)
-            if fl and "ms_per_frame" in fl:
-                fl["ratio_to_replay"] = fl["ms_per_frame"] / (1e3 * dt / args.steps)
-        others = None
-        if world == 1 and args.config == 4 and not args.no_other_configs:
-            try:
-                eng.close()
-            except Exception:
-                pass
-            others = other_configs(engine, synth, with_cpu=not args.no_cpu)
-        nominal = None
-        if world == 1 and args.config in (4, 5) and not args.no_other_configs:
-            try:
-                nominal = nominal_rows(engine, synth, args.config, dev, max(100, min(args.steps, 1000)), with_cpu=not args.no_cpu,
-                                       with_frame_loop=not args.no_frame_loop)
-                # (the nominal-rows scenario is the one to read against BASELINE.md's F_alg = 2.008 GFLOP)
-                roof["frac_at_nominal_rows"] = nominal.get("roofline_frac_dominant_launch")
-                roof["achieved_at_nominal_rows"] = (nominal["roofline_frac_dominant_launch"] * FP64_PEAK_TFLOPS
-                                                    if nominal.get("roofline_frac_dominant_launch") is not None else None)
-            except Exception as ex:      # an extra must not take the headline line down
-                nominal = {"error": repr(ex)[:300]}
-        small = None
-        if world == 1 and args.config in (4, 5) and not args.no_other_configs:
-            try:
-                small = small_frames(engine, synth, dev, with_frame_loop=not args.no_frame_loop)
-            except Exception as ex:
-                small = {"error": repr(ex)[:200]}
-        cpu = None
-        parity = None
-        if world == 1 and not args.no_cpu:
-            cpu = cpu_baseline(sc)
-            ref = cpu.pop("_ref", None)
-            if ref is not None and gpu_res is not None:
-                def _rel(a, b):
-                    nb = float(np.linalg.norm(b))
-                    return float(np.linalg.norm(np.asarray(a) - np.asarray(b)) / nb) if nb > 0 else float(np.linalg.norm(a))
-                parity = {"rel_dP_fro": _rel(gpu_res["P"], ref["P"]), "rel_dcorrection": _rel(gpu_res["correction"], ref["correction"]),
-                          "inlier_masks_identical": bool(np.array_equal(gpu_res["inlier"], ref["inlier"])),
-                          "inliers": int(np.sum(ref["inlier"])), "bar_rel_dP": 1e-6,
-                          "checker": "oracle/xk_oracle.c on the same inputs (the cpu_baseline leg's result; parity unpinned, DESIGN 5)"}
+        cfg_full, line_full = full_legs(args, engine, synth, eng, sc, sigma, dev, world, dt) if args.full else ({}, {})
         value = world * args.steps / dt
         out = {"metric": "EKF updates/sec (window=30, 400 MSCKF feats)" if args.config in (4, 5)
                else f"EKF updates/sec (config {args.config})",
@@ -815,8 +858,8 @@ def main():
                                       + (f"request/response every {ci_every} updates: binary-VLAD request, best keyframe of the responder's database back (ring)" if args.config == 5
                                          else f"CI payload all-gather every {ci_every} updates"),
                           "n_poses_max": N, "k_msckf": K, "m_slam": M, "agents": world,
-                          "tracks_passing_the_gate_rank0": (int(np.sum(gpu_res["inlier"])) if gpu_res is not None else None),
-                          "rows_stacked_rank0": rows,
+                          "tracks_passing_the_gate_rank0": cfg_full.get("tracks_passing_the_gate_rank0"),
+                          "rows_stacked_rank0": cfg_full.get("rows_stacked_rank0"),
                           "ci_every": ci_every, "payload_bytes": 8 * pay_n, "ci_tracks_per_round": CI_TRACKS,
                           "ci_replay": "every CI round fuses the STAGED prior with the snapshots that arrive and the prior is restored on the device "
                                        "afterwards (xk_snapshot_P), like every update of the replay: in the reference applyCI's posterior becomes the "
@@ -826,9 +869,7 @@ def main():
                                        "runs the fed-back form with filter steps in between)",
                           "ci_rounds_rank0": ci_stats["rounds"], "ci_fused_rank0": ci_stats["fused"],
                           **({"keyframes_received_rank0": ci_stats.get("keyframes_received", 0)} if args.config == 5 else {})},
-               "value_at_nominal_rows": (nominal.get("value") if nominal else None), "nominal_rows": nominal,
-               "roofline": roof, "frame_loop": fl, "other_configs": others, "small_frames": small, "parity": parity, "cpu_baseline": cpu,
-               "speedup_vs_cpu_1core": (value / world / cpu["value"]) if cpu else None}
+               **line_full}
         print(json.dumps(out), flush=True)
     try:
         eng.close()

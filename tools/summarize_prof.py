@@ -55,7 +55,7 @@ if stats:
     for k, (t, c) in tot.items():
         avg_ns[k] = (t / max(c, 1), c)
     with open(os.path.join(PROF, f"{tag}{suf}_kernel_stats.md"), "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --stats -- python bench.py --config {cfg} --steps 20 --warmup 3 --no-cpu --no-frame-loop ({tag})\n\n")
+        f.write(f"# rocprofv3 --kernel-trace --stats -- python bench.py --config {cfg} --steps 20 --warmup 3 --full --no-cpu --no-frame-loop ({tag})\n\n")
         f.write("| kernel | calls | total ms | avg us | % |\n|---|---|---|---|---|\n")
         for r in rows[:16]:
             f.write(f"| `{r['Name'][:70]}` | {r['Calls']} | {float(r['TotalDurationNs'])/1e6:.3f} | "
