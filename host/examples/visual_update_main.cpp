@@ -30,7 +30,7 @@ static std::vector<double> slurp(const char *path) {
 }
 
 int main(int argc, char **argv) {
-  if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [iekf_iter [resident [core.bin]]]\n", argv[0]); return 2; }
+  if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin [iekf_iter [resident [core.bin [aux.bin]]]]\n", argv[0]); return 2; }
   const int iekf_iter = argc > 3 ? atoi(argv[3]) : 1;
   const bool resident = argc > 4 && atoi(argv[4]) != 0;
   const std::vector<double> in = slurp(argv[1]);
@@ -86,7 +86,26 @@ int main(int argc, char **argv) {
     anchors.resize(M_used);
   }
 
-  VioUpdater updater(0, N, M, K > 0 ? K : 1, sigma_img, 0.1, 0.4, iekf_iter);
+  // aux.bin (optional): an LRF reading on a facet of SLAM features and a sun-sensor reading (vio_updater.cpp:352-405):
+  // [has_range, range, img_x_n, img_y_n, facet0, facet1, facet2, sigma_range, has_sun, x_angle, y_angle]
+  double sigma_range = 0.05;
+  if (argc > 6) {
+    const std::vector<double> aux = slurp(argv[6]);
+    if (aux.size() != 11) { fprintf(stderr, "aux.bin: 11 doubles expected\n"); return 2; }
+    if (aux[0] != 0.0) {
+      meas.range.timestamp = 1.0;
+      meas.range.range = aux[1];
+      meas.range.img_pt_n = Feature(aux[2], aux[3]);
+      meas.range_facet = {(int)aux[4], (int)aux[5], (int)aux[6]};
+      sigma_range = aux[7];
+    }
+    if (aux[8] != 0.0) {
+      meas.sun_angle.timestamp = 1.0;
+      meas.sun_angle.x_angle = aux[9];
+      meas.sun_angle.y_angle = aux[10];
+    }
+  }
+  VioUpdater updater(0, N, M, K > 0 ? K : 1, sigma_img, 0.1, 0.4, iekf_iter, 0.05, 0.5, 0.4, sigma_range);
   updater.setWindow(n_poses, anchors);
   updater.setMeasurement(meas);
   Ekf ekf(updater);

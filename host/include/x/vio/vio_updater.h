@@ -12,6 +12,17 @@
 #include "x/vio/state_manager.h"
 
 namespace x {
+// LRF and sun-sensor measurements (include/x/vio/types.h:224-254); timestamp = -1 (kInvalid): none, or already used.
+struct RangeMeasurement {
+  double timestamp = -1.0;
+  double range = 0.0;
+  Feature img_pt, img_pt_n;        // image / undistorted normalised coordinates of the LRF beam (vio.cpp:289-294)
+};
+struct SunAngleMeasurement {
+  double timestamp = -1.0;
+  double x_angle = 0.0, y_angle = 0.0;   // degrees
+};
+
 struct VioMeasurement {
   double timestamp = 0.0;
   TrackList msckf_tracks;          // full-length tracks ending at the current frame (track_manager.cpp:376-386)
@@ -22,13 +33,17 @@ struct VioMeasurement {
   std::vector<unsigned int> lost_slam_track_idxs;   // persistent features to remove in manage() (vio_updater.cpp:170,202)
   MsckfMatches msckf_matches;      // this agent's MSCKF tracks also seen by other agents (place_recognition.cpp:137)
   SlamMatches slam_matches;        // persistent features matched to other agents' (processed in collaborativeUpdate)
+  RangeMeasurement range;          // vio_updater.cpp:358-382
+  SunAngleMeasurement sun_angle;   // :386-405
+  std::vector<int> range_facet;    // the three SLAM feature ids around the LRF point: TrackManager::featureTriangleAtPoint (:368-369)
+                                   // runs in the caller's front end; empty = no facet found
 };
 
 class VioUpdater : public Updater {
  public:
   VioUpdater(int device, int n_poses_max, int n_feat_max, int k_max, double sigma_img, double sigma_landmark = 0.1,
              double ci_slam_w = 0.4, int iekf_iter = 1, double ci_msckf_w = 0.05, double rho_0 = 0.5,
-             double sigma_rho_0 = 0.4);
+             double sigma_rho_0 = 0.4, double sigma_range = 0.05);
   ~VioUpdater() override;
   VioUpdater(const VioUpdater &) = delete;
 
@@ -72,7 +87,8 @@ class VioUpdater : public Updater {
   int n_poses_max_, n_feat_max_, k_max_;
   StateManager state_manager_;
   bool manage_window_ = false;
-  double sigma_img_, sigma_landmark_, ci_slam_w_, ci_msckf_w_, rho_0_, sigma_rho_0_;
+  double sigma_img_, sigma_landmark_, ci_slam_w_, ci_msckf_w_, rho_0_, sigma_rho_0_, sigma_range_;
+  int stageAuxRows(const State &state, bool with_slam);   // range / sun rows under the reference's conditions; returns how many
   std::vector<int> inlier_msckf_, inlier_slam_;
   int n_ci_entries_ = 0;
   bool flags_pending_ = false;

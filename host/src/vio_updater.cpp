@@ -44,10 +44,10 @@ static void toCsr(const TrackList &tr, std::vector<int> &off, std::vector<double
 }
 
 VioUpdater::VioUpdater(int device, int n_poses_max, int n_feat_max, int k_max, double sigma_img, double sigma_landmark,
-                       double ci_slam_w, int iekf_iter, double ci_msckf_w, double rho_0, double sigma_rho_0)
+                       double ci_slam_w, int iekf_iter, double ci_msckf_w, double rho_0, double sigma_rho_0, double sigma_range)
     : n_poses_max_(n_poses_max), n_feat_max_(n_feat_max), k_max_(k_max), state_manager_(n_poses_max, n_feat_max, nullptr),
       sigma_img_(sigma_img), sigma_landmark_(sigma_landmark), ci_slam_w_(ci_slam_w), ci_msckf_w_(ci_msckf_w),
-      rho_0_(rho_0), sigma_rho_0_(sigma_rho_0) {
+      rho_0_(rho_0), sigma_rho_0_(sigma_rho_0), sigma_range_(sigma_range) {
   iekf_iter_ = iekf_iter;
   check(nullptr, xk_create(device, n_poses_max, n_feat_max, k_max, &xk_), "xk_create");  // no CPU fallback
   state_manager_.setEngine(xk_);
@@ -88,6 +88,28 @@ void VioUpdater::windowLists(const State &state, std::vector<double> &q, std::ve
   p.assign(pa.data(), pa.data() + 3 * np);
 }
 
+// The range and sun rows of constructUpdate (vio_updater.cpp:352-405), staged for the next build under the reference's conditions and
+// marked used (timestamp = -1, :380, :402): in the IEKF loop only the first pass carries them.  Not part of the short-track update.
+int VioUpdater::stageAuxRows(const State &state, bool with_slam) {
+  if (!with_slam) return 0;
+  int rows = 0;
+  RangeMeasurement &rg = measurement_.range;
+  if (rg.timestamp > 0.1 && !measurement_.slam_tracks.empty() && measurement_.range_facet.size() == 3) {
+    check(xk_, xk_stage_range(xk_, rg.range, rg.img_pt_n.getX(), rg.img_pt_n.getY(), measurement_.range_facet.data(), sigma_range_),
+          "xk_stage_range");
+    rg.timestamp = -1.0;
+    rows += 1;
+  }
+  SunAngleMeasurement &sn = measurement_.sun_angle;
+  if (sn.timestamp > -1.0) {
+    const double q[4] = {state.q_.x(), state.q_.y(), state.q_.z(), state.q_.w()};   // state.getOrientation()
+    check(xk_, xk_stage_sun_angle(xk_, q, sn.x_angle, sn.y_angle, nullptr), "xk_stage_sun_angle");
+    sn.timestamp = -1.0;
+    rows += 2;
+  }
+  return rows;
+}
+
 void VioUpdater::buildAndCompress(const State &state, const TrackList &tr, bool with_slam, Matrix &h, Matrix &res, Matrix &r) {
   const int n = state.nErrorStates();
   std::vector<double> q, p;
@@ -114,6 +136,7 @@ void VioUpdater::buildAndCompress(const State &state, const TrackList &tr, bool 
     toCsr(mt, moff, mobs);
     check(xk_, xk_stage_msckf_slam(xk_, moff.data(), mobs.data(), (int)mt.size()), "xk_stage_msckf_slam");
   }
+  const int naux = stageAuxRows(state, with_slam);
   if (!resident_) check(xk_, xk_upload_P(xk_, state.getCovariance().data(), n, n), "xk_upload_P");   // Matrix P = state.getCovariance()
   inlier_msckf_.assign(tr.size(), 0);
   inlier_slam_.assign(M, 0);
@@ -143,8 +166,26 @@ void VioUpdater::buildAndCompress(const State &state, const TrackList &tr, bool 
     h = Matrix::Zero(n, n);
     res = Matrix::Zero(n, 1);
     check(xk_, xk_qr_compress(xk_, h.data(), n, res.data()), "xk_qr_compress");       // applyQRDecomposition
-    r = Matrix::Zero(n, n);
+    r = Matrix::Zero(n + naux, n + naux);
     for (int i = 0; i < n; ++i) r(i, i) = sigma_img_ * sigma_img_;                       // vio_updater.cpp:508-509
+    if (naux > 0) {
+      // the range / sun rows as built, under T_H, with the variances the reference gives them (xk.h: xk_aux_rows)
+      double ra[3], va[3];
+      int rows = 0;
+      std::vector<double> hbuf((size_t)3 * n);
+      check(xk_, xk_aux_rows(xk_, hbuf.data(), 3, ra, va, &rows), "xk_aux_rows");
+      Matrix h2 = Matrix::Zero(n + rows, n), res2 = Matrix::Zero(n + rows, 1);
+      for (int c = 0; c < n; ++c)
+        for (int i = 0; i < n; ++i) h2(i, c) = h(i, c);
+      for (int i = 0; i < n; ++i) res2(i, 0) = res(i, 0);
+      for (int k = 0; k < rows; ++k) {
+        for (int c = 0; c < n; ++c) h2(n + k, c) = hbuf[k + (size_t)3 * c];
+        res2(n + k, 0) = ra[k];
+        r(n + k, n + k) = va[k];
+      }
+      h = std::move(h2);
+      res = std::move(res2);
+    }
   }
   compressed_on_device_ = true;
 }

@@ -335,6 +335,33 @@ int xk_build_compress_update_pass_async(xk_handle *h, double sigma_img, const do
 /* The gate results of the last build (any pointer may be NULL); synchronises the stream if it is still busy. */
 int xk_fetch_flags(xk_handle *h, int *inlier_msckf, double *gamma_msckf, int *inlier_slam, double *gamma_slam);
 
+/* ---- range-facet and sun-angle rows (VioUpdater::constructUpdate, vio_updater.cpp:352-423) ----
+ * Staged like the visual inputs and consumed by the next build (xk_msckf_build, xk_build_compress*_async, xk_visual_update_staged): the
+ * reference uses a measurement once (timestamp = -1, :380, :402), so a build with nothing newly staged has no such rows; xk_run_steps /
+ * xk_bench_staged replay the staged update with them in every step, as do the retries of an update.  The rows never go through the QR:
+ * they are appended as built to whatever system the update applies ([T; H_aux]^T [T; H_aux] is the Gram matrix of the whole stack).
+ * Their variances follow the reference's stack: it compresses when its rows -- 2 L - 3 per MSCKF / MSCKF-SLAM track, 2 M, 1 range, 2 sun,
+ * gated out or not -- exceed n + 1, and then weighs EVERY row with sigma_img^2 (vio_updater.cpp:487-509: a compressed range row counts as
+ * if sigma_range were sigma_img, a reference quirk kept on purpose); uncompressed, each row keeps its own variance. */
+
+/* RangeUpdate::processRangedFacet (src/x/vio/range_update.cpp:61-270) as stacked at vio_updater.cpp:358-382: one row, the LRF range
+ * against the plane of the facet of SLAM features facet[3] (indices into the staged features: TrackManager::featureTriangleAtPoint, which
+ * stays with the caller, as does the camera model that gives the undistorted normalised image point (img_x_n, img_y_n) of the ray,
+ * vio.cpp:289-294), gated by chi2_1(0.9) against the prior: a rejected row stays as a zero row of variance 1.  Preconditions of the
+ * reference (range.timestamp > 0.1, a SLAM track, a facet found) are the caller's.  XK_EINVAL: no SLAM features staged, an id outside
+ * [0, M) or repeated, sigma_range <= 0. */
+int xk_stage_range(xk_handle *h, double range, double img_x_n, double img_y_n, const int facet[3], double sigma_range);
+/* SolarUpdate::processSunAngle (src/x/vio/solar_update.cpp:36-94) as stacked at vio_updater.cpp:386-405: two rows over the IMU attitude
+ * error (columns 6..8) from the IMU attitude q_xyzw (state.getOrientation()) and the sensor's x / y angles in degrees.
+ * calib: 8 doubles S_q_I (w, x, y, z), G_sun (x, y, z; normalised here), var_sun (deg^2); NULL = the reference's constants
+ * (solar_update.cpp:47-56, marked "TODO import from param file" there: a real sensor needs its own values). */
+int xk_stage_sun_angle(xk_handle *h, const double q_xyzw[4], double x_angle_deg, double y_angle_deg, const double *calib);
+/* Range gate of the last build (range_update.cpp:246-262): *range_inlier = 1 / 0, or -1 if it had no range row; *range_gamma. */
+int xk_fetch_aux_flags(xk_handle *h, int *range_inlier, double *range_gamma);
+/* The rows of the last build as built (h_lrf then h_sns, vio_updater.cpp:407-421): *rows (0..3), H (rows x n, ldh >= 3, column-major),
+ * res (rows), r_diag (rows: the variances the update gives them) -- for a host that runs xk_apply_update_dense on the stack itself. */
+int xk_aux_rows(xk_handle *h, double *H, int ldh, double *res, double *r_diag, int *rows);
+
 /* Updater::applyCI (updater.cpp:144-161) on the RESIDENT covariance: P <- sym((I - K H) ci_P), K = ci_P H^T S^-1,
  * replaces the handle's covariance and stays on the device; only the n-vector correction comes back.  A compressed
  * [T_H | z] waiting for xk_apply_update is left alone, so the reference's order -- constructUpdate, the applyCI loop,

@@ -22,8 +22,9 @@
 #include "xk_linalg.hip.h"
 #include "xk_caqr_pipe.hip.h"
 #include "xk_ci.hip.h"
+#include "xk_aux.hip.h"
 
-#define XK_VERSION_NUM 200
+#define XK_VERSION_NUM 201
 #define XK_STAGE_SLOTS 8
 #define XK_PDBG_WORDS 65536     // debug stamps of the single launch (lab build)
 
@@ -159,6 +160,16 @@ struct xk_handle {
   char *trk_slot;          // xk_stage_tracks_begin .. _end: the staging slot being filled
   int trk_slot_K, trk_slot_nobs;
   bool async_pending;      // xk_build_compress_async ran: xk_apply_update owns the retry if the single-launch CAQR gave up
+  // range-facet / sun-angle rows (xk_stage_range / xk_stage_sun_angle, xk_aux.hip.h).  Staged measurements wait in aux_in until the next
+  // build, which consumes them (the reference uses a measurement once: timestamp = -1, vio_updater.cpp:380,402) and fixes the plan of that
+  // update in aux_mask / naux: which rows, how many, and which variances they carry.  A replay of the same update (a retry after a single
+  // launch gave up, xk_run_steps, xk_bench_staged) rebuilds them from the same staged measurement; a build with nothing staged has none.
+  XkAuxIn aux_in;
+  int aux_staged;          // 1 range, 2 sun: staged since the last build
+  int aux_mask;            // ... the rows of the current update
+  int naux;                // 0..3 rows appended to the system the update applies
+  double *d_aux;           // [naux x (n + 1) rows | rdiag 3 | flags 2]
+  double *d_Taug;          // the applied system with the rows appended: CM x (n + 1) row-major, then CM variances
   // host pinned staging
   double *h_pin;
   size_t h_pin_doubles;
@@ -248,7 +259,7 @@ static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, x
   h->DB = dmax <= 64 ? 64 : 128;   // rows per tile slot (one track per tile; SLAM rows are packed DB per tile)
   const int slam_tiles = (2 * n_feat_max + h->DB - 1) / h->DB;
   h->ntiles_max = k_max + n_feat_max + slam_tiles;   // MSCKF tracks, MSCKF-SLAM tracks, packed SLAM rows
-  h->CM = round_up(h->n + 1, 16);
+  h->CM = round_up(h->n + 1 + 3, 16);   // (+ 3: the range-facet and sun-angle rows appended to an uncompressed stack of n rows)
   h->LDA = h->CM + round_up(h->n + 1, 16);
   HIPCHK(h, hipSetDevice(device));
   HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -378,6 +389,8 @@ static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, x
   HIPCHK(h, dalloc(&h->d_tmpP, nn));
   HIPCHK(h, dalloc(&h->d_rdiag, (size_t)h->CM));
   HIPCHK(h, dalloc(&h->d_tmpz, (size_t)h->CM));
+  HIPCHK(h, dalloc(&h->d_aux, 3 * ((size_t)h->n + 1) + 8));
+  HIPCHK(h, dalloc(&h->d_Taug, (size_t)h->CM * ((size_t)h->n + 2)));
   // The status words and the correction of the resident path (xk_apply_update) are written by the kernels straight into
   // pinned host memory through its device-visible address: after the stream synchronisation that ends an update the host
   // reads them in place -- no device-to-host copy (a ~4 us blit kernel plus its launch gap at the end of every frame).
@@ -442,6 +455,8 @@ extern "C" int xk_destroy(xk_handle *h) {
   if (h->d_csr_v) hipFree(h->d_csr_v);
   if (h->d_Hc) hipFree(h->d_Hc);
   if (h->d_R2) hipFree(h->d_R2);
+  if (h->d_aux) hipFree(h->d_aux);
+  if (h->d_Taug) hipFree(h->d_Taug);
   delete h->fused_ct;
   if (h->d_Psnap) hipFree(h->d_Psnap);
   if (h->d_Psnap2) hipFree(h->d_Psnap2);
@@ -654,6 +669,50 @@ extern "C" int xk_stage_msckf_slam(xk_handle *h, const int *trk_off, const doubl
   return XK_OK;
 }
 
+// LRF facet row (RangeUpdate::processRangedFacet, range_update.cpp:61-270, stacked at vio_updater.cpp:358-382).  The facet search
+// (TrackManager::featureTriangleAtPoint) and the camera model stay with the caller, which passes the three SLAM feature ids and the
+// undistorted, normalised image point of the LRF ray.
+extern "C" int xk_stage_range(xk_handle *h, double range, double img_x_n, double img_y_n, const int facet[3], double sigma_range) {
+  if (!h || !facet) return XK_EINVAL;
+  if (h->M <= 0) return fail(h, XK_EINVAL, "range row without SLAM features");
+  if (!(sigma_range > 0.0)) return fail(h, XK_EINVAL, "sigma_range <= 0");
+  for (int j = 0; j < 3; ++j) {
+    if (facet[j] < 0 || facet[j] >= h->M) return fail(h, XK_EINVAL, "facet feature id outside [0, M)");
+    for (int i = 0; i < j; ++i)
+      if (facet[i] == facet[j]) return fail(h, XK_EINVAL, "facet feature id repeated");
+  }
+  if (!std::isfinite(range) || !std::isfinite(img_x_n) || !std::isfinite(img_y_n)) return fail(h, XK_EINVAL, "non-finite range measurement");
+  XkAuxIn &a = h->aux_in;
+  a.range = range; a.img_x = img_x_n; a.img_y = img_y_n; a.var_range = sigma_range * sigma_range;
+  for (int j = 0; j < 3; ++j) a.facet[j] = facet[j];
+  h->aux_staged |= 1;
+  return XK_OK;
+}
+
+// Sun-sensor rows (SolarUpdate::processSunAngle, solar_update.cpp:36-94, stacked at vio_updater.cpp:386-405).  calib (optional):
+// S_q_I (w, x, y, z), G_sun (3), var_sun (deg^2) -- 8 doubles; NULL = the reference's constants (solar_update.cpp:47-56, "TODO import
+// from param file": a real sensor needs its own).
+extern "C" int xk_stage_sun_angle(xk_handle *h, const double q_xyzw[4], double x_angle_deg, double y_angle_deg, const double *calib) {
+  if (!h || !q_xyzw) return XK_EINVAL;
+  static const double ref_calib[8] = {0.360346005598587, -0.063338979194957, 0.007502445522018, 0.930635612981541,
+                                      -0.29385515271891938, -0.55080445540063927, 0.78119370269565391, 10000 * 0.01777777777};
+  const double *c = calib ? calib : ref_calib;
+  for (int i = 0; i < 8; ++i)
+    if (!std::isfinite(c[i])) return fail(h, XK_EINVAL, "non-finite sun sensor calibration");
+  if (!(c[7] > 0.0)) return fail(h, XK_EINVAL, "var_sun <= 0");
+  if (!(c[4] * c[4] + c[5] * c[5] + c[6] * c[6] > 0.0) || !(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + c[3] * c[3] > 0.0) ||
+      !(q_xyzw[0] * q_xyzw[0] + q_xyzw[1] * q_xyzw[1] + q_xyzw[2] * q_xyzw[2] + q_xyzw[3] * q_xyzw[3] > 0.0))
+    return fail(h, XK_EINVAL, "zero quaternion or sun vector");
+  XkAuxIn &a = h->aux_in;
+  for (int i = 0; i < 4; ++i) a.q_imu[i] = q_xyzw[i];
+  a.ang[0] = x_angle_deg; a.ang[1] = y_angle_deg;
+  a.s_q_i[0] = c[1]; a.s_q_i[1] = c[2]; a.s_q_i[2] = c[3]; a.s_q_i[3] = c[0];    // (w, x, y, z) -> xyzw
+  for (int i = 0; i < 3; ++i) a.g_sun[i] = c[4 + i];
+  a.var_sun = c[7];
+  h->aux_staged |= 2;
+  return XK_OK;
+}
+
 extern "C" int xk_msckf_slam_results(xk_handle *h, int *inlier, double *gamma, double *H1, int ldh1, double *H2, int ldh2,
                                      double *r1, double *features) {
   if (!h) return XK_EINVAL;
@@ -793,7 +852,39 @@ extern "C" int xk_download_P(xk_handle *h, double *P, int ldp, int n) {
 
 static int split_plan(const xk_handle *h);
 static long split_rows_nominal(const xk_handle *h);
-static int launch_build(xk_handle *h, double sigma_img) {
+
+// The range / sun rows of this update (xk_aux.hip.h), queued behind the per-feature kernels: one workgroup, no host synchronisation.
+// Their variances follow the REFERENCE's stack, not this engine's schedule: the reference compresses when its rows -- every MSCKF and
+// MSCKF-SLAM track's 2 L - 3, the SLAM features' 2 M, 1 range row, 2 sun rows, accepted or not -- exceed n + 1
+// (vio_updater.cpp:487-490), and then gives EVERY row sigma_img^2 (:507-509): a compressed range row weighs as if sigma_range were
+// sigma_img.  Uncompressed, each row keeps its own: sigma_range^2 (1 for a gated-out row), var_sun.
+static int launch_aux(xk_handle *h, double sigma_img) {
+  XkAuxIn in = h->aux_in;
+  in.has_range = (h->aux_mask & 1) ? 1 : 0;
+  in.has_sun = (h->aux_mask & 2) ? 1 : 0;
+  if (in.has_range) {
+    if (h->M < 3) return fail(h, XK_EINVAL, "range row: fewer than 3 SLAM features staged");
+    for (int j = 0; j < 3; ++j)
+      if (in.facet[j] >= h->M) return fail(h, XK_EINVAL, "range row: facet feature id outside the staged SLAM features");
+  }
+  const long nominal = split_rows_nominal(h) + 2L * h->M + h->naux;
+  in.compressed = nominal > (long)h->n + 1 ? 1 : 0;
+  in.var_comp = sigma_img * sigma_img;
+  in.chi1 = XK_CHI2_090[1];
+  XkAuxArgs a;
+  a.q = h->d_q; a.p = h->d_p; a.n_poses = h->n_poses; a.N = h->N;
+  a.feat = h->d_feat; a.anchor = h->d_anchor; a.P = h->d_P; a.n = h->n;
+  a.in = in;                                      // (by value: no host-to-device copy, no staging slot, replays included)
+  a.rows = h->d_aux;
+  a.rdiag = a.rows + 3 * ((size_t)h->n + 1);
+  a.flags = a.rdiag + 3;
+  hipLaunchKernelGGL(xk_aux_rows, dim3(1), dim3(XK_AUX_THREADS), 0, h->stream, a);
+  return XK_OK;
+}
+
+// replay: the build of an update that is being redone (a retry) or repeated (xk_run_steps / xk_bench_staged past the first step) -- the
+// range / sun rows of that update are built again; any other build takes what has been staged since the last one (possibly nothing).
+static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
   if (h->n_poses < 2) return fail(h, XK_EINVAL, "window not staged");
   if (h->K > 0 && h->h_pin_i[0] > h->n_poses) return fail(h, XK_EINVAL, "track longer than the staged window");
   const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
@@ -861,6 +952,12 @@ static int launch_build(xk_handle *h, double sigma_img) {
                        h->stream) != hipSuccess)
       return fail(h, XK_EDEVICE, "tile_rows upload");
   }
+  if (h->aux_staged || !replay) {                  // (a replay keeps the rows of the update it repeats)
+    h->aux_mask = h->aux_staged;
+    h->aux_staged = 0;
+  }
+  h->naux = ((h->aux_mask & 1) ? 1 : 0) + ((h->aux_mask & 2) ? 2 : 0);
+  if (h->naux) { int rca = launch_aux(h, sigma_img); if (rca != XK_OK) return rca; }
   h->sigma_img = sigma_img;
   h->have_rows = true;
   h->have_R = false;
@@ -902,6 +999,7 @@ struct UpdateSpec {
   unsigned long long *done_flag;   // optional completion marker (pinned host memory) written by the last launch ...
   unsigned long long done_seq;     // ... with this value
   int tri;           // T is upper trapezoidal (T[r][k] == 0 for k < r: the compressed R): the products skip the zero blocks
+  int naux;          // range / sun rows of this update (d_aux) to append: launch_update applies [T ; rows] over all n columns
 };
 
 template <int RPL>
@@ -1101,7 +1199,7 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
       h->pipe_tag = (h->pipe_tag % 0x7fff) + 1;               // 1 .. 32767: tags the accepted-rows word of THIS launch (eval_status)
       pa.acc_tag = h->pipe_tag;
       pa.kal = 0; pa.kn = h->n; pa.Pin = nullptr; pa.Pout = nullptr; pa.sigma2 = 0.0; pa.corr = nullptr; pa.ct = nullptr; pa.done_flag = nullptr; pa.done_seq = 0;
-      if (fuse && narrow && h->opt_kalman && !fuse->S && !fuse->rdiag && fuse->T == h->d_R &&
+      if (fuse && narrow && h->opt_kalman && !fuse->S && !fuse->rdiag && !fuse->naux && fuse->T == h->d_R &&
           h->n <= 206 && h->n_cu == 256) {
         // (a pass that leaves the covariance alone, cov_update = 0: the role needs the block-by-block posterior to get the
         //  correction right, so it runs as ever and its posterior goes to a scratch matrix; Pout becomes a copy of the prior below)
@@ -1323,8 +1421,23 @@ static void gemm(xk_handle *h, const XkGemmArgs &g) {
 
 // Kalman algebra on the device (updater.cpp:117-141 / :144-161).  ev (optional)
 // = {before, after-gemm-part...} is not used here; stage split is timed by the caller.
-static int launch_update(xk_handle *h, const UpdateSpec &u, float *gemm_ms_accum = nullptr) {
+static int launch_update(xk_handle *h, const UpdateSpec &u_in, float *gemm_ms_accum = nullptr) {
   (void)gemm_ms_accum;
+  UpdateSpec u = u_in;
+  if (u.naux > 0) {
+    // the range / sun rows join the system as built (they never go through the QR): [T ; H_aux]^T [T ; H_aux] is the Gram matrix of the
+    // whole stack, and the same for the residual -- the argument of the split form for the SLAM rows.  The sun rows touch core columns
+    // 6..8, so the system is widened to all n columns, with one variance per row (xk_aux.hip.h chose the rows' own).
+    if (u.c + u.naux > h->CM) return fail(h, XK_ECAPACITY, "measurement rows exceed workspace");
+    XkAuxStackArgs s;
+    s.T = u.T; s.str = u.str; s.stc = u.stc; s.c = u.c; s.kdim = u.kdim; s.col0 = u.col0;
+    s.z = u.z; s.sz = u.sz; s.rdiag = u.rdiag; s.rscalar = u.rscalar;
+    s.aux = h->d_aux; s.aux_rdiag = s.aux + 3 * ((size_t)h->n + 1); s.naux = u.naux;
+    s.n = h->n; s.out = h->d_Taug; s.out_rdiag = h->d_Taug + (size_t)h->CM * (h->n + 1);
+    hipLaunchKernelGGL(xk_aux_stack, dim3(u.c + u.naux), dim3(256), 0, h->stream, s);
+    u.T = s.out; u.str = h->n + 1; u.stc = 1; u.c += u.naux; u.kdim = h->n; u.col0 = 0;
+    u.z = s.out + h->n; u.sz = h->n + 1; u.rdiag = s.out_rdiag; u.tri = 0; u.naux = 0;
+  }
   const int c = u.c, n = h->n, LDA = h->LDA;
   if (c <= 0 || c > h->CM) return fail(h, XK_ECAPACITY, "measurement rows exceed workspace");
   XkGemmArgs g;
@@ -1450,7 +1563,16 @@ static int split_plan(const xk_handle *h) {
           (h->overflow_rows == 0 || R < h->overflow_rows)) ? 1 : 0;
 }
 
+static UpdateSpec compressed_spec_base(xk_handle *h, const double *d_ct, int cov_update);
 static UpdateSpec compressed_spec(xk_handle *h, const double *d_ct, int cov_update) {
+  UpdateSpec u = compressed_spec_base(h, d_ct, cov_update);
+  if (h->naux > 0) {
+    u.naux = h->naux;
+    if (h->K + h->K2 + h->M == 0) u.c = 0;        // (no visual row at all: the update is the range / sun rows alone)
+  }
+  return u;
+}
+static UpdateSpec compressed_spec_base(xk_handle *h, const double *d_ct, int cov_update) {
   UpdateSpec u;
   memset(&u, 0, sizeof(u));
   if (const int mode = h->have_R ? h->split_active : split_plan(h)) {
@@ -1570,7 +1692,7 @@ extern "C" int xk_qr_compress(xk_handle *h, double *T_H, int ldt, double *z) {
   int rc = launch_compress(h);
   if (rc == XK_OK) rc = read_status(h, true);
   if (rc == XK_RETRY_CLASSIC) {                  // rebuild the rows (the tiles were worked on in place) and compress the slow way
-    if ((rc = launch_build(h, h->sigma_img)) == XK_OK && (rc = launch_compress(h)) == XK_OK) rc = read_status(h);
+    if ((rc = launch_build(h, h->sigma_img, true)) == XK_OK && (rc = launch_compress(h)) == XK_OK) rc = read_status(h);
   }
   h->want_full_T = false;
   if (rc != XK_OK) return rc;
@@ -1625,7 +1747,8 @@ extern "C" int xk_build_compress_async(xk_handle *h, double sigma_img) {
   // update along (narrow geometry, n <= 206) the compression is not queued now but by xk_apply_update, behind those entries, with
   // the Kalman role on the covariance they left: one launch there instead of one here and five there.
   h->compress_deferred = h->opt_resident && h->persist_ok && h->opt_kalman && h->C1 <= XkPipeNarrow::COLS && h->n <= 206 && h->n_cu == 256 &&
-                         h->K + h->K2 + h->M > 0 && split_plan(h) < 2;   // (stacks that are not compressed at all: nothing to defer)
+                         h->K + h->K2 + h->M > 0 && split_plan(h) < 2 &&   // (stacks that are not compressed at all: nothing to defer)
+                         h->naux == 0;   // (range / sun rows: the update is not taken along by the launch anyway)
   if (h->compress_deferred) h->have_R = true;     // (as far as xk_apply_update's precondition goes: it runs the compression itself)
   else if ((rc = launch_compress(h)) != XK_OK) return rc;
   h->async_pending = true;
@@ -1695,6 +1818,42 @@ extern "C" int xk_fetch_flags(xk_handle *h, int *inlier_msckf, double *gamma_msc
   return XK_OK;
 }
 
+// Gate result of the range row of the last build (range_update.cpp:246-262): *range_inlier 1 / 0, -1 if that build had no range row.
+// Synchronises the stream.
+extern "C" int xk_fetch_aux_flags(xk_handle *h, int *range_inlier, double *range_gamma) {
+  if (!h) return XK_EINVAL;
+  double f[2] = {0.0, 0.0};
+  if (h->aux_mask & 1) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(f, h->d_aux + 3 * ((size_t)h->n + 1) + 3, sizeof(f), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  if (range_inlier) *range_inlier = (h->aux_mask & 1) ? (f[1] != 0.0 ? 1 : 0) : -1;
+  if (range_gamma) *range_gamma = f[0];
+  return XK_OK;
+}
+
+// The range / sun rows of the last build as built (h_lrf, h_sns, their residuals and r_diag entries, vio_updater.cpp:407-421), for a host
+// that applies the dense system itself (xk_apply_update_dense).  H: rows x n, column-major, ldh >= 3 (any pointer may be NULL).
+extern "C" int xk_aux_rows(xk_handle *h, double *H, int ldh, double *res, double *r_diag, int *rows) {
+  if (!h) return XK_EINVAL;
+  const int na = h->naux, n = h->n;
+  if (H && ldh < 3) return XK_EINVAL;
+  if (rows) *rows = na;
+  if (na == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> b((size_t)3 * (n + 1) + 3);
+  HIPCHK(h, hipMemcpyAsync(b.data(), h->d_aux, sizeof(double) * b.size(), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int r = 0; r < na; ++r) {
+    if (H)
+      for (int c = 0; c < n; ++c) H[r + (size_t)c * ldh] = b[(size_t)r * (n + 1) + c];
+    if (res) res[r] = b[(size_t)r * (n + 1) + n];
+    if (r_diag) r_diag[r] = b[(size_t)3 * (n + 1) + r];
+  }
+  return XK_OK;
+}
+
 extern "C" int xk_apply_update(xk_handle *h, const double *corr_total, int cov_update, double *correction) {
   if (!h || !correction) return XK_EINVAL;
   if (!h->have_R) return fail(h, XK_EINVAL, "xk_qr_compress has not run on the staged inputs");
@@ -1731,7 +1890,7 @@ extern "C" int xk_apply_update(xk_handle *h, const double *corr_total, int cov_u
         // on the tiles in place, and it has not run)
         h->have_rows = true;
       } else {
-        if ((rc = launch_build(h, h->sigma_img)) != XK_OK) return rc;
+        if ((rc = launch_build(h, h->sigma_img, true)) != XK_OK) return rc;
         if ((rc = cache_flags(h)) != XK_OK) return rc;
       }
       if ((rc = launch_compress(h)) != XK_OK) return rc;
@@ -1790,13 +1949,13 @@ extern "C" int xk_visual_update_staged(xk_handle *h, double sigma_img, double *c
                                        double *gamma_msckf, int *inlier_slam, double *gamma_slam) {
   if (!h || !correction || !(sigma_img > 0.0)) return XK_EINVAL;
   HIPCHK(h, hipSetDevice(h->device));
-  if (h->K == 0 && h->K2 == 0 && h->M == 0) {  // h.size() == 0 -> no update (updater.cpp:106); MSCKF-SLAM rows count (vio_updater.cpp:413-419)
+  if (h->K == 0 && h->K2 == 0 && h->M == 0 && !h->aux_staged) {  // h.size() == 0 -> no update (updater.cpp:106); MSCKF-SLAM rows count (vio_updater.cpp:413-419)
     for (int i = 0; i < h->n; ++i) correction[i] = 0.0;
     return XK_OK;
   }
   int rc = XK_OK;
   for (int attempt = 0; attempt < 2; ++attempt) {
-    rc = launch_build(h, sigma_img);
+    rc = launch_build(h, sigma_img, attempt > 0);
     if (rc != XK_OK) return rc;
     UpdateSpec u = compressed_spec(h, nullptr, 1);
     rc = launch_compress(h, nullptr, &u);            // (the single launch takes the Kalman update along where it can)
@@ -1911,7 +2070,7 @@ static int settle_async(xk_handle *h) {
   stage_stream_idle(h);
   int rc = eval_status(h, h->d_status[0], h->d_status[1], true);
   if (rc == XK_RETRY_CLASSIC) {
-    if ((rc = launch_build(h, h->sigma_img)) != XK_OK) return rc;
+    if ((rc = launch_build(h, h->sigma_img, true)) != XK_OK) return rc;
     if ((rc = cache_flags(h)) != XK_OK) return rc;
     if ((rc = launch_compress(h)) != XK_OK) return rc;
   }
@@ -1984,7 +2143,7 @@ extern "C" int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int s
   tot = 0;
   for (int it = 0; it < warmup + steps; ++it) {
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    int rc = launch_build(h, sigma_img);
+    int rc = launch_build(h, sigma_img, attempt > 0 || it > 0);   // (staged range / sun rows: in every step)
     if (rc != XK_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     UpdateSpec u = compressed_spec(h, nullptr, 1);
@@ -2705,7 +2864,7 @@ extern "C" int xk_run_steps(xk_handle *h, double sigma_img, int steps) {
   //  processes sharing one GPU, each with a grid that wants every CU -- costs one more pass with the multi-launch schedule)
   for (int attempt = 0; attempt < 2; ++attempt) {
     for (int it = 0; it < steps; ++it) {
-      int rc = launch_build(h, sigma_img);
+      int rc = launch_build(h, sigma_img, attempt > 0 || it > 0);   // (staged range / sun rows: in every step)
       if (rc != XK_OK) return rc;
       UpdateSpec u = compressed_spec(h, nullptr, 1);
       rc = launch_compress(h, nullptr, &u);

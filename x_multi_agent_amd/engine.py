@@ -32,6 +32,7 @@ SYMBOLS = [
     "xk_stage_msckf_slam", "xk_msckf_slam_results", "xk_init_msckf_slam_features", "xk_init_standard_slam_features",
     "xk_payload_doubles", "xk_pack_payload", "xk_bench_staged", "xk_run_steps",
     "xk_apply_ci_resident", "xk_snapshot_P", "xk_caqr_status", "xk_set_option", "xk_build_compress_async", "xk_build_compress_update_async", "xk_build_compress_update_pass_async", "xk_fetch_flags",
+    "xk_stage_range", "xk_stage_sun_angle", "xk_fetch_aux_flags", "xk_aux_rows",
     "xk_pr_create", "xk_pr_destroy", "xk_pr_vlad_bytes", "xk_pr_size", "xk_pr_compute_vlad", "xk_pr_add_keyframe",
     "xk_pr_find_candidate", "xk_pr_keyframe", "xk_pr_copy_keyframe", "xk_pr_knn_match",
 ]
@@ -466,6 +467,34 @@ class Engine:
         self._chk(self.L.xk_pack_payload(self.h, C.c_double(agent_id), C.c_double(timestamp), dp, dst,
                                          C.byref(ptr)), "xk_pack_payload")
         return C.cast(ptr, C.c_void_p).value
+
+    # ---- range-facet / sun-angle rows (include/xk.h) ----------------------
+    def stage_range(self, range_m, img_pt, facet, sigma_range):
+        f, fp = _i(facet)
+        self._chk(self.L.xk_stage_range(self.h, C.c_double(range_m), C.c_double(img_pt[0]), C.c_double(img_pt[1]), fp,
+                                        C.c_double(sigma_range)), "xk_stage_range")
+
+    def stage_sun_angle(self, q_xyzw, x_angle, y_angle, calib=None):
+        q, qp = _d(q_xyzw)
+        cp = None
+        if calib is not None:
+            cb, cp = _d(calib)
+        self._chk(self.L.xk_stage_sun_angle(self.h, qp, C.c_double(x_angle), C.c_double(y_angle), cp), "xk_stage_sun_angle")
+
+    def fetch_aux_flags(self):
+        """-> (range_inlier 1 / 0 / -1 = no range row in the last build, range_gamma)"""
+        inl, gam = C.c_int(), C.c_double()
+        self._chk(self.L.xk_fetch_aux_flags(self.h, C.byref(inl), C.byref(gam)), "xk_fetch_aux_flags")
+        return inl.value, gam.value
+
+    def aux_rows(self):
+        """-> (H [rows x n], res [rows], r_diag [rows]) of the last build's range / sun rows"""
+        H = np.zeros((3, self.n), order="F")
+        res, rd, rows = np.zeros(3), np.zeros(3), C.c_int()
+        self._chk(self.L.xk_aux_rows(self.h, H.ctypes.data_as(c_dp), C.c_int(3), res.ctypes.data_as(c_dp), rd.ctypes.data_as(c_dp),
+                                     C.byref(rows)), "xk_aux_rows")
+        m = rows.value
+        return np.ascontiguousarray(H[:m]), res[:m].copy(), rd[:m].copy()
 
     def run_steps(self, sigma_img, steps):
         self._chk(self.L.xk_run_steps(self.h, C.c_double(sigma_img), C.c_int(steps)), "xk_run_steps")

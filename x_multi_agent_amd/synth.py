@@ -366,3 +366,34 @@ def observe_descriptors(base, flip_bits, seed):
         for b in rng.choice(nbits, size=flip_bits, replace=False):
             out[i, b >> 3] ^= np.uint8(1 << (b & 7))
     return out
+
+
+def make_range(sc, facet=(0, 1, 2), weights=(0.3, 0.3, 0.4), range_err=0.0, sigma_range=0.05):
+    """An LRF reading consistent with scenario `sc` (make_scenario with SLAM features): the true point at barycentric `weights` inside
+    the facet of true landmarks of SLAM features `facet`, seen from the TRUE current camera.  img_pt is the ray's normalised image point,
+    range its depth along the camera axis -- what RangeUpdate predicts as a / b (range_update.cpp:127-133) -- plus range_err.
+    Returns dict(range, img_pt, facet, sigma_range)."""
+    K = len(sc["trk_off"]) - 1
+    lm = sc["landmarks_true"]
+    X = sum(w * lm[K + int(f)] for w, f in zip(weights, facet))
+    c = sc["R_true"][-1].T @ (X - sc["p_true"][-1])
+    return dict(range=float(c[2] + range_err), img_pt=np.array([c[0] / c[2], c[1] / c[2]]), facet=np.asarray(facet, np.int32),
+                sigma_range=float(sigma_range))
+
+
+def make_sun(seed, err_deg=0.5, noise_deg=0.0, calib=None):
+    """A sun-sensor reading consistent with a true IMU attitude near level (the reference's sensor points at the zenith): returns
+    dict(q, x, y, calib) with q the ESTIMATED attitude (xyzw, truth perturbed by err_deg) and x / y the angles the sensor reads at the
+    truth (solar_update.cpp:58-69) plus noise_deg.  calib: None = the reference's constants (8 doubles, S_q_I as (w, x, y, z))."""
+    rng = SplitMix(seed)
+    c = np.array([0.360346005598587, -0.063338979194957, 0.007502445522018, 0.930635612981541,
+                  -0.29385515271891938, -0.55080445540063927, 0.78119370269565391, 10000 * 0.01777777777]) if calib is None \
+        else np.asarray(calib, float)
+    R_true = _small_rot(0.2 * (rng.uniform(3) - 0.5))
+    R_est = R_true @ _small_rot(np.deg2rad(err_deg) * (rng.uniform(3) - 0.5) * 2.0)
+    Rs = _quat_to_rot(np.array([c[1], c[2], c[3], c[0]]))
+    g = c[4:7] / np.linalg.norm(c[4:7])
+    s = Rs.T @ R_true.T @ g
+    s = s / np.linalg.norm(s)
+    ang = 57.2957795130 * np.array([np.arctan2(s[0], s[2]), np.arctan2(s[1], s[2])]) + noise_deg * rng.normal(2)
+    return dict(q=_rot_to_quat_xyzw(R_est), x=float(ang[0]), y=float(ang[1]), calib=None if calib is None else c)
