@@ -401,7 +401,8 @@ int xk_run_steps(xk_handle *h, double sigma_img, int steps);
  * register-resident kernel, no longer built), 3 the multi-launch CAQR for the first panels of a tall system (windows of 34..64
  * poses) and one or two single launches for its last <= 192 columns, 4 no compression at all: the stack was the SLAM features' rows alone
  * (2 M rows against n > 3 M columns) or a small stack whose nominal rows are at most n -- the reference compresses only when rows >
- * columns, vio_updater.cpp:487, and neither does this: the rows go to the update as built -- whether the single-launch path is armed for the next update, how many launches have given up on
+ * columns, vio_updater.cpp:487, and neither does this: the rows go to the update as built -- or the update had no track and no SLAM
+ * feature at all (nothing to compress) -- whether the single-launch path is armed for the next update, how many launches have given up on
  * this handle so far (workgroups not co-resident: another process on the GPU, a CU mask) and the reason code of the last one
  * (2 XCD-local hand-off, 3 uneven XCD placement, 4 / 5 / 6 waiting for the last level / the roots / the tiles, 8 the Kalman role
  * waiting for rows of R, 9 more rows passed the gates than the tiles of the launch hold -- not a co-residency problem: the fast

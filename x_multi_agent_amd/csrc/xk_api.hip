@@ -80,7 +80,12 @@ struct xk_handle {
   // the whole stack) goes to d_R2; xk_qr_compress, which hands out the reference's upper-triangular T_H, keeps compressing everything.
   double *d_R2;         // [C1P][C1P] row-major: rows [0, 6 N) = R1 of the tracks' rows, rows [6 N, 6 N + 2 M) = the SLAM rows as built
   int split_active;     // what the last launch_compress left in d_R2 (compressed_spec follows it): 0 nothing, 1 the split compression,
-                        // 2 the SLAM rows alone, uncompressed (no track in the stack: rows <= columns, vio_updater.cpp:487 does not compress either)
+                        // 2 the SLAM rows alone, uncompressed (no track in the stack: rows <= columns, vio_updater.cpp:487 does not compress either),
+                        // 3 a small stack, uncompressed; launch_build resets it to 0
+  int plan;             // split_plan of the staged update, latched by launch_build: the rows were built for it (tiles or factor records), and
+                        // launch_compress and compressed_spec take it -- an option changed in between does not split the two
+  bool d_R2_dirty;      // a small stack (plan 3) left dense rows in d_R2: the next split compression clears rows [0, 6 N) before it writes R1
+  bool last_empty;      // the last update had no measurement rows at all: nothing compressed (xk_caqr_status: schedule 4)
   bool want_full_T;     // xk_qr_compress is running: compress everything into d_R
   int opt_slam_split;
   int opt_pipe_min_rows;   // nominal rows from which the single launch is queued (1; lab: XK_PIPE_MIN_ROWS)
@@ -892,6 +897,8 @@ static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
   memset(&fa, 0, sizeof(fa));
   size_t feat_lds = 0;
   { int rcw = flush_window(h); if (rcw != XK_OK) return rcw; }   // (normally carried by the frame's congruence launch already)
+  h->plan = split_plan(h);
+  h->split_active = 0;                            // (d_R2 holds nothing of THIS update until launch_compress writes it)
   if (h->K > 0) {
     XkFeatArgs &a = fa;
     a.q = h->d_q; a.p = h->d_p; a.n_poses = h->n_poses; a.n_poses_max = h->N;
@@ -903,7 +910,7 @@ static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
     // costs more than the tiles' trip through HBM -- config 2: 1546 -> 1521 updates/s -- so those keep their tiles), or the
     // first pass of the multi-launch schedule (128-row slots: always; 64-row slots: when the single launch was armed and then
     // not taken or gave up).
-    h->rows_compact = h->opt_hlite && h->d_Hc && !h->feat_dbg && split_plan(h) != 3 &&      // (an uncompressed small stack is copied from tiles)
+    h->rows_compact = h->opt_hlite && h->d_Hc && !h->feat_dbg && h->plan != 3 &&      // (an uncompressed small stack is copied from tiles)
                       (h->DB == 128 || (h->opt_resident && h->persist_ok && (h->C1 <= XkPipeNarrow::COLS || h->opt_hlite >= 2)));   // (lab: 2 = the wide geometry too)
     a.Hc = h->rows_compact ? h->d_Hc : nullptr; a.hs = h->hc_stride; a.hcvr = xk_hc_vr(h->DB);
     a.tile_rows = h->d_tile_rows; a.inlier = h->d_inl; a.gamma = h->d_gam; a.gpf = h->d_gpf; a.gn_iters = h->d_gn;
@@ -1069,9 +1076,11 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
   if (!h->have_rows) return fail(h, XK_EINVAL, "xk_msckf_build has not run on the staged inputs");
   const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
   const int ntiles = h->K + h->K2 + slam_tiles;
+  h->split_active = 0;
+  h->last_empty = ntiles == 0;
   if (ntiles == 0) {   // no measurement rows at all: [T_H | z] = 0 (the reference skips the update, updater.cpp:106)
     if (hipMemsetAsync(h->d_R, 0, sizeof(double) * (size_t)h->C1P * h->C1P, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "R memset");
-    h->nleaf = 0; h->nlevels = 0; h->have_R = true;
+    h->nleaf = 0; h->nlevels = 0; h->have_R = true; h->last_resident = false; h->last_pipe = false;
     return XK_OK;
   }
   // (d_R was zeroed at creation; the merges rewrite the whole upper trapezoid every update and nothing else)
@@ -1102,9 +1111,8 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
   // register-resident single launch (xk_caqr_pipe.hip.h): MSCKF tracks only, valid rows <= 184 fat tiles of 128
   const int resident_env = h->opt_resident;
   const bool fast_shape = h->K + h->K2 > 0 || h->M > 0;
-  const int sp_mode = split_plan(h);              // (before the re-arming below: what compressed_spec saw)
+  const int sp_mode = h->want_full_T ? 0 : h->plan;   // (latched at the build: what compressed_spec saw; xk_qr_compress: the whole stack)
   const bool sp = sp_mode == 1;
-  h->split_active = 0;
   if (sp_mode == 3) {
     // a small stack, not compressed (see split_plan): tracks' rows by slot, MSCKF-SLAM tracks' behind them, then the SLAM rows
     const int Rt = h->K > 0 ? 2 * h->h_trk_off[h->K] - 3 * h->K : 0;   // (h_trk_off holds nothing when no track is staged)
@@ -1118,6 +1126,7 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
       return fail(h, XK_EDEVICE, "SLAM rows");
     if (mid) hipEventRecord(mid, h->stream);
     h->split_active = 3;
+    h->d_R2_dirty = true;                         // (rows below R1's diagonal and in the features' columns: the split compression never writes them)
     h->nleaf = 0; h->nlevels = 0; h->have_R = true; h->last_resident = false; h->last_pipe = false;
     hipError_t e3 = hipGetLastError();
     if (e3 != hipSuccess) return fail(h, XK_EDEVICE, "stack rows", e3);
@@ -1130,6 +1139,8 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
     if (mid) hipEventRecord(mid, h->stream);
     h->split_active = 2;
     h->nleaf = 0; h->nlevels = 0; h->have_R = true; h->last_resident = false; h->last_pipe = false;
+    hipError_t e2 = hipGetLastError();
+    if (e2 != hipSuccess) return fail(h, XK_EDEVICE, "SLAM rows", e2);
     return XK_OK;
   }
   if (resident_env && !h->persist_ok && h->fast_capable && h->rearm_after > 0 && fast_shape && ++h->clean_classic > h->rearm_after) {
@@ -1209,6 +1220,11 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
         h->last_fused = true;
       }
       h->last_split = split;
+      if (sp && h->d_R2_dirty) {
+        // the launch writes R1's upper trapezoid and the residual column only, and the update reads rows [0, 6 N) whole (u.tri = 0)
+        if (hipMemsetAsync(h->d_R2, 0, sizeof(double) * (size_t)6 * h->N * h->C1P, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "R2 memset");
+        h->d_R2_dirty = false;
+      }
       if (split) hipLaunchKernelGGL(xk_caqr_pipe<XkPipeNarrow2>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
       else if (narrow) hipLaunchKernelGGL(xk_caqr_pipe<XkPipeNarrow>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
       else hipLaunchKernelGGL(xk_caqr_pipe<XkPipeWide>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
@@ -1533,9 +1549,9 @@ static int launch_update(xk_handle *h, const UpdateSpec &u_in, float *gemm_ms_ac
   return XK_OK;
 }
 
-// Will (did) the compression of the staged update take the split form?  One predicate for compressed_spec -- which callers evaluate
-// BEFORE launch_compress -- and for launch_compress itself, on handle state neither of them changes in between; it repeats the
-// conditions under which the single launch is taken at all (a split system goes nowhere else).
+// Will the compression of the staged update take the split form?  Evaluated once per build (launch_build latches it in h->plan) for
+// compressed_spec -- which callers evaluate BEFORE launch_compress -- and for launch_compress itself; it repeats the conditions under
+// which the single launch is taken at all (a split system goes nowhere else).
 static int split_geometry_rows(const xk_handle *h) { return 6 * h->N + 1 <= XkPipeNarrow::COLS ? XkPipeNarrow::ROWS : XkPipeWide::ROWS; }
 static long split_rows_nominal(const xk_handle *h) {
   long r = 0;
@@ -1575,7 +1591,7 @@ static UpdateSpec compressed_spec(xk_handle *h, const double *d_ct, int cov_upda
 static UpdateSpec compressed_spec_base(xk_handle *h, const double *d_ct, int cov_update) {
   UpdateSpec u;
   memset(&u, 0, sizeof(u));
-  if (const int mode = h->have_R ? h->split_active : split_plan(h)) {
+  if (const int mode = h->have_R ? h->split_active : h->plan) {
     // the split form (d_R2): 6 N rows of R1 over the pose columns, then the 2 M rows of the SLAM features as built; mode 2: those rows alone
     const int r0 = mode == 2 ? 6 * h->N : 0;
     u.T = h->d_R2 + (size_t)r0 * h->C1P; u.str = h->C1P; u.stc = 1;
@@ -1747,7 +1763,7 @@ extern "C" int xk_build_compress_async(xk_handle *h, double sigma_img) {
   // update along (narrow geometry, n <= 206) the compression is not queued now but by xk_apply_update, behind those entries, with
   // the Kalman role on the covariance they left: one launch there instead of one here and five there.
   h->compress_deferred = h->opt_resident && h->persist_ok && h->opt_kalman && h->C1 <= XkPipeNarrow::COLS && h->n <= 206 && h->n_cu == 256 &&
-                         h->K + h->K2 + h->M > 0 && split_plan(h) < 2 &&   // (stacks that are not compressed at all: nothing to defer)
+                         h->K + h->K2 + h->M > 0 && h->plan < 2 &&   // (stacks that are not compressed at all: nothing to defer)
                          h->naux == 0;   // (range / sun rows: the update is not taken along by the launch anyway)
   if (h->compress_deferred) h->have_R = true;     // (as far as xk_apply_update's precondition goes: it runs the compression itself)
   else if ((rc = launch_compress(h)) != XK_OK) return rc;
@@ -1951,6 +1967,7 @@ extern "C" int xk_visual_update_staged(xk_handle *h, double sigma_img, double *c
   HIPCHK(h, hipSetDevice(h->device));
   if (h->K == 0 && h->K2 == 0 && h->M == 0 && !h->aux_staged) {  // h.size() == 0 -> no update (updater.cpp:106); MSCKF-SLAM rows count (vio_updater.cpp:413-419)
     for (int i = 0; i < h->n; ++i) correction[i] = 0.0;
+    h->last_empty = true;
     return XK_OK;
   }
   int rc = XK_OK;
@@ -2954,7 +2971,7 @@ extern "C" int xk_set_option(xk_handle *h, const char *name, int value) {
 
 extern "C" int xk_caqr_status(const xk_handle *h, int *schedule, int *armed, int *giveups, int *last_reason) {
   if (!h) return XK_EINVAL;
-  if (schedule) *schedule = h->split_active >= 2 ? 4 : (h->last_tail ? 3 : (!h->last_resident ? 0 : (h->last_pipe ? 2 : 1)));
+  if (schedule) *schedule = (h->last_empty || h->split_active >= 2) ? 4 : (h->last_tail ? 3 : (!h->last_resident ? 0 : (h->last_pipe ? 2 : 1)));
   if (armed) *armed = (h->persist_ok || h->tail_ok) ? 1 : 0;
   if (giveups) *giveups = h->fast_giveups;
   if (last_reason) *last_reason = h->fast_reason;
