@@ -41,6 +41,8 @@ struct VioMeasurement {
 
 class VioUpdater : public Updater {
  public:
+  // ci_slam_w / ci_msckf_w: 0 < w <= 1 fixed CI weights; -1 <= w < 0 switches the engine's weight search on (include/xk.h,
+  // "ci_weight_search").  The defaults stay fixed weights (the reference's are -1: search).
   VioUpdater(int device, int n_poses_max, int n_feat_max, int k_max, double sigma_img, double sigma_landmark = 0.1,
              double ci_slam_w = 0.4, int iekf_iter = 1, double ci_msckf_w = 0.05, double rho_0 = 0.5,
              double sigma_rho_0 = 0.4, double sigma_range = 0.05);

@@ -50,6 +50,8 @@ VioUpdater::VioUpdater(int device, int n_poses_max, int n_feat_max, int k_max, d
       rho_0_(rho_0), sigma_rho_0_(sigma_rho_0), sigma_range_(sigma_range) {
   iekf_iter_ = iekf_iter;
   check(nullptr, xk_create(device, n_poses_max, n_feat_max, k_max, &xk_), "xk_create");  // no CPU fallback
+  // a negative CI weight asks for searched weights (ci.cpp:65-73,105-119; the reference's own defaults are -1, vio.cpp:191-192)
+  if (ci_slam_w < 0.0 || ci_msckf_w < 0.0) check(xk_, xk_set_option(xk_, "ci_weight_search", 1), "xk_set_option");
   state_manager_.setEngine(xk_);
   state_manager_.restore(n_poses_max, 0, std::vector<int>(n_feat_max, -1), true);
 }

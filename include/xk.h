@@ -138,18 +138,48 @@ int xk_apply_ci(xk_handle *h, double *P_out, int ldp, const double *ci_P, int ld
                 const double *H, int ldh, int m, const double *res, const double *S, int lds,
                 double *correction);
 
-/* ---- covariance intersection (fixed weights) ------------------------- */
+/* ---- covariance intersection (fixed or searched weights) ------------- */
+
+/* The weight argument of the five CI entries below (xk_fuse_ci_msckf, xk_fuse_ci_slam, xk_multi_slam_match,
+ * xk_msckf_ci_track, xk_ci_round_device) follows CovarianceIntersection::fuseCI (src/x/ekf/ci.cpp):
+ *   0 < w <= 1     fixed weights.
+ *   w > 1, w == 0, w < -1   XK_EINVAL (the reference throws, ci.cpp:59-62,98-101).
+ *   -1 <= w < 0    "search the weights" (ci.cpp:65-73,105-119 -> solveW, :143-190).  XK_EINVAL unless
+ *                  xk_set_option(h, "ci_weight_search", 1) was called (default 0); xk_ci_round_device takes
+ *                  fixed weights only and answers XK_EINVAL either way.
+ * The search minimises the reference's objective under the reference's bounds,
+ *   det((sum_i w_i M_i)^-1),  M_i = H_i P_i^-1 H_i^T,  1e-4 <= w_i <= 1,  sum_i w_i = 1,
+ * as f(w) = -log det(sum_i w_i M_i): convex, so the minimiser is one point, found by an active-set Newton iteration in a
+ * few steps (fp64, fixed summation order: the same inputs give the same bits on every call; no wall-time limit).  Every
+ * covariance is factored once per call (the Kalman stage's blocked Cholesky with the rows of H_i as right-hand sides).
+ * What is returned is the MINIMISER, not the iterate NLopt's COBYLA stops at: the reference stops on ftol_abs = 1e-6 of a
+ * determinant that is 1e-38 or smaller for filter covariances, i.e. at once.  Two more deliberate deviations:
+ *   - the start point is feasible.  The reference starts the k-agent form from w_0 = 1 - k w > 1, w_i = w < 0, which NLopt
+ *     rejects, and then falls back to the NEGATIVE weight as a fixed one (ci.cpp:70-73): an indefinite S.  Here the start is
+ *     w_i = |w|, w_0 = 1 - k |w| (uniform if that is below 1e-4); pairwise (1 + w, -w) clamped into [1e-4, 1 - 1e-4].
+ *   - w = -1 (the reference's default, vio.cpp:191-192) is valid and means "search from no prior"; the result does not
+ *     depend on the start.
+ * A search that does not converge within 50 steps, or meets a sum_i w_i M_i or a covariance that is not positive definite,
+ * returns XK_ESINGULAR (text in xk_last_error); there is no silent fallback to |w| (ci.cpp:70-73,114-116).
+ * Limits of a searched entry: m <= 21 rows, at most 8 agents including the own one. */
+
+/* The search alone: k1 (2..8) symmetric positive definite m x m matrices M (host, k1 * m * m doubles, m <= 21), start point
+ * w_start (k1 weights >= 1e-4 that sum to one) or NULL = uniform; w (out, k1), *iters (out, may be NULL) = Newton steps taken. */
+int xk_ci_solve_weights(xk_handle *h, const double *M, int m, int k1, const double *w_start, double *w, int *iters);
+/* The weights of the last searched entry on this handle (also of xk_ci_solve_weights): w (out, 8; own agent first, unused
+ * ones zero), *k1 their number, *iters the Newton steps.  All zero before the first search. */
+int xk_ci_last_weights(const xk_handle *h, double *w, int *k1, int *iters);
 
 /* CovarianceIntersection::fuseCI, k-agent MSCKF form (src/x/ekf/ci.cpp:49-92):
  * S = (1/w0) H P H^T + sum_i (1/w) H_i P_i H_i^T, w0 = 1 - k w,
- * *w_result = 1/w0.  w outside (0,1] -> XK_EINVAL (the reference throws for
- * w>1, w==0, w<-1; the NLopt branch -1<=w<0 is out of scope). */
+ * *w_result = 1/w0.  Searched (w < 0): S = sum_i H_i P_i H_i^T / w_i with the searched per-agent weights,
+ * *w_result = 1/w_0 (ci.cpp:78-90). */
 int xk_fuse_ci_msckf(xk_handle *h, const double *P, int ldp, int n, const double *H, int ldh, int m,
                      int k, const double *const *Ps, const int *ns, const double *const *Hs,
                      double w_other, double *S, int lds, double *w_result);
 
 /* Pairwise SLAM form (ci.cpp:94-127): S = P_a/(1-w) + P_b/w in measurement
- * space, *w_result = 1/(1-w). */
+ * space, *w_result = 1/(1-w).  Searched (w < 0): the same with w = the searched second weight w_b (ci.cpp:117-122). */
 int xk_fuse_ci_slam(xk_handle *h, const double *Pa, int lda, int na, const double *Ha, int ldha,
                     const double *Pb, int ldb, int nb, const double *Hb, int ldhb, int m,
                     double w_other, double *S, int lds, double *w_result);

@@ -22,6 +22,7 @@
 #include "xk_linalg.hip.h"
 #include "xk_caqr_pipe.hip.h"
 #include "xk_ci.hip.h"
+#include "xk_ciw.hip.h"
 #include "xk_aux.hip.h"
 
 #define XK_VERSION_NUM 201
@@ -136,6 +137,11 @@ struct xk_handle {
   double *d_payload;
   double *d_ci;  // scratch for the CI kernels
   double *d_ciws;          // workspace of the device-resident CI round (lazily allocated)
+  // CI weight search (xk_ciw.hip.h): option "ci_weight_search"; d_ciw = [8 weights | 8 start | 2 info words | 8 M_i | 8 H_i P_i H_i^T]
+  int opt_ci_search;
+  double *d_ciw;
+  double ci_last_w[8];     // what xk_ci_last_weights hands out: the weights of the last searched entry,
+  int ci_last_k1, ci_last_iters;   // how many there were and the Newton steps they took
   hipStream_t ci_stream[8];   // ... and its side streams: shared track j >= 1 runs its stages before the gate on ci_stream[j],
   hipEvent_t ci_fork, ci_join[8];   // next to track 0 on the engine's stream (forked and joined with events)
   XkFeatBatch *d_batch;    // per-agent descriptors of the batched feature launch, [8 tracks][8 agents]
@@ -404,6 +410,7 @@ static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, x
   h->d_status = (int *)(h->h_out + h->n);
   HIPCHK(h, dalloc(&h->d_payload, (size_t)xk_payload_doubles(n_poses_max, n_feat_max)));
   HIPCHK(h, dalloc(&h->d_ci, (size_t)4 * nn + 64 * (size_t)h->n + 1024));
+  HIPCHK(h, dalloc(&h->d_ciw, (size_t)XK_CIW_WS));
   h->h_pin_doubles = nn + 8 * (size_t)h->n + 4 * (size_t)k_max + 4 * (size_t)n_feat_max + 1024;
   HIPCHK(h, hipHostMalloc((void **)&h->h_pin, sizeof(double) * h->h_pin_doubles));
   h->csr_cap = 24 * (size_t)h->n + 3 * (size_t)n_feat_max * h->n;
@@ -471,6 +478,7 @@ extern "C" int xk_destroy(xk_handle *h) {
   for (void *p3 : {(void *)h->d_x1, (void *)h->d_pdbg})
     if (p3) hipFree(p3);
   if (h->d_ciws) hipFree(h->d_ciws);
+  if (h->d_ciw) hipFree(h->d_ciw);
   if (h->d_batch) hipFree(h->d_batch);
   if (h->h_batch) hipHostFree(h->h_batch);
   if (h->h_ci_cols) hipHostFree(h->h_ci_cols);
@@ -2207,16 +2215,36 @@ extern "C" int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int s
 }
 
 // ---------------------------------------------------------------------------
-// covariance intersection (fixed weights)
+// covariance intersection: fixed weights, or searched ones (option "ci_weight_search", xk_ciw.hip.h)
 // ---------------------------------------------------------------------------
-static int check_w(double w) {  // ci.cpp:59-62,98-101 throw; -1<=w<0 is the NLopt branch (out of scope)
-  if (w > 1.0 || w == 0 || w < -1) return XK_EINVAL;
-  if (w < 0.0) return XK_EINVAL;
-  return XK_OK;
+// 0: a fixed weight; 1: -1 <= w < 0 with the search switched on (ci.cpp:65-73,105-119); -1: what ci.cpp:59-62,98-101 throw on,
+// and every negative weight while the search is off
+static int check_w(const xk_handle *h, double w) {
+  if (w > 1.0 || w == 0 || w < -1) return -1;
+  if (w < 0.0) return h->opt_ci_search ? 1 : -1;
+  return 0;
 }
 
-// S (device, m x m row-major ld m in d_tmpS) (+)= alpha * Hd (m x nn col-major) * Pd (nn x nn) * Hd^T
-static void hpht_accum(xk_handle *h, const double *Hd, const double *Pd, int m, int nn, double alpha, bool first) {
+// the entry's device-side weights, the start point of a search, its two result words, and per agent M_i and H_i P_i H_i^T
+static double *ciw_M(xk_handle *h, int i) { return h->d_ciw + 24 + (size_t)i * 576; }
+static double *ciw_T(xk_handle *h, int i) { return h->d_ciw + 24 + (size_t)(XK_CIW_MAXK1 + i) * 576; }
+
+static void ciw_set(xk_handle *h, double *slot, const double *v, int k1) {
+  XkCiwSetArgs s;
+  s.w = slot;
+  for (int i = 0; i < XK_CIW_MAXK1; ++i) s.v[i] = i < k1 ? v[i] : 0.0;
+  hipLaunchKernelGGL(xk_ciw_set, dim3(1), dim3(64), 0, h->stream, s);
+}
+
+// S (m x m in Sd) (+)= T / w_i with the weights of the entry's device slots (xk_ciw_sum)
+static void ciw_sum(xk_handle *h, const double *T, double *Sd, int m, int i, bool pair, bool first, bool add_diag, double diag,
+                    double *d_w_result) {
+  XkCiwSumArgs s{T, Sd, m, first ? 1 : 0, i, pair ? 1 : 0, add_diag ? 1 : 0, diag, h->d_ciw, d_w_result};
+  hipLaunchKernelGGL(xk_ciw_sum, dim3((m * m + 255) / 256), dim3(256), 0, h->stream, s);
+}
+
+// T (device, m x m, ld m) = Hd (m x nn col-major) * Pd (nn x nn) * Hd^T
+static void hpht(xk_handle *h, const double *Hd, const double *Pd, int m, int nn, double *T) {
   XkGemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = Hd; g.sar = 1; g.sac = m;
@@ -2227,35 +2255,148 @@ static void hpht_accum(xk_handle *h, const double *Hd, const double *Pd, int m, 
   memset(&g, 0, sizeof(g));
   g.A = h->d_Maug; g.sar = nn; g.sac = 1;
   g.B = Hd; g.sbr = m; g.sbc = 1;  // B[k][j] = H[j][k]
-  g.C = h->d_tmpS; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
-  g.M = m; g.N = m; g.K = nn; g.alpha = alpha; g.beta = first ? 0.0 : 1.0;
+  g.C = T; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
+  g.M = m; g.N = m; g.K = nn; g.alpha = 1.0; g.beta = 0.0;
   gemm(h, g);
+}
+
+// Information projection M = Hd Pd^-1 Hd^T (m x m, ld m) with the Kalman stage's factorisation: the system is [P | H^T],
+// xk_chol_whole per 192-row slab with the Schur-complement GEMM between slabs (launch_update), X = L^-1 H^T, M = X^T X.
+// ONE factorisation of Pd serves all m right-hand sides.  A pivot that is not positive sets the handle's status word.
+static int ci_info(xk_handle *h, const double *Hd, const double *Pd, int m, int nn, double *Mout) {
+  const int LDA = h->LDA, c = nn, ncols = nn + m;
+  if (nn > h->CM || ncols > LDA) return fail(h, XK_ECAPACITY, "CI weight search: covariance exceeds the workspace");
+  XkCopyArgs cp{Pd, h->d_Maug, nn, nn, 1, (long)nn, (long)LDA, 1};
+  hipLaunchKernelGGL(xk_copy2d, dim3((nn * nn + 255) / 256), dim3(256), 0, h->stream, cp);
+  XkCopyArgs ch{Hd, h->d_Maug + nn, nn, m, (long)m, 1, (long)LDA, 1};        // row r of the right-hand sides = column r of H
+  hipLaunchKernelGGL(xk_copy2d, dim3((nn * m + 255) / 256), dim3(256), 0, h->stream, ch);
+  const int B = 16 * XK_CHOLW_MAXB;
+  for (int off = 0; off < c;) {
+    const int cb = std::min(B, c - off);
+    XkCholWholeArgs d;
+    d.Maug = h->d_Maug + (size_t)off * LDA + off; d.ld = LDA; d.c = cb; d.ncols = ncols - off;
+    d.X = h->d_X + (size_t)off * LDA + off; d.status = h->d_status;
+#ifdef XK_CHOLW_PROBE
+    d.dbg = nullptr;
+#endif
+    xk_cholw_table((cb + 15) / 16, d.tab);
+    hipLaunchKernelGGL(xk_chol_whole, dim3((ncols - off - cb + 15) / 16), dim3(64 * XK_CHOLW_WAVES), 0, h->stream, d);
+    off += cb;
+    if (off < c) {
+      XkGemmArgs s;
+      memset(&s, 0, sizeof(s));
+      const double *Xs = h->d_X + (size_t)(off - cb) * LDA + off;
+      s.A = Xs; s.sar = 1; s.sac = LDA;
+      s.B = Xs; s.sbr = LDA; s.sbc = 1;
+      s.C = h->d_Maug + (size_t)off * LDA + off; s.scr = LDA; s.scc = 1;
+      s.D = s.C; s.sdr = LDA; s.sdc = 1;
+      s.M = c - off; s.N = ncols - off; s.K = cb; s.alpha = -1.0; s.beta = 1.0; s.mode = 0;
+      s.sym_cols = c - off;
+      gemm(h, s);
+    }
+  }
+  XkGemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = h->d_X + nn; g.sar = 1; g.sac = LDA;       // A[i][k] = X[k][nn + i]
+  g.B = h->d_X + nn; g.sbr = LDA; g.sbc = 1;       // B[k][j] = X[k][nn + j]
+  g.C = Mout; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
+  g.M = m; g.N = m; g.K = nn; g.alpha = 1.0; g.beta = 0.0;
+  gemm(h, g);
+  return XK_OK;
+}
+
+// after the stream has been synchronised: did a factorisation of ci_info meet a pivot that is not positive?
+static int ciw_chol_status(xk_handle *h) {
+  if (h->d_status[0] == 0) return XK_OK;
+  h->d_status[0] = 0;
+  return fail(h, XK_ESINGULAR, "CI weight search: a covariance is not positive definite");
+}
+
+// queue the search over the k1 matrices in ciw_M (stride mstride); start = null: from the uniform point
+static void ciw_solve(xk_handle *h, int m, int k1, int mstride, const double *start) {
+  if (start) ciw_set(h, h->d_ciw + 8, start, k1);
+  XkCiwArgs a{ciw_M(h, 0), 0, mstride, m, k1, start ? h->d_ciw + 8 : nullptr, h->d_ciw, (int *)(h->d_ciw + 16), nullptr};
+  hipLaunchKernelGGL(xk_ci_weights, dim3(1), dim3(XK_CIW_THREADS), 0, h->stream, a);
+}
+
+// fetch the searched weights (synchronises), check both failure words, remember them for xk_ci_last_weights
+static int ciw_fetch(xk_handle *h, int k1, double *w) {
+  double buf[17];
+  HIPCHK(h, hipMemcpyAsync(buf, h->d_ciw, sizeof(buf), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = ciw_chol_status(h)) return rc;
+  int info[2];
+  memcpy(info, buf + 16, sizeof(info));
+  if (info[1] != 0)
+    return fail(h, XK_ESINGULAR, info[0] >= XK_CIW_MAXIT ? "CI weight search: no convergence within 50 Newton steps"
+                                                           : "CI weight search: sum w_i M_i is not positive definite");
+  for (int i = 0; i < 8; ++i) h->ci_last_w[i] = i < k1 ? buf[i] : 0.0;
+  h->ci_last_k1 = k1;
+  h->ci_last_iters = info[0];
+  if (w) memcpy(w, buf, sizeof(double) * k1);
+  return XK_OK;
+}
+
+// start points of the two forms.  The reference's own (ci.cpp:66-67,109-110) are infeasible for k agents resp. for w = -1 and make
+// NLopt give up; these are feasible, and the result does not depend on them.
+static void ciw_start_pair(double w, double *st) {
+  st[1] = std::min(std::max(-w, XK_CIW_LB), 1.0 - XK_CIW_LB);
+  st[0] = 1.0 - st[1];
+}
+static const double *ciw_start_multi(double w, int k, double *st) {
+  const double wo = -w, w0 = 1.0 - k * wo;
+  if (!(wo >= XK_CIW_LB) || !(w0 >= XK_CIW_LB)) return nullptr;      // uniform
+  st[0] = w0;
+  for (int i = 1; i <= k; ++i) st[i] = wo;
+  return st;
 }
 
 extern "C" int xk_fuse_ci_msckf(xk_handle *h, const double *P, int ldp, int n, const double *H, int ldh, int m,
                                 int k, const double *const *Ps, const int *ns, const double *const *Hs,
                                 double w_other, double *S, int lds, double *w_result) {
   if (!h || !P || !H || !S || !w_result || k < 0 || m <= 0 || ldp < n || ldh < m || lds < m) return XK_EINVAL;
-  if (check_w(w_other) != XK_OK) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
+  const int srch = check_w(h, w_other);
+  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
   if (n > h->n || m > h->CM) return fail(h, XK_ECAPACITY, "fuse_ci dims exceed workspace");
+  if (srch && k < 1) return fail(h, XK_EINVAL, "CI weight search: no other agent");
+  if (srch && (m > XK_CIW_MAXM || k + 1 > XK_CIW_MAXK1)) return fail(h, XK_ECAPACITY, "CI weight search: at most 21 rows and 7 other agents");
   HIPCHK(h, hipSetDevice(h->device));
   const double w0 = 1.0 - (double)k * w_other;
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, H, sizeof(double) * ldh, sizeof(double) * m, n,
-                             hipMemcpyHostToDevice, h->stream));
-  hpht_accum(h, h->d_tmpH, h->d_tmpP, m, n, 1.0 / w0, true);
-  for (int i = 0; i < k; ++i) {
-    if (ns[i] > h->n) return fail(h, XK_ECAPACITY, "other agent's state larger than workspace");
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_tmpP, Ps[i], sizeof(double) * (size_t)ns[i] * ns[i], hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_tmpH, Hs[i], sizeof(double) * (size_t)m * ns[i], hipMemcpyHostToDevice, h->stream));
-    hpht_accum(h, h->d_tmpH, h->d_tmpP, m, ns[i], 1.0 / w_other, false);
+  if (!srch) {
+    const double v[2] = {w0, w_other};                                 // (every other agent has the same fixed weight: slot 1)
+    ciw_set(h, h->d_ciw, v, 2);
+  }
+  for (int i = 0; i <= k; ++i) {
+    const int n_i = i ? ns[i - 1] : n;
+    if (n_i > h->n) return fail(h, XK_ECAPACITY, "other agent's state larger than workspace");
+    if (i) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->d_tmpP, Ps[i - 1], sizeof(double) * (size_t)n_i * n_i, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->d_tmpH, Hs[i - 1], sizeof(double) * (size_t)m * n_i, hipMemcpyHostToDevice, h->stream));
+    } else {
+      HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
+                                 hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, H, sizeof(double) * ldh, sizeof(double) * m, n,
+                                 hipMemcpyHostToDevice, h->stream));
+    }
+    // fixed weights: the term joins the sum at once; searched: H_i P_i H_i^T and M_i are kept until the weights are known
+    double *T = srch ? ciw_T(h, i) : h->d_X;
+    hpht(h, h->d_tmpH, h->d_tmpP, m, n_i, T);
+    if (!srch) ciw_sum(h, T, h->d_tmpS, m, i ? 1 : 0, false, i == 0, false, 0.0, nullptr);
+    else if (int rc = ci_info(h, h->d_tmpH, h->d_tmpP, m, n_i, ciw_M(h, i))) return rc;
+  }
+  double wr = 1.0 / w0;
+  if (srch) {
+    double st[XK_CIW_MAXK1], w[XK_CIW_MAXK1];
+    ciw_solve(h, m, k + 1, 576, ciw_start_multi(w_other, k, st));
+    if (int rc = ciw_fetch(h, k + 1, w)) return rc;
+    for (int i = 0; i <= k; ++i) ciw_sum(h, ciw_T(h, i), h->d_tmpS, m, i, false, i == 0, false, 0.0, nullptr);
+    wr = 1.0 / w[0];                                                   // ci.cpp:78-90 with the searched w_0
   }
   HIPCHK(h, hipMemcpy2DAsync(S, sizeof(double) * lds, h->d_tmpS, sizeof(double) * m, sizeof(double) * m, m,
                              hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  *w_result = 1.0 / w0;
+  *w_result = wr;
   return XK_OK;
 }
 
@@ -2265,25 +2406,41 @@ extern "C" int xk_fuse_ci_slam(xk_handle *h, const double *Pa, int lda, int na, 
   if (!h || !Pa || !Ha || !Pb || !Hb || !S || !w_result || m <= 0 || lda < na || ldb < nb || ldha < m || ldhb < m ||
       lds < m)
     return XK_EINVAL;
-  if (check_w(w_other) != XK_OK)
-    return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger than 0.0");
+  const int srch = check_w(h, w_other);
+  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger than 0.0");
   if (na > h->n || nb > h->n || m > h->CM) return fail(h, XK_ECAPACITY, "fuse_ci dims exceed workspace");
+  if (srch && m > XK_CIW_MAXM) return fail(h, XK_ECAPACITY, "CI weight search: at most 21 rows");
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * na, Pa, sizeof(double) * lda, sizeof(double) * na, na,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, Ha, sizeof(double) * ldha, sizeof(double) * m, na,
-                             hipMemcpyHostToDevice, h->stream));
-  hpht_accum(h, h->d_tmpH, h->d_tmpP, m, na, 1.0 / (1.0 - w_other), true);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * nb, Pb, sizeof(double) * ldb, sizeof(double) * nb, nb,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, Hb, sizeof(double) * ldhb, sizeof(double) * m, nb,
-                             hipMemcpyHostToDevice, h->stream));
-  hpht_accum(h, h->d_tmpH, h->d_tmpP, m, nb, 1.0 / w_other, false);
+  if (!srch) {
+    const double v[2] = {1.0 - w_other, w_other};
+    ciw_set(h, h->d_ciw, v, 2);
+  }
+  for (int i = 0; i < 2; ++i) {
+    const double *Pi = i ? Pb : Pa, *Hi = i ? Hb : Ha;
+    const int n_i = i ? nb : na, ldp_i = i ? ldb : lda, ldh_i = i ? ldhb : ldha;
+    if (i) HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n_i, Pi, sizeof(double) * ldp_i, sizeof(double) * n_i, n_i,
+                               hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, Hi, sizeof(double) * ldh_i, sizeof(double) * m, n_i,
+                               hipMemcpyHostToDevice, h->stream));
+    double *T = srch ? ciw_T(h, i) : h->d_X;
+    hpht(h, h->d_tmpH, h->d_tmpP, m, n_i, T);
+    if (!srch) ciw_sum(h, T, h->d_tmpS, m, i, true, i == 0, false, 0.0, nullptr);
+    else if (int rc = ci_info(h, h->d_tmpH, h->d_tmpP, m, n_i, ciw_M(h, i))) return rc;
+  }
+  double wr = 1.0 / (1.0 - w_other);
+  if (srch) {
+    double st[2], w[2];
+    ciw_start_pair(w_other, st);
+    ciw_solve(h, m, 2, 576, st);
+    if (int rc = ciw_fetch(h, 2, w)) return rc;
+    for (int i = 0; i < 2; ++i) ciw_sum(h, ciw_T(h, i), h->d_tmpS, m, i, true, i == 0, false, 0.0, nullptr);
+    wr = 1.0 / (1.0 - w[1]);                                           // ci.cpp:117-122 with the searched w_b
+  }
   HIPCHK(h, hipMemcpy2DAsync(S, sizeof(double) * lds, h->d_tmpS, sizeof(double) * m, sizeof(double) * m, m,
                              hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  *w_result = 1.0 / (1.0 - w_other);
+  *w_result = wr;
   return XK_OK;
 }
 
@@ -2304,16 +2461,17 @@ extern "C" int xk_multi_slam_match(xk_handle *h, const double *C_q_G, const doub
       o_anchor_idx < 0 || o_anchor_idx >= o_n_poses)
     return XK_EINVAL;
   if (feat[3 * feature_id + 2] == 0) return fail(h, XK_EINVAL, "rho = 0");  // throws, :86-88
-  if (check_w(ci_slam_w) != XK_OK)
-    return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger than 0.0");
+  const int srch = check_w(h, ci_slam_w);
+  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger than 0.0");
   if (no > h->n || n_poses > h->N || o_n_poses > h->N) return fail(h, XK_ECAPACITY, "match dims exceed workspace");
   HIPCHK(h, hipSetDevice(h->device));
   // scratch layout in d_ci
   double *d = h->d_ci;
   double *dq = d, *dp = dq + 4 * h->N, *df = dp + 3 * h->N, *doq = df + 3 * (Mf > 0 ? Mf : 1);
   double *dop = doq + 4 * h->N, *dof = dop + 3 * h->N, *dH = dof + 3 * (oMf > 0 ? oMf : 1);
-  double *dout = dH + 3 * (size_t)n, *dcols_f = dout + 16;
+  double *dout = dH + 3 * (size_t)n, *dcols_f = dout + 16, *doH = dcols_f + 2;
   int *dcols = (int *)dcols_f;
+  double *doP = h->d_ci + 64 * (size_t)h->n + 1024;   // (the lists above end long before: < 11 n + 64 doubles)
   HIPCHK(h, hipMemcpyAsync(dq, C_q_G, sizeof(double) * 4 * n_poses, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dp, G_p_C, sizeof(double) * 3 * n_poses, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(df, feat, sizeof(double) * 3 * Mf, hipMemcpyHostToDevice, h->stream));
@@ -2322,14 +2480,31 @@ extern "C" int xk_multi_slam_match(xk_handle *h, const double *C_q_G, const doub
   HIPCHK(h, hipMemcpyAsync(dof, o_feat, sizeof(double) * 3 * oMf, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
                              hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_Maug, sizeof(double) * no, o_P, sizeof(double) * ldop, sizeof(double) * no, no,
+  HIPCHK(h, hipMemcpy2DAsync(doP, sizeof(double) * no, o_P, sizeof(double) * ldop, sizeof(double) * no, no,
                              hipMemcpyHostToDevice, h->stream));
   XkSlamMatchArgs a;
   a.q = dq; a.p = dp; a.feat = df; a.P = h->d_tmpP; a.anchor = anchor_idx; a.fid = feature_id; a.n = n; a.npm = n_poses_max;
-  a.oq = doq; a.op = dop; a.ofeat = dof; a.oP = h->d_Maug; a.oanchor = o_anchor_idx; a.ofid = o_feature_id; a.no = no;
+  a.oq = doq; a.op = dop; a.ofeat = dof; a.oP = doP; a.oanchor = o_anchor_idx; a.ofid = o_feature_id; a.no = no;
   a.onpm = o_n_poses_max;
-  a.var_l = sigma_landmark * sigma_landmark; a.w = ci_slam_w; a.chi = XK_CHI2_090[3];
-  a.H = dH; a.out = dout; a.cols = dcols;
+  a.var_l = sigma_landmark * sigma_landmark; a.w = h->d_ciw; a.chi = XK_CHI2_090[3];
+  a.H = dH; a.out = dout; a.cols = dcols; a.oH = nullptr; a.gate_only = 0;
+  if (!srch) {
+    const double v[2] = {1.0 - ci_slam_w, ci_slam_w};
+    ciw_set(h, h->d_ciw, v, 2);
+  } else {
+    // the Jacobians and the gate first (neither depends on the weights, multi_slam_update.cpp:216-220 precedes :222), then the two
+    // information projections and the search; the launch below reads the searched w_b
+    a.oH = doH; a.gate_only = 1;
+    hipLaunchKernelGGL(xk_slam_match, dim3(1), dim3(64), 0, h->stream, a);
+    a.oH = nullptr; a.gate_only = 0;
+    int rc = ci_info(h, dH, h->d_tmpP, 3, n, ciw_M(h, 0));
+    if (rc == XK_OK) rc = ci_info(h, doH, doP, 3, no, ciw_M(h, 1));
+    if (rc != XK_OK) return rc;
+    double st[2];
+    ciw_start_pair(ci_slam_w, st);
+    ciw_solve(h, 3, 2, 576, st);
+    if ((rc = ciw_fetch(h, 2, nullptr)) != XK_OK) return rc;
+  }
   hipLaunchKernelGGL(xk_slam_match, dim3(1), dim3(64), 0, h->stream, a);
   XkScaleArgs sc{h->d_tmpP, h->d_Pout, n, 3, dcols, dout + 14};
   hipLaunchKernelGGL(xk_scale_blocks, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, sc);
@@ -2366,8 +2541,8 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
   if (k > 0 && (!m_obs || !m_L || !m_q || !m_p || !m_nposes || !m_P || !m_n || !H || !res || !S || !P_j || !ci_gamma ||
                 ldh < 3 * k || lds < 3 * k || ldpj < n))
     return XK_EINVAL;
-  if (k > 0 && check_w(ci_msckf_w) != XK_OK)
-    return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
+  const int srch = k > 0 ? check_w(h, ci_msckf_w) : 0;
+  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
   int Ltot = L, nmax = n;
   for (int i = 0; i < k; ++i) {
     if (m_L[i] < 2 || m_L[i] > m_nposes[i] || m_nposes[i] > 64 || m_n[i] < XK_CORE + 6 * m_nposes[i]) return XK_EINVAL;
@@ -2462,26 +2637,42 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
     g.C = h->d_Maug; g.scr = n_i; g.scc = 1; g.D = g.C; g.sdr = n_i; g.sdc = 1;
     g.M = m; g.N = n_i; g.K = n_i; g.alpha = 1.0; g.beta = 0.0;
     gemm(h, g);  // W = H_i P_i
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = 0; pass < 2; ++pass) {  // 0: the gate's sum (weights play no part in it); 1: H_i P_i H_i^T on its own, weighted below
       memset(&g, 0, sizeof(g));
       g.A = h->d_Maug; g.sar = n_i; g.sac = 1; g.B = pa.H[i]; g.sbr = m; g.sbc = 1;
-      g.C = pass ? S2 : S1; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
+      g.C = pass ? ciw_T(h, i) : S1; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
       g.M = m; g.N = m; g.K = n_i;
-      g.alpha = pass ? (i == 0 ? 1.0 / w0 : 1.0 / ci_msckf_w) : 1.0;
-      g.beta = (i == 0) ? 0.0 : 1.0;
-      g.mode = (i == k) ? 1 : 0;            // noise once, on the last term
+      g.alpha = 1.0;
+      g.beta = (i == 0 || pass) ? 0.0 : 1.0;
+      g.mode = (i == k && !pass) ? 1 : 0;   // noise once, on the last term
       g.diag = nullptr; g.diag_scalar = var_img;
       gemm(h, g);
     }
+    // searched weights: M_i = H_i P_i^-1 H_i^T while P_i is on the device -- one factorisation per agent
+    if (srch)
+      if (int rc = ci_info(h, pa.H[i], aP, m, n_i, ciw_M(h, i))) return rc;
   }
   hipLaunchKernelGGL(xk_small_gamma, dim3(1), dim3(1), 0, h->stream, S1, dres, m, dscal);
   double g_ci = 0;
   HIPCHK(h, hipMemcpyAsync(&g_ci, dscal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (srch)
+    if (int rc = ciw_chol_status(h)) return rc;
   *ci_gamma = g_ci;
   const int dof = 2 * Ltot - 3;
   if (dof >= XK_CHI2_LEN) return fail(h, XK_ECAPACITY, "chi-square table too short");
   if (!(g_ci < XK_CHI2_095[dof])) return XK_OK;   // :243-250
+  // the CI-weighted S (ci.cpp:78-85 + :255): the weights sit in the entry's device slots, the host's constants or the searched ones
+  if (!srch) {
+    double v[XK_CIW_MAXK1] = {w0};
+    for (int i = 1; i <= k; ++i) v[i] = ci_msckf_w;
+    ciw_set(h, h->d_ciw, v, k1);
+  } else {
+    double st[XK_CIW_MAXK1];
+    ciw_solve(h, m, k1, 576, ciw_start_multi(ci_msckf_w, k, st));
+    if (int rc = ciw_fetch(h, k1, nullptr)) return rc;
+  }
+  for (int i = 0; i < k1; ++i) ciw_sum(h, ciw_T(h, i), S2, m, i, false, i == 0, i == k, var_img, i == 0 ? dscal + 1 : nullptr);
   // P_j: diagonal 3x3 blocks of the L observed poses scaled by w_result = 1/w0 (:256-267)
   std::vector<int> cols(2 * L);
   for (int i = 0; i < L; ++i) {
@@ -2489,10 +2680,8 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
     cols[2 * i] = XK_CORE + 3 * pos;
     cols[2 * i + 1] = XK_CORE + 3 * pos + 3 * n_poses_max;
   }
-  const double wres = 1.0 / w0;
-  int *dcols = dint + 16;
+  int *dcols = dint + 16;   // (dscal[1] = w_result = 1 / w_0 was left there by xk_ciw_sum)
   HIPCHK(h, hipMemcpyAsync(dcols, cols.data(), sizeof(int) * 2 * L, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dscal + 1, &wres, sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n, hipMemcpyHostToDevice, h->stream));
   XkScaleArgs sc{h->d_tmpP, h->d_Pout, n, 2 * L, dcols, dscal + 1};
   hipLaunchKernelGGL(xk_scale_blocks, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, sc);
@@ -2502,6 +2691,34 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
   HIPCHK(h, hipMemcpy2DAsync(P_j, sizeof(double) * ldpj, h->d_Pout, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *has_ci = 1;
+  return XK_OK;
+}
+
+// The search alone, on matrices the caller supplies (include/xk.h).
+extern "C" int xk_ci_solve_weights(xk_handle *h, const double *M, int m, int k1, const double *w_start, double *w, int *iters) {
+  if (!h || !M || !w) return XK_EINVAL;
+  if (m < 1 || m > XK_CIW_MAXM || k1 < 2 || k1 > XK_CIW_MAXK1) return fail(h, XK_EINVAL, "xk_ci_solve_weights: 1 <= m <= 21, 2 <= k1 <= 8");
+  if (w_start) {
+    double sum = 0.0;
+    for (int i = 0; i < k1; ++i) {
+      if (!(w_start[i] >= XK_CIW_LB)) return fail(h, XK_EINVAL, "xk_ci_solve_weights: every start weight must be at least 1e-4");
+      sum += w_start[i];
+    }
+    if (!(fabs(sum - 1.0) <= 1e-12)) return fail(h, XK_EINVAL, "xk_ci_solve_weights: the start weights must sum to one");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(ciw_M(h, 0), M, sizeof(double) * (size_t)k1 * m * m, hipMemcpyHostToDevice, h->stream));
+  ciw_solve(h, m, k1, m * m, w_start);
+  if (int rc = ciw_fetch(h, k1, w)) return rc;
+  if (iters) *iters = h->ci_last_iters;
+  return XK_OK;
+}
+
+extern "C" int xk_ci_last_weights(const xk_handle *h, double *w, int *k1, int *iters) {
+  if (!h || !w) return XK_EINVAL;
+  for (int i = 0; i < 8; ++i) w[i] = h->ci_last_w[i];
+  if (k1) *k1 = h->ci_last_k1;
+  if (iters) *iters = h->ci_last_iters;
   return XK_OK;
 }
 
@@ -2591,7 +2808,9 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
   if (self_rank < 0 || self_rank >= world || n_tracks < 0 || n_tracks > 8) return XK_EINVAL;
   if (payload_stride != xk_payload_doubles(N, h->Mmax)) return fail(h, XK_EINVAL, "payload layout differs from this handle's (N, M)");
   if (h->n_poses < 2) return fail(h, XK_EINVAL, "window not staged");
-  if (check_w(ci_msckf_w) != XK_OK) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
+  if (const int cw = check_w(h, ci_msckf_w))
+    return fail(h, XK_EINVAL, cw > 0 ? "xk_ci_round_device takes fixed weights only: the weight search is built into xk_msckf_ci_track, not into the device round"
+                                     : "The CI weights must be lower than 1.0 and larger 0.0");
   if (m > h->CM) return fail(h, XK_ECAPACITY, "m exceeds the dense workspace");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t upsz = 3 * (size_t)n + 16;
@@ -2956,6 +3175,10 @@ extern "C" int xk_set_option(xk_handle *h, const char *name, int value) {
   else if (!strcmp(name, "caqr_rearm")) h->rearm_after = value;
   else if (!strcmp(name, "caqr_tail")) h->opt_tail = value;
   else if (!strcmp(name, "slam_split")) h->opt_slam_split = value;
+  else if (!strcmp(name, "ci_weight_search")) {
+    if (value != 0 && value != 1) return fail(h, XK_EINVAL, "xk_set_option: ci_weight_search is 0 or 1");
+    h->opt_ci_search = value;
+  }
 #ifdef XK_LAB
   // test hooks and A/B switches (include/xk_lab.h)
   else if (!strcmp(name, "caqr_poison")) h->opt_poison = value;

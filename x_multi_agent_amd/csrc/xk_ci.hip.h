@@ -15,7 +15,10 @@ struct XkSlamMatchArgs {
   // other side
   const double *oq, *op, *ofeat, *oP;
   int oanchor, ofid, no, onpm;
-  double var_l, w, chi;  // sigma_landmark^2, ci_slam_w, chi2_3(0.9)
+  double var_l, chi;     // sigma_landmark^2, chi2_3(0.9)
+  const double *w;       // device: the entry's weights (1 - w_b, w_b) -- the host's ci_slam_w or the searched pair (xk_ciw.hip.h)
+  int gate_only;         // 1: Jacobians, residual and gate only (the first launch of a searched entry; S waits for the weights)
+  double *oH;            // optional: the other side's Jacobian, 3 x no column-major (the search projects it)
   // outputs
   double *H;    // 3 x n column-major (ld 3)
   double *out;  // [0..2] res, [3..11] S (col-major 3x3), [12] gamma, [13] inlier, [14] w_result
@@ -56,8 +59,8 @@ __device__ inline void xk_hPht(const double *P, int n, const int cols[3], const 
 }
 
 __global__ __launch_bounds__(64) void xk_slam_match(XkSlamMatchArgs a) {
-  __shared__ double blk[3][3][3];
-  __shared__ int cols[3];
+  __shared__ double blk[3][3][3], oblk_s[3][3][3];
+  __shared__ int cols[3], ocol[3];
   const int lane = threadIdx.x;
   if (lane == 0) {
     double gpf[3], ogpf[3], oblk[3][3][3], mb[3][3][3];
@@ -82,21 +85,40 @@ __global__ __launch_bounds__(64) void xk_slam_match(XkSlamMatchArgs a) {
       for (int y = 0; y < 3; ++y) g += res[x] * inv[x + 3 * y] * res[y];
     const bool inl = g < a.chi;  // :216-220
     // fuseCI pairwise (ci.cpp:120-122) + noise (:226)
-    const double wr = 1.0 / (1.0 - a.w);
-    for (int i = 0; i < 9; ++i) a.out[3 + i] = wr * Pa[i] + (1.0 / a.w) * Pb[i];
-    a.out[3] += a.var_l; a.out[7] += a.var_l; a.out[11] += a.var_l;
+    if (!a.gate_only) {
+      const double wb = a.w[1], wr = 1.0 / (1.0 - wb);
+      for (int i = 0; i < 9; ++i) a.out[3 + i] = wr * Pa[i] + (1.0 / wb) * Pb[i];
+      a.out[3] += a.var_l; a.out[7] += a.var_l; a.out[11] += a.var_l;
+      a.out[14] = wr;
+    }
     for (int k = 0; k < 3; ++k) a.out[k] = res[k];
     a.out[12] = g;
     a.out[13] = inl ? 1.0 : 0.0;
-    a.out[14] = wr;
     for (int b = 0; b < 3; ++b) {
       cols[b] = mc[b];
       a.cols[b] = mc[b];
       for (int x = 0; x < 3; ++x)
         for (int y = 0; y < 3; ++y) blk[b][x][y] = mb[b][x][y];
     }
+    if (a.oH) {
+      for (int b = 0; b < 3; ++b) {
+        ocol[b] = ocols[b];
+        for (int x = 0; x < 3; ++x)
+          for (int y = 0; y < 3; ++y) oblk_s[b][x][y] = oblk[b][x][y];
+      }
+    }
   }
   __syncthreads();
+  if (a.oH)
+    for (int c = lane; c < a.no; c += 64) {
+      double v[3] = {0, 0, 0};
+      for (int b = 0; b < 3; ++b)
+        if (c >= ocol[b] && c < ocol[b] + 3)
+          for (int x = 0; x < 3; ++x) v[x] = oblk_s[b][x][c - ocol[b]];
+      a.oH[3 * (size_t)c] = v[0];
+      a.oH[3 * (size_t)c + 1] = v[1];
+      a.oH[3 * (size_t)c + 2] = v[2];
+    }
   for (int c = lane; c < a.n; c += 64) {
     double v[3] = {0, 0, 0};
     for (int b = 0; b < 3; ++b)

@@ -28,7 +28,7 @@ SYMBOLS = [
     "xk_stage_window", "xk_stage_tracks", "xk_stage_tracks_begin", "xk_stage_tracks_end", "xk_stage_slam", "xk_upload_P", "xk_download_P",
     "xk_msckf_build", "xk_qr_compress", "xk_apply_update", "xk_visual_update_staged", "xk_visual_update",
     "xk_apply_update_dense", "xk_apply_ci", "xk_fuse_ci_msckf", "xk_fuse_ci_slam", "xk_multi_slam_match", "xk_msckf_ci_track",
-    "xk_ci_round_device", "xk_cov_congruence", "xk_cov_propagate",
+    "xk_ci_round_device", "xk_ci_solve_weights", "xk_ci_last_weights", "xk_cov_congruence", "xk_cov_propagate",
     "xk_stage_msckf_slam", "xk_msckf_slam_results", "xk_init_msckf_slam_features", "xk_init_standard_slam_features",
     "xk_payload_doubles", "xk_pack_payload", "xk_bench_staged", "xk_run_steps",
     "xk_apply_ci_resident", "xk_snapshot_P", "xk_caqr_status", "xk_set_option", "xk_build_compress_async", "xk_build_compress_update_async", "xk_build_compress_update_pass_async", "xk_fetch_flags",
@@ -301,6 +301,25 @@ class Engine:
                                           S.ctypes.data_as(c_dp), C.c_int(m), C.byref(wr)), "xk_fuse_ci_msckf")
         return np.ascontiguousarray(S), wr.value
 
+    def ci_solve_weights(self, Ms, w_start=None):
+        """xk_ci_solve_weights: argmin -log det(sum w_i M_i) over sum w = 1, w_i >= 1e-4 -> (w, Newton steps)."""
+        Ms = np.ascontiguousarray(Ms, dtype=np.float64)
+        k1, m = Ms.shape[0], Ms.shape[1]
+        w = np.zeros(k1)
+        it = C.c_int()
+        st = None if w_start is None else _d(w_start)
+        self._chk(self.L.xk_ci_solve_weights(self.h, Ms.ctypes.data_as(c_dp), C.c_int(m), C.c_int(k1),
+                                             st[1] if st else None, w.ctypes.data_as(c_dp), C.byref(it)),
+                  "xk_ci_solve_weights")
+        return w, it.value
+
+    def ci_last_weights(self):
+        """xk_ci_last_weights: (weights of the last searched CI entry, own agent first; Newton steps)."""
+        w = np.zeros(8)
+        k1, it = C.c_int(), C.c_int()
+        self._chk(self.L.xk_ci_last_weights(self.h, w.ctypes.data_as(c_dp), C.byref(k1), C.byref(it)), "xk_ci_last_weights")
+        return w[:k1.value].copy(), it.value
+
     def multi_slam_match(self, C_q_G, G_p_C, feat, anchor_idx, feature_id, P, n_poses_max, o_C_q_G, o_G_p_C,
                          o_feat, o_anchor_idx, o_feature_id, o_P, o_n_poses_max, sigma_landmark, ci_slam_w):
         n, no = P.shape[0], o_P.shape[0]
@@ -447,7 +466,7 @@ class Engine:
         return dict(schedule=v[0].value, armed=bool(v[1].value), giveups=v[2].value, last_reason=v[3].value)
 
     def set_option(self, name, value):
-        """xk_set_option: "caqr_resident", "caqr_rearm" (release library); the lab build (Engine(..., lab=True)) adds the test hooks and
+        """xk_set_option: "caqr_resident", "caqr_rearm", "ci_weight_search" (release library); the lab build (Engine(..., lab=True)) adds the test hooks and
         A/B switches "caqr_poison", "caqr_test_stall", "caqr_tall26", "pipe_kalman" (include/xk_lab.h)."""
         self._chk(self.L.xk_set_option(self.h, name.encode(), C.c_int(int(value))), "xk_set_option")
 
