@@ -167,6 +167,7 @@ struct Agent {
       HIPOK(hipStreamSynchronize(stream));
       for (int j = 0; j < n_shared; ++j) tl[n_shared + j] = (int)len[j];
       nv[0] = N; nv[1] = (int)hdr8[5];
+      if (ci_w < 0) xkok(h, xk_set_option(h, "ci_weight_search", 1), "xk_set_option");   // a negative weight asks for the searched weights
       xkok(h, xk_ci_round_device(h, d_ci_pay, pay_n, 2, 0, d_ci_trk, n_shared, tl.data(), nv.data(), self.data(), sigma_img, ci_w,
                                  &n_fused, nullptr), "xk_ci_round_device");
     }

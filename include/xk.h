@@ -145,8 +145,7 @@ int xk_apply_ci(xk_handle *h, double *P_out, int ldp, const double *ci_P, int ld
  *   0 < w <= 1     fixed weights.
  *   w > 1, w == 0, w < -1   XK_EINVAL (the reference throws, ci.cpp:59-62,98-101).
  *   -1 <= w < 0    "search the weights" (ci.cpp:65-73,105-119 -> solveW, :143-190).  XK_EINVAL unless
- *                  xk_set_option(h, "ci_weight_search", 1) was called (default 0); xk_ci_round_device takes
- *                  fixed weights only and answers XK_EINVAL either way.
+ *                  xk_set_option(h, "ci_weight_search", 1) was called (default 0).
  * The search minimises the reference's objective under the reference's bounds,
  *   det((sum_i w_i M_i)^-1),  M_i = H_i P_i^-1 H_i^T,  1e-4 <= w_i <= 1,  sum_i w_i = 1,
  * as f(w) = -log det(sum_i w_i M_i): convex, so the minimiser is one point, found by an active-set Newton iteration in a
@@ -169,6 +168,11 @@ int xk_ci_solve_weights(xk_handle *h, const double *M, int m, int k1, const doub
 /* The weights of the last searched entry on this handle (also of xk_ci_solve_weights): w (out, 8; own agent first, unused
  * ones zero), *k1 their number, *iters the Newton steps.  All zero before the first search. */
 int xk_ci_last_weights(const xk_handle *h, double *w, int *k1, int *iters);
+/* The weights the last searched xk_ci_round_device found for its shared track `track`: w (out, 8; own agent first, then the
+ * others by rank, unused ones zero), *k1 their number, *iters the Newton steps (both may be NULL).  A track that gave no entry
+ * (a gate rejected it) has *k1 = 0 and all weights zero.  XK_EINVAL before the first searched round and for a track index
+ * outside the last one.  After a searched round xk_ci_last_weights reports the last fused track's weights. */
+int xk_ci_round_weights(const xk_handle *h, int track, double *w, int *k1, int *iters);
 
 /* CovarianceIntersection::fuseCI, k-agent MSCKF form (src/x/ekf/ci.cpp:49-92):
  * S = (1/w0) H P H^T + sum_i (1/w) H_i P_i H_i^T, w0 = 1 - k w,
@@ -267,7 +271,20 @@ int xk_cov_propagate(xk_handle *h, const double *f_d, int ldf, const double *q_d
  *   self_track   host [n_tracks]: index of each shared track among this handle's staged tracks
  * The handle's staged window and its RESIDENT covariance are this agent's side.  Every entry is built from the
  * same prior and applyCI overwrites P each time (the reference's behaviour): on return the resident covariance
- * is the posterior of the last fused entry.  corrections (host, optional): [*n_fused][n]. */
+ * is the posterior of the last fused entry.  corrections (host, optional): [*n_fused][n].
+ * Searched weights (-1 <= ci_msckf_w < 0 with "ci_weight_search" on): per shared track j the weights minimise
+ * -log det sum_i w_i M_i^(j), M_i^(j) = H_ij P_i^-1 H_ij^T (m = 3 (world - 1) rows, world matrices; index 0 = own agent, then
+ * the others by rank), exactly as xk_msckf_ci_track's searched path.  The two gates are computed before the weights and
+ * without them.  Every agent's covariance is factored ONCE per round on the device with the rows of all tracks as right-hand
+ * sides; the weights go from the solver to S_ci = sum_i H_i P_i H_i^T / w_i + sigma^2 I and to the scaling of the own pose
+ * blocks (1 / w_0) without leaving the device, and reach the host -- with the solver's step counts -- in pinned memory with
+ * the gate words: the host still waits once.  A fixed-weight round queues what it always queued.
+ *   XK_ESINGULAR   a covariance of ANY agent is not positive definite, whatever the gates say (the text names the agent's
+ *                  rank), or the search failed on a track that passes both gates.  Nothing is applied: the resident
+ *                  covariance is untouched, *n_fused = 0, the handle keeps working.  A failed search on a track the gates
+ *                  reject is ignored.
+ * Limit: the FULL n x n covariance of every agent must be positive definite (the reference and the host route invert the full
+ * matrix too), so a payload whose unused window slots are zero blocks cannot be searched. */
 int xk_ci_round_device(xk_handle *h, const double *d_payloads, long payload_stride, int world, int self_rank,
                        const double *d_tracks, int n_tracks, const int *track_len, const int *n_poses_valid,
                        const int *self_track, double sigma_img, double ci_msckf_w, int *n_fused, double *corrections);

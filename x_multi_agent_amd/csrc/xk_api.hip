@@ -23,6 +23,7 @@
 #include "xk_caqr_pipe.hip.h"
 #include "xk_ci.hip.h"
 #include "xk_ciw.hip.h"
+#include "xk_ciw_round.hip.h"
 #include "xk_aux.hip.h"
 
 #define XK_VERSION_NUM 201
@@ -142,12 +143,18 @@ struct xk_handle {
   double *d_ciw;
   double ci_last_w[8];     // what xk_ci_last_weights hands out: the weights of the last searched entry,
   int ci_last_k1, ci_last_iters;   // how many there were and the Newton steps they took
+  // searched device round (xk_ciw_round.hip.h), allocated by the first searched round:
+  // d_ciwr = per agent [Maug | X] (n x (n + 168) each), then M [8 tracks][8 agents][576], start [8][8], weights [8][8], 1/w0 [8], info [8][2], status [8]
+  double *d_ciwr;
+  int ci_round_tracks;             // shared tracks of the last searched round (0 before the first one)
+  double ci_round_w[8][8];         // what xk_ci_round_weights hands out
+  int ci_round_k1[8], ci_round_iters[8];
   hipStream_t ci_stream[8];   // ... and its side streams: shared track j >= 1 runs its stages before the gate on ci_stream[j],
   hipEvent_t ci_fork, ci_join[8];   // next to track 0 on the engine's stream (forked and joined with events)
   XkFeatBatch *d_batch;    // per-agent descriptors of the batched feature launch, [8 tracks][8 agents]
   XkFeatBatch *h_batch;    // pinned staging of the same
   int *h_ci_cols;          // pinned: per shared track, the block columns of xk_scale_blocks [8][128]
-  double *h_ci_w;          // pinned: per shared track, 1/w0 [8]
+  double *h_ci_w;          // pinned: per shared track, 1/w0 [8]; the gate words; from [48] on what a searched round reports
   int *h_trk_off;          // host copy of the staged track offsets
   // MSCKF-SLAM tracks (features being initialised this frame)
   int anchor_max;          // largest staged SLAM anchor index (rechecked against the staged window at build time)
@@ -479,6 +486,7 @@ extern "C" int xk_destroy(xk_handle *h) {
     if (p3) hipFree(p3);
   if (h->d_ciws) hipFree(h->d_ciws);
   if (h->d_ciw) hipFree(h->d_ciw);
+  if (h->d_ciwr) hipFree(h->d_ciwr);
   if (h->d_batch) hipFree(h->d_batch);
   if (h->h_batch) hipHostFree(h->h_batch);
   if (h->h_ci_cols) hipHostFree(h->h_ci_cols);
@@ -2714,6 +2722,14 @@ extern "C" int xk_ci_solve_weights(xk_handle *h, const double *M, int m, int k1,
   return XK_OK;
 }
 
+extern "C" int xk_ci_round_weights(const xk_handle *h, int track, double *w, int *k1, int *iters) {
+  if (!h || !w || track < 0 || track >= h->ci_round_tracks) return XK_EINVAL;
+  for (int i = 0; i < 8; ++i) w[i] = h->ci_round_w[track][i];
+  if (k1) *k1 = h->ci_round_k1[track];
+  if (iters) *iters = h->ci_round_iters[track];
+  return XK_OK;
+}
+
 extern "C" int xk_ci_last_weights(const xk_handle *h, double *w, int *k1, int *iters) {
   if (!h || !w) return XK_EINVAL;
   for (int i = 0; i < 8; ++i) w[i] = h->ci_last_w[i];
@@ -2808,11 +2824,18 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
   if (self_rank < 0 || self_rank >= world || n_tracks < 0 || n_tracks > 8) return XK_EINVAL;
   if (payload_stride != xk_payload_doubles(N, h->Mmax)) return fail(h, XK_EINVAL, "payload layout differs from this handle's (N, M)");
   if (h->n_poses < 2) return fail(h, XK_EINVAL, "window not staged");
-  if (const int cw = check_w(h, ci_msckf_w))
-    return fail(h, XK_EINVAL, cw > 0 ? "xk_ci_round_device takes fixed weights only: the weight search is built into xk_msckf_ci_track, not into the device round"
-                                     : "The CI weights must be lower than 1.0 and larger 0.0");
+  const int srch = check_w(h, ci_msckf_w);
+  if (srch < 0)
+    return fail(h, XK_EINVAL, (ci_msckf_w < 0 && ci_msckf_w >= -1 && !h->opt_ci_search)
+                                  ? "xk_ci_round_device: a negative CI weight asks for the weight search, which is switched off (xk_set_option \"ci_weight_search\", 1)"
+                                  : "The CI weights must be lower than 1.0 and larger 0.0");
   if (m > h->CM) return fail(h, XK_ECAPACITY, "m exceeds the dense workspace");
   HIPCHK(h, hipSetDevice(h->device));
+  // searched weights: per agent [P_i | H_i^T of all tracks] and the solve's output, then the solver's operands and results
+  const int ciwr_ld = n + XK_CIWR_MAXRHS;
+  const size_t ciwr_agent = 2 * (size_t)n * ciwr_ld;
+  if (srch && !h->d_ciwr)
+    HIPCHK(h, hipMalloc((void **)&h->d_ciwr, sizeof(double) * (XK_CIW_MAXK1 * ciwr_agent + 64 * 576 + 64 + 64 + 8 + 8 + 4)));
   const size_t upsz = 3 * (size_t)n + 16;
   const size_t Lcap = (size_t)k1 * 64;
   const size_t ci_ws_doubles = (size_t)9 * 8 * 64 + 8 * upsz + (size_t)21 * 8 * n + 8 * XK_CI_MAXCHUNK * 576 + 2 * 576 + 512;
@@ -2821,8 +2844,10 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
     HIPCHK(h, hipMalloc((void **)&h->d_batch, sizeof(XkFeatBatch) * 64));
     HIPCHK(h, hipHostMalloc((void **)&h->h_batch, sizeof(XkFeatBatch) * 64));
     HIPCHK(h, hipHostMalloc((void **)&h->h_ci_cols, sizeof(int) * (8 * 128 + 8)));   // + the per-track own-gate flags
-    HIPCHK(h, hipHostMalloc((void **)&h->h_ci_w, sizeof(double) * 48));   // [0..7] 1/w0, [8..15] joint gamma; [16 + 4 j ..] track j: own verdict, joint gamma, marker
-    memset(h->h_ci_w, 0, sizeof(double) * 48);
+    // [0..7] 1/w0, [8..15] joint gamma; [16 + 4 j ..] track j: own verdict, joint gamma, marker; a searched round adds
+    // [48 + 8 j ..] track j's weights, [112 ..] the solver's two info words per track (ints), [120 ..] the pivot status per agent (ints)
+    HIPCHK(h, hipHostMalloc((void **)&h->h_ci_w, sizeof(double) * 128));
+    memset(h->h_ci_w, 0, sizeof(double) * 128);
     hipFuncSetAttribute((const void *)xk_ci_hph, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     HIPCHK(h, hipEventCreateWithFlags(&h->ci_fork, hipEventDisableTiming));
     for (int j = 1; j < 8; ++j) {
@@ -2845,7 +2870,8 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
   // payload layout (fleet.py / xk_pack_payload): hdr[8] dyn[16] pos[3N] att[4N] feat[3M] anchors[M] cov[n*n]
   const size_t o_pos = 24, o_att = o_pos + 3 * (size_t)N, o_cov = o_att + 4 * (size_t)N + 4 * (size_t)h->Mmax;
   const size_t trk_stride = 1 + 2 * (size_t)N;
-  const double w0 = 1.0 - (double)k * ci_msckf_w, var_img = sigma_img * sigma_img;
+  // (searched: xk_ci_combine's own S_ci is formed with unit weights and replaced by xk_ciwr_finish)
+  const double w0 = srch ? 1.0 : 1.0 - (double)k * ci_msckf_w, w_oth = srch ? 1.0 : ci_msckf_w, var_img = sigma_img * sigma_img;
   { int rcw = flush_window(h); if (rcw != XK_OK) return rcw; }
   int fused = 0;
   int trk_L0[8], trk_dof[8];
@@ -2880,6 +2906,16 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
   const unsigned long long ci_seq = ++h->done_seq;
   static const int side_env = env_int("XK_CI_SIDE_STREAMS", 1);
   const bool side = side_env && n_tracks > 1;
+  double *ciwr_M = nullptr, *ciwr_start = nullptr, *ciwr_w = nullptr, *ciwr_winv = nullptr;
+  int *ciwr_info = nullptr, *ciwr_status = nullptr;
+  if (srch) {
+    ciwr_M = h->d_ciwr + XK_CIW_MAXK1 * ciwr_agent; ciwr_start = ciwr_M + 64 * 576; ciwr_w = ciwr_start + 64; ciwr_winv = ciwr_w + 64;
+    ciwr_info = (int *)(ciwr_winv + 8); ciwr_status = ciwr_info + 16;
+  }
+  XkCiwrAssembleArgs ciwr_as;
+  XkCiwrFinishArgs ciwr_fin;
+  memset(&ciwr_as, 0, sizeof(ciwr_as));
+  memset(&ciwr_fin, 0, sizeof(ciwr_fin));
   if (side) CI_CHK(hipEventRecord(h->ci_fork, h->stream));
   // Round 6: the launches of a track's chain are PREPARED here and issued stage by stage over all tracks below.  The round was bound by
   // the host issuing 2 x 8 launches one track after the other (~7 us each: the second track's chain started 60 us after the first
@@ -2948,8 +2984,15 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
     ci_stage[5].push_back([=]() { hipLaunchKernelGGL(xk_ci_hph, dim3(k1, nchunk), dim3(256), sizeof(double) * ((size_t)m * n + 24 * 33), sj, ha); return hipSuccess; });
     // the two gate decisions (own chi-square test :180, joint test :243-250) come back per track: written by the kernel into
     // pinned host memory, a marker behind them
-    XkCiCombineArgs ca{k1, m, Si, nchunk, w0, ci_msckf_w, var_img, dres, S1, S2, dscal,
-                       dint, h->h_ci_w + 16 + 4 * j, reinterpret_cast<unsigned long long *>(h->h_ci_w + 16 + 4 * j + 2), ci_seq};
+    // (searched: the gate words and the marker come from the last kernel of the searched chain instead)
+    XkCiCombineArgs ca{k1, m, Si, nchunk, w0, w_oth, var_img, dres, S1, S2, dscal,
+                       dint, h->h_ci_w + 16 + 4 * j, srch ? nullptr : reinterpret_cast<unsigned long long *>(h->h_ci_w + 16 + 4 * j + 2), ci_seq};
+    if (srch) {
+      ciwr_as.H[j] = Hs;
+      if (j == 0)
+        for (int i = 0; i < k1; ++i) ciwr_as.P[i] = aP[i];
+      ciwr_fin.Si[j] = Si; ciwr_fin.S_ci[j] = S2; ciwr_fin.own_inlier[j] = dint; ciwr_fin.gamma[j] = dscal;
+    }
     ci_stage[6].push_back([=]() { hipLaunchKernelGGL(xk_ci_combine, dim3(1), dim3(512), 0, sj, ca); return hipSuccess; });
     if (side && j > 0) {
       hipEvent_t ej = h->ci_join[j];
@@ -2961,6 +3004,44 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
   }
   for (auto &stage : ci_stage)
     for (auto &issue : stage) CI_CHK(issue());
+  if (srch && n_tracks > 0) {
+    // The searched chain, on the engine's stream behind the join of the side streams (it needs every track's Jacobians): the
+    // information projections of all agents and tracks with ONE factorisation per agent, the search per track, the weighted S_ci.
+    XkCiwrAgents ag;
+    memset(&ag, 0, sizeof(ag));
+    ag.ld = ciwr_ld;
+    for (int i = 0; i < k1; ++i) { ag.Maug[i] = h->d_ciwr + (size_t)i * ciwr_agent; ag.X[i] = ag.Maug[i] + (size_t)n * ciwr_ld; }
+    const int ncols = n + n_tracks * m;
+    double st[XK_CIW_MAXK1];
+    const double *start = ciw_start_multi(ci_msckf_w, k, st);
+    ciwr_as.ag = ag; ciwr_as.n = n; ciwr_as.m = m; ciwr_as.k1 = k1; ciwr_as.nt = n_tracks;
+    ciwr_as.start = start ? ciwr_start : nullptr; ciwr_as.status = ciwr_status;
+    for (int i = 0; i < XK_CIW_MAXK1; ++i) ciwr_as.st[i] = (start && i < k1) ? st[i] : 0.0;
+    hipLaunchKernelGGL(xk_ciwr_assemble, dim3((unsigned)(((size_t)n * ncols + 255) / 256), k1), dim3(256), 0, h->stream, ciwr_as);
+    const int B = 16 * XK_CHOLW_MAXB;
+    for (int off = 0; off < n;) {
+      const int cb = std::min(B, n - off);
+      XkCiwrCholArgs d;
+      d.ag = ag; d.off = off; d.c = cb; d.ncols = ncols - off; d.status = ciwr_status;
+      xk_cholw_table((cb + 15) / 16, d.tab);
+      hipLaunchKernelGGL(xk_ciwr_chol, dim3((ncols - off - cb + 15) / 16, k1), dim3(64 * XK_CHOLW_WAVES), 0, h->stream, d);
+      off += cb;
+      if (off < n) {
+        XkCiwrSchurArgs sa{ag, off, cb, n - off, ncols - off};
+        hipLaunchKernelGGL(xk_ciwr_schur, dim3((ncols - off + 15) / 16, (n - off + 15) / 16, k1), dim3(64), 0, h->stream, sa);
+      }
+    }
+    XkCiwrXtxArgs xa{ag, n, m, ciwr_M};
+    hipLaunchKernelGGL(xk_ciwr_xtx, dim3(n_tracks, k1), dim3(256), 0, h->stream, xa);
+    // (no handle status word: a failing problem on a track the gates reject must not poison the handle)
+    XkCiwArgs wa{ciwr_M, (long)XK_CIW_MAXK1 * 576, 576, m, k1, start ? ciwr_start : nullptr, ciwr_w, ciwr_info, nullptr, 1};
+    hipLaunchKernelGGL(xk_ci_weights, dim3(n_tracks), dim3(XK_CIW_THREADS), 0, h->stream, wa);
+    ciwr_fin.nt = n_tracks; ciwr_fin.k1 = k1; ciwr_fin.m = m; ciwr_fin.nchunk = (n + XK_CI_CHUNK - 1) / XK_CI_CHUNK;
+    ciwr_fin.var_img = var_img; ciwr_fin.w = ciwr_w; ciwr_fin.info = ciwr_info; ciwr_fin.status = ciwr_status;
+    ciwr_fin.winv = ciwr_winv; ciwr_fin.host = h->h_ci_w; ciwr_fin.seq = ci_seq;
+    hipLaunchKernelGGL(xk_ciwr_finish, dim3(1), dim3(512), 0, h->stream, ciwr_fin);
+    CI_CHK(hipGetLastError());
+  }
 #undef CI_CHK
   if (n_tracks > 0) {
     // wait for the markers of all tracks (XK_SPIN_DONE=0, or a marker that does not come within ~1 s: the runtime's signal)
@@ -2982,6 +3063,37 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
   int last_fused = -1;
   for (int j = 0; j < n_tracks; ++j)
     if (h->h_ci_w[16 + 4 * j] != 0.0 && h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]]) last_fused = j;
+  if (srch && n_tracks > 0) {
+    // what the searched chain left in pinned memory with the gate words.  No silent fallback: a covariance that is not positive
+    // definite fails the round whatever the gates say (as the host route, which checks before the gate decision), and so does a
+    // failed search on a track that passes both gates.  Nothing has been applied at this point.
+    const int *pst = reinterpret_cast<const int *>(h->h_ci_w + 120), *pinfo = reinterpret_cast<const int *>(h->h_ci_w + 112);
+    for (int i = 0; i < k1; ++i)
+      if (pst[i] != 0) {
+        const int rank = i == 0 ? self_rank : (i - 1 < self_rank ? i - 1 : i);
+        char msg[128];
+        snprintf(msg, sizeof(msg), "CI weight search: the covariance of the agent of rank %d is not positive definite", rank);
+        return fail(h, XK_ESINGULAR, msg);
+      }
+    for (int j = 0; j < n_tracks; ++j) {
+      const bool pass = h->h_ci_w[16 + 4 * j] != 0.0 && h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]];
+      if (pass && pinfo[2 * j + 1] != 0)
+        return fail(h, XK_ESINGULAR, pinfo[2 * j] >= XK_CIW_MAXIT ? "CI weight search: no convergence within 50 Newton steps"
+                                                                   : "CI weight search: sum w_i M_i is not positive definite");
+    }
+    h->ci_round_tracks = n_tracks;
+    for (int j = 0; j < n_tracks; ++j) {
+      const bool pass = h->h_ci_w[16 + 4 * j] != 0.0 && h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]];
+      for (int i = 0; i < 8; ++i) h->ci_round_w[j][i] = (pass && i < k1) ? h->h_ci_w[48 + 8 * j + i] : 0.0;
+      h->ci_round_k1[j] = pass ? k1 : 0;
+      h->ci_round_iters[j] = pass ? pinfo[2 * j] : 0;
+    }
+    if (last_fused >= 0) {
+      memcpy(h->ci_last_w, h->ci_round_w[last_fused], sizeof(h->ci_last_w));
+      h->ci_last_k1 = k1;
+      h->ci_last_iters = h->ci_round_iters[last_fused];
+    }
+  }
   static const int spin_done = env_int("XK_SPIN_DONE", 1);
   unsigned long long *done = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2);
   unsigned long long wait_seq = 0;
@@ -2993,7 +3105,8 @@ extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long p
     // P_j: diagonal 3x3 blocks of the observed poses scaled by 1/w0 (:256-267), then applyCI (updater.cpp:144-161)
     const int L = trk_L0[j];
     // (the blocks are those of the last L window poses: the kernel works their columns out itself -- no staging copies)
-    XkScaleArgs sc{h->d_P, h->d_tmpP, n, 2 * L, nullptr, nullptr, 1, h->n_poses - L, L, N, 1.0 / w0};
+    // (searched: the factor is the device word 1 / w_0 the searched chain left for this track)
+    XkScaleArgs sc{h->d_P, h->d_tmpP, n, 2 * L, nullptr, nullptr, 1, h->n_poses - L, L, N, 1.0 / w0, srch ? ciwr_winv + j : nullptr};
     (void)dint; (void)dscal;
     hipLaunchKernelGGL(xk_scale_blocks, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, sc);
     UpdateSpec u;

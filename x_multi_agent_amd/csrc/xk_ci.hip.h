@@ -140,8 +140,10 @@ struct XkScaleArgs {
   const double *w;   // device scalar (w_result)
   // arith != 0: the blocks are the position and attitude blocks of window poses [p0, p0 + L) -- first columns
   // XK_CORE + 3 pos and XK_CORE + 3 N + 3 pos -- and the factor is wval: nothing to fetch, nothing to stage from the host
+  // ... or, when wdev is given, the device word it points to (the searched 1 / w_0 of the device CI round)
   int arith, p0, L, N;
   double wval;
+  const double *wdev;
 };
 __global__ void xk_scale_blocks(XkScaleArgs a) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -152,7 +154,7 @@ __global__ void xk_scale_blocks(XkScaleArgs a) {
     const int rb = (r - 15) / 3, cb = (c - 15) / 3;                 // 3 x 3 block coordinates behind the core states
     if (r >= 15 && c >= 15 && rb == cb) {
       const int pos = rb < a.N ? rb : rb - a.N;                     // position blocks, then attitude blocks
-      if (rb < 2 * a.N && pos >= a.p0 && pos < a.p0 + a.L) v *= a.wval;
+      if (rb < 2 * a.N && pos >= a.p0 && pos < a.p0 + a.L) v *= a.wdev ? *a.wdev : a.wval;
     }
   } else {
     for (int b = 0; b < a.nblk; ++b) {

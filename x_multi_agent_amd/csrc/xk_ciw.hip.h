@@ -29,6 +29,13 @@ struct XkCiwArgs {
   double *w;          // out [problem][8]
   int *info;          // out [problem][2]: Newton steps taken, status (0, or 2 = A not positive definite / no convergence)
   int *status;        // optional status word of the handle: set to 2 when a problem fails, never cleared here
+  // precise != 0 (the device CI round): the result must not depend on the start beyond rounding, also for M_i that are rank-deficient
+  // inside the m x m block (sum_i M_i with a condition number of 1e7).  Two things, both exact in exact arithmetic:
+  //   - the problem is whitened first, M_i <- L0^-1 M_i L0^-T with sum_i M_i / k1 = L0 L0^T: the objective changes by a constant, the
+  //     iteration then works on matrices whose uniform sum is the identity (the gradient's rounding error scales with cond(A));
+  //   - once the convergence test passes after at least one step, ONE more Newton step is taken: the test allows a gradient residual
+  //     of 1e-10 lam, i.e. weights a few 1e-11 from the minimiser depending on where the iteration came from; the step squares that.
+  int precise;
 };
 
 // One workgroup per problem.  Every sum runs in a fixed order (no atomics, no order that depends on timing).
@@ -51,11 +58,12 @@ __global__ __launch_bounds__(XK_CIW_THREADS) void xk_ci_weights(XkCiwArgs a) {
     ctl[0] = ctl[1] = 0;
   }
   __syncthreads();
+  bool whiten = a.precise != 0, polished = false;   // (whiten: uniform over the workgroup; polished: thread 0's)
   for (;;) {
-    // A = sum_i w_i M_i
+    // A = sum_i w_i M_i  (whitening pass: the uniform sum)
     for (int e = tid; e < mm; e += XK_CIW_THREADS) {
       double s = 0.0;
-      for (int i = 0; i < k1; ++i) s = fma(ws[i], Ms[i * XK_CIW_MM + e], s);
+      for (int i = 0; i < k1; ++i) s = fma(whiten ? 1.0 / k1 : ws[i], Ms[i * XK_CIW_MM + e], s);
       As[e % m][e / m] = s;
     }
     __syncthreads();
@@ -102,6 +110,15 @@ __global__ __launch_bounds__(XK_CIW_THREADS) void xk_ci_weights(XkCiwArgs a) {
       }
     }
     __syncthreads();
+    if (whiten) {                                                   // M_i <- L0^-1 M_i L0^-T (symmetric part), then the iteration proper
+      for (int t = tid; t < k1 * mm; t += XK_CIW_THREADS) {
+        const int i = t / mm, e = t % mm, r = e % m, c = e / m;
+        Ms[i * XK_CIW_MM + e] = 0.5 * (Ys[i * XK_CIW_MM + r + m * c] + Ys[i * XK_CIW_MM + c + m * r]);
+      }
+      whiten = false;
+      __syncthreads();
+      continue;
+    }
     // H_ij = <Y_i, Y_j>, g_i = tr Y_i: four interleaved partial sums per value, added in their order below
     if (tid < 44 * 4) {
       const int p = tid >> 2, q = tid & 3;
@@ -147,9 +164,12 @@ __global__ __launch_bounds__(XK_CIW_THREADS) void xk_ci_weights(XkCiwArgs a) {
       double worst = 0.0;
       for (int i = 0; i < k1; ++i)
         if (!act[i]) worst = fmax(worst, fabs(gs[i] - lam));
-      if (worst <= XK_CIW_TOL * lam) ctl[0] = 1;                  // (tested BEFORE the step: a flat objective returns its start)
+      const bool conv = worst <= XK_CIW_TOL * lam;
+      const bool polish = conv && a.precise && !polished && ctl[1] > 0 && ctl[1] < XK_CIW_MAXIT;
+      if (conv && !polish) ctl[0] = 1;                             // (tested BEFORE the step: a flat objective returns its start)
       else if (ctl[1] >= XK_CIW_MAXIT) ctl[0] = 2;
       else {
+        if (polish) polished = true;
         // Newton step on the free coordinates with sum d = 0: the constraint is eliminated through the largest free weight r
         // (d_r = -sum of the others), the reduced system <Y_i - Y_r, Y_j - Y_r> d = g_i - g_r is solved by Cholesky.  A free
         // coordinate that sits on the bound and would leave the feasible set goes back into the active set, and the step is redone.

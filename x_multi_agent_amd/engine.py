@@ -28,7 +28,7 @@ SYMBOLS = [
     "xk_stage_window", "xk_stage_tracks", "xk_stage_tracks_begin", "xk_stage_tracks_end", "xk_stage_slam", "xk_upload_P", "xk_download_P",
     "xk_msckf_build", "xk_qr_compress", "xk_apply_update", "xk_visual_update_staged", "xk_visual_update",
     "xk_apply_update_dense", "xk_apply_ci", "xk_fuse_ci_msckf", "xk_fuse_ci_slam", "xk_multi_slam_match", "xk_msckf_ci_track",
-    "xk_ci_round_device", "xk_ci_solve_weights", "xk_ci_last_weights", "xk_cov_congruence", "xk_cov_propagate",
+    "xk_ci_round_device", "xk_ci_round_weights", "xk_ci_solve_weights", "xk_ci_last_weights", "xk_cov_congruence", "xk_cov_propagate",
     "xk_stage_msckf_slam", "xk_msckf_slam_results", "xk_init_msckf_slam_features", "xk_init_standard_slam_features",
     "xk_payload_doubles", "xk_pack_payload", "xk_bench_staged", "xk_run_steps",
     "xk_apply_ci_resident", "xk_snapshot_P", "xk_caqr_status", "xk_set_option", "xk_build_compress_async", "xk_build_compress_update_async", "xk_build_compress_update_pass_async", "xk_fetch_flags",
@@ -320,6 +320,15 @@ class Engine:
         self._chk(self.L.xk_ci_last_weights(self.h, w.ctypes.data_as(c_dp), C.byref(k1), C.byref(it)), "xk_ci_last_weights")
         return w[:k1.value].copy(), it.value
 
+    def ci_round_weights(self, track):
+        """xk_ci_round_weights: (weights the last searched ci_round_device found for shared track `track`, own agent first and
+        then the others by rank; Newton steps).  A track that gave no entry returns an empty vector."""
+        w = np.zeros(8)
+        k1, it = C.c_int(), C.c_int()
+        self._chk(self.L.xk_ci_round_weights(self.h, C.c_int(track), w.ctypes.data_as(c_dp), C.byref(k1), C.byref(it)),
+                  "xk_ci_round_weights")
+        return w[:k1.value].copy(), it.value
+
     def multi_slam_match(self, C_q_G, G_p_C, feat, anchor_idx, feature_id, P, n_poses_max, o_C_q_G, o_G_p_C,
                          o_feat, o_anchor_idx, o_feature_id, o_P, o_n_poses_max, sigma_landmark, ci_slam_w):
         n, no = P.shape[0], o_P.shape[0]
@@ -434,7 +443,10 @@ class Engine:
                         n_poses_valid, self_track, sigma_img, ci_msckf_w, want_corrections=False):
         """CI round against gathered payloads that already sit in device memory (RCCL receive buffer).
         payloads_ptr / tracks_ptr are device addresses (e.g. torch tensor.data_ptr()).  Returns
-        (n_fused, corrections or None); the resident covariance becomes the last fused posterior."""
+        (n_fused, corrections or None); the resident covariance becomes the last fused posterior.
+        -1 <= ci_msckf_w < 0 with set_option("ci_weight_search", 1): the weights are searched per shared track on the device
+        (ci_round_weights(track) returns them); a covariance that is not positive definite or a failed search on a fused track
+        raises XkError with status 2 and applies nothing."""
         tl, tlp = _i(np.asarray(track_len, dtype=np.int32).ravel())
         nv, nvp = _i(np.asarray(n_poses_valid, dtype=np.int32).ravel())
         st, stp = _i(np.asarray(self_track, dtype=np.int32).ravel())

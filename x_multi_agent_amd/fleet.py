@@ -216,7 +216,9 @@ def ci_round_device(eng, sc, rank, world, payloads, tracks, n_tracks, ci_msckf_w
     """The same CI round with everything the other agents sent left in device memory.
     payloads: torch CUDA tensor [world, payload_doubles] (the all-gather output); tracks: torch CUDA tensor
     [world, n_tracks * (1 + 2N)] (pack_tracks of every agent).  The engine must have agent `rank`'s problem staged
-    (its shared tracks are its first n_tracks staged tracks).  Only the few header / length words come to the host."""
+    (its shared tracks are its first n_tracks staged tracks).  Only the few header / length words come to the host.
+    A negative ci_msckf_w (with eng.set_option("ci_weight_search", 1)) searches the weights per shared track inside the same
+    round: nothing n x n leaves the device, and eng.ci_round_weights(j) reports what track j was fused with."""
     N = sc["n_poses_max"]
     # the few words the host needs -- every agent's track lengths and window size -- in ONE device-to-host copy
     words = payloads.new_empty(world * (n_tracks + 1))
