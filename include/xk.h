@@ -445,7 +445,7 @@ int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int steps, xk_ti
 int xk_run_steps(xk_handle *h, double sigma_img, int steps);
 
 /* Which schedule compressed the last update -- 0 the multi-launch CAQR, 2 the pipelined single launch (1 was round 2's
- * register-resident kernel, no longer built), 3 the multi-launch CAQR for the first panels of a tall system (windows of 34..64
+ * register-resident kernel, no longer built: the value is never reported), 3 the multi-launch CAQR for the first panels of a tall system (windows of 34..64
  * poses) and one or two single launches for its last <= 192 columns, 4 no compression at all: the stack was the SLAM features' rows alone
  * (2 M rows against n > 3 M columns) or a small stack whose nominal rows are at most n -- the reference compresses only when rows >
  * columns, vio_updater.cpp:487, and neither does this: the rows go to the update as built -- or the update had no track and no SLAM

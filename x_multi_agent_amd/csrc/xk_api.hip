@@ -27,188 +27,8 @@
 #include "xk_aux.hip.h"
 
 #define XK_VERSION_NUM 201
-#define XK_STAGE_SLOTS 8
-#define XK_PDBG_WORDS 65536     // debug stamps of the single launch (lab build)
 
-struct xk_handle {
-  int device;
-  hipStream_t stream;
-  hipStream_t copy_stream;   // gate flags travel to the host beside the QR kernels, not between them
-  hipEvent_t ev_flags, ev_flags_done;
-  hipEvent_t ev[16];
-  // capacities
-  int N, Mmax, Kmax, n, na, C1, C1P, DB, ntiles_max;
-  // staged problem
-  int n_poses, K, M;
-  size_t obs_cap;
-  double *d_q, *d_p, *d_obs, *d_feat, *d_zlast;
-  int *d_trk_off, *d_anchor, *d_tsz;
-  double *d_P, *d_Pout;
-  double *d_Psnap;        // xk_snapshot_P (slot of the caller)
-  double *d_Psnap2;       // ... slot of the filter loop (x::Ekf saves the prior of an update the IMU thread may lap)
-  double *d_fq;           // f_d, q_d of xk_cov_propagate
-  double *d_chi95, *d_chi90;
-  double *d_A;
-  double *d_Hc;            // factor records of the MSCKF tracks (xk_feature.hip.h: XkFeatArgs::Hc), hc_stride doubles each, 64-row slots only
-  int hc_stride;
-  int opt_hlite;           // 1 (default): the per-feature kernel leaves factor records when the single launch is expected to run
-  bool rows_compact;       // the last build left records, not tiles, for slots [0, K)
-  int *d_tile_rows;
-  double *d_panel[2];   // CAQR: 16 x 16 panel blocks of the even (tiles, level 2, ..) / odd merge levels
-  int *d_inl, *d_inl_s, *d_gn;
-  double *d_gam, *d_gam_s, *d_gpf;
-  double *d_R;
-  int nleaf, nlevels;   // of the last compression
-  // single-launch CAQR (xk_caqr_pipe.hip.h): cross-XCD exchange slabs, XCD-local strips and panel blocks,
-  // two sets of sync words (a launch uses one and zeroes the other for its successor)
-  double *d_x1;            // both sets of the cross-XCD slabs (X1 | X2 | X1P each)
-  size_t xslab_doubles;    // ... doubles per set
-  double *d_rs, *d_rpb;
-  unsigned *d_xsync;
-  int xsync_phase;
-  int pipe_rows_nominal;   // rows the last single launch was queued for, every track counted as accepted
-  // Geometry with two first-level groups per XCD (XkPipeNarrow2: 152 tiles): taken when the rows expected to pass the gates fit it.
-  // The expectation is the acceptance ratio the last single launch reported (status word 2) applied to this update's nominal rows.
-  int opt_split;           // 0 never, 1 adaptive (default); lab: 2 whenever the NOMINAL rows fit, 3 always
-  double acc_ratio;        // accepted / nominal rows of the last single launch (0: none yet)
-  int pipe_tag;            // tag of the last single launch's accepted-rows word (status word 2)
-  bool last_split;         // the last single launch used that geometry
-  int split_backoff;       // updates for which it stays off after it found more rows than it holds
-  int overflow_rows;       // a single launch of that many nominal rows found more accepted rows than its tiles hold: not tried again at that size
-  // SPLIT compression (round 6; systems with SLAM features whose update cannot ride inside the launch, n > 206: BASELINE config 2).
-  // The rows of MSCKF tracks are zero in the features' columns (msckf_update.cpp:412-416) and the features' own rows are 2 M in number:
-  // only the tracks' rows need compressing, and only in the 6 N pose columns (+ the residual) -- a system of <= 199 columns instead of
-  // 6 N + 3 M + 1.  T = [R1 | 0 | z1 ; H_slam | res_slam] (6 N + 2 M rows, T^T T = H^T H and T^T z = H^T res exactly as for the R of
-  // the whole stack) goes to d_R2; xk_qr_compress, which hands out the reference's upper-triangular T_H, keeps compressing everything.
-  double *d_R2;         // [C1P][C1P] row-major: rows [0, 6 N) = R1 of the tracks' rows, rows [6 N, 6 N + 2 M) = the SLAM rows as built
-  int split_active;     // what the last launch_compress left in d_R2 (compressed_spec follows it): 0 nothing, 1 the split compression,
-                        // 2 the SLAM rows alone, uncompressed (no track in the stack: rows <= columns, vio_updater.cpp:487 does not compress either),
-                        // 3 a small stack, uncompressed; launch_build resets it to 0
-  int plan;             // split_plan of the staged update, latched by launch_build: the rows were built for it (tiles or factor records), and
-                        // launch_compress and compressed_spec take it -- an option changed in between does not split the two
-  bool d_R2_dirty;      // a small stack (plan 3) left dense rows in d_R2: the next split compression clears rows [0, 6 N) before it writes R1
-  bool last_empty;      // the last update had no measurement rows at all: nothing compressed (xk_caqr_status: schedule 4)
-  bool want_full_T;     // xk_qr_compress is running: compress everything into d_R
-  int opt_slam_split;
-  int opt_pipe_min_rows;   // nominal rows from which the single launch is queued (1; lab: XK_PIPE_MIN_ROWS)
-  bool last_resident;   // the last launch_compress took the single-launch resident schedule
-  bool last_pipe;       // ... the pipelined one (its sync words: a launch that gave up leaves them dirty)
-  // Tall systems (128-row slots: windows of 34..64 poses, BASELINE config 3): the multi-launch schedule factors the first panels,
-  // ONE launch of xk_caqr_pipe<XkPipeTail> the last <= 96 columns with every row in registers (round 6)
-  bool tail_capable;    // decided at xk_create: 128-row slots, 256 CUs, the kernel fits a CU
-  bool tail_ok;         // armed (cleared when a tail launch gave up; re-armed like the fast path)
-  bool last_tail;       // the last launch_compress ended in such a launch
-  int tail_backoff_len; // updates the tail stays off after it found more rows than it holds (reason 9): 64, doubling while that keeps happening
-  int tail_clean, tail_backoff, opt_tail;   // opt_tail: 0 off, 1 (default) the plan that fits (192 columns in one or two launches, else 96 in one), 2 the 96-column launch only
-  bool tail_four;       // the plan of this compression uses the 4-lanes-per-column geometry (<= 192 columns)
-  long long *d_pdbg;
-  long long *feat_dbg;  // probe builds only: per-workgroup phase stamps of xk_msckf_feature
-  bool attr_slaminit, attr_feat_batch;   // hipFuncSetAttribute done for this handle's device
-  int n_cu;
-  bool persist_ok;      // cleared when a launch gave up (workgroups not co-resident): the multi-launch schedule takes over
-  bool fast_capable;    // decided at xk_create: 256 CUs, one 768-thread workgroup of the single-launch kernels fits a CU
-  int fast_giveups, fast_reason;   // launches that gave up so far / why the last one did (xk_caqr_status)
-  int clean_classic, rearm_after;  // multi-launch updates since the last give-up / how many of them re-arm the fast path
-  // experiment switches and test hooks of the compression, read from the environment ONCE at xk_create (the per-update path
-  // calls no getenv); xk_set_option changes them on a live handle (tests do)
-  int opt_resident, opt_poison, opt_test_stall, opt_tall26;
-  int opt_kalman;          // the Kalman update inside the single launch (xk_pipe_kalman) where the geometry allows it
-  bool last_fused;         // the last launch_compress also queued the Kalman update (posterior in d_Pout, correction written)
-  bool compress_deferred;  // xk_build_compress_async queued the rows only: the compression waits for xk_apply_update, where the Kalman
-                           // role can ride along on the covariance the applyCI entries in between have left (MULTI_UAV order)
-  int fused_cov_update;    // what the queued pass was asked for (xk_build_compress_update[_pass]_async): xk_apply_update must ask the same
-  bool fused_ct_zero;
-  std::vector<double> *fused_ct;
-  bool fused_pending;      // xk_build_compress_update_async ran: xk_apply_update only has to wait
-  unsigned long long fused_seq;   // ... for this completion marker (0: for the stream)
-  bool xsync_dirty;     // a pipelined launch gave up: its counters are mid-count, clear both sets before the next one
-  bool have_rows, have_R;
-  double sigma_img;
-  // update workspace
-  int CM, LDA;
-  double *d_Maug, *d_X, *d_corr, *d_ct, *d_tmpH, *d_tmpS, *d_tmpP, *d_rdiag, *d_tmpz;
-  double *h_win;        // host copy of the staged window lists (7 doubles per pose), see flush_window
-  bool win_pending;     // ... which have not reached d_q / d_p yet
-  bool win_valid;       // h_win holds the lists of the window in use
-  unsigned *d_done_cnt;  // workgroup counter of the completion marker
-  unsigned long long done_seq, done_seen, flags_after_seq;   // completion markers (XK_SPIN_DONE): launched / seen / launched when the gate flags were queued
-  int *d_status;        // status words; they live in PINNED HOST memory (h_out + n): kernels write them only on failure
-  double *h_out;        // pinned host, device-visible: [n] correction of xk_apply_update + the status words
-  // CI / payload
-  double *d_payload;
-  double *d_ci;  // scratch for the CI kernels
-  double *d_ciws;          // workspace of the device-resident CI round (lazily allocated)
-  // CI weight search (xk_ciw.hip.h): option "ci_weight_search"; d_ciw = [8 weights | 8 start | 2 info words | 8 M_i | 8 H_i P_i H_i^T]
-  int opt_ci_search;
-  double *d_ciw;
-  double ci_last_w[8];     // what xk_ci_last_weights hands out: the weights of the last searched entry,
-  int ci_last_k1, ci_last_iters;   // how many there were and the Newton steps they took
-  // searched device round (xk_ciw_round.hip.h), allocated by the first searched round:
-  // d_ciwr = per agent [Maug | X] (n x (n + 168) each), then M [8 tracks][8 agents][576], start [8][8], weights [8][8], 1/w0 [8], info [8][2], status [8]
-  double *d_ciwr;
-  int ci_round_tracks;             // shared tracks of the last searched round (0 before the first one)
-  double ci_round_w[8][8];         // what xk_ci_round_weights hands out
-  int ci_round_k1[8], ci_round_iters[8];
-  hipStream_t ci_stream[8];   // ... and its side streams: shared track j >= 1 runs its stages before the gate on ci_stream[j],
-  hipEvent_t ci_fork, ci_join[8];   // next to track 0 on the engine's stream (forked and joined with events)
-  XkFeatBatch *d_batch;    // per-agent descriptors of the batched feature launch, [8 tracks][8 agents]
-  XkFeatBatch *h_batch;    // pinned staging of the same
-  int *h_ci_cols;          // pinned: per shared track, the block columns of xk_scale_blocks [8][128]
-  double *h_ci_w;          // pinned: per shared track, 1/w0 [8]; the gate words; from [48] on what a searched round reports
-  int *h_trk_off;          // host copy of the staged track offsets
-  // MSCKF-SLAM tracks (features being initialised this frame)
-  int anchor_max;          // largest staged SLAM anchor index (rechecked against the staged window at build time)
-  int K2;
-  bool ms_built;           // their column-space rows on the device belong to the staged tracks
-  int *d_trk2_off, *h_trk2_off, *d_inl2, *d_gn2;
-  double *d_obs2, *d_gpf2, *d_W2, *d_gam2, *d_H1, *d_H2, *d_r1, *d_feat2;
-  int *d_csr_i;            // sparse congruence operand: row pointers then column indices
-  double *d_csr_v;         //   and values
-  size_t csr_cap;          //   capacity in non-zeros
-  // pinned staging ring for inputs copied to the device WITHOUT a host synchronisation (window, tracks, sparse operands):
-  // a slot is reused XK_STAGE_SLOTS calls later, by which time an update's final synchronisation has long passed
-  char *h_stage[XK_STAGE_SLOTS];
-  int stage_since_sync;    // slots handed out since the stream was last known to be idle (stage_slot)
-  size_t stage_bytes;
-  int stage_next;
-  bool flags_direct;       // no SLAM rows in the last build: nothing was copied, the kernel wrote the cache
-  bool flags_cached;       // h_flag_* hold the gate results of the last build (fetched with the update's status)
-  int *h_flag_i;
-  double *h_flag_d;
-  char *trk_slot;          // xk_stage_tracks_begin .. _end: the staging slot being filled
-  int trk_slot_K, trk_slot_nobs;
-  bool async_pending;      // xk_build_compress_async ran: xk_apply_update owns the retry if the single-launch CAQR gave up
-  // range-facet / sun-angle rows (xk_stage_range / xk_stage_sun_angle, xk_aux.hip.h).  Staged measurements wait in aux_in until the next
-  // build, which consumes them (the reference uses a measurement once: timestamp = -1, vio_updater.cpp:380,402) and fixes the plan of that
-  // update in aux_mask / naux: which rows, how many, and which variances they carry.  A replay of the same update (a retry after a single
-  // launch gave up, xk_run_steps, xk_bench_staged) rebuilds them from the same staged measurement; a build with nothing staged has none.
-  XkAuxIn aux_in;
-  int aux_staged;          // 1 range, 2 sun: staged since the last build
-  int aux_mask;            // ... the rows of the current update
-  int naux;                // 0..3 rows appended to the system the update applies
-  double *d_aux;           // [naux x (n + 1) rows | rdiag 3 | flags 2]
-  double *d_Taug;          // the applied system with the rows appended: CM x (n + 1) row-major, then CM variances
-  // host pinned staging
-  double *h_pin;
-  size_t h_pin_doubles;
-  int *h_pin_i;
-  char err[256];
-};
-
-static int fail(xk_handle *h, int code, const char *what, hipError_t e = hipSuccess) {
-  if (h) {
-    if (e != hipSuccess) snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-    else snprintf(h->err, sizeof(h->err), "%s", what);
-  }
-  return code;
-}
-#define HIPCHK(h, call)                                                   \
-  do {                                                                    \
-    hipError_t e_ = (call);                                               \
-    if (e_ != hipSuccess) return fail((h), XK_EDEVICE, #call, e_);        \
-  } while (0)
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+#include "xk_handle.hip.h"
 
 extern "C" const char *xk_strerror(int s) {
   switch (s) {
@@ -226,25 +46,9 @@ extern "C" const char *xk_last_error(const xk_handle *h) { return h ? h->err : "
 extern "C" int xk_version(void) { return XK_VERSION_NUM; }
 extern "C" void *xk_stream(xk_handle *h) { return h ? (void *)h->stream : nullptr; }
 
-template <typename T>
-static hipError_t dalloc(T **p, size_t count) {
-  return hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-}
-
 static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, xk_handle **out);
 extern "C" int xk_destroy(xk_handle *h);
 // (a failure part-way through releases everything allocated so far)
-// Experiment switches.  The RELEASE library (libxk.so) never looks at the environment: every switch has its default.  The LAB
-// build (-DXK_LAB: x_multi_agent_amd/lab/libxk.so, include/xk_lab.h) reads them -- once each -- and carries the test hooks,
-// the debug exports and the probe kernels the tests and tools/exp use.
-#ifdef XK_LAB
-static int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-#else
-static inline int env_int(const char *, int dflt) { return dflt; }
-#endif
 
 extern "C" int xk_create(int device, int n_poses_max, int n_feat_max, int k_max, xk_handle **out) {
   if (!out) return XK_EINVAL;
@@ -914,7 +718,7 @@ static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
   size_t feat_lds = 0;
   { int rcw = flush_window(h); if (rcw != XK_OK) return rcw; }   // (normally carried by the frame's congruence launch already)
   h->plan = split_plan(h);
-  h->split_active = 0;                            // (d_R2 holds nothing of THIS update until launch_compress writes it)
+  outcome_release_R2(h->last);                    // (d_R2 holds nothing of THIS update until launch_compress writes it)
   if (h->K > 0) {
     XkFeatArgs &a = fa;
     a.q = h->d_q; a.p = h->d_p; a.n_poses = h->n_poses; a.n_poses_max = h->N;
@@ -990,459 +794,10 @@ static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
   return XK_OK;
 }
 
-// The stack of an update that is NOT compressed (rows <= columns: vio_updater.cpp:487 compresses only `if (h.rows() > h.cols())`): slot t's rows
-// -- the tile the per-feature kernel left -- go to rows [off_t, off_t + 2 L_t - 3) of T, off_t = 2 trk_off[t] - 3 t (every track counted in:
-// the host queues the update before it knows the gates' verdicts); a rejected track's rows (tile_rows = 0) are zero rows, which the update
-// ignores (a zero row of H with noise sigma^2 moves nothing).  One workgroup per slot.
-__global__ __launch_bounds__(256) void xk_stack_rows(const double *A, const int *tile_rows, const int *trk_off, int DB, int C1P, int row0, double *T) {
-  const int t = blockIdx.x;
-  const int nr = 2 * (trk_off[t + 1] - trk_off[t]) - 3, off = row0 + 2 * trk_off[t] - 3 * t, valid = min(tile_rows[t], nr);
-  const double *src = A + (size_t)t * DB * C1P;
-  double *dst = T + (size_t)off * C1P;
-  for (int e = threadIdx.x; e < nr * C1P; e += blockDim.x) dst[e] = (e / C1P < valid) ? src[e] : 0.0;
-}
-
-__global__ void xk_mark_done(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-
-struct UpdateSpec {
-  const double *T;   // c x kdim measurement matrix over state columns [col0, col0+kdim)
-  long str, stc;
-  int c, kdim, col0;
-  const double *z;   // residual (device), stride sz
-  long sz;
-  const double *rdiag;  // device vector (c) or null -> rscalar
-  double rscalar;
-  const double *S;   // externally supplied innovation covariance (device, row stride ss, col stride 1)... or null
-  long ssr, ssc;
-  const double *Pin;  // n x n col-major
-  double *Pout;       // n x n col-major (may equal neither Pin)
-  const double *ct;   // device corr_total or null
-  int cov_update;
-  double *corr;       // where the correction goes: null -> h->d_corr (device); xk_apply_update passes pinned host memory
-  unsigned long long *done_flag;   // optional completion marker (pinned host memory) written by the last launch ...
-  unsigned long long done_seq;     // ... with this value
-  int tri;           // T is upper trapezoidal (T[r][k] == 0 for k < r: the compressed R): the products skip the zero blocks
-  int naux;          // range / sun rows of this update (d_aux) to append: launch_update applies [T ; rows] over all n columns
-};
-
-template <int RPL>
-
-static void launch_merge(xk_handle *h, XkCaqrArgs &a, int groups, int csplit) {
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_merge<RPL>), dim3(groups, csplit), dim3(16 * (16 + a.chalf)), 0, h->stream, a);
-}
-
-// QR compression of the staged tile stack (vio_updater.cpp:487-512): CAQR, panels of 16 columns.
-// fuse: (optional) the Kalman update that follows this compression.  If the single launch takes it along (narrow geometry,
-// correction_total = 0, covariance update, no external S), h->last_fused says so and the caller must NOT queue launch_update.
-// The last columns [ccut, C1) of a tall system in ONE launch or TWO (xk_caqr_pipe<XkPipeTail> / <XkPipeTail4>): the rows of slots
-// [slot0, slot0 + nslots) -- as the multi-launch schedule left them after the panels before ccut: R's rows zeroed where they were
-// taken out, the leaders' first 32 rows holding merged rows -- plus `nextra` rows from behind the slots (the R of the launch before)
-// are gathered into registers once, the panels run as in the single launch of the narrow systems, and rows ccut.. of R go to Rout
-// (row stride C1P, column ccut at Rout[0]).
-static int launch_pipe_tail(xk_handle *h, bool four, int ccut, int slot0, int nslots, int arity1, int nextra, double *Rout) {
-  XkCaqrPipeArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.A = h->d_A + (size_t)slot0 * h->DB * h->C1P + ccut; pa.tile_rows = h->d_tile_rows + slot0; pa.nslots = nslots; pa.slot_rows = h->DB;
-  pa.lead_stride = arity1;                        // (slot0 is a multiple of it)
-  pa.nextra = nextra; pa.extra_row0 = (long)(h->ntiles_max - slot0) * h->DB;
-  pa.Hc = nullptr; pa.hs = 0; pa.nhc = 0;
-  pa.C1P = h->C1P; pa.C1 = h->C1 - ccut; pa.Rout = Rout; pa.S = h->d_rs; pa.PB = h->d_rpb;
-  pa.status = h->d_status;
-  if (h->xsync_dirty) {
-    if (hipMemsetAsync(h->d_xsync, 0, sizeof(unsigned) * 2 * XP_WORDS * 16, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "sync words");
-    if (hipMemsetD32Async((hipDeviceptr_t)h->d_x1, (int)(XK_NOTYET_BITS & 0xffffffffu), 2 * 2 * h->xslab_doubles, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "slabs");
-    h->xsync_dirty = false; h->xsync_phase = 0;
-  }
-  {
-    const size_t np_ = (size_t)(pa.C1 + 15) / 16, strips_ = np_ * XK_PIPE_RLS, x1n = strips_ * 16 * h->C1P;
-    double *set = h->d_x1 + (size_t)h->xsync_phase * h->xslab_doubles;
-    pa.X1 = set; pa.X2 = set + x1n; pa.X1P = set + 2 * x1n;
-    pa.Xnext = h->d_x1 + (size_t)(h->xsync_phase ^ 1) * h->xslab_doubles;
-    pa.xnext_doubles = (long)h->xslab_doubles;
-  }
-  pa.sync = h->d_xsync + (size_t)h->xsync_phase * XP_WORDS * 16;
-  pa.sync_next = h->d_xsync + (size_t)(h->xsync_phase ^ 1) * XP_WORDS * 16;
-  h->xsync_phase ^= 1;
-  if (h->opt_poison) {   // test hook, as in the single launch of the narrow systems: every workgroup gives up at its first spin
-    const unsigned seven = 7u;
-    if (hipMemcpyAsync(pa.sync + XP_ABORT * 16, &seven, sizeof(unsigned), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "poison");
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "poison");
-  }
-  static const int pdbg2 = env_int("XK_CAQR_PERSIST_DBG", 0);
-  pa.dbg = pdbg2 ? h->d_pdbg : nullptr;
-  pa.test_stall = h->opt_test_stall;
-  h->pipe_tag = (h->pipe_tag % 0x7fff) + 1;
-  pa.acc_tag = h->pipe_tag;
-  h->pipe_rows_nominal = 0;                       // (the acceptance ratio belongs to the narrow geometries)
-  if (four) hipLaunchKernelGGL(xk_caqr_pipe<XkPipeTail4>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
-  else hipLaunchKernelGGL(xk_caqr_pipe<XkPipeTail>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
-  h->last_tail = true;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "caqr tail launch", e);
-  return XK_OK;
-}
-
-static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateSpec *fuse = nullptr) {
-  h->last_fused = false;
-  h->last_tail = false;
-  // A compression that xk_build_compress_async left for xk_apply_update is no longer pending once ANY compression runs (xk_apply_update
-  // takes the flag down before it comes here; an xk_qr_compress in between does the work now, and xk_apply_update then applies d_R as
-  // it stands instead of compressing rows the multi-launch schedule has already reduced in place).
-  h->compress_deferred = false;
-  if (!h->have_rows) return fail(h, XK_EINVAL, "xk_msckf_build has not run on the staged inputs");
-  const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
-  const int ntiles = h->K + h->K2 + slam_tiles;
-  h->split_active = 0;
-  h->last_empty = ntiles == 0;
-  if (ntiles == 0) {   // no measurement rows at all: [T_H | z] = 0 (the reference skips the update, updater.cpp:106)
-    if (hipMemsetAsync(h->d_R, 0, sizeof(double) * (size_t)h->C1P * h->C1P, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "R memset");
-    h->nleaf = 0; h->nlevels = 0; h->have_R = true; h->last_resident = false; h->last_pipe = false;
-    return XK_OK;
-  }
-  // (d_R was zeroed at creation; the merges rewrite the whole upper trapezoid every update and nothing else)
-  XkCaqrArgs a;
-  memset(&a, 0, sizeof(a));
-  a.A = h->d_A; a.tile_rows = h->d_tile_rows; a.ntiles = ntiles; a.TS = h->DB;
-  a.C1P = h->C1P; a.C1 = h->C1; a.Rout = h->d_R; a.dbg = nullptr;
-  static const int wt_env = env_int("XK_CAQR_WT", 0);
-  a.wt = wt_env;
-  {   // tallest tile: 2 L_max - 3 rows for the track tiles, full slots for packed SLAM rows
-    const int lmax = std::max(h->K > 0 ? h->h_pin_i[0] : 0, h->K2 > 0 ? h->h_pin_i[1] : 0);
-    a.rows_max = (h->M > 0) ? h->DB : std::min(h->DB, std::max(16, 2 * lmax - 3));
-  }
-  // first-level arity: 40 strips per workgroup once 20 x 20 no longer covers the stack in two levels
-  static const int arity1_env = env_int("XK_CAQR_ARITY1", 0);
-  const int arity1 = arity1_env ? arity1_env : (ntiles > 400 ? 40 : 20);
-  static const int chalf = env_int("XK_CAQR_CHALF", 8);
-  static const int overlap_env = env_int("XK_CAQR_OVERLAP", 1);
-  // per-tile kernel: 4 lanes per column, at most 192 (64-row tiles) / 128 (128-row tiles) columns per workgroup
-  const int tile_cols = (h->DB == 64) ? 192 : 128;
-  const int groups1 = (ntiles + arity1 - 1) / arity1;
-  // overlapped schedule (xk_caqr_fused): exactly two merge levels, the second one a single 20-way group
-  const bool overlap = overlap_env && (arity1 == 20 || arity1 == 40) && groups1 >= 2 && groups1 <= 20;
-  a.hole_stride = 0; a.lead_off = 0; a.lead_all = 0; a.pend = 0;
-  static const int skip_env = env_int("XK_CAQR_SKIP_REJECTED", 1);
-  a.lead_stride = skip_env ? arity1 : 0;
-  int launches = 0;
-  // register-resident single launch (xk_caqr_pipe.hip.h): MSCKF tracks only, valid rows <= 184 fat tiles of 128
-  const int resident_env = h->opt_resident;
-  const bool fast_shape = h->K + h->K2 > 0 || h->M > 0;
-  const int sp_mode = h->want_full_T ? 0 : h->plan;   // (latched at the build: what compressed_spec saw; xk_qr_compress: the whole stack)
-  const bool sp = sp_mode == 1;
-  if (sp_mode == 3) {
-    // a small stack, not compressed (see split_plan): tracks' rows by slot, MSCKF-SLAM tracks' behind them, then the SLAM rows
-    const int Rt = h->K > 0 ? 2 * h->h_trk_off[h->K] - 3 * h->K : 0;   // (h_trk_off holds nothing when no track is staged)
-    if (h->K > 0) hipLaunchKernelGGL(xk_stack_rows, dim3(h->K), dim3(256), 0, h->stream, h->d_A, h->d_tile_rows, h->d_trk_off, h->DB, h->C1P, 0, h->d_R2);
-    if (h->K2 > 0)
-      hipLaunchKernelGGL(xk_stack_rows, dim3(h->K2), dim3(256), 0, h->stream, h->d_A + (size_t)h->K * h->DB * h->C1P, h->d_tile_rows + h->K, h->d_trk2_off, h->DB,
-                         h->C1P, Rt, h->d_R2);
-    const long Rall = split_rows_nominal(h);
-    if (h->M > 0 && hipMemcpyAsync(h->d_R2 + (size_t)Rall * h->C1P, h->d_A + (size_t)(h->K + h->K2) * h->DB * h->C1P, sizeof(double) * 2 * (size_t)h->M * h->C1P,
-                                   hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-      return fail(h, XK_EDEVICE, "SLAM rows");
-    if (mid) hipEventRecord(mid, h->stream);
-    h->split_active = 3;
-    h->d_R2_dirty = true;                         // (rows below R1's diagonal and in the features' columns: the split compression never writes them)
-    h->nleaf = 0; h->nlevels = 0; h->have_R = true; h->last_resident = false; h->last_pipe = false;
-    hipError_t e3 = hipGetLastError();
-    if (e3 != hipSuccess) return fail(h, XK_EDEVICE, "stack rows", e3);
-    return XK_OK;
-  }
-  if (sp_mode == 2) {
-    // SLAM rows only: no compression (see split_plan) -- the rows as built are the system the update applies
-    if (hipMemcpyAsync(h->d_R2 + (size_t)6 * h->N * h->C1P, h->d_A, sizeof(double) * 2 * (size_t)h->M * h->C1P, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-      return fail(h, XK_EDEVICE, "SLAM rows");
-    if (mid) hipEventRecord(mid, h->stream);
-    h->split_active = 2;
-    h->nleaf = 0; h->nlevels = 0; h->have_R = true; h->last_resident = false; h->last_pipe = false;
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return fail(h, XK_EDEVICE, "SLAM rows", e2);
-    return XK_OK;
-  }
-  if (resident_env && !h->persist_ok && h->fast_capable && h->rearm_after > 0 && fast_shape && ++h->clean_classic > h->rearm_after) {
-    h->persist_ok = true;                         // (the sync words of a launch that gave up are cleared below)
-    h->clean_classic = 0;
-  }
-  if (resident_env && h->persist_ok && fast_shape) {
-    // The launch compacts the stack itself (xk_pipe_rowplan: rows of rejected tracks cost nothing), so what the tiles must hold
-    // is the rows that PASS the gates -- which the host does not know when it queues the launch.  It queues on the nominal count
-    // (every track accepted) up to a quarter over the capacity; a launch that finds more accepted rows than its tiles hold gives
-    // up at once (reason 9) and the multi-launch schedule serves the update -- and the following ones of that size.
-    // (split compression, see xk_handle::d_R2: the tracks' rows only, in the pose columns + the residual)
-    const int C1s = sp ? 6 * h->N + 1 : h->C1, nslots_p = sp ? h->K + h->K2 : ntiles;
-    const bool narrow = C1s <= XkPipeNarrow::COLS;
-    const int rows_cap = narrow ? XkPipeNarrow::ROWS : XkPipeWide::ROWS;
-    int R_nom = sp ? 0 : 2 * h->M;
-    for (int k = 0; k < h->K; ++k) R_nom += 2 * (h->h_trk_off[k + 1] - h->h_trk_off[k]) - 3;
-    for (int k = 0; k < h->K2; ++k) R_nom += 2 * (h->h_trk2_off[k + 1] - h->h_trk2_off[k]) - 3;
-    // two first-level groups per XCD when the rows expected to pass fit 152 tiles (2 % and half a tile's worth of margin); a launch
-    // that finds more gives up at once (reason 9) and that geometry stays off for a while -- the 184-tile launch redoes the update
-    bool split = false;
-    if (narrow && h->opt_split > 0) {
-      if (h->split_backoff > 0) --h->split_backoff;
-      else if (h->opt_split >= 3) split = true;                              // (lab: always -- a stack that does not fit gives up, reason 9)
-      else if (h->opt_split == 2) split = R_nom <= XkPipeNarrow2::ROWS;
-      else if (h->acc_ratio > 0.0) split = (long)(h->acc_ratio * 1.02 * R_nom) + 64 <= XkPipeNarrow2::ROWS;
-    }
-    const int NTP = 8 * (narrow ? (split ? XkPipeNarrow2::NT : XkPipeNarrow::NT) : XkPipeWide::NT);
-    h->pipe_rows_nominal = R_nom;
-    if (R_nom >= h->opt_pipe_min_rows && nslots_p <= XK_PIPE_SLOTS_MAX && (long)R_nom * 4 <= (long)rows_cap * 5 && (h->overflow_rows == 0 || R_nom < h->overflow_rows)) {
-      XkCaqrPipeArgs pa;
-      memset(&pa, 0, sizeof(pa));
-      pa.A = h->d_A; pa.tile_rows = h->d_tile_rows; pa.nslots = nslots_p; pa.slot_rows = 64;   // (no leaders, no extra rows: lead_stride = nextra = 0)
-      pa.Hc = h->d_Hc; pa.hs = h->hc_stride; pa.nhc = h->rows_compact ? h->K : 0;
-      pa.C1P = h->C1P; pa.C1 = C1s; pa.Rout = sp ? h->d_R2 : h->d_R; pa.S = h->d_rs; pa.PB = h->d_rpb;
-      pa.res_col = sp ? h->na : 0;
-      h->split_active = sp ? 1 : 0;
-      pa.status = h->d_status;
-      if (h->xsync_dirty) {
-        if (hipMemsetAsync(h->d_xsync, 0, sizeof(unsigned) * 2 * XP_WORDS * 16, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "sync words");
-        // (a launch that gave up leaves its slabs half written and the other set half re-armed: arm both)
-        if (hipMemsetD32Async((hipDeviceptr_t)h->d_x1, (int)(XK_NOTYET_BITS & 0xffffffffu), 2 * 2 * h->xslab_doubles, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "slabs");
-        h->xsync_dirty = false; h->xsync_phase = 0;
-      }
-      {
-        // (panels of THIS launch's system: the launch re-arms the other set by the same count, xk_caqr_pipe entry)
-        const size_t np_ = (size_t)(C1s + 15) / 16, strips_ = np_ * XK_PIPE_RLS, x1n = strips_ * 16 * h->C1P;
-        double *set = h->d_x1 + (size_t)h->xsync_phase * h->xslab_doubles;
-        pa.X1 = set; pa.X2 = set + x1n; pa.X1P = set + 2 * x1n;
-        pa.Xnext = h->d_x1 + (size_t)(h->xsync_phase ^ 1) * h->xslab_doubles;
-        pa.xnext_doubles = (long)h->xslab_doubles;
-      }
-      pa.sync = h->d_xsync + (size_t)h->xsync_phase * XP_WORDS * 16;
-      pa.sync_next = h->d_xsync + (size_t)(h->xsync_phase ^ 1) * XP_WORDS * 16;
-      h->xsync_phase ^= 1;
-      // test hook: raise the abort word before the launch -- every workgroup gives up at its first spin, exactly what an
-      // uneven placement or a missing workgroup leads to, and the host has to redo the update with the multi-launch schedule
-      if (h->opt_poison) {
-        const unsigned seven = 7u;
-        if (hipMemcpyAsync(pa.sync + XP_ABORT * 16, &seven, sizeof(unsigned), hipMemcpyHostToDevice, h->stream) != hipSuccess)
-          return fail(h, XK_EDEVICE, "poison");
-        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "poison");
-      }
-      static const int pdbg2 = env_int("XK_CAQR_PERSIST_DBG", 0);
-      pa.dbg = pdbg2 ? h->d_pdbg : nullptr;
-      pa.test_stall = h->opt_test_stall;
-      h->pipe_tag = (h->pipe_tag % 0x7fff) + 1;               // 1 .. 32767: tags the accepted-rows word of THIS launch (eval_status)
-      pa.acc_tag = h->pipe_tag;
-      pa.kal = 0; pa.kn = h->n; pa.Pin = nullptr; pa.Pout = nullptr; pa.sigma2 = 0.0; pa.corr = nullptr; pa.ct = nullptr; pa.done_flag = nullptr; pa.done_seq = 0;
-      if (fuse && narrow && h->opt_kalman && !fuse->S && !fuse->rdiag && !fuse->naux && fuse->T == h->d_R &&
-          h->n <= 206 && h->n_cu == 256) {
-        // (a pass that leaves the covariance alone, cov_update = 0: the role needs the block-by-block posterior to get the
-        //  correction right, so it runs as ever and its posterior goes to a scratch matrix; Pout becomes a copy of the prior below)
-        pa.kal = 1; pa.Pin = fuse->Pin; pa.Pout = fuse->cov_update ? fuse->Pout : h->d_tmpP; pa.sigma2 = fuse->rscalar; pa.ct = fuse->ct;
-        pa.corr = fuse->corr ? fuse->corr : h->d_corr;
-        pa.done_flag = fuse->done_flag; pa.done_seq = fuse->done_seq;
-        h->last_fused = true;
-      }
-      h->last_split = split;
-      if (sp && h->d_R2_dirty) {
-        // the launch writes R1's upper trapezoid and the residual column only, and the update reads rows [0, 6 N) whole (u.tri = 0)
-        if (hipMemsetAsync(h->d_R2, 0, sizeof(double) * (size_t)6 * h->N * h->C1P, h->stream) != hipSuccess) return fail(h, XK_EDEVICE, "R2 memset");
-        h->d_R2_dirty = false;
-      }
-      if (split) hipLaunchKernelGGL(xk_caqr_pipe<XkPipeNarrow2>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
-      else if (narrow) hipLaunchKernelGGL(xk_caqr_pipe<XkPipeNarrow>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
-      else hipLaunchKernelGGL(xk_caqr_pipe<XkPipeWide>, dim3(h->n_cu), dim3(XK_PIPE_THREADS), 0, h->stream, pa);
-      if (sp) {
-        // the SLAM features' rows go into the compressed system as they were built: 2 M rows behind R1's 6 N (BEHIND the launch: row 6 N
-        // of its output -- the residual column's own row of R, which nobody reads -- is the first of them)
-        const int slam0 = h->K + h->K2;
-        if (hipMemcpyAsync(h->d_R2 + (size_t)6 * h->N * h->C1P, h->d_A + (size_t)slam0 * h->DB * h->C1P, sizeof(double) * 2 * (size_t)h->M * h->C1P,
-                           hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-          return fail(h, XK_EDEVICE, "SLAM rows");
-      }
-      if (pa.kal && !fuse->cov_update && fuse->Pout != fuse->Pin &&
-          hipMemcpyAsync(fuse->Pout, fuse->Pin, sizeof(double) * (size_t)h->n * h->n, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-        return fail(h, XK_EDEVICE, "prior copy");
-      if (mid) hipEventRecord(mid, h->stream);
-      h->nleaf = NTP; h->nlevels = 1; h->have_R = true; h->last_resident = true; h->last_pipe = true;
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return fail(h, XK_EDEVICE, "caqr launch", e);
-      return XK_OK;
-    }
-  }
-  // (the tiles of the tracks may be factor records: the first tile pass below forms its rows from them and leaves tiles behind)
-  a.Hc = h->d_Hc; a.hs = h->hc_stride; a.hcvr = xk_hc_vr(h->DB); a.nhc = (h->rows_compact && h->K > 0) ? h->K : 0;
-  h->rows_compact = false;
-  // 128-row slots whose tallest tile has <= 104 rows: 26 rows per lane (two workgroups per CU), see xk_caqr_tile
-  const int tall26_env = h->opt_tall26;
-  auto tile_geom = [&](int c0, int &tsplit, int &tchalf, int &tthreads) {
-    const int trail = std::max(0, h->C1 - c0 - 16);
-    tsplit = std::max(1, (trail + (tile_cols - 16) - 1) / (tile_cols - 16));
-    tchalf = (trail + tsplit - 1) / tsplit;
-    tthreads = round_up(4 * (16 + tchalf), 64);
-  };
-  auto launch_tile = [&](XkCaqrArgs &t) {
-    int tsplit, tthreads;
-    tile_geom(t.c0, tsplit, t.chalf, tthreads);
-    const dim3 tgrid(ntiles, tsplit), tblock(tthreads);
-    if (h->DB == 64) {
-      if (tsplit == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_tile<16, false>), tgrid, tblock, 0, h->stream, t);
-      else hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_tile<16, true>), tgrid, tblock, 0, h->stream, t);
-    } else if (t.rows_max <= 104 && tall26_env) {
-      if (tsplit == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_tile<26, false>), tgrid, tblock, 0, h->stream, t);
-      else hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_tile<26, true>), tgrid, tblock, 0, h->stream, t);
-    } else {
-      if (tsplit == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_tile<32, false>), tgrid, tblock, 0, h->stream, t);
-      else hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_tile<32, true>), tgrid, tblock, 0, h->stream, t);
-    }
-  };
-  // Tall systems: the LAST columns in one launch with every row in registers (xk_caqr_pipe<XkPipeTail>, xk_caqr_pipe.hip.h).  ccut =
-  // first column the tail takes (a panel boundary; 0: no tail).  Like the single launch of the narrow systems it is queued on the
-  // nominal row count up to 5/4 of its capacity -- the launch counts the rows that passed the gates itself and gives up at once
-  // (reason 9) when they do not fit -- and only reads the stack: a tail that gives up is redone from the rows as they stand.
-  int ccut = 0, tail_half = 0;                    // tail_half > 0: two launches, slots [0, tail_half) then [tail_half, ntiles) + the first one's R
-  if (h->tail_capable && !h->tail_ok && h->opt_resident && h->opt_tail && h->rearm_after > 0 && h->tail_backoff == 0 && ++h->tail_clean > h->rearm_after) {
-    h->tail_ok = true;
-    h->tail_clean = 0;
-  }
-  if (h->tail_backoff > 0) --h->tail_backoff;
-  else if (overlap && h->tail_ok && h->opt_resident && h->opt_tail && ntiles <= XK_PIPE_SLOTS_MAX) {
-    // nominal rows (every track accepted) of the slots before each group boundary -- MSCKF tracks, then tracks that become features,
-    // then the SLAM rows packed DB to a slot (vio_updater.cpp:406-422) --; a leader's first 32 rows count whatever its slot holds
-    std::vector<long> pre((size_t)groups1 + 1, 0);
-    auto slot_rows_nominal = [&](int t) {
-      if (t < h->K) return 2 * (h->h_trk_off[t + 1] - h->h_trk_off[t]) - 3;
-      if (t < h->K + h->K2) return 2 * (h->h_trk2_off[t - h->K + 1] - h->h_trk2_off[t - h->K]) - 3;
-      return std::min(h->DB, 2 * h->M - (t - h->K - h->K2) * h->DB);
-    };
-    for (int g = 0; g < groups1; ++g) {
-      long r = 0;
-      for (int t = g * arity1; t < std::min(ntiles, (g + 1) * arity1); ++t) {
-        const int v = slot_rows_nominal(t);
-        r += (t % arity1 == 0) ? std::max(v, 32) : v;
-      }
-      pre[g + 1] = pre[g] + r;
-    }
-    const long R_nom = pre[groups1];
-    if (R_nom >= 64 * 8) {
-    const int cc4 = 16 * std::max(1, (h->C1 - XkPipeTail4::COLS + 15) / 16), cc8 = 16 * ((h->C1 - XkPipeTail::COLS + 15) / 16);
-    const int nx = h->C1 - cc4;                   // rows of the first launch's R
-    int gh = 0;                                   // groups in the first half: the boundary that balances first half against second half + R
-    for (int g = 1; g < groups1; ++g)
-      if (std::labs(2 * pre[g] - R_nom - nx) < std::labs(2 * pre[gh] - R_nom - nx) || gh == 0) gh = g;
-    const long capq = (long)XkPipeTail4::ROWS * 5 / 4;
-    h->tail_four = false;
-    if (h->opt_tail != 2 && R_nom * 4 <= (long)XkPipeTail4::ROWS * 5) { ccut = cc4; tail_half = 0; h->tail_four = true; }   // (the whole stack fits one 192-column launch)
-    else if (h->opt_tail != 2 && gh > 0 && pre[gh] <= capq && R_nom - pre[gh] + nx <= capq) { ccut = cc4; tail_half = gh * arity1; h->tail_four = true; }
-    else if (cc8 >= 16 && R_nom * 4 <= (long)XkPipeTail::ROWS * 5) { ccut = cc8; tail_half = 0; }
-    if (ccut >= h->C1) ccut = 0;
-    }
-  }
-  h->last_tail = false;
-  if (overlap) {
-    a.rows_max = std::max(a.rows_max, 32);        // a leader's pivot strip alternates between rows 0..15 and 16..31
-    for (int c0 = 0, k = 0; c0 < h->C1; c0 += 16, ++k) {
-      const int trail = std::max(0, h->C1 - c0 - 16);
-      const int csplit = std::max(1, (trail + chalf - 1) / chalf);
-      // last level inside the fused launch: 32 lanes per column next to 64-row tiles (768-thread workgroups),
-      // 16 next to 128-row tiles (512-thread workgroups); whole waves either way
-      // (2 trailing columns per workgroup next to 64-row tiles: 9 waves; measured 22.5 us per fused launch against
-      //  23.4 at 4-8 columns -- the fewer waves share a step, the shorter it is, and there are CUs to spare)
-      static const int lchalf_env = env_int("XK_CAQR_LCHALF", 0);
-      const int llanes = (h->DB == 64) ? 32 : 16;
-      // (about 84 last-level workgroups at most: wider systems take more columns per workgroup)
-      const int lauto = std::min(8, 2 * std::max(1, (trail + 2 * 84 - 1) / (2 * 84)));
-      const int lchalf = (h->DB == 64) ? std::min(8, 2 * std::max(1, (lchalf_env ? lchalf_env : lauto) / 2))
-                                       : std::min(16, 4 * std::max(1, (lchalf_env ? lchalf_env : 16) / 4));   // (16: config 3 418 -> 425 updates/s against 8, round 5 sweep)
-      const int lsplit = std::max(1, (trail + lchalf - 1) / lchalf);
-      const int lead_off = (k & 1) ? 16 : 0;
-      if (k == 0) {
-        XkCaqrArgs t = a;
-        t.c0 = 0; t.stride = 1; t.final_level = 0; t.pin = nullptr; t.pout = h->d_panel[0];
-        launch_tile(t);
-        if (mid) hipEventRecord(mid, h->stream);
-      }
-      XkCaqrArgs m = a;                            // first level: leaders' pivot strips at lead_off, + the pending strips
-      // columns per workgroup: at least `chalf`, and enough that groups x splits fits one workgroup per CU -- two
-      // merge workgroups on a CU run ~1.6x longer than one (28.8 us at 420 workgroups, 17-19 us below 256)
-      static const int adapt = env_int("XK_CAQR_ADAPT", 1);
-      static const int cus = env_int("XK_CAQR_CUS", 256);
-      const int per_cu = std::max(1, cus / groups1);
-      const int mchalf = adapt ? std::min(arity1 == 40 ? 16 : 32, std::max(chalf, 2 * ((trail + 2 * per_cu - 1) / (2 * per_cu)))) : chalf;
-      const int msplit = std::max(1, (trail + mchalf - 1) / mchalf);
-      m.c0 = c0; m.stride = 1; m.final_level = 0; m.pin = h->d_panel[0]; m.pout = h->d_panel[1]; m.chalf = mchalf;
-      m.lead_off = lead_off; m.lead_all = 0; m.pend = (k > 0) ? 1 : 0;
-      static const int m32_env = env_int("XK_CAQR_M32", 1);
-      if (arity1 == 40 && m32_env) hipLaunchKernelGGL(xk_caqr_merge32, dim3(groups1, msplit), dim3(32 * (16 + mchalf)), 0, h->stream, m);
-      else if (arity1 == 40) launch_merge<42>(h, m, groups1, msplit);
-      else launch_merge<22>(h, m, groups1, msplit);
-      ++launches;
-      XkCaqrArgs l = a;                            // last level: the leaders' pivot strips -> 16 rows of R
-      l.c0 = c0; l.stride = arity1; l.final_level = 1; l.pin = h->d_panel[1]; l.pout = h->d_panel[0]; l.chalf = lchalf;
-      l.lead_off = lead_off; l.lead_all = 1; l.pend = 0;
-      if (ccut > 0 && c0 + 16 == ccut) {
-        // the last panel of the multi-launch part: its last level alone, then the tail launch takes the stack as it stands
-        launch_merge<20>(h, l, 1, lsplit);
-        ++launches;
-        int rct;
-        if (tail_half > 0) {
-          double *Ra = h->d_A + (size_t)h->ntiles_max * h->DB * h->C1P + ccut;           // the first launch's R: behind the slots
-          rct = launch_pipe_tail(h, true, ccut, 0, tail_half, arity1, 0, Ra);
-          if (rct == XK_OK) rct = launch_pipe_tail(h, true, ccut, tail_half, ntiles - tail_half, arity1, h->C1 - ccut, h->d_R + (size_t)ccut * h->C1P + ccut);
-          ++launches;
-        } else rct = launch_pipe_tail(h, h->tail_four, ccut, 0, ntiles, arity1, 0, h->d_R + (size_t)ccut * h->C1P + ccut);
-        if (rct != XK_OK) return rct;
-        ++launches;
-        break;
-      }
-      if (c0 + 16 < h->C1) {
-        XkCaqrArgs t = a;                          // ... next to the tile step of the next panel
-        t.c0 = c0 + 16; t.stride = 1; t.final_level = 0; t.pin = nullptr; t.pout = h->d_panel[0];
-        t.hole_stride = arity1; t.lead_off = 16 - lead_off;
-        int tsplit, tthreads;
-        tile_geom(t.c0, tsplit, t.chalf, tthreads);
-                const dim3 grid(lsplit + ntiles * tsplit), block(std::max(tthreads, round_up(llanes * (16 + lchalf), 64)));
-        if (h->DB == 64) {
-          if (tsplit == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_fused<16, false>), grid, block, 0, h->stream, t, l, lsplit, tsplit);
-          else hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_fused<16, true>), grid, block, 0, h->stream, t, l, lsplit, tsplit);
-        } else if (t.rows_max <= 104 && tall26_env) {
-          if (tsplit == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_fused<26, false>), grid, block, 0, h->stream, t, l, lsplit, tsplit);
-          else hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_fused<26, true>), grid, block, 0, h->stream, t, l, lsplit, tsplit);
-        } else {
-          if (tsplit == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_fused<32, false>), grid, block, 0, h->stream, t, l, lsplit, tsplit);
-          else hipLaunchKernelGGL(HIP_KERNEL_NAME(xk_caqr_fused<32, true>), grid, block, 0, h->stream, t, l, lsplit, tsplit);
-        }
-      } else {
-        launch_merge<20>(h, l, 1, lsplit);
-      }
-      ++launches;
-    }
-  } else {
-    for (int c0 = 0; c0 < h->C1; c0 += 16) {
-      const int trail = std::max(0, h->C1 - c0 - 16);
-      a.c0 = c0; a.stride = 1; a.final_level = 0; a.pin = nullptr; a.pout = h->d_panel[0];
-      launch_tile(a);
-      if (c0 == 0 && mid) hipEventRecord(mid, h->stream);
-      if (c0 > 0) ++launches;                                        // (the first tile launch is timed as its own stage)
-      a.chalf = chalf;
-      const int csplit = std::max(1, (trail + a.chalf - 1) / a.chalf);
-      int stride = 1, level = 0;
-      do {
-        const int left = (ntiles + stride - 1) / stride;             // strips still alive at this level
-        const int arity = (stride == 1) ? arity1 : (left > 20 ? 40 : 20);
-        a.stride = stride;
-        a.final_level = (left <= arity) ? 1 : 0;
-        const int groups = (left + arity - 1) / arity;
-        a.pin = h->d_panel[level & 1];
-        a.pout = h->d_panel[(level + 1) & 1];
-        ++level;
-        if (arity == 40) launch_merge<40>(h, a, groups, csplit);
-        else launch_merge<20>(h, a, groups, csplit);
-        ++launches;
-        stride *= arity;
-      } while (stride < ntiles);
-    }
-  }
-  h->nleaf = ntiles;
-  h->nlevels = launches;
-  h->have_R = true;
-  h->last_resident = false; h->last_pipe = h->last_tail;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "caqr launch", e);
-  return XK_OK;
-}
+// ---------------------------------------------------------------------------
+// compression of the staged rows: schedules, the system they leave for the update, status words
+// ---------------------------------------------------------------------------
+#include "xk_compress.hip.h"
 
 static void gemm(xk_handle *h, const XkGemmArgs &g) {
   const int tiles = xk_gemm_grid(g);
@@ -1453,8 +808,7 @@ static void gemm(xk_handle *h, const XkGemmArgs &g) {
 
 // Kalman algebra on the device (updater.cpp:117-141 / :144-161).  ev (optional)
 // = {before, after-gemm-part...} is not used here; stage split is timed by the caller.
-static int launch_update(xk_handle *h, const UpdateSpec &u_in, float *gemm_ms_accum = nullptr) {
-  (void)gemm_ms_accum;
+static int launch_update(xk_handle *h, const UpdateSpec &u_in) {
   UpdateSpec u = u_in;
   if (u.naux > 0) {
     // the range / sun rows join the system as built (they never go through the QR): [T ; H_aux]^T [T ; H_aux] is the Gram matrix of the
@@ -1565,137 +919,6 @@ static int launch_update(xk_handle *h, const UpdateSpec &u_in, float *gemm_ms_ac
   return XK_OK;
 }
 
-// Will the compression of the staged update take the split form?  Evaluated once per build (launch_build latches it in h->plan) for
-// compressed_spec -- which callers evaluate BEFORE launch_compress -- and for launch_compress itself; it repeats the conditions under
-// which the single launch is taken at all (a split system goes nowhere else).
-static int split_geometry_rows(const xk_handle *h) { return 6 * h->N + 1 <= XkPipeNarrow::COLS ? XkPipeNarrow::ROWS : XkPipeWide::ROWS; }
-static long split_rows_nominal(const xk_handle *h) {
-  long r = 0;
-  for (int k = 0; k < h->K; ++k) r += 2 * (h->h_trk_off[k + 1] - h->h_trk_off[k]) - 3;
-  for (int k = 0; k < h->K2; ++k) r += 2 * (h->h_trk2_off[k + 1] - h->h_trk2_off[k]) - 3;
-  return r;
-}
-static int split_plan(const xk_handle *h) {
-  if (!h->d_R2 || !h->opt_slam_split || h->want_full_T) return 0;
-  // 3: a SMALL stack -- a handful of tracks ended this frame (+ the SLAM rows): nominal rows <= n.  Not compressed either (the same branch of
-  // vio_updater.cpp:487; the reference counts accepted rows, this counts nominal ones: it cannot wait for the verdicts): rows as built -> update.
-  if (h->K + h->K2 > 0) {
-    const long R = split_rows_nominal(h) + 2L * h->M;
-    if (R <= std::min(h->n, h->CM)) return 3;
-  }
-  if (h->M <= 0) return 0;
-  // 2: the stack is the SLAM features' rows and nothing else (no track ended this frame -- the common frame of a filter with persistent
-  // features): 2 M rows against n > 3 M columns.  The reference compresses only when rows > columns (vio_updater.cpp:487); neither does this:
-  // the rows go to the update as built, no QR launch at all (any n, any window).
-  if (h->K + h->K2 == 0) return 2 * h->M <= h->CM ? 2 : 0;
-  if (h->DB != 64 || !h->opt_resident || !h->persist_ok) return 0;
-  if (h->n <= 206 || 6 * h->N + 1 > XkPipeWide::COLS) return 0;
-  const long R = split_rows_nominal(h);
-  return (R >= h->opt_pipe_min_rows && h->K + h->K2 <= XK_PIPE_SLOTS_MAX && R * 4 <= (long)split_geometry_rows(h) * 5 &&
-          (h->overflow_rows == 0 || R < h->overflow_rows)) ? 1 : 0;
-}
-
-static UpdateSpec compressed_spec_base(xk_handle *h, const double *d_ct, int cov_update);
-static UpdateSpec compressed_spec(xk_handle *h, const double *d_ct, int cov_update) {
-  UpdateSpec u = compressed_spec_base(h, d_ct, cov_update);
-  if (h->naux > 0) {
-    u.naux = h->naux;
-    if (h->K + h->K2 + h->M == 0) u.c = 0;        // (no visual row at all: the update is the range / sun rows alone)
-  }
-  return u;
-}
-static UpdateSpec compressed_spec_base(xk_handle *h, const double *d_ct, int cov_update) {
-  UpdateSpec u;
-  memset(&u, 0, sizeof(u));
-  if (const int mode = h->have_R ? h->split_active : h->plan) {
-    // the split form (d_R2): 6 N rows of R1 over the pose columns, then the 2 M rows of the SLAM features as built; mode 2: those rows alone
-    const int r0 = mode == 2 ? 6 * h->N : 0;
-    u.T = h->d_R2 + (size_t)r0 * h->C1P; u.str = h->C1P; u.stc = 1;
-    u.c = mode == 3 ? (int)split_rows_nominal(h) + 2 * h->M : 6 * h->N + 2 * h->M - r0;   // (3: every track's rows, then the SLAM rows)
-    u.kdim = h->na; u.col0 = XK_CORE;
-    u.z = u.T + h->na; u.sz = h->C1P;
-    u.rdiag = nullptr; u.rscalar = h->sigma_img * h->sigma_img;    // the SLAM rows carry sigma_img^2 too (slam_update.cpp: r = var_img I)
-    u.Pin = h->d_P; u.Pout = h->d_Pout; u.ct = d_ct; u.cov_update = cov_update;
-    u.tri = 0;                                     // (the SLAM rows are not below anybody's diagonal)
-    return u;
-  }
-  u.T = h->d_R; u.str = h->C1P; u.stc = 1;      // R[0], rows 0..na-1, active columns
-  u.c = h->na; u.kdim = h->na; u.col0 = XK_CORE;
-  u.z = h->d_R + h->na; u.sz = h->C1P;           // residual column
-  u.rdiag = nullptr; u.rscalar = h->sigma_img * h->sigma_img;  // vio_updater.cpp:508-509
-  u.Pin = h->d_P; u.Pout = h->d_Pout; u.ct = d_ct; u.cov_update = cov_update;
-  u.tri = 1;                                      // d_R: zero below the diagonal (zeroed at creation, only the trapezoid is ever written)
-  return u;
-}
-
-#define XK_RETRY_CLASSIC 1000   // internal: the single-launch CAQR gave up, the multi-launch schedule must redo the update
-static int eval_status(xk_handle *h, int st, int pst, bool allow_retry) {
-  // What the last single launch found (status word 2): accepted rows in the low 15 bits, the launch's tag above them.  The word is a
-  // relaxed system-scope store of a tile workgroup, not ordered with the completion marker (another workgroup's store): a count that
-  // carries another launch's tag is a late arrival and is left alone -- it must not be divided by THIS launch's nominal rows.
-  if (h->last_pipe && h->pipe_rows_nominal > 0) {
-    const int w2 = h->d_status[2];
-    if (w2 > 0 && (w2 >> 15) == h->pipe_tag) h->acc_ratio = (double)(w2 & 0x7fff) / h->pipe_rows_nominal;
-  }
-  if (pst == 0 && h->last_tail) h->tail_backoff_len = 64;      // (a tail that ran through: the next overflow starts at 64 updates off again)
-  if (st != 0 || pst != 0) {
-    hipStreamSynchronize(h->stream);
-    h->d_status[0] = h->d_status[1] = 0;
-  }
-  if (pst != 0) {
-    // reasons: 1 grid not resident, 2 XCD barrier, 3 uneven XCD placement, 4/5 waiting for the last / first level
-    // The fast path steps aside, but not for the life of the handle: after `rearm_after` clean multi-launch updates it is
-    // tried again (the other tenant of the GPU may be gone); every further give-up doubles that distance, so a permanently
-    // shared GPU costs one bounded retry (<= 2 ms, xk_spin_ge) every few thousand updates at most.
-    if (h->last_tail) {
-      // the tail launch of a tall system gave up: it only READ the stack, but the retry below rebuilds the rows anyway (one code path);
-      // reason 9 = more rows passed the gates than its tiles hold -- off for the next 64 updates; anything else = co-residency
-      if (pst == 9) { h->tail_backoff = std::max(64, h->tail_backoff_len); h->tail_backoff_len = std::min(4096, 2 * std::max(64, h->tail_backoff_len)); }
-      else { h->tail_ok = false; h->tail_clean = -1; if (h->fast_giveups >= 1) h->rearm_after = std::min(4096, std::max(1, h->rearm_after) * 2); }
-      h->fast_giveups++; h->fast_reason = pst;
-      h->xsync_dirty = true;
-      h->have_rows = h->have_R = false;
-      snprintf(h->err, sizeof(h->err), "single-launch CAQR tail gave up (reason %d); the multi-launch schedule finishes the factorisation", pst);
-      return allow_retry ? XK_RETRY_CLASSIC : XK_EDEVICE;
-    }
-    if (pst == 9 && h->last_split) {
-      // the 152-tile geometry was chosen on the LAST update's acceptance ratio and this update passed more: not a co-residency
-      // problem and not a capacity cliff of the fast path -- the 184-tile launch redoes the update, the split geometry stays off
-      // for the next 64 updates
-      h->split_backoff = 64;
-      h->fast_giveups++; h->fast_reason = pst;
-      h->xsync_dirty = true;
-      h->have_rows = h->have_R = false;
-      snprintf(h->err, sizeof(h->err), "single-launch CAQR (152 tiles): more rows passed the gates than expected; redone with 184 tiles");
-      return allow_retry ? XK_RETRY_CLASSIC : XK_EDEVICE;
-    }
-    if (pst == 9) {
-      // not a co-residency problem: more rows passed the gates than the tiles of the single launch hold.  The fast path stays
-      // armed for smaller stacks; this size goes to the multi-launch schedule from now on.
-      h->overflow_rows = h->overflow_rows ? std::min(h->overflow_rows, h->pipe_rows_nominal) : h->pipe_rows_nominal;
-      h->fast_giveups++; h->fast_reason = pst;
-      h->xsync_dirty = true;
-      h->have_rows = h->have_R = false;
-      snprintf(h->err, sizeof(h->err), "single-launch CAQR: %d nominal rows held more accepted rows than its tiles; multi-launch schedule from that size on", h->pipe_rows_nominal);
-      return allow_retry ? XK_RETRY_CLASSIC : XK_EDEVICE;
-    }
-    h->persist_ok = false;
-    h->fast_giveups++; h->fast_reason = pst; h->clean_classic = -1;   // (-1: the retry of THIS update is not a clean update)
-    if (h->fast_giveups > 1) h->rearm_after = std::min(4096, std::max(1, h->rearm_after) * 2);
-    h->xsync_dirty = true;
-    h->have_rows = h->have_R = false;
-    snprintf(h->err, sizeof(h->err), "single-launch CAQR gave up (reason %d): workgroups not co-resident; multi-launch schedule for the next %d updates", pst, h->rearm_after);
-    return allow_retry ? XK_RETRY_CLASSIC : XK_EDEVICE;
-  }
-  if (st != 0) return fail(h, st, "innovation covariance not positive definite");
-  return XK_OK;
-}
-static int read_status(xk_handle *h, bool allow_retry = false) {
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  stage_stream_idle(h);
-  return eval_status(h, h->d_status[0], h->d_status[1], allow_retry);
-}
-
 static int fetch_flags(xk_handle *h, int *inl, double *gam, int *inls, double *gams) {
   if (h->K > 0 && inl) HIPCHK(h, hipMemcpyAsync(inl, h->d_inl, sizeof(int) * h->K, hipMemcpyDeviceToHost, h->stream));
   if (h->K > 0 && gam) HIPCHK(h, hipMemcpyAsync(gam, h->d_gam, sizeof(double) * h->K, hipMemcpyDeviceToHost, h->stream));
@@ -1778,7 +1001,7 @@ extern "C" int xk_build_compress_async(xk_handle *h, double sigma_img) {
   // covariance -- the gates have read the prior in the per-feature kernel above -- so where the single launch can take the Kalman
   // update along (narrow geometry, n <= 206) the compression is not queued now but by xk_apply_update, behind those entries, with
   // the Kalman role on the covariance they left: one launch there instead of one here and five there.
-  h->compress_deferred = h->opt_resident && h->persist_ok && h->opt_kalman && h->C1 <= XkPipeNarrow::COLS && h->n <= 206 && h->n_cu == 256 &&
+  h->compress_deferred = h->opt_resident && h->persist_ok && kalman_rides(h) &&
                          h->K + h->K2 + h->M > 0 && h->plan < 2 &&   // (stacks that are not compressed at all: nothing to defer)
                          h->naux == 0;   // (range / sun rows: the update is not taken along by the launch anyway)
   if (h->compress_deferred) h->have_R = true;     // (as far as xk_apply_update's precondition goes: it runs the compression itself)
@@ -1814,7 +1037,7 @@ static int build_compress_update_pass(xk_handle *h, double sigma_img, const doub
   static const int spin_env = env_int("XK_SPIN_DONE", 1);
   if (spin_env) { u.done_flag = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2); u.done_seq = ++h->done_seq; }
   if ((rc = launch_compress(h, nullptr, &u)) != XK_OK) return rc;
-  if (!h->last_fused && (rc = launch_update(h, u)) != XK_OK) return rc;
+  if (!h->last.fused && (rc = launch_update(h, u)) != XK_OK) return rc;
   h->async_pending = true;
   h->fused_pending = true;
   h->fused_seq = spin_env ? u.done_seq : 0;
@@ -1940,7 +1163,7 @@ extern "C" int xk_apply_update(xk_handle *h, const double *corr_total, int cov_u
       if (spin_env) { u.done_flag = done; u.done_seq = ++h->done_seq; }
       if (deferred && attempt == 0) {                      // the compression xk_build_compress_async left for now, Kalman role inside
         if ((rc = launch_compress(h, nullptr, &u)) != XK_OK) return rc;
-        rc = h->last_fused ? XK_OK : launch_update(h, u);
+        rc = h->last.fused ? XK_OK : launch_update(h, u);
       } else rc = launch_update(h, u);
       if (rc != XK_OK) return rc;
     }
@@ -1983,7 +1206,7 @@ extern "C" int xk_visual_update_staged(xk_handle *h, double sigma_img, double *c
   HIPCHK(h, hipSetDevice(h->device));
   if (h->K == 0 && h->K2 == 0 && h->M == 0 && !h->aux_staged) {  // h.size() == 0 -> no update (updater.cpp:106); MSCKF-SLAM rows count (vio_updater.cpp:413-419)
     for (int i = 0; i < h->n; ++i) correction[i] = 0.0;
-    h->last_empty = true;
+    h->last.schedule = XK_SCHED_EMPTY;            // (xk_caqr_status: 4; staging cleared have_R, or the compression it stands for was of this same empty stack: nothing else reads the record before the next one)
     return XK_OK;
   }
   int rc = XK_OK;
@@ -1993,7 +1216,7 @@ extern "C" int xk_visual_update_staged(xk_handle *h, double sigma_img, double *c
     UpdateSpec u = compressed_spec(h, nullptr, 1);
     rc = launch_compress(h, nullptr, &u);            // (the single launch takes the Kalman update along where it can)
     if (rc != XK_OK) return rc;
-    if (!h->last_fused) rc = launch_update(h, u);
+    if (!h->last.fused) rc = launch_update(h, u);
     if (rc != XK_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(correction, h->d_corr, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
     rc = fetch_flags(h, inlier_msckf, gamma_msckf, inlier_slam, gamma_slam);
@@ -2183,7 +1406,7 @@ extern "C" int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int s
     rc = launch_compress(h, h->ev[2], &u);
     if (rc != XK_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    if (!h->last_fused) rc = launch_update(h, u);     // (fused: the Kalman update is inside stage 2's launch, stage 4 reads 0)
+    if (!h->last.fused) rc = launch_update(h, u);     // (fused: the Kalman update is inside stage 2's launch, stage 4 reads 0)
     if (rc != XK_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2205,10 +1428,10 @@ extern "C" int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int s
   out->total_ms = (float)(tot / steps);
   out->stage_launches[0] = (h->K > 0) + (h->M > 0);
   out->stage_launches[2] = 1;
-  out->stage_launches[3] = h->last_resident ? 0 : h->nlevels;   // (the resident schedule IS stage 2's one launch)
+  out->stage_launches[3] = outcome_single(h->last) ? 0 : h->last.launches;   // (the single launch IS stage 2's one launch)
   const int nblk = (h->na + XK_CHOL_NB - 1) / XK_CHOL_NB;
-  out->stage_launches[4] = h->last_fused ? 0 : 4 + 3 * nblk;
-  out->n = h->n; out->c1 = h->C1; out->k_tracks = h->K; out->n_leaf = h->nleaf; out->n_levels = h->nlevels;
+  out->stage_launches[4] = h->last.fused ? 0 : 4 + 3 * nblk;
+  out->n = h->n; out->c1 = h->C1; out->k_tracks = h->K; out->n_leaf = h->last.leaves; out->n_levels = h->last.launches;
   // stacked rows actually folded (inlier rows)
   {
     const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
@@ -3218,7 +2441,7 @@ extern "C" int xk_run_steps(xk_handle *h, double sigma_img, int steps) {
       UpdateSpec u = compressed_spec(h, nullptr, 1);
       rc = launch_compress(h, nullptr, &u);
       if (rc != XK_OK) return rc;
-      if (!h->last_fused) rc = launch_update(h, u);
+      if (!h->last.fused) rc = launch_update(h, u);
       if (rc != XK_OK) return rc;
     }
     const int rc = read_status(h, attempt == 0);
@@ -3280,7 +2503,6 @@ extern "C" int xk_probe_fp64_peak(xk_handle *h, int use_mfma, double *tflops) {
 }
 #endif   // XK_LAB
 
-// Which schedule compressed the last update, and how the fast path has fared on this handle (include/xk.h).
 extern "C" int xk_set_option(xk_handle *h, const char *name, int value) {
   if (!h || !name) return XK_EINVAL;
   // operational switches of the release library: the schedule of the compression and how soon a fast path that gave up is retried
@@ -3305,9 +2527,10 @@ extern "C" int xk_set_option(xk_handle *h, const char *name, int value) {
   return XK_OK;
 }
 
+// Which schedule compressed the last update, and how the fast path has fared on this handle (include/xk.h).
 extern "C" int xk_caqr_status(const xk_handle *h, int *schedule, int *armed, int *giveups, int *last_reason) {
   if (!h) return XK_EINVAL;
-  if (schedule) *schedule = (h->last_empty || h->split_active >= 2) ? 4 : (h->last_tail ? 3 : (!h->last_resident ? 0 : (h->last_pipe ? 2 : 1)));
+  if (schedule) *schedule = outcome_status(h->last);
   if (armed) *armed = (h->persist_ok || h->tail_ok) ? 1 : 0;
   if (giveups) *giveups = h->fast_giveups;
   if (last_reason) *last_reason = h->fast_reason;

@@ -471,7 +471,7 @@ class Engine:
                     n_levels=t.n_levels)
 
     def caqr_status(self):
-        """xk_caqr_status: schedule of the last compression (0 multi-launch, 1 resident, 2 pipelined), whether the
+        """xk_caqr_status: schedule of the last compression (0 multi-launch, 2 single launch, 3 multi-launch + tail, 4 none), whether the
         single-launch path is armed, give-ups so far, reason of the last one."""
         v = [C.c_int() for _ in range(4)]
         self._chk(self.L.xk_caqr_status(self.h, *[C.byref(x) for x in v]), "xk_caqr_status")
