@@ -33,6 +33,11 @@ int xk_is_lab(void);
  * workgroup (phase by phase), out[1536 ..] = start-up and exit.  n_out <= 256 + 64 * 256. */
 int xk_debug_persist_stamps(xk_handle *h, long long *out, int n_out);
 
+/* What the per-feature kernel left for the K tracks of the last build and nothing else exports: gpf [K][3] the triangulated landmarks
+ * (world frame; a track whose Gauss-Newton system was singular has a NaN first component), gn_iters [K] the Gauss-Newton iterations
+ * taken.  K = the staged track count.  Waits for the handle's stream.  tests/test_gpu_feature_geometry.py compares both per track. */
+int xk_debug_feature_points(xk_handle *h, double *gpf, int *gn_iters, int K);
+
 /* Micro-benchmark of the fp64 ceiling this path is priced against: a grid of waves issuing independent
  * v_mfma_f64_16x16x4_f64 (use_mfma=1) or v_fma_f64 (use_mfma=0) chains.  Reports sustained TFLOP/s. */
 int xk_probe_fp64_peak(xk_handle *h, int use_mfma, double *tflops);

@@ -44,11 +44,24 @@ def load_case(name):
     return sc, exp
 
 
+def check_gamma_per_track(got_gamma, got_inlier, ref_gamma, tol=1e-8):
+    """The gate statistic TRACK BY TRACK: |gamma - ref| <= tol |ref| on every track whose reference is finite (outliers have gamma in
+    the hundreds or thousands, inliers around 10 - 30: one norm over all tracks hides an inlier's error behind one outlier), and a track
+    whose reference is not finite (a triangulation that failed, msckf_update.cpp:349-357) is rejected."""
+    got_gamma, ref_gamma = np.asarray(got_gamma, float), np.asarray(ref_gamma, float)
+    fin = np.isfinite(ref_gamma)
+    assert not np.asarray(got_inlier)[~fin].any(), "a track without a finite reference gamma was accepted"
+    err = np.abs(got_gamma[fin] - ref_gamma[fin])
+    bad = np.where(fin)[0][~(err <= tol * np.abs(ref_gamma[fin]))]
+    assert bad.size == 0, f"per-track gamma: tracks {bad.tolist()}, worst {np.max(err / np.abs(ref_gamma[fin])):.2e}"
+
+
 def check_visual(got, exp, tol=TOL_TIGHT):
     """got: dict(P, correction, inlier, gamma[, inlier_slam, gamma_slam])"""
     assert np.array_equal(np.asarray(got["inlier"]).astype(int), exp["inlier"].astype(int)), "MSCKF inlier mask"
     fin = np.isfinite(exp["gamma"])
     assert rel(np.asarray(got["gamma"])[fin], exp["gamma"][fin]) <= 1e-8, "gamma"
+    check_gamma_per_track(got["gamma"], got["inlier"], exp["gamma"])
     if "inlier_slam" in exp:
         assert np.array_equal(np.asarray(got["inlier_slam"]).astype(int), exp["inlier_slam"].astype(int))
         assert rel(got["gamma_slam"], exp["gamma_slam"]) <= 1e-8

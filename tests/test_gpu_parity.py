@@ -4,7 +4,7 @@ tests hold the GPU path to 1e-9 (TOL_TIGHT) on the small cases and 1e-8 at full 
 import numpy as np
 import pytest
 
-from helpers import TOL_NORTH_STAR, TOL_TIGHT, VISUAL_CASES, check_visual, load_case, rel
+from helpers import TOL_NORTH_STAR, TOL_TIGHT, VISUAL_CASES, check_gamma_per_track, check_visual, load_case, rel
 from x_multi_agent_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +121,7 @@ def test_against_c_oracle(xk, oracle_c, name):
     assert np.array_equal(got["inlier_slam"], ref["inlier_slam"])
     fin = np.isfinite(ref["gamma"])
     assert rel(got["gamma"][fin], ref["gamma"][fin]) <= 1e-8
+    check_gamma_per_track(got["gamma"], got["inlier"], ref["gamma"])     # 1e-8 on every finite track; non-finite ones rejected
     rp, rc = rel(got["P"], ref["P"]), rel(got["correction"], ref["correction"])
     assert rp <= 1e-8 and rp <= TOL_NORTH_STAR, rp
     assert rc <= 1e-7, rc

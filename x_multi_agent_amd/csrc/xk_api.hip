@@ -2549,6 +2549,16 @@ extern "C" int xk_debug_persist_stamps(xk_handle *h, long long *out, int n_out) 
   HIPCHK(h, hipMemcpy(out, h->d_pdbg, sizeof(long long) * (size_t)std::min(n_out, XK_PDBG_WORDS), hipMemcpyDeviceToHost));
   return XK_OK;
 }
+// The triangulated landmarks and Gauss-Newton iteration counts of the last build's tracks (include/xk_lab.h): d_gpf / d_gn as xk_msckf_feature left them.
+extern "C" int xk_debug_feature_points(xk_handle *h, double *gpf, int *gn_iters, int K) {
+  if (!h || !gpf || !gn_iters || K < 0 || K != h->K) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (K == 0) return XK_OK;
+  HIPCHK(h, hipMemcpy(gpf, h->d_gpf, sizeof(double) * 3 * (size_t)K, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(gn_iters, h->d_gn, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost));
+  return XK_OK;
+}
 #endif   // XK_LAB
 
 #if defined(XK_FEAT_PROBE) && defined(XK_LAB)

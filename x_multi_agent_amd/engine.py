@@ -39,7 +39,7 @@ SYMBOLS = [
 
 
 # what include/xk_lab.h adds (lab build only; the release library must NOT export them)
-LAB_SYMBOLS = ["xk_is_lab", "xk_probe_fp64_peak", "xk_debug_persist_stamps"]
+LAB_SYMBOLS = ["xk_is_lab", "xk_probe_fp64_peak", "xk_debug_persist_stamps", "xk_debug_feature_points"]
 
 
 class XkTiming(C.Structure):
@@ -486,6 +486,15 @@ class Engine:
         t = C.c_double()
         self._chk(self.L.xk_probe_fp64_peak(self.h, C.c_int(int(use_mfma)), C.byref(t)), "xk_probe_fp64_peak")
         return t.value
+
+    def debug_feature_points(self):
+        """xk_debug_feature_points (lab build): what the per-feature kernel left for the tracks of the last build -- the triangulated
+        landmarks [K, 3] (world frame) and the Gauss-Newton iteration counts [K]."""
+        K = max(self._K, 1)
+        gpf, it = np.zeros((K, 3)), np.zeros(K, dtype=np.int32)
+        self._chk(self.L.xk_debug_feature_points(self.h, gpf.ctypes.data_as(c_dp), it.ctypes.data_as(c_ip), C.c_int(self._K)),
+                  "xk_debug_feature_points")
+        return gpf[:self._K], it[:self._K]
 
     def payload_doubles(self):
         return int(self.L.xk_payload_doubles(C.c_int(self.N), C.c_int(self.M)))
