@@ -72,6 +72,13 @@ class Database {                   // database.h / database.cpp
   // matcher_->knnMatch(received, current, matches_, 2) (place_recognition.cpp:249): idx / dist [rows][2]
   void knnMatch(const Descriptors &received, const Descriptors &current, std::vector<int> &idx, std::vector<int> &dist);
 
+  // cv::findEssentialMat(current_points, received_points, K, cv::RANSAC, 0.99, threshold, mask) (:269-281): the inlier
+  // mask of the good matches' pixel positions ([n][2], x then y), from n_hyp five-point hypotheses on the device
+  // (xk_pr_essential_ransac; every hypothesis is evaluated, so there is no `prob`).  All zero for fewer than 5 points.
+  std::vector<unsigned char> essentialInliers(const std::vector<float> &current_points, const std::vector<float> &received_points,
+                                              double fx, double fy, double cx, double cy, double threshold = 1.0,
+                                              int n_hyp = 1024, unsigned long seed = 0);
+
  private:
   xk_handle *xk_;
   xk_pr *pr_ = nullptr;
@@ -80,8 +87,12 @@ class Database {                   // database.h / database.cpp
 };
 
 // The rest of findCorrespondences' non-GT branch on the 2-NN result: distance + ratio test (:252-263), optional
-// RANSAC inlier mask (:268-281; the essential-matrix estimate itself is the caller's), duplicate removal (:283-301).
+// RANSAC inlier mask (:268-281; Database::essentialInliers estimates it on the device), duplicate removal (:283-301).
 struct GoodMatch { int queryIdx, trainIdx; };
+// The survivors of the distance + ratio test alone (:252-263), before the mask and the duplicate removal: the matches whose
+// pixel positions the reference collects for findEssentialMat (:264-267), and the list an inlier mask is indexed by.
+std::vector<GoodMatch> ratioTestMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
+                                        double pr_ratio_thr);
 std::vector<GoodMatch> goodMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
                                    double pr_ratio_thr, const std::vector<unsigned char> *inlier_mask = nullptr);
 

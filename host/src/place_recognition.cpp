@@ -59,14 +59,34 @@ void Database::knnMatch(const Descriptors &rec, const Descriptors &cur, std::vec
   check(xk_, xk_pr_knn_match(pr_, rec.ptr(), rec.rows, cur.ptr(), cur.rows, idx.data(), dist.data()), "xk_pr_knn_match");
 }
 
-std::vector<GoodMatch> x::goodMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
-                                      double pr_ratio_thr, const std::vector<unsigned char> *mask) {
+std::vector<unsigned char> Database::essentialInliers(const std::vector<float> &cur, const std::vector<float> &rec, double fx,
+                                                      double fy, double cx, double cy, double threshold, int n_hyp,
+                                                      unsigned long seed) {
+  if (cur.size() != rec.size() || cur.size() % 2) throw std::runtime_error("essentialInliers: point lists of different or odd size");
+  const int n = (int)(cur.size() / 2);
+  std::vector<unsigned char> mask((size_t)n + 1, 0);          // (+1: never a null pointer)
+  int n_inliers = 0;
+  check(xk_, xk_pr_essential_ransac(pr_, cur.data(), rec.data(), n, fx, fy, cx, cy, threshold, n_hyp, seed, mask.data(), nullptr,
+                                    &n_inliers),
+        "xk_pr_essential_ransac");
+  mask.resize((size_t)n);
+  return mask;
+}
+
+std::vector<GoodMatch> x::ratioTestMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
+                                           double pr_ratio_thr) {
   std::vector<GoodMatch> good;
   for (size_t q = 0; 2 * q + 1 < idx.size(); ++q) {
     if (idx[2 * q + 1] < 0) continue;                        // fewer than two neighbours
     const float d0 = (float)dist[2 * q], d1 = (float)dist[2 * q + 1];   // cv::DMatch::distance is a float
     if (d0 < pr_min_distance && d0 < d1 * pr_ratio_thr) good.push_back({(int)q, idx[2 * q]});
   }
+  return good;
+}
+
+std::vector<GoodMatch> x::goodMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
+                                      double pr_ratio_thr, const std::vector<unsigned char> *mask) {
+  std::vector<GoodMatch> good = ratioTestMatches(idx, dist, pr_min_distance, pr_ratio_thr);
   if (good.empty()) return good;
   if (mask) {                                                // :275-281
     int corr_id = 0;

@@ -352,6 +352,26 @@ int xk_pr_copy_keyframe(xk_pr *p, int index, double *d_payload_dst, double *d_tr
  * idx / dist HOST [nq][2], ascending (distance, train index); idx = -1 where the train set is too short. */
 int xk_pr_knn_match(xk_pr *p, const unsigned char *query, int nq, const unsigned char *train, int nt, int *idx, int *dist);
 
+/* cv::findEssentialMat(current_points, received_points, K, cv::RANSAC, 0.99, 1.0, mask) of findCorrespondences
+ * (place_recognition.cpp:269-281): cur_xy / rec_xy HOST [n][2] float32 pixels of the good matches, in order; mask HOST
+ * [n] (1 = inlier), E HOST [9] row-major with rec^T E cur = 0 on normalised coordinates (may be NULL), *n_inliers.
+ * n_hyp (1...4096) five-point hypotheses from the counter-based sampler (seed) are ALL evaluated -- the reference's
+ * prob = 0.99 only stops a sequential loop early, so it is not a parameter; the winner has the most inliers under the
+ * squared Sampson distance <= (threshold_px / ((fx+fy)/2))^2, ties to the lowest hypothesis; no refit.  Three launches
+ * on the handle's stream, one synchronisation.  n < 5: XK_OK, *n_inliers = 0, mask and E zeroed (F_1.empty() -> return
+ * false); n > max_desc: XK_ECAPACITY; null pointers, fx / fy <= 0, threshold_px < 0, n_hyp out of range: XK_EINVAL. */
+int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, int n, double fx, double fy, double cx,
+                           double cy, double threshold_px, int n_hyp, unsigned long seed, unsigned char *mask,
+                           double *E /* 9, row-major, may be NULL */, int *n_inliers);
+
+/* What the last xk_pr_essential_ransac (place_recognition.cpp:269-281) left for hypotheses first ... first+count-1:
+ * n_cand HOST [count] (0...10 real solutions of the five-point problem), E HOST [count][10][9] (unit Frobenius norm,
+ * unused slots zero), inliers HOST [count][10].  Any output may be NULL.  XK_EINVAL outside the last call's range.
+ * An inspection path, not part of a frame: it copies straight into the caller's buffers (720 bytes of E per hypothesis, no
+ * pinned staging block is kept for it) and waits for the copies once. */
+int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n_cand, double *E /* [count][10][9] */,
+                               int *inliers /* [count][10] */);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and

@@ -2581,6 +2581,7 @@ extern "C" int xk_debug_feature_phases(xk_handle *h, double sigma_img, long long
 // exchange on the communication axis.  Mirrors VLAD / Database / Keyframe of src/x/place_recognition.
 // ---------------------------------------------------------------------------
 #include "xk_place.hip.h"
+#include "xk_essential.hip.h"
 
 #define XK_PR_MAX_KEYFRAMES 15   // database.h:70
 
@@ -2605,7 +2606,18 @@ struct xk_pr {
   int *h_int;                 // pinned
   unsigned int *h_words;      // pinned staging for descriptors / VLADs
   size_t h_words_cap;
+  // essential-matrix RANSAC (xk_essential.hip.h): allocated by the first xk_pr_essential_ransac, not by xk_pr_create
+  double *d_ess;              // candidates [4096][10][9], sums [4096][10], E [9], key; then the int and byte parts
+  unsigned char *h_ess;       // pinned: pixel pairs in, E / n_inliers / winner / mask out
+  int ess_n_hyp;              // hypotheses of the last call (0: none yet)
 };
+
+// layout of the scratch block d_ess (doubles first, so everything stays aligned)
+#define XK_ESS_OFF_SUM ((size_t)XK_ESS_MAX_HYP * XK_ESS_MAXC * 9)
+#define XK_ESS_OFF_E (XK_ESS_OFF_SUM + (size_t)XK_ESS_MAX_HYP * XK_ESS_MAXC)
+#define XK_ESS_OFF_KEY (XK_ESS_OFF_E + 9)
+#define XK_ESS_DOUBLES (XK_ESS_OFF_KEY + 1)
+#define XK_ESS_INTS ((size_t)XK_ESS_MAX_HYP * (XK_ESS_MAXC + 2) + 2)   // cnt, ncand, bestc, res
 
 extern "C" void xk_pr_destroy(xk_pr *p) {
   if (!p) return;
@@ -2614,6 +2626,8 @@ extern "C" void xk_pr_destroy(xk_pr *p) {
   hipFree(p->d_q); hipFree(p->d_t); hipFree(p->d_qvlad); hipFree(p->d_ham); hipFree(p->d_knn);
   if (p->h_int) hipHostFree(p->h_int);
   if (p->h_words) hipHostFree(p->h_words);
+  hipFree(p->d_ess);
+  if (p->h_ess) hipHostFree(p->h_ess);
   for (auto &u : p->uav_ids) delete u;
   free(p);
 }
@@ -2816,5 +2830,99 @@ extern "C" int xk_pr_knn_match(xk_pr *p, const unsigned char *query, int nq, con
   HIPCHK(h, hipStreamSynchronize(h->stream));
   memcpy(idx, p->h_int, sizeof(int) * 2 * (size_t)nq);
   memcpy(dist, p->h_int + 2 * (size_t)nq, sizeof(int) * 2 * (size_t)nq);
+  return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Essential-matrix RANSAC filter of findCorrespondences (place_recognition.cpp:269-281), xk_essential.hip.h
+// ---------------------------------------------------------------------------
+static XkEssArgs ess_args(xk_pr *p) {
+  XkEssArgs a{};
+  a.cand = p->d_ess;
+  a.sum = p->d_ess + XK_ESS_OFF_SUM;
+  a.E = p->d_ess + XK_ESS_OFF_E;
+  a.key = (unsigned long long *)(p->d_ess + XK_ESS_OFF_KEY);
+  a.cnt = (int *)(p->d_ess + XK_ESS_DOUBLES);
+  a.ncand = a.cnt + (size_t)XK_ESS_MAX_HYP * XK_ESS_MAXC;
+  a.bestc = a.ncand + XK_ESS_MAX_HYP;
+  a.res = a.bestc + XK_ESS_MAX_HYP;
+  float *xy = (float *)(a.res + 2);
+  a.cur_xy = xy;                                             // (rec_xy follows the n pairs of the call)
+  a.mask = (unsigned char *)(xy + 4 * (size_t)p->max_desc);
+  return a;
+}
+
+extern "C" int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, int n, double fx, double fy, double cx,
+                                      double cy, double threshold_px, int n_hyp, unsigned long seed, unsigned char *mask,
+                                      double *E, int *n_inliers) {
+  if (!p) return XK_EINVAL;
+  xk_handle *h = p->h;
+  if (!mask || !n_inliers || n < 0 || (n > 0 && (!cur_xy || !rec_xy)))
+    return fail(h, XK_EINVAL, "xk_pr_essential_ransac: null argument or negative n");
+  if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+    return fail(h, XK_EINVAL, "xk_pr_essential_ransac: focal lengths must be positive and the intrinsics finite");
+  if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) return fail(h, XK_EINVAL, "xk_pr_essential_ransac: threshold_px < 0");
+  if (n_hyp < 1 || n_hyp > XK_ESS_MAX_HYP) return fail(h, XK_EINVAL, "xk_pr_essential_ransac: n_hyp outside 1...4096");
+  if (n > p->max_desc) return fail(h, XK_ECAPACITY, "xk_pr_essential_ransac: more point pairs than max_desc");
+  *n_inliers = 0;
+  memset(mask, 0, (size_t)n);
+  if (E) memset(E, 0, 9 * sizeof(double));
+  if (n < 5) return XK_OK;                                   // F_1.empty() -> return false
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t xy_bytes = sizeof(float) * 4 * (size_t)p->max_desc, out_bytes = 9 * sizeof(double) + 2 * sizeof(int) + (size_t)p->max_desc;
+  if (!p->d_ess) {
+    void *d = nullptr, *hp = nullptr;
+    if (hipMalloc(&d, sizeof(double) * XK_ESS_DOUBLES + sizeof(int) * XK_ESS_INTS + xy_bytes + (size_t)p->max_desc) != hipSuccess)
+      return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: scratch block");
+    if (hipHostMalloc(&hp, xy_bytes + out_bytes) != hipSuccess) { hipFree(d); return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: pinned block"); }
+    p->d_ess = (double *)d;
+    p->h_ess = (unsigned char *)hp;
+  }
+  XkEssArgs a = ess_args(p);
+  a.n = n; a.n_hyp = n_hyp;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+  const double t = threshold_px / ((fx + fy) / 2.0);
+  a.t2 = t * t;
+  a.seed = (unsigned long long)seed;
+  float *h_xy = (float *)p->h_ess;                           // cur [n][2], then rec [n][2] right behind it: one copy of 4n floats
+  memcpy(h_xy, cur_xy, sizeof(float) * 2 * (size_t)n);
+  memcpy(h_xy + 2 * (size_t)n, rec_xy, sizeof(float) * 2 * (size_t)n);
+  a.rec_xy = a.cur_xy + 2 * (size_t)n;
+  p->ess_n_hyp = 0;
+  HIPCHK(h, hipMemcpyAsync((void *)a.cur_xy, h_xy, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_ess_solve, dim3((n_hyp + XK_ESS_SOLVE_T - 1) / XK_ESS_SOLVE_T), dim3(XK_ESS_SOLVE_T), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ess_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ess_mask, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "essential RANSAC launch", e);
+  unsigned char *h_out = p->h_ess + xy_bytes;                // E [9] | n_inliers, winner | mask [n]
+  HIPCHK(h, hipMemcpyAsync(h_out, a.E, 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h_out + 9 * sizeof(double), a.res, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h_out + 9 * sizeof(double) + 2 * sizeof(int), a.mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  p->ess_n_hyp = n_hyp;
+  if (E) memcpy(E, h_out, 9 * sizeof(double));
+  memcpy(n_inliers, h_out + 9 * sizeof(double), sizeof(int));
+  memcpy(mask, h_out + 9 * sizeof(double) + 2 * sizeof(int), (size_t)n);
+  return XK_OK;
+}
+
+extern "C" int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n_cand, double *E, int *inliers) {
+  if (!p) return XK_EINVAL;
+  xk_handle *h = p->h;
+  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_pr_essential_hypotheses: negative range");
+  if (!p->d_ess || first + (long)count > p->ess_n_hyp)
+    return fail(h, XK_EINVAL, "xk_pr_essential_hypotheses: range outside the hypotheses of the last xk_pr_essential_ransac");
+  if (count == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkEssArgs a = ess_args(p);
+  if (n_cand) HIPCHK(h, hipMemcpyAsync(n_cand, a.ncand + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  if (E)
+    HIPCHK(h, hipMemcpyAsync(E, a.cand + (size_t)first * XK_ESS_MAXC * 9, sizeof(double) * (size_t)count * XK_ESS_MAXC * 9,
+                             hipMemcpyDeviceToHost, h->stream));
+  if (inliers)
+    HIPCHK(h, hipMemcpyAsync(inliers, a.cnt + (size_t)first * XK_ESS_MAXC, sizeof(int) * (size_t)count * XK_ESS_MAXC,
+                             hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
 }

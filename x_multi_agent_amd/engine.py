@@ -35,6 +35,7 @@ SYMBOLS = [
     "xk_stage_range", "xk_stage_sun_angle", "xk_fetch_aux_flags", "xk_aux_rows",
     "xk_pr_create", "xk_pr_destroy", "xk_pr_vlad_bytes", "xk_pr_size", "xk_pr_compute_vlad", "xk_pr_add_keyframe",
     "xk_pr_find_candidate", "xk_pr_keyframe", "xk_pr_copy_keyframe", "xk_pr_knn_match",
+    "xk_pr_essential_ransac", "xk_pr_essential_hypotheses",
 ]
 
 

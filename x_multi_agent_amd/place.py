@@ -122,10 +122,40 @@ class Database:
                                          dist.ctypes.data_as(c_ip)), "xk_pr_knn_match")
         return idx, dist
 
+    def essential_ransac(self, cur_xy, rec_xy, K, threshold_px=1.0, n_hyp=1024, seed=0):
+        """cv::findEssentialMat(current, received, K, RANSAC, 0.99, threshold_px, mask) of findCorrespondences
+        (place_recognition.cpp:269-281) on the device: cur_xy / rec_xy [n, 2] pixels of the good matches, K = (fx, fy,
+        cx, cy) or a 3 x 3 camera matrix -> (mask uint8 [n], E [3, 3] with rec^T E cur = 0, n_inliers).  All n_hyp
+        hypotheses are evaluated; the mask is what good_matches takes as inlier_mask."""
+        K = np.asarray(K, np.float64)
+        fx, fy, cx, cy = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.ravel()
+        cur = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
+        rec = np.ascontiguousarray(rec_xy, np.float32).reshape(-1, 2)
+        if len(cur) != len(rec):
+            raise ValueError("cur_xy and rec_xy differ in length")
+        n = len(cur)
+        mask, E, ninl = np.zeros(max(n, 1), np.uint8), np.zeros(9), C.c_int(0)
+        c_fp = C.POINTER(C.c_float)
+        self._chk(self.L.xk_pr_essential_ransac(self.p, cur.ctypes.data_as(c_fp), rec.ctypes.data_as(c_fp), C.c_int(n), C.c_double(fx),
+                                                C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(threshold_px),
+                                                C.c_int(n_hyp), C.c_ulong(seed), mask.ctypes.data_as(c_ub), E.ctypes.data_as(c_dp),
+                                                C.byref(ninl)), "xk_pr_essential_ransac")
+        return mask[:n], E.reshape(3, 3), ninl.value
+
+    def essential_hypotheses(self, first, count):
+        """What the last essential_ransac left for hypotheses first ... first+count-1 -> (n_cand [count], E [count, 10, 3, 3]
+        of unit Frobenius norm, inliers [count, 10]): the runners-up, and what the solver-level test compares."""
+        nc = np.zeros(max(count, 1), np.int32)
+        E = np.zeros((max(count, 1), 10, 3, 3))
+        inl = np.zeros((max(count, 1), 10), np.int32)
+        self._chk(self.L.xk_pr_essential_hypotheses(self.p, C.c_int(first), C.c_int(count), nc.ctypes.data_as(c_ip), E.ctypes.data_as(c_dp),
+                                                    inl.ctypes.data_as(c_ip)), "xk_pr_essential_hypotheses")
+        return nc[:count], E[:count], inl[:count]
+
 
 def good_matches(idx, dist, min_distance, ratio_thr, inlier_mask=None):
     """Host half of findCorrespondences (place_recognition.cpp:252-301): distance + ratio test on the device's
-    2-NN result, optional RANSAC inlier mask (the essential-matrix filter is the caller's), duplicate removal."""
+    2-NN result, optional RANSAC inlier mask (Database.essential_ransac produces it), duplicate removal."""
     good = []
     for q in range(len(idx)):
         if idx[q, 1] < 0:
