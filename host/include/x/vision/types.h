@@ -1,6 +1,7 @@
 // x/vision/types.h -- the input types the update path reads (include/x/vision/types.h:83-198, feature.h:29,
 // track.h:32 of the reference): Feature::getX()/getY(), Track (a feature list with a unique id), the window lists,
-// and the match records the multi-agent updates consume (MsckfMatch / SlamMatch, types.h:83-116).
+// the match records the multi-agent updates consume (MsckfMatch / SlamMatch, types.h:83-116), and what the tracker's
+// outlier removal reads and writes: TrackedFeature (a Feature with its distorted pixels), FeatureList, Match / MatchList (types.h:39-57).
 #pragma once
 #include <memory>
 #include <vector>
@@ -15,11 +16,28 @@ class Feature {
  public:
   Feature() = default;
   Feature(double x, double y) : x_(x), y_(y) {}
-  double getX() const { return x_; }   // normalised, undistorted image coordinates
+  double getX() const { return x_; }   // undistorted image coordinates: normalised on the update path, pixels in the tracker
   double getY() const { return y_; }
+  void setX(double x) { x_ = x; }
+  void setY(double y) { y_ = y; }
  private:
-  double x_ = 0, y_ = 0;
+  double x_ = 0, y_ = 0;               // (nothing else: the update path copies whole tracks as pairs of doubles)
 };
+// A Feature as the tracker holds it (feature.h:141-146: x_dist_, y_dist_): the distorted pixels as detected beside the undistorted ones.
+class TrackedFeature : public Feature {
+ public:
+  TrackedFeature() = default;
+  TrackedFeature(double x, double y, double x_dist, double y_dist) : Feature(x, y), x_dist_(x_dist), y_dist_(y_dist) {}
+  double getXDist() const { return x_dist_; }
+  double getYDist() const { return y_dist_; }
+  void setXDist(double x_dist) { x_dist_ = x_dist; }
+  void setYDist(double y_dist) { y_dist_ = y_dist; }
+ private:
+  double x_dist_ = 0, y_dist_ = 0;
+};
+using FeatureList = std::vector<TrackedFeature>;      // the tracker's lists (types.h:49)
+struct Match { TrackedFeature previous, current; };   // types.h:39-42, :57
+using MatchList = std::vector<Match>;
 
 typedef unsigned long long uniqueId;                  // types.h:81
 // Track (track.h:32): a std::vector<Feature> with an id unique across the run (the tracker assigns it).

@@ -372,6 +372,55 @@ int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, i
 int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n_cand, double *E /* [count][10][9] */,
                                int *inliers /* [count][10] */);
 
+/* ---- outlier removal of the tracker's matches (Tracker::track, tracker.cpp:233-293) -----------------------------
+ * Every frame the reference undistorts the previous and the current feature list through the FOV model
+ * (camera.cpp:62-87,163-168), runs cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) on their float casts
+ * and keeps the masked pairs as the frame's matches.  An xk_trk does that on the device of its handle; it needs no
+ * vocabulary and no xk_pr.  Intrinsics in pixels (Camera's fx_ ... cy_, camera.cpp:30-33) and the FOV parameter s are
+ * fixed at creation; max_matches: most pairs per call. */
+typedef struct xk_trk xk_trk;
+
+/* Camera::Camera (camera.cpp:27-48).  max_matches < 1, fx / fy <= 0, non-finite intrinsics: XK_EINVAL. */
+int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy, double cx, double cy, double s, xk_trk **out);
+void xk_trk_destroy(xk_trk *t);
+
+/* Camera::undistort (camera.cpp:62-87): dist_xy HOST [n][2] distorted pixels -> xy HOST [n][2] undistorted pixels, fp64:
+ * r = |((u - cx)/fx, (v - cy)/fy)|, factor tan(r s) / (2 tan(s/2)) / r where r > 0.01 and s != 0, else 1. */
+int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double *xy);
+
+/* cv::findFundamentalMat(pts1, pts2, cv::RANSAC, threshold_px, 0.99, mask) (tracker.cpp:243-260): prev_xy / cur_xy HOST
+ * [n][2] float32 undistorted pixels (the cv::Point2f of :251-256); mask HOST [n] (1 = inlier), F HOST [9] row-major in
+ * pixel coordinates with cur^T F prev = 0 and unit Frobenius norm (may be NULL), *n_inliers.  n_hyp (1...4096) seven-point
+ * hypotheses from the counter-based sampler (seed) are ALL evaluated -- prob = 0.99 only stops a sequential loop early, so
+ * it is not a parameter; the error of a pair is the larger of its two squared point-to-epipolar-line distances in pixels
+ * (OpenCV's, not Sampson's), an inlier has error <= threshold_px^2; the winner has the most inliers, ties to the lowest
+ * hypothesis; no refit, no degeneracy test of the sample.  Three launches, one synchronisation.  n < 7: XK_OK,
+ * *n_inliers = 0, mask and F zeroed (OpenCV returns an empty mask, the loop of :263-268 keeps nothing); n > max_matches:
+ * XK_ECAPACITY; null pointers, n < 0, threshold_px < 0, n_hyp out of range: XK_EINVAL. */
+int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, double threshold_px, int n_hyp,
+                              unsigned long seed, unsigned char *mask, double *F /* 9, row-major, may be NULL */,
+                              int *n_inliers);
+
+/* What the last RANSAC of an xk_trk (tracker.cpp:259-260; either entry) left for hypotheses first ... first+count-1:
+ * n_cand HOST [count] (0...3 candidates of the seven-point problem), F HOST [count][3][9] (pixel coordinates, unit
+ * Frobenius norm, unused slots zero), inliers HOST [count][3].  Any output may be NULL.  XK_EINVAL outside the last call's
+ * range;
+ * a call with n < 7 ran no hypotheses, so every non-empty range is outside it.  An inspection path, not part of a frame: it copies
+ * straight into the caller's buffers. */
+int xk_trk_fundamental_hypotheses(xk_trk *t, int first, int count, int *n_cand, double *F /* [count][3][9] */,
+                                  int *inliers /* [count][3] */);
+
+/* The per-frame call, tracker.cpp:233-293 whole: prev_dist_xy / cur_dist_xy HOST [n][2] DISTORTED pixels of the tracked
+ * pairs (Feature::getXDist / getYDist) -> mask HOST [n], keep_idx HOST [n] (the first *n_inliers entries: the positions
+ * of the kept pairs, ascending), prev_xy / cur_xy HOST [n][2] (the first *n_inliers rows: the UNDISTORTED fp64 pixels of
+ * the kept pairs in input order, what :262-271 pushes and the matches of :286-293 carry).  The RANSAC sees the float casts
+ * of the undistorted pixels, as in xk_trk_fundamental_ransac.  Four launches on the handle's stream, one copy in, one
+ * copy out through a pinned block allocated by xk_trk_create, one synchronisation.  Status codes as above; every
+ * output pointer is required. */
+int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *cur_dist_xy, int n, double threshold_px,
+                          int n_hyp, unsigned long seed, unsigned char *mask, int *keep_idx, double *prev_xy, double *cur_xy,
+                          int *n_inliers);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and

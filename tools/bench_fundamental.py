@@ -1,0 +1,67 @@
+"""Cost of the per-frame outlier removal of the tracker's matches on the GPU box: milliseconds per
+xk_trk_filter_matches call (host buffers in and out, four launches, one synchronisation) at n = 100 and 400 and at
+n_hyp = 256 and 1024, timed with HIP events on the handle's stream over >= 500 calls after warm-up (repeated three times:
+the spread is printed), and one core's time for the NumPy restatement beside it:
+    python tools/bench_fundamental.py [--calls 500]
+The per-kernel split comes from a run of its own under the profiler (tracing slows the host, so the times above are taken
+without it):
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_fundamental.py --calls 50 --no-cpu
+    python tools/bench_fundamental.py --kernel-stats DIR"""
+import argparse, csv, glob, os, sys, time
+import numpy as np
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--calls", type=int, default=500)
+ap.add_argument("--no-cpu", action="store_true", help="skip the NumPy restatement (profiler runs)")
+ap.add_argument("--kernel-stats", metavar="DIR", help="print the xk_fund_* rows of a rocprofv3 --kernel-trace --stats run and exit")
+args = ap.parse_args()
+if args.kernel_stats:
+    files = glob.glob(os.path.join(args.kernel_stats, "**", "*kernel_stats.csv"), recursive=True)
+    if not files:
+        sys.exit("bench_fundamental: no *kernel_stats.csv under " + args.kernel_stats)
+    for r in csv.DictReader(open(files[0])):
+        if "xk_fund" in r["Name"]:
+            print(f"{r['Name'][:40]:40s} calls {r['Calls']:>6s} avg_us {float(r['AverageNs']) / 1e3:8.2f} min_us {float(r['MinNs']) / 1e3:8.2f} "
+                  f"max_us {float(r['MaxNs']) / 1e3:8.2f}")
+    sys.exit(0)
+
+import torch
+import fundamental_np as fnp
+from x_multi_agent_amd import engine, tracker
+
+if not torch.cuda.is_available():
+    sys.exit("bench_fundamental: no GPU -- a time measured anywhere else says nothing")
+K, S, THR = fnp.K_DEFAULT, 0.95, 0.3
+eng = engine.Engine(4, 0, 4)
+mf = tracker.MatchFilter(eng, 512, K, S)
+stream = torch.cuda.ExternalStream(eng.L.xk_stream(eng.h))
+for n in (100, 400):
+    prev, cur, _ = fnp.make_pair(n, 0.2, 0.05, 50 + n, "general", S)
+    for n_hyp in (256, 1024):
+        for w in range(20):
+            mf.filter_matches(prev, cur, THR, n_hyp, w)
+        per_call = []
+        for rep in range(3):
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            ev0.record(stream)
+            for i in range(args.calls):
+                mask, keep, pxy, cxy = mf.filter_matches(prev, cur, THR, n_hyp, i)
+            ev1.record(stream)
+            ev1.synchronize()
+            wall = (time.perf_counter() - t0) / args.calls
+            per_call.append((ev0.elapsed_time(ev1) / args.calls, 1e3 * wall))
+        line = (f"n = {n:3d}, n_hyp = {n_hyp:4d}: " + " / ".join(f"{e:6.3f}" for e, _ in per_call) + " ms per call (HIP events, three repeats), "
+                + " / ".join(f"{w:6.3f}" for _, w in per_call) + f" ms host wall, {len(keep)} kept")
+        if not args.no_cpu:
+            t0 = time.perf_counter()
+            ref = fnp.filter_matches(prev, cur, K, S, THR, n_hyp, args.calls - 1)
+            cpu = time.perf_counter() - t0
+            line += (f";  NumPy restatement, one core: {1e3 * cpu:8.1f} ms, same mask: {np.array_equal(ref['mask'], mask)}"
+                     f" (margin {ref['margin']:.1e})")
+        print(line, flush=True)
+mf.close()
+eng.close()

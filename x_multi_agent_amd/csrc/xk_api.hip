@@ -2926,3 +2926,212 @@ extern "C" int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Fundamental-matrix RANSAC filter of the tracker's matches (tracker.cpp:233-293, camera.cpp:62-87), xk_fundamental.hip.h
+// ---------------------------------------------------------------------------
+#include "xk_fundamental.hip.h"
+
+struct xk_trk {
+  xk_handle *h;
+  int max_matches;
+  double fx, fy, cx, cy, s, s_term;
+  double *d_blk;              // distorted / undistorted / float-cast points, candidates, sums, key; then the result block
+  unsigned char *d_res;       // result block inside d_blk: F | kept previous | kept current | res | keep_idx | mask, packed per call
+  unsigned char *h_blk;       // pinned: points in (4 max_matches doubles), then the result block out
+  int n_hyp;                  // hypotheses of the last RANSAC (0: none yet)
+};
+
+// layout of d_blk in doubles: dist, und, pts [4 max_matches] each, then
+#define XK_FUND_OFF_SUM ((size_t)XK_FUND_MAX_HYP * XK_FUND_MAXC * 9)
+#define XK_FUND_OFF_KEY (XK_FUND_OFF_SUM + (size_t)XK_FUND_MAX_HYP * XK_FUND_MAXC)
+#define XK_FUND_DOUBLES (XK_FUND_OFF_KEY + 1)
+#define XK_FUND_INTS ((size_t)XK_FUND_MAX_HYP * (XK_FUND_MAXC + 2))   // cnt, ncand, bestc
+// the result block for n pairs: F [9] and the kept coordinates [2][n][2] in doubles, res [2] and keep_idx [n] in ints, mask [n]
+static size_t trk_res_bytes(int n) { return sizeof(double) * (9 + 4 * (size_t)n) + sizeof(int) * (2 + (size_t)n) + (size_t)n; }
+
+extern "C" void xk_trk_destroy(xk_trk *t) {
+  if (!t) return;
+  hipFree(t->d_blk);
+  if (t->h_blk) hipHostFree(t->h_blk);
+  free(t);
+}
+
+extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy, double cx, double cy, double s, xk_trk **out) {
+  if (!h || !out) return XK_EINVAL;
+  if (max_matches < 1) return fail(h, XK_EINVAL, "xk_trk_create: max_matches < 1");
+  if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(s))
+    return fail(h, XK_EINVAL, "xk_trk_create: focal lengths must be positive and the intrinsics finite");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_trk *t = (xk_trk *)calloc(1, sizeof(xk_trk));
+  if (!t) return XK_ENOMEM;
+  t->h = h; t->max_matches = max_matches;
+  t->fx = fx; t->fy = fy; t->cx = cx; t->cy = cy; t->s = s;
+  t->s_term = s != 0.0 ? 1.0 / (2.0 * std::tan(s / 2.0)) : 0.0;        // camera.cpp:39
+  const size_t pts = sizeof(double) * 4 * (size_t)max_matches;
+  const size_t head = 3 * pts + sizeof(double) * XK_FUND_DOUBLES + sizeof(int) * XK_FUND_INTS;   // (a multiple of 8)
+  void *d = nullptr, *hp = nullptr;
+  if (hipMalloc(&d, head + trk_res_bytes(max_matches)) != hipSuccess || hipHostMalloc(&hp, pts + trk_res_bytes(max_matches)) != hipSuccess) {
+    hipFree(d);
+    free(t);
+    return fail(h, XK_ENOMEM, "xk_trk_create: allocation failed");
+  }
+  t->d_blk = (double *)d;
+  t->d_res = (unsigned char *)d + head;
+  t->h_blk = (unsigned char *)hp;
+  *out = t;
+  return XK_OK;
+}
+
+static XkFundArgs trk_args(xk_trk *t, int n) {
+  XkFundArgs a{};
+  const size_t m4 = 4 * (size_t)t->max_matches;
+  a.dist = t->d_blk; a.und = t->d_blk + m4; a.pts = t->d_blk + 2 * m4;
+  a.cand = t->d_blk + 3 * m4;
+  a.sum = a.cand + XK_FUND_OFF_SUM;
+  a.key = (unsigned long long *)(a.cand + XK_FUND_OFF_KEY);
+  a.cnt = (int *)(a.cand + XK_FUND_DOUBLES);
+  a.ncand = a.cnt + (size_t)XK_FUND_MAX_HYP * XK_FUND_MAXC;
+  a.bestc = a.ncand + XK_FUND_MAX_HYP;
+  a.F = (double *)t->d_res;
+  a.kept_prev = a.F + 9; a.kept_cur = a.kept_prev + 2 * (size_t)n;
+  a.res = (int *)(a.kept_cur + 2 * (size_t)n);
+  a.keep_idx = a.res + 2;
+  a.mask = (unsigned char *)(a.keep_idx + n);
+  a.n = n; a.n_pts = 2 * n;
+  a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.s = t->s; a.s_term = t->s_term;
+  return a;
+}
+
+/* Camera::undistort (camera.cpp:62-87) */
+extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double *xy) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (n < 0 || (n > 0 && (!dist_xy || !xy))) return fail(h, XK_EINVAL, "xk_trk_undistort: null argument or negative n");
+  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_undistort: more points than max_matches");
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, 0);
+  a.n_pts = n;
+  memcpy(t->h_blk, dist_xy, sizeof(double) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->h_blk, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_fund_undistort, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "undistort launch", e);
+  HIPCHK(h, hipMemcpyAsync(t->h_blk, a.und, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  memcpy(xy, t->h_blk, sizeof(double) * 2 * (size_t)n);
+  return XK_OK;
+}
+
+// The launches behind both RANSAC entries: the points are in the pinned block (4n doubles: previous, then current), distorted
+// (undistort = true: they go through xk_fund_undistort) or already what the RANSAC sees.  One copy in, one copy out, one wait.
+static int trk_run(xk_trk *t, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
+  xk_handle *h = t->h;
+  const int n = a.n;
+  a.n_hyp = n_hyp;
+  a.t2 = threshold_px * threshold_px;
+  a.seed = (unsigned long long)seed;
+  if (!undistort) a.und = a.pts;
+  t->n_hyp = 0;
+  HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->h_blk, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "fundamental RANSAC launch", e);
+  HIPCHK(h, hipMemcpyAsync(t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  t->n_hyp = n_hyp;
+  return XK_OK;
+}
+
+static int trk_check(xk_trk *t, const char *who, int n, double threshold_px, int n_hyp, bool nulls) {
+  xk_handle *h = t->h;
+  char msg[160];
+  const char *what = nullptr;
+  int rc = XK_EINVAL;
+  if (nulls || n < 0) what = "null argument or negative n";
+  else if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) what = "threshold_px < 0";
+  else if (n_hyp < 1 || n_hyp > XK_FUND_MAX_HYP) what = "n_hyp outside 1...4096";
+  else if (n > t->max_matches) { what = "more point pairs than max_matches"; rc = XK_ECAPACITY; }
+  if (!what) return XK_OK;
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(h, rc, msg);
+}
+
+/* cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) (tracker.cpp:243-260) */
+extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, double threshold_px, int n_hyp,
+                                         unsigned long seed, unsigned char *mask, double *F, int *n_inliers) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  int rc = trk_check(t, "xk_trk_fundamental_ransac", n, threshold_px, n_hyp, !mask || !n_inliers || (n > 0 && (!prev_xy || !cur_xy)));
+  if (rc != XK_OK) return rc;
+  *n_inliers = 0;
+  memset(mask, 0, (size_t)n);
+  if (F) memset(F, 0, 9 * sizeof(double));
+  if (n < 7) { t->n_hyp = 0; return XK_OK; }                 // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, n);
+  double *h_pts = (double *)t->h_blk;
+  for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
+  rc = trk_run(t, a, false, threshold_px, n_hyp, seed);
+  if (rc != XK_OK) return rc;
+  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
+  if (F) memcpy(F, r, 9 * sizeof(double));
+  memcpy(n_inliers, r + ((unsigned char *)a.res - t->d_res), sizeof(int));
+  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
+  return XK_OK;
+}
+
+/* What the last RANSAC of the tracker's matches (tracker.cpp:259-260) left for hypotheses first ... first+count-1 */
+extern "C" int xk_trk_fundamental_hypotheses(xk_trk *t, int first, int count, int *n_cand, double *F, int *inliers) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_trk_fundamental_hypotheses: negative range");
+  if (first + (long)count > t->n_hyp)
+    return fail(h, XK_EINVAL, "xk_trk_fundamental_hypotheses: range outside the hypotheses of the last RANSAC");
+  if (count == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkFundArgs a = trk_args(t, 0);
+  if (n_cand) HIPCHK(h, hipMemcpyAsync(n_cand, a.ncand + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  if (F)
+    HIPCHK(h, hipMemcpyAsync(F, a.cand + (size_t)first * XK_FUND_MAXC * 9, sizeof(double) * (size_t)count * XK_FUND_MAXC * 9,
+                             hipMemcpyDeviceToHost, h->stream));
+  if (inliers)
+    HIPCHK(h, hipMemcpyAsync(inliers, a.cnt + (size_t)first * XK_FUND_MAXC, sizeof(int) * (size_t)count * XK_FUND_MAXC,
+                             hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+/* The outlier removal of Tracker::track (tracker.cpp:233-293): undistort both lists, RANSAC, keep the masked pairs */
+extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *cur_dist_xy, int n, double threshold_px,
+                                     int n_hyp, unsigned long seed, unsigned char *mask, int *keep_idx, double *prev_xy, double *cur_xy,
+                                     int *n_inliers) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  int rc = trk_check(t, "xk_trk_filter_matches", n, threshold_px, n_hyp,
+                     !mask || !keep_idx || !prev_xy || !cur_xy || !n_inliers || (n > 0 && (!prev_dist_xy || !cur_dist_xy)));
+  if (rc != XK_OK) return rc;
+  *n_inliers = 0;
+  memset(mask, 0, (size_t)n);
+  if (n < 7) { t->n_hyp = 0; return XK_OK; }
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, n);
+  memcpy(t->h_blk, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
+  memcpy(t->h_blk + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
+  rc = trk_run(t, a, true, threshold_px, n_hyp, seed);
+  if (rc != XK_OK) return rc;
+  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
+  int kept = 0;
+  memcpy(&kept, r + ((unsigned char *)a.res - t->d_res), sizeof(int));
+  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_filter_matches: inlier count out of range");
+  *n_inliers = kept;
+  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
+  memcpy(keep_idx, r + ((unsigned char *)a.keep_idx - t->d_res), sizeof(int) * (size_t)kept);
+  memcpy(prev_xy, r + ((unsigned char *)a.kept_prev - t->d_res), sizeof(double) * 2 * (size_t)kept);
+  memcpy(cur_xy, r + ((unsigned char *)a.kept_cur - t->d_res), sizeof(double) * 2 * (size_t)kept);
+  return XK_OK;
+}

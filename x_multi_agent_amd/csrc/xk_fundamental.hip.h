@@ -1,0 +1,392 @@
+// xk_fundamental.hip.h -- fundamental-matrix RANSAC filter of the tracker's matches, Tracker::track (gfx950).
+//
+//   camera_.undistort(current_features); camera_.undistort(previous_features_);           (tracker.cpp:233-237, camera.cpp:62-87)
+//   cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask); keep the masked pairs (tracker.cpp:243-293)
+//
+// Four launches on the handle's stream, no host round trip between them:
+//   xk_fund_undistort  one thread per point, both lists: the FOV model's inverse (camera.cpp:69-87), the fp64 undistorted
+//                      pixels (what the matches carry) and their float cast widened back to fp64 (what the RANSAC sees: the
+//                      reference casts to cv::Point2f, tracker.cpp:251-256)
+//   xk_fund_solve      one thread per hypothesis: seven distinct pairs from the counter-based splitmix64 sampler, the
+//                      seven-point minimal solver, up to three unit-norm candidates in PIXEL coordinates
+//   xk_fund_score      one workgroup per hypothesis, lanes over points: max(d1^2, d2^2) of the two point-to-epipolar-line
+//                      distances of every pair under every candidate, inlier count and summed inlier error per candidate, the
+//                      hypothesis' best candidate, and a packed 64-bit atomicMax key (count << 32 | ~hypothesis)
+//   xk_fund_mask       one workgroup: the winner's mask, F and count (counted here, with the mask), and the ORDERED
+//                      compaction (workgroup scan) of the kept indices and of the kept pairs' undistorted fp64 pixels
+//                      (tracker.cpp:262-271 pushes them in order)
+//
+// All n_hyp hypotheses are evaluated, so there is no `prob` (xk_essential.hip.h says why).  No refit.
+//
+// fp64 throughout.  Convention: p1 = previous, p2 = current, p2^T F p1 = 0, F row-major.  The solve runs on conditioned
+// coordinates x = (u - cx)/fx, y = (v - cy)/fy; the score runs on pixels.
+//
+// The minimal solver, every step stated so that a CPU restatement can follow it:
+//   1. null space of the 7 x 9 epipolar system (row p: p2_i p1_j at 3i + j): seven Householder reflectors on its
+//      transpose; the last two columns of Q are F1, F2 (unit norm, orthogonal)
+//   2. det(l F1 + (1 - l) F2) = det(F2 + l D), D = F1 - F2: c0 = [a0 a1 a2], c1 = [d0 a1 a2] + [a0 d1 a2] + [a0 a1 d2],
+//      c2 = [d0 d1 a2] + [d0 a1 d2] + [a0 d1 d2], c3 = [d0 d1 d2] in triple products of the rows a of F2 and d of D
+//   3. degenerate cubics, with m = max |c_k| and f = XK_FUND_COEF_FLOOR:
+//        m <= f                    every member of the pencil is singular (F1, F2 have unit norm, so the floor is relative to
+//                                  them): the candidates are F1 and F2 themselves
+//        |c3| <= f m               a root at infinity: the candidate F1 - F2, and the roots of the polynomial deflated to its
+//                                  highest coefficient above f m
+//   4. real roots by xk_essential.hip.h's scheme: the roots of each derivative bracket the roots of the next, its safeguarded
+//      Newton inside each bracket (no trigonometric closed form)
+//   5. per root F = l F1 + (1 - l) F2, unit Frobenius norm, K^-T F K^-1, unit norm again; ascending l, special candidates
+//      last; a non-finite candidate is dropped
+// There is NO collinearity or other degeneracy test of the sample: a degenerate sample yields candidates that score badly.
+//
+// Mapping: the 63 doubles of the system stay in registers (every loop below has constant bounds and is unrolled), one
+// thread per hypothesis, no LDS workspace.  The solver functions are __host__ __device__ so that the same text can be
+// exercised on a CPU.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "xk_essential.hip.h"     // xk_ess_mix (the sampler's stream), xk_ess_horner, xk_ess_bracket_root
+
+#define XK_FUND_MAXC 3             // candidates per hypothesis
+#define XK_FUND_MAX_HYP 4096
+#define XK_FUND_COEF_FLOOR 1e-12   // relative: to max |c_k| for the leading coefficient, to the unit-norm pencil for all of them
+#define XK_FUND_SOLVE_T 64         // hypotheses per workgroup of the solve kernel: one wavefront
+
+// Hypothesis h draws values 7h .. 7h+6 of the stream of xk_ess_sample (value i = mix(seed + (i+1) golden)); draw k lands in
+// [0, n-k) and is shifted past the earlier picks in ascending order: seven distinct indices, no rejection loop.
+XK_ESS_HD void xk_fund_sample(unsigned long long seed, int h, int n, int pick[7]) {
+  unsigned int sorted[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    const unsigned long long z = xk_ess_mix(seed + (unsigned long long)(7ll * h + k + 1) * 0x9E3779B97F4A7C15ull);
+    unsigned int r = (unsigned int)(((z >> 32) * (unsigned long long)(n - k)) >> 32);
+#pragma unroll
+    for (int m = 0; m < k; ++m)
+      if (r >= sorted[m]) ++r;
+    pick[k] = (int)r;
+    sorted[k] = r;
+#pragma unroll
+    for (int j = k; j > 0; --j)
+      if (sorted[j] < sorted[j - 1]) { const unsigned int t = sorted[j]; sorted[j] = sorted[j - 1]; sorted[j - 1] = t; }
+  }
+}
+
+XK_ESS_HD double xk_fund_triple(const double *x, const double *y, const double *z) {
+  return x[0] * (y[1] * z[2] - y[2] * z[1]) - x[1] * (y[0] * z[2] - y[2] * z[0]) + x[2] * (y[0] * z[1] - y[1] * z[0]);
+}
+
+// Real roots of c[0..D] (ascending powers, |c[D]| > 0), ascending; -1 where the bound on the roots is not finite.
+template <int D>
+XK_ESS_HD int xk_fund_real_roots(const double *c, double *roots) {
+  double prev[3] = {0.0, 0.0, 0.0}, cur[3] = {0.0, 0.0, 0.0}, pd[4];
+  int nprev = 0;
+#pragma unroll
+  for (int d = 1; d <= D; ++d) {
+    const int m = D - d;                       // pd = m-th derivative of c
+    double big = 0.0;
+#pragma unroll
+    for (int k = 0; k <= d; ++k) {
+      double f = c[k + m];
+#pragma unroll
+      for (int j = k + 1; j <= k + m; ++j) f *= (double)j;
+      pd[k] = f;
+    }
+#pragma unroll
+    for (int k = 0; k < d; ++k) big = fmax(big, fabs(pd[k] / pd[d]));
+    const double R = 1.0 + big;                // Cauchy's bound
+    if (!(R < 1e300)) return -1;
+    int nc = 0;
+    double lo = -R, flo = xk_ess_horner(pd, d, lo);
+#pragma unroll
+    for (int s = 0; s < d; ++s) {              // (at most d - 1 roots of the derivative: d brackets)
+      if (s <= nprev) {
+        const double hi = s < nprev ? prev[s] : R;
+        const double fhi = xk_ess_horner(pd, d, hi);
+        if ((flo < 0) != (fhi < 0)) {
+          const double r = xk_ess_bracket_root(pd, d, lo, hi, flo);
+#pragma unroll
+          for (int t = 0; t < 3; ++t)
+            if (t == nc) cur[t] = r;
+          ++nc;
+        }
+        lo = hi; flo = fhi;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) prev[s] = cur[s];
+    nprev = nc;
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) roots[s] = prev[s];
+  return nprev;
+}
+
+// Fn (conditioned coordinates, any scale) -> unit norm, K^-T Fn K^-1, unit norm again, into out[9]; false if not finite.
+XK_ESS_HD bool xk_fund_to_pixels(const double *Fn, double fx, double fy, double cx, double cy, double *out) {
+  double nn = 0.0, F[9], G[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) nn += Fn[e] * Fn[e];
+  double inv = 1.0 / sqrt(nn);
+#pragma unroll
+  for (int e = 0; e < 9; ++e) F[e] = Fn[e] * inv;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {                // G = F K^-1
+    G[3 * i] = F[3 * i] / fx;
+    G[3 * i + 1] = F[3 * i + 1] / fy;
+    G[3 * i + 2] = F[3 * i + 2] - F[3 * i] * cx / fx - F[3 * i + 1] * cy / fy;
+  }
+  nn = 0.0;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {                // K^-T G
+    F[j] = G[j] / fx;
+    F[3 + j] = G[3 + j] / fy;
+    F[6 + j] = G[6 + j] - G[j] * cx / fx - G[3 + j] * cy / fy;
+    nn += F[j] * F[j] + F[3 + j] * F[3 + j] + F[6 + j] * F[6 + j];
+  }
+  inv = 1.0 / sqrt(nn);
+  bool ok = true;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    out[e] = F[e] * inv;
+    ok = ok && (fabs(out[e]) <= 2.0);          // (false for a NaN too)
+  }
+  return ok;
+}
+
+// Seven conditioned pairs -> candidates Fout[<= 3][9] (row-major, pixel coordinates, unit Frobenius norm); returns their number.
+XK_ESS_HD int xk_fund_solve7(const double (*p1)[2], const double (*p2)[2], double fx, double fy, double cx, double cy,
+                             double *Fout) {
+  // 1. null space
+  double a[7][9], beta[7], F1[9], F2[9];
+#pragma unroll
+  for (int p = 0; p < 7; ++p) {
+    const double u[3] = {p2[p][0], p2[p][1], 1.0}, v[3] = {p1[p][0], p1[p][1], 1.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) a[p][3 * i + j] = u[i] * v[j];
+  }
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    double s = 0.0;
+#pragma unroll
+    for (int t = k; t < 9; ++t) s += a[k][t] * a[k][t];
+    const double nrm = sqrt(s);
+    beta[k] = 0.0;
+    if (nrm > 0.0) {
+      const double alpha = a[k][k] > 0 ? -nrm : nrm;
+      a[k][k] -= alpha;
+      double vv = 0.0;
+#pragma unroll
+      for (int t = k; t < 9; ++t) vv += a[k][t] * a[k][t];
+      beta[k] = 2.0 / vv;
+#pragma unroll
+      for (int j = k + 1; j < 7; ++j) {
+        double d = 0.0;
+#pragma unroll
+        for (int t = k; t < 9; ++t) d += a[k][t] * a[j][t];
+        d *= beta[k];
+#pragma unroll
+        for (int t = k; t < 9; ++t) a[j][t] -= d * a[k][t];
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    double q[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) q[t] = (t == 7 + v) ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 6; k >= 0; --k) {
+      double d = 0.0;
+#pragma unroll
+      for (int t = k; t < 9; ++t) d += a[k][t] * q[t];
+      d *= beta[k];
+#pragma unroll
+      for (int t = k; t < 9; ++t) q[t] -= d * a[k][t];
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) (v == 0 ? F1 : F2)[t] = q[t];
+  }
+  // 2. the cubic
+  double D[9], c[4];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) D[e] = F1[e] - F2[e];
+  c[0] = xk_fund_triple(F2, F2 + 3, F2 + 6);
+  c[1] = xk_fund_triple(D, F2 + 3, F2 + 6) + xk_fund_triple(F2, D + 3, F2 + 6) + xk_fund_triple(F2, F2 + 3, D + 6);
+  c[2] = xk_fund_triple(D, D + 3, F2 + 6) + xk_fund_triple(D, F2 + 3, D + 6) + xk_fund_triple(F2, D + 3, D + 6);
+  c[3] = xk_fund_triple(D, D + 3, D + 6);
+  const double cmax = fmax(fmax(fabs(c[0]), fabs(c[1])), fmax(fabs(c[2]), fabs(c[3])));
+  if (!(cmax < 1e300)) return 0;               // (non-finite input)
+  int nc = 0;
+  // 3. degenerate cubics
+  if (cmax <= XK_FUND_COEF_FLOOR) {
+    if (xk_fund_to_pixels(F1, fx, fy, cx, cy, Fout + 9 * nc)) ++nc;
+    if (xk_fund_to_pixels(F2, fx, fy, cx, cy, Fout + 9 * nc)) ++nc;
+    return nc;
+  }
+  const double flo = XK_FUND_COEF_FLOOR * cmax;
+  const int deg = fabs(c[3]) > flo ? 3 : (fabs(c[2]) > flo ? 2 : (fabs(c[1]) > flo ? 1 : 0));
+  // 4. real roots
+  double roots[3] = {0.0, 0.0, 0.0};
+  int nr = 0;
+  if (deg == 3) nr = xk_fund_real_roots<3>(c, roots);
+  else if (deg == 2) nr = xk_fund_real_roots<2>(c, roots);
+  else if (deg == 1) nr = xk_fund_real_roots<1>(c, roots);
+  if (nr < 0) nr = 0;
+  // 5. candidates
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    if (s < nr && nc < XK_FUND_MAXC) {
+      double Fn[9];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) Fn[e] = F2[e] + roots[s] * D[e];
+      if (xk_fund_to_pixels(Fn, fx, fy, cx, cy, Fout + 9 * nc)) ++nc;
+    }
+  }
+  if (deg < 3 && nc < XK_FUND_MAXC && xk_fund_to_pixels(D, fx, fy, cx, cy, Fout + 9 * nc)) ++nc;
+  return nc;
+}
+
+// OpenCV's fundamental-matrix error of the pair (p1, p2) in pixels: the larger of the two squared point-to-epipolar-line
+// distances (not Sampson's).
+XK_ESS_HD double xk_fund_error(const double *F, double x1, double y1, double x2, double y2) {
+  double a = F[0] * x1 + F[1] * y1 + F[2], b = F[3] * x1 + F[4] * y1 + F[5], c = F[6] * x1 + F[7] * y1 + F[8];
+  const double e2 = x2 * a + y2 * b + c, s2 = a * a + b * b;
+  a = F[0] * x2 + F[3] * y2 + F[6]; b = F[1] * x2 + F[4] * y2 + F[7]; c = F[2] * x2 + F[5] * y2 + F[8];
+  const double e1 = x1 * a + y1 * b + c, s1 = a * a + b * b;
+  return fmax(e1 * e1 / s1, e2 * e2 / s2);     // (fmax drops one NaN; two, 0/0 under F = 0, compare false against t2)
+}
+
+// camera.cpp:69-87 on one distorted pixel; s_term = 1 / (2 tan(s/2)) (camera.cpp:39), unused where s = 0.
+XK_ESS_HD void xk_fund_undistort1(double ud, double vd, double fx, double fy, double cx, double cy, double s, double s_term,
+                                  double *u, double *v) {
+  const double x = (ud - cx) / fx, y = (vd - cy) / fy;
+  const double r = sqrt(x * x + y * y);
+  double f = 1.0;
+  if (r > 0.01 && s != 0.0) f = tan(r * s) * s_term / r;
+  *u = f * x * fx + cx;
+  *v = f * y * fy + cy;
+}
+
+struct XkFundArgs {
+  const double *dist;               // [n_pts][2] distorted pixels (xk_fund_undistort only)
+  double *und;                      // [n_pts][2] undistorted pixels, fp64: previous list, then the current one behind it
+  double *pts;                      // [n_pts][2] the same through float
+  int n_pts;                        // points of xk_fund_undistort (2 n for a frame)
+  int n, n_hyp;
+  double fx, fy, cx, cy, s, s_term, t2;
+  unsigned long long seed;
+  // scratch block
+  double *cand;                     // [XK_FUND_MAX_HYP][3][9]
+  double *sum;                      // [XK_FUND_MAX_HYP][3]
+  int *cnt;                         // [XK_FUND_MAX_HYP][3]
+  int *ncand, *bestc;               // [XK_FUND_MAX_HYP]
+  unsigned long long *key;
+  // result
+  double *F;                        // [9]
+  double *kept_prev, *kept_cur;     // [n][2] each, the first n_inliers rows written
+  int *res;                         // n_inliers, winner hypothesis
+  int *keep_idx;                    // [n]
+  unsigned char *mask;              // [n]
+};
+
+__global__ __launch_bounds__(256) void xk_fund_undistort(XkFundArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_pts) return;
+  double u, v;
+  xk_fund_undistort1(a.dist[2 * i], a.dist[2 * i + 1], a.fx, a.fy, a.cx, a.cy, a.s, a.s_term, &u, &v);
+  a.und[2 * i] = u; a.und[2 * i + 1] = v;
+  a.pts[2 * i] = (double)(float)u; a.pts[2 * i + 1] = (double)(float)v;
+}
+
+__global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {
+  const int h = blockIdx.x * XK_FUND_SOLVE_T + threadIdx.x;
+  if (h == 0) *a.key = 0ull;
+  if (h >= a.n_hyp) return;
+  int pick[7];
+  xk_fund_sample(a.seed, h, a.n, pick);
+  const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
+  double p1[7][2], p2[7][2];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    p1[k][0] = (P1[2 * pick[k]] - a.cx) / a.fx; p1[k][1] = (P1[2 * pick[k] + 1] - a.cy) / a.fy;
+    p2[k][0] = (P2[2 * pick[k]] - a.cx) / a.fx; p2[k][1] = (P2[2 * pick[k] + 1] - a.cy) / a.fy;
+  }
+  double *F = a.cand + (size_t)h * (XK_FUND_MAXC * 9);   // (written in place: a slot index in registers would be a runtime one)
+  const int nc = xk_fund_solve7(p1, p2, a.fx, a.fy, a.cx, a.cy, F);
+  for (int i = nc * 9; i < XK_FUND_MAXC * 9; ++i) F[i] = 0.0;
+  a.ncand[h] = nc;
+}
+
+__global__ __launch_bounds__(256) void xk_fund_score(XkFundArgs a) {
+  __shared__ int s_cnt[4];
+  __shared__ double s_sum[4];
+  const int h = blockIdx.x, nc = a.ncand[h];
+  const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
+  int best_c = -1, best_cnt = -1;
+  double best_sum = 0.0;
+  for (int c = 0; c < XK_FUND_MAXC; ++c) {
+    int cnt = 0;
+    double sum = 0.0;
+    if (c < nc) {
+      const double *Fp = a.cand + ((size_t)h * XK_FUND_MAXC + c) * 9;
+      const double F[9] = {Fp[0], Fp[1], Fp[2], Fp[3], Fp[4], Fp[5], Fp[6], Fp[7], Fp[8]};
+      for (int i = threadIdx.x; i < a.n; i += 256) {
+        const double d = xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]);
+        if (d <= a.t2) { ++cnt; sum += d; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_down(cnt, o, 64); sum += __shfl_down(sum, o, 64); }
+      if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_sum[threadIdx.x >> 6] = sum; }
+      __syncthreads();
+      cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+      sum = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+      __syncthreads();
+      if (cnt > best_cnt || (cnt == best_cnt && sum < best_sum)) { best_cnt = cnt; best_sum = sum; best_c = c; }
+    }
+    if (threadIdx.x == 0) { a.cnt[h * XK_FUND_MAXC + c] = cnt; a.sum[h * XK_FUND_MAXC + c] = sum; }
+  }
+  if (threadIdx.x == 0) {
+    a.bestc[h] = best_c;
+    // count in the high word, inverted hypothesis index in the low word: the maximum is the highest count, then the lowest h
+    if (best_c >= 0) atomicMax(a.key, ((unsigned long long)best_cnt << 32) | (unsigned long long)(0xffffffffu - (unsigned int)h));
+  }
+}
+
+__global__ __launch_bounds__(256) void xk_fund_mask(XkFundArgs a) {
+  __shared__ int s_w[4];
+  const unsigned long long key = *a.key;
+  const bool valid = key != 0ull;            // (false: no hypothesis produced a candidate)
+  const int h = valid ? (int)(0xffffffffu - (unsigned int)(key & 0xffffffffull)) : 0;
+  const double *Fp = a.cand + ((size_t)h * XK_FUND_MAXC + (valid ? a.bestc[h] : 0)) * 9;
+  const double F[9] = {Fp[0], Fp[1], Fp[2], Fp[3], Fp[4], Fp[5], Fp[6], Fp[7], Fp[8]};
+  const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
+  const double *U1 = a.und, *U2 = a.und + 2 * (size_t)a.n;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int base = 0;                              // pairs kept before this chunk of 256
+  for (int i0 = 0; i0 < a.n; i0 += 256) {
+    const int i = i0 + threadIdx.x;
+    bool keep = false;
+    if (i < a.n) {
+      keep = valid && xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]) <= a.t2;
+      a.mask[i] = keep ? 1 : 0;
+    }
+    const unsigned long long b = __ballot(keep);
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) s_w[w] = __popcll(b);
+    __syncthreads();
+    int off = base;
+    for (int j = 0; j < w; ++j) off += s_w[j];
+    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (keep) {                              // (off + before < n: it counts kept pairs of index < i)
+      const int pos = off + before;
+      a.keep_idx[pos] = i;
+      a.kept_prev[2 * pos] = U1[2 * i]; a.kept_prev[2 * pos + 1] = U1[2 * i + 1];
+      a.kept_cur[2 * pos] = U2[2 * i]; a.kept_cur[2 * pos + 1] = U2[2 * i + 1];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 9) a.F[threadIdx.x] = valid ? Fp[threadIdx.x] : 0.0;
+  // (the count is this kernel's own: the length of what it compacted, whatever the scoring kernel's rounding made of the same pairs)
+  if (threadIdx.x == 0) { a.res[0] = base; a.res[1] = valid ? h : -1; }
+}
