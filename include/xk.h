@@ -421,6 +421,51 @@ int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *c
                           int n_hyp, unsigned long seed, unsigned char *mask, int *keep_idx, double *prev_xy, double *cur_xy,
                           int *n_inliers);
 
+/* ---- feature tracking in front of that filter (Tracker::featureTracking, tracker.cpp:623-690) --------------------
+ * Every frame the reference runs cv::calcOpticalFlowPyrLK(previous image, current image, pts1, ..., win_size_, max_level_,
+ * term_crit_, cv::OPTFLOW_LK_GET_MIN_EIGENVALS, min_eig_thr_) on the previous features' distorted pixels and drops every
+ * point that failed or left the frame; what is left is the match list xk_trk_filter_matches takes.  The same xk_trk does
+ * that on the device.  The algorithm is this project's statement of that call: OpenCV's steps with every
+ * integer quantity kept exact -- the sums over the window included -- and fp64 where OpenCV uses float. */
+
+/* The parameters Tracker holds (tracker.h:234-261: win_size_ 31 x 31, max_level_ 2, term_crit_ 30 iterations / eps 0.01,
+ * min_eig_thr_ 0.003) and the image size.  Allocates two image slots (pyramid and Scharr derivatives of levels 0 ...
+ * levels) on the device and the pinned staging of one image and of the results; calling it again replaces both and
+ * forgets the images -- once the new buffers exist: a call that fails (XK_EINVAL, XK_ENOMEM) leaves the earlier setup and
+ * its images as they were.  levels is the largest l <= max_level whose size (halved with rounding up, l times) still exceeds
+ * the window in both directions, as for every level below it.  XK_EINVAL: width / height outside 16...4096, win_w / win_h
+ * outside 3...31 or not smaller than the image, max_level outside 0...4, max_iter outside 1...100, eps outside (0, 10],
+ * min_eig_thr < 0. */
+int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int win_h, int max_level, int max_iter, double eps,
+                     double min_eig_thr);
+/* levels as above, or -1 before xk_trk_klt_setup. */
+int xk_trk_klt_levels(xk_trk *t);
+
+/* previous_img_ = current_img.clone() (tracker.cpp:302) and the new current image: img HOST [height][stride] uint8, stride
+ * >= width.  The current slot becomes the previous one; the image is copied (through the pinned staging: the caller's
+ * buffer is free on return) and its pyramid and derivatives are queued on the handle's stream -- one launch per level
+ * each, no synchronisation but a wait for the previous push's upload.  XK_EINVAL before xk_trk_klt_setup, img NULL,
+ * stride < width. */
+int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride);
+
+/* Tracker::featureTracking (tracker.cpp:623-690) from the previous image to the current one: prev_xy HOST [n][2] float32,
+ * the cv::Point2f of Feature::getDistPoint2f (:629-633), widened to fp64 -> cur_xy HOST [n][2], status HOST [n] (1 =
+ * tracked), min_eig HOST [n] (the err of OPTFLOW_LK_GET_MIN_EIGENVALS: the level-0 minimal eigenvalue per window pixel; 0
+ * for a point outside level 0), and the post-filter of :658-686 -- kept iff status != 0 and -0.5 <= x <= width - 0.5,
+ * -0.5 <= y <= height - 0.5: keep_idx HOST [n] (the first *n_kept entries, ascending), kept_prev_xy / kept_cur_xy HOST
+ * [n][2] (the first *n_kept rows, in input order as the erase loop of :660-686 leaves them).  A non-finite point comes back
+ * as it went in with status 0.  One copy in, one launch pair, one copy out, one synchronisation.  Every output is
+ * required.  XK_EINVAL: null pointers, n < 0, before xk_trk_klt_setup, fewer than two images pushed; n > max_matches:
+ * XK_ECAPACITY; n = 0: XK_OK and *n_kept = 0. */
+int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_xy, unsigned char *status, double *min_eig, int *keep_idx,
+                 double *kept_prev_xy, double *kept_cur_xy, int *n_kept);
+
+/* One pyramid level of the previous (which = 0) or the current (1) image as the device holds it (the pyramid that
+ * cv::calcOpticalFlowPyrLK builds inside the call of tracker.cpp:648-651): img HOST [h][w] uint8, dIx / dIy HOST [h][w]
+ * int16, *w, *h.  Any output may be NULL.  An inspection path, not part of a frame: straight copies.  XK_EINVAL: a level
+ * above levels, an image that has not been pushed. */
+int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short *dIx, short *dIy, int *w, int *h);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and

@@ -38,6 +38,7 @@ SYMBOLS = [
     "xk_pr_essential_ransac", "xk_pr_essential_hypotheses",
     "xk_trk_create", "xk_trk_destroy", "xk_trk_undistort", "xk_trk_fundamental_ransac", "xk_trk_fundamental_hypotheses",
     "xk_trk_filter_matches",
+    "xk_trk_klt_setup", "xk_trk_klt_levels", "xk_trk_push_image", "xk_trk_track", "xk_trk_klt_level",
 ]
 
 

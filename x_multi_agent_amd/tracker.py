@@ -3,7 +3,10 @@
 (src/x/vision/tracker.cpp:233-293, camera.cpp:62-87): what every frame's match list passes through before the track
 manager sees it.
 
-No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h)."""
+`Klt` is the step in front of it: the pyramidal Lucas-Kanade tracking of `Tracker::featureTracking` (tracker.cpp:623-690),
+from two images and the previous features to the pairs that filter takes.
+
+No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +15,7 @@ from .engine import XkError, c_dp, c_ip
 
 c_ub = C.POINTER(C.c_ubyte)
 c_fp = C.POINTER(C.c_float)
+c_sp = C.POINTER(C.c_short)
 
 
 class MatchFilter:
@@ -93,3 +97,85 @@ class MatchFilter:
                                                C.byref(ninl)), "xk_trk_filter_matches")
         m = ninl.value
         return mask[:n], keep[:m], pxy[:m], cxy[:m]
+
+
+class Klt:
+    """cv::calcOpticalFlowPyrLK as x::Tracker calls it (tracker.cpp:642-651, parameters tracker.h:234-261) and the post-filter
+    behind it (:658-686) on one agent's GPU: push_image per frame, track per frame.  match_filter: an existing MatchFilter
+    whose xk_trk this object shares, so that one device object serves both steps of a frame (max_features is then its
+    max_matches); without one the object owns an xk_trk with placeholder intrinsics, which the tracking never reads."""
+
+    def __init__(self, eng, max_features, width, height, win=(31, 31), max_level=2, max_iter=30, eps=0.01, min_eig_thr=0.003,
+                 match_filter=None):
+        self.eng, self.L = eng, eng.L
+        self.owner = match_filter
+        if match_filter is not None:
+            self.p, self.max_features = match_filter.p, match_filter.max_matches
+        else:
+            self.max_features = int(max_features)
+            self.p = C.c_void_p()
+            rc = self.L.xk_trk_create(eng.h, C.c_int(self.max_features), C.c_double(1.0), C.c_double(1.0), C.c_double(0.0),
+                                      C.c_double(0.0), C.c_double(0.0), C.byref(self.p))
+            if rc != 0:
+                raise XkError(rc, "xk_trk_create", (self.L.xk_last_error(eng.h) or b"").decode())
+        try:
+            self.setup(width, height, win, max_level, max_iter, eps, min_eig_thr)
+        except XkError:
+            self.close()
+            raise
+
+    def setup(self, width, height, win=(31, 31), max_level=2, max_iter=30, eps=0.01, min_eig_thr=0.003):
+        """xk_trk_klt_setup: new sizes and parameters; the pushed images are forgotten."""
+        self._chk(self.L.xk_trk_klt_setup(self.p, C.c_int(width), C.c_int(height), C.c_int(win[0]), C.c_int(win[1]), C.c_int(max_level),
+                                          C.c_int(max_iter), C.c_double(eps), C.c_double(min_eig_thr)), "xk_trk_klt_setup")
+        self.width, self.height, self.win = int(width), int(height), (int(win[0]), int(win[1]))
+
+    def close(self):
+        if self.owner is None and self.p:
+            self.L.xk_trk_destroy(self.p)
+        self.p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise XkError(rc, what, (self.L.xk_last_error(self.eng.h) or b"").decode())
+
+    def levels(self):
+        """The highest pyramid level in use (rule 1 of DESIGN 3.11)."""
+        return int(self.L.xk_trk_klt_levels(self.p))
+
+    def push_image(self, img):
+        """The next frame, uint8 [height, >= width]; a row stride beyond the width (a view of a wider array) is passed on."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] != self.height or img.shape[1] < self.width:
+            raise ValueError("push_image: a uint8 image of the set-up height and at least the set-up width")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        self._chk(self.L.xk_trk_push_image(self.p, img.ctypes.data_as(c_ub), C.c_int(img.strides[0])), "xk_trk_push_image")
+
+    def track(self, prev_xy):
+        """Tracker::featureTracking: float32 pixels [n, 2] in the previous image -> dict of cur_xy fp64 [n, 2], status uint8
+        [n], min_eig [n], keep_idx [m] ascending, kept_prev [m, 2], kept_cur [m, 2] (input order)."""
+        prev = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+        n, m = len(prev), max(len(prev), 1)
+        cur, status, eig = np.zeros((m, 2)), np.zeros(m, np.uint8), np.zeros(m)
+        keep, kp, kc, nk = np.zeros(m, np.int32), np.zeros((m, 2)), np.zeros((m, 2)), C.c_int(0)
+        self._chk(self.L.xk_trk_track(self.p, prev.ctypes.data_as(c_fp), C.c_int(n), cur.ctypes.data_as(c_dp), status.ctypes.data_as(c_ub),
+                                      eig.ctypes.data_as(c_dp), keep.ctypes.data_as(c_ip), kp.ctypes.data_as(c_dp), kc.ctypes.data_as(c_dp),
+                                      C.byref(nk)), "xk_trk_track")
+        k = nk.value
+        return dict(cur_xy=cur[:n], status=status[:n], min_eig=eig[:n], keep_idx=keep[:k], kept_prev=kp[:k], kept_cur=kc[:k])
+
+    def level(self, which, level):
+        """Pyramid level `level` of the previous (which = 0) or current (1) image -> (image uint8, dIx int16, dIy int16)."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._chk(self.L.xk_trk_klt_level(self.p, C.c_int(which), C.c_int(level), None, None, None, C.byref(w), C.byref(h)), "xk_trk_klt_level")
+        img, dx, dy = np.zeros((h.value, w.value), np.uint8), np.zeros((h.value, w.value), np.int16), np.zeros((h.value, w.value), np.int16)
+        self._chk(self.L.xk_trk_klt_level(self.p, C.c_int(which), C.c_int(level), img.ctypes.data_as(c_ub), dx.ctypes.data_as(c_sp),
+                                          dy.ctypes.data_as(c_sp), None, None), "xk_trk_klt_level")
+        return img, dx, dy
