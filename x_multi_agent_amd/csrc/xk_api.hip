@@ -2577,766 +2577,35 @@ extern "C" int xk_debug_feature_phases(xk_handle *h, double sigma_img, long long
 #endif
 
 // ---------------------------------------------------------------------------
-// Place-recognition request filter + keyframe store: the component either side of the CI
-// exchange on the communication axis.  Mirrors VLAD / Database / Keyframe of src/x/place_recognition.
+// The vision stages in front of the filter: place recognition (xk_pr_*) and the tracker's front end (xk_trk_*).  Their host
+// side lives in the two headers included below; their RANSAC filters share xk_ransac.hip.h.
 // ---------------------------------------------------------------------------
-#include "xk_place.hip.h"
-#include "xk_essential.hip.h"
+#include "xk_ransac.hip.h"
 
-#define XK_PR_MAX_KEYFRAMES 15   // database.h:70
-
-struct xk_pr {
-  xk_handle *h;
-  int k, L, n_nodes, kmax, W, n_words, clusters, VW, max_desc;
-  long pay_n, trk_n;
-  unsigned int *d_node_desc;
-  int *d_children, *d_word_of_node, *d_node_of_word;
-  // keyframe store: slot s of the ring holds one keyframe; order[] lists the live slots oldest first
-  unsigned int *d_vlad;       // [15][VW]
-  unsigned int *d_kfdesc;     // [15][max_desc][W]
-  double *d_payload;          // [15][pay_n]
-  double *d_tracks;           // [15][trk_n]
-  int n_desc[XK_PR_MAX_KEYFRAMES];
-  long tag[XK_PR_MAX_KEYFRAMES];
-  std::vector<int> *uav_ids[XK_PR_MAX_KEYFRAMES];   // Keyframe::uav_ids_ (a std::set in the reference)
-  int order[XK_PR_MAX_KEYFRAMES], live;
-  // scratch
-  unsigned int *d_q, *d_t, *d_qvlad;
-  int *d_ham, *d_knn;
-  int *h_int;                 // pinned
-  unsigned int *h_words;      // pinned staging for descriptors / VLADs
-  size_t h_words_cap;
-  // essential-matrix RANSAC (xk_essential.hip.h): allocated by the first xk_pr_essential_ransac, not by xk_pr_create
-  double *d_ess;              // candidates [4096][10][9], sums [4096][10], E [9], key; then the int and byte parts
-  unsigned char *h_ess;       // pinned: pixel pairs in, E / n_inliers / winner / mask out
-  int ess_n_hyp;              // hypotheses of the last call (0: none yet)
-};
-
-// layout of the scratch block d_ess (doubles first, so everything stays aligned)
-#define XK_ESS_OFF_SUM ((size_t)XK_ESS_MAX_HYP * XK_ESS_MAXC * 9)
-#define XK_ESS_OFF_E (XK_ESS_OFF_SUM + (size_t)XK_ESS_MAX_HYP * XK_ESS_MAXC)
-#define XK_ESS_OFF_KEY (XK_ESS_OFF_E + 9)
-#define XK_ESS_DOUBLES (XK_ESS_OFF_KEY + 1)
-#define XK_ESS_INTS ((size_t)XK_ESS_MAX_HYP * (XK_ESS_MAXC + 2) + 2)   // cnt, ncand, bestc, res
-
-extern "C" void xk_pr_destroy(xk_pr *p) {
-  if (!p) return;
-  hipFree(p->d_node_desc); hipFree(p->d_children); hipFree(p->d_word_of_node); hipFree(p->d_node_of_word);
-  hipFree(p->d_vlad); hipFree(p->d_kfdesc); hipFree(p->d_payload); hipFree(p->d_tracks);
-  hipFree(p->d_q); hipFree(p->d_t); hipFree(p->d_qvlad); hipFree(p->d_ham); hipFree(p->d_knn);
-  if (p->h_int) hipHostFree(p->h_int);
-  if (p->h_words) hipHostFree(p->h_words);
-  hipFree(p->d_ess);
-  if (p->h_ess) hipHostFree(p->h_ess);
-  for (auto &u : p->uav_ids) delete u;
-  free(p);
-}
-
-extern "C" int xk_pr_create(xk_handle *h, int k, int L, int n_nodes, int kmax, int desc_bytes,
-                            const unsigned char *node_desc, const int *children, const int *word_of_node,
-                            const int *node_of_word, int n_words, long payload_doubles, long tracks_doubles,
-                            int max_desc, xk_pr **out) {
-  if (!h || !out || !node_desc || !children || !word_of_node || !node_of_word) return XK_EINVAL;
-  if (k < 1 || L < 1 || n_nodes < 2 || kmax < 1 || n_words < 1 || max_desc < 1 || payload_doubles < 0 || tracks_doubles < 0)
-    return fail(h, XK_EINVAL, "xk_pr_create: bad sizes");
-  if (desc_bytes < 4 || desc_bytes % 4 || desc_bytes > 4 * XK_PR_MAXW)
-    return fail(h, XK_EINVAL, "xk_pr_create: descriptor size must be a multiple of 4 bytes, at most 64");
-  double cl = 1.0;
-  for (int i = 0; i < L; ++i) cl *= k;                       // pow(k, L), vlad.cpp:27-28
-  if (cl * desc_bytes > (double)(64 << 20)) return fail(h, XK_ECAPACITY, "xk_pr_create: VLAD larger than 64 MB");
-  for (int i = 0; i < n_nodes; ++i)
-    if (word_of_node[i] >= n_words || word_of_node[i] >= (int)cl) return fail(h, XK_EINVAL, "xk_pr_create: word id out of range");
-  xk_pr *p = (xk_pr *)calloc(1, sizeof(xk_pr));
-  if (!p) return XK_ENOMEM;
-  p->h = h; p->k = k; p->L = L; p->n_nodes = n_nodes; p->kmax = kmax; p->W = desc_bytes / 4; p->n_words = n_words;
-  p->clusters = (int)cl; p->VW = p->clusters * p->W; p->max_desc = max_desc; p->pay_n = payload_doubles; p->trk_n = tracks_doubles;
-  for (auto &u : p->uav_ids) u = new std::vector<int>();
-  const size_t wcap = std::max((size_t)max_desc * p->W * 2, (size_t)p->VW * 2);
-  p->h_words_cap = wcap;
-  bool ok = dalloc(&p->d_node_desc, (size_t)n_nodes * p->W) == hipSuccess && dalloc(&p->d_children, (size_t)n_nodes * kmax) == hipSuccess &&
-            dalloc(&p->d_word_of_node, (size_t)n_nodes) == hipSuccess && dalloc(&p->d_node_of_word, (size_t)n_words) == hipSuccess &&
-            dalloc(&p->d_vlad, (size_t)XK_PR_MAX_KEYFRAMES * p->VW) == hipSuccess &&
-            dalloc(&p->d_kfdesc, (size_t)XK_PR_MAX_KEYFRAMES * max_desc * p->W) == hipSuccess &&
-            dalloc(&p->d_payload, (size_t)XK_PR_MAX_KEYFRAMES * payload_doubles) == hipSuccess &&
-            dalloc(&p->d_tracks, (size_t)XK_PR_MAX_KEYFRAMES * tracks_doubles) == hipSuccess &&
-            dalloc(&p->d_q, (size_t)max_desc * p->W) == hipSuccess && dalloc(&p->d_t, (size_t)max_desc * p->W) == hipSuccess &&
-            dalloc(&p->d_qvlad, (size_t)p->VW) == hipSuccess && dalloc(&p->d_ham, (size_t)XK_PR_MAX_KEYFRAMES) == hipSuccess &&
-            dalloc(&p->d_knn, (size_t)max_desc * 4) == hipSuccess &&
-            hipHostMalloc((void **)&p->h_int, sizeof(int) * ((size_t)max_desc * 4 + 64)) == hipSuccess &&
-            hipHostMalloc((void **)&p->h_words, sizeof(unsigned int) * wcap) == hipSuccess;
-  if (ok) {
-    ok = hipMemcpy(p->d_node_desc, node_desc, (size_t)n_nodes * desc_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_children, children, sizeof(int) * (size_t)n_nodes * kmax, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_word_of_node, word_of_node, sizeof(int) * (size_t)n_nodes, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_node_of_word, node_of_word, sizeof(int) * (size_t)n_words, hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (!ok) { xk_pr_destroy(p); return fail(h, XK_ENOMEM, "xk_pr_create: allocation failed"); }
-  *out = p;
-  return XK_OK;
-}
-
-extern "C" int xk_pr_vlad_bytes(const xk_pr *p) { return p ? p->VW * 4 : 0; }
-extern "C" int xk_pr_size(const xk_pr *p) { return p ? p->live : 0; }
-
-// descriptors (host) -> VLAD in `d_dst` (device); the descriptors stay in p->d_q afterwards
-static int pr_vlad_device(xk_pr *p, const unsigned char *desc, int n, unsigned int *d_dst) {
-  xk_handle *h = p->h;
-  if (n < 0 || n > p->max_desc) return fail(h, XK_ECAPACITY, "place recognition: more descriptors than max_desc");
-  HIPCHK(h, hipMemsetAsync(d_dst, 0, sizeof(unsigned int) * p->VW, h->stream));
-  if (n > 0) {
-    if (!desc) return fail(h, XK_EINVAL, "place recognition: null descriptors");
-    memcpy(p->h_words, desc, (size_t)n * p->W * 4);
-    HIPCHK(h, hipMemcpyAsync(p->d_q, p->h_words, (size_t)n * p->W * 4, hipMemcpyHostToDevice, h->stream));
-    XkVladArgs a{p->d_q, n, p->W, p->d_node_desc, p->d_children, p->kmax, p->d_word_of_node, p->d_node_of_word, d_dst};
-    hipLaunchKernelGGL(xk_vlad_build, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
-  }
-  return XK_OK;
-}
-
-extern "C" int xk_pr_compute_vlad(xk_pr *p, const unsigned char *desc, int n, unsigned char *vlad_out) {
-  if (!p || !vlad_out) return XK_EINVAL;
-  xk_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = pr_vlad_device(p, desc, n, p->d_qvlad);
-  if (rc != XK_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(p->h_words, p->d_qvlad, sizeof(unsigned int) * p->VW, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  memcpy(vlad_out, p->h_words, sizeof(unsigned int) * p->VW);
-  return XK_OK;
-}
-
-extern "C" int xk_pr_add_keyframe(xk_pr *p, const unsigned char *desc, int n_desc, const double *d_payload,
-                                  const double *d_tracks, long tag) {
-  if (!p) return XK_EINVAL;
-  xk_handle *h = p->h;
-  // (checked BEFORE the oldest keyframe is dropped: a rejected call leaves the database as it was)
-  if (n_desc < 0 || n_desc > p->max_desc) return fail(h, XK_ECAPACITY, "place recognition: more descriptors than max_desc");
-  if (n_desc > 0 && !desc) return fail(h, XK_EINVAL, "place recognition: null descriptors");
-  HIPCHK(h, hipSetDevice(h->device));
-  // slot: a free one, or the oldest keyframe's (erase(begin()), database.cpp:56-58)
-  int slot;
-  if (p->live < XK_PR_MAX_KEYFRAMES) {
-    bool used[XK_PR_MAX_KEYFRAMES] = {false};
-    for (int i = 0; i < p->live; ++i) used[p->order[i]] = true;
-    slot = 0;
-    while (used[slot]) ++slot;
-  } else {
-    slot = p->order[0];
-    for (int i = 1; i < p->live; ++i) p->order[i - 1] = p->order[i];
-    --p->live;
-  }
-  int rc = pr_vlad_device(p, desc, n_desc, p->d_vlad + (size_t)slot * p->VW);
-  if (rc != XK_OK) return rc;
-  if (n_desc > 0)
-    HIPCHK(h, hipMemcpyAsync(p->d_kfdesc + (size_t)slot * p->max_desc * p->W, p->d_q, (size_t)n_desc * p->W * 4,
-                             hipMemcpyDeviceToDevice, h->stream));
-  if (d_payload && p->pay_n)
-    HIPCHK(h, hipMemcpyAsync(p->d_payload + (size_t)slot * p->pay_n, d_payload, sizeof(double) * p->pay_n, hipMemcpyDeviceToDevice, h->stream));
-  if (d_tracks && p->trk_n)
-    HIPCHK(h, hipMemcpyAsync(p->d_tracks + (size_t)slot * p->trk_n, d_tracks, sizeof(double) * p->trk_n, hipMemcpyDeviceToDevice, h->stream));
-  p->n_desc[slot] = n_desc; p->tag[slot] = tag; p->uav_ids[slot]->clear();
-  p->order[p->live++] = slot;
-  return XK_OK;
-}
-
-extern "C" int xk_pr_find_candidate(xk_pr *p, int uav_id, const unsigned char *query_vlad, double pr_score_thr, int *index,
-                                    double *score, long *tag) {
-  if (!p || !query_vlad || !index) return XK_EINVAL;
-  xk_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  *index = -1;
-  if (score) *score = 0.0;
-  if (tag) *tag = -1;
-  if (p->live == 0) return XK_OK;
-  memcpy(p->h_words, query_vlad, sizeof(unsigned int) * p->VW);
-  HIPCHK(h, hipMemcpyAsync(p->d_qvlad, p->h_words, sizeof(unsigned int) * p->VW, hipMemcpyHostToDevice, h->stream));
-  XkVladHamArgs a{p->d_qvlad, p->d_vlad, p->VW, p->d_ham};
-  hipLaunchKernelGGL(xk_vlad_hamming, dim3(XK_PR_MAX_KEYFRAMES), dim3(256), 0, h->stream, a);
-  HIPCHK(h, hipMemcpyAsync(p->h_int, p->d_ham, sizeof(int) * XK_PR_MAX_KEYFRAMES, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  // the selection loop of Database::findCandidate (database.cpp:32-45), keyframes oldest first
-  const double v_length = (double)p->VW * 32.0;
-  double best = 0.0;
-  int best_pos = -1;
-  for (int i = 0; i < p->live; ++i) {
-    const int s = p->order[i];
-    bool seen = false;
-    for (int u : *p->uav_ids[s]) seen |= (u == uav_id);
-    if (seen) continue;
-    const double sc = (v_length - (double)p->h_int[s]) / v_length;      // vlad.cpp:71
-    if (sc > pr_score_thr && sc > best) { best = sc; best_pos = i; }
-  }
-  if (best_pos >= 0) {
-    p->uav_ids[p->order[best_pos]]->push_back(uav_id);
-    *index = best_pos;
-    if (score) *score = best;
-    if (tag) *tag = p->tag[p->order[best_pos]];
-  }
-  return XK_OK;
-}
-
-extern "C" int xk_pr_keyframe(xk_pr *p, int index, const double **d_payload, const double **d_tracks, int *n_desc, long *tag,
-                              unsigned char *desc_out) {
-  if (!p) return XK_EINVAL;
-  xk_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (index < 0 || index >= p->live) return fail(h, XK_EINVAL, "xk_pr_keyframe: no such keyframe");
-  const int s = p->order[index];
-  if (d_payload) *d_payload = p->d_payload + (size_t)s * p->pay_n;
-  if (d_tracks) *d_tracks = p->d_tracks + (size_t)s * p->trk_n;
-  if (n_desc) *n_desc = p->n_desc[s];
-  if (tag) *tag = p->tag[s];
-  if (desc_out && p->n_desc[s] > 0) {
-    HIPCHK(h, hipMemcpyAsync(p->h_words, p->d_kfdesc + (size_t)s * p->max_desc * p->W, (size_t)p->n_desc[s] * p->W * 4,
-                             hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(desc_out, p->h_words, (size_t)p->n_desc[s] * p->W * 4);
-  }
-  return XK_OK;
-}
-
-extern "C" int xk_pr_copy_keyframe(xk_pr *p, int index, double *d_payload_dst, double *d_tracks_dst) {
-  if (!p) return XK_EINVAL;
-  xk_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (index < 0 || index >= p->live) return fail(h, XK_EINVAL, "xk_pr_copy_keyframe: no such keyframe");
-  const int s = p->order[index];
-  if (d_payload_dst && p->pay_n)
-    HIPCHK(h, hipMemcpyAsync(d_payload_dst, p->d_payload + (size_t)s * p->pay_n, sizeof(double) * p->pay_n, hipMemcpyDeviceToDevice, h->stream));
-  if (d_tracks_dst && p->trk_n)
-    HIPCHK(h, hipMemcpyAsync(d_tracks_dst, p->d_tracks + (size_t)s * p->trk_n, sizeof(double) * p->trk_n, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return XK_OK;
-}
-
-extern "C" int xk_pr_knn_match(xk_pr *p, const unsigned char *query, int nq, const unsigned char *train, int nt, int *idx,
-                               int *dist) {
-  if (!p || !idx || !dist || nq < 0 || nt < 0) return XK_EINVAL;
-  xk_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (nq > p->max_desc || nt > p->max_desc) return fail(h, XK_ECAPACITY, "xk_pr_knn_match: more descriptors than max_desc");
-  if (nq == 0) return XK_OK;
-  if (!query || (nt > 0 && !train)) return fail(h, XK_EINVAL, "xk_pr_knn_match: null descriptors");
-  const size_t qb = (size_t)nq * p->W * 4, tb = (size_t)nt * p->W * 4;
-  memcpy(p->h_words, query, qb);
-  if (nt) memcpy(p->h_words + (size_t)nq * p->W, train, tb);
-  HIPCHK(h, hipMemcpyAsync(p->d_q, p->h_words, qb, hipMemcpyHostToDevice, h->stream));
-  if (nt) HIPCHK(h, hipMemcpyAsync(p->d_t, p->h_words + (size_t)nq * p->W, tb, hipMemcpyHostToDevice, h->stream));
-  XkKnnArgs a{p->d_q, p->d_t, nq, nt, p->W, p->d_knn, p->d_knn + 2 * (size_t)p->max_desc};
-  hipLaunchKernelGGL(xk_desc_knn2, dim3((nq + XK_KNN_Q - 1) / XK_KNN_Q), dim3(256), 0, h->stream, a);
-  HIPCHK(h, hipMemcpyAsync(p->h_int, p->d_knn, sizeof(int) * 2 * (size_t)nq, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->h_int + 2 * (size_t)nq, p->d_knn + 2 * (size_t)p->max_desc, sizeof(int) * 2 * (size_t)nq,
-                           hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  memcpy(idx, p->h_int, sizeof(int) * 2 * (size_t)nq);
-  memcpy(dist, p->h_int + 2 * (size_t)nq, sizeof(int) * 2 * (size_t)nq);
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Essential-matrix RANSAC filter of findCorrespondences (place_recognition.cpp:269-281), xk_essential.hip.h
-// ---------------------------------------------------------------------------
-static XkEssArgs ess_args(xk_pr *p) {
-  XkEssArgs a{};
-  a.cand = p->d_ess;
-  a.sum = p->d_ess + XK_ESS_OFF_SUM;
-  a.E = p->d_ess + XK_ESS_OFF_E;
-  a.key = (unsigned long long *)(p->d_ess + XK_ESS_OFF_KEY);
-  a.cnt = (int *)(p->d_ess + XK_ESS_DOUBLES);
-  a.ncand = a.cnt + (size_t)XK_ESS_MAX_HYP * XK_ESS_MAXC;
-  a.bestc = a.ncand + XK_ESS_MAX_HYP;
-  a.res = a.bestc + XK_ESS_MAX_HYP;
-  float *xy = (float *)(a.res + 2);
-  a.cur_xy = xy;                                             // (rec_xy follows the n pairs of the call)
-  a.mask = (unsigned char *)(xy + 4 * (size_t)p->max_desc);
-  return a;
-}
-
-extern "C" int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, int n, double fx, double fy, double cx,
-                                      double cy, double threshold_px, int n_hyp, unsigned long seed, unsigned char *mask,
-                                      double *E, int *n_inliers) {
-  if (!p) return XK_EINVAL;
-  xk_handle *h = p->h;
-  if (!mask || !n_inliers || n < 0 || (n > 0 && (!cur_xy || !rec_xy)))
-    return fail(h, XK_EINVAL, "xk_pr_essential_ransac: null argument or negative n");
-  if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-    return fail(h, XK_EINVAL, "xk_pr_essential_ransac: focal lengths must be positive and the intrinsics finite");
-  if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) return fail(h, XK_EINVAL, "xk_pr_essential_ransac: threshold_px < 0");
-  if (n_hyp < 1 || n_hyp > XK_ESS_MAX_HYP) return fail(h, XK_EINVAL, "xk_pr_essential_ransac: n_hyp outside 1...4096");
-  if (n > p->max_desc) return fail(h, XK_ECAPACITY, "xk_pr_essential_ransac: more point pairs than max_desc");
-  *n_inliers = 0;
-  memset(mask, 0, (size_t)n);
-  if (E) memset(E, 0, 9 * sizeof(double));
-  if (n < 5) return XK_OK;                                   // F_1.empty() -> return false
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t xy_bytes = sizeof(float) * 4 * (size_t)p->max_desc, out_bytes = 9 * sizeof(double) + 2 * sizeof(int) + (size_t)p->max_desc;
-  if (!p->d_ess) {
-    void *d = nullptr, *hp = nullptr;
-    if (hipMalloc(&d, sizeof(double) * XK_ESS_DOUBLES + sizeof(int) * XK_ESS_INTS + xy_bytes + (size_t)p->max_desc) != hipSuccess)
-      return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: scratch block");
-    if (hipHostMalloc(&hp, xy_bytes + out_bytes) != hipSuccess) { hipFree(d); return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: pinned block"); }
-    p->d_ess = (double *)d;
-    p->h_ess = (unsigned char *)hp;
-  }
-  XkEssArgs a = ess_args(p);
-  a.n = n; a.n_hyp = n_hyp;
-  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
-  const double t = threshold_px / ((fx + fy) / 2.0);
-  a.t2 = t * t;
-  a.seed = (unsigned long long)seed;
-  float *h_xy = (float *)p->h_ess;                           // cur [n][2], then rec [n][2] right behind it: one copy of 4n floats
-  memcpy(h_xy, cur_xy, sizeof(float) * 2 * (size_t)n);
-  memcpy(h_xy + 2 * (size_t)n, rec_xy, sizeof(float) * 2 * (size_t)n);
-  a.rec_xy = a.cur_xy + 2 * (size_t)n;
-  p->ess_n_hyp = 0;
-  HIPCHK(h, hipMemcpyAsync((void *)a.cur_xy, h_xy, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(xk_ess_solve, dim3((n_hyp + XK_ESS_SOLVE_T - 1) / XK_ESS_SOLVE_T), dim3(XK_ESS_SOLVE_T), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_ess_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_ess_mask, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "essential RANSAC launch", e);
-  unsigned char *h_out = p->h_ess + xy_bytes;                // E [9] | n_inliers, winner | mask [n]
-  HIPCHK(h, hipMemcpyAsync(h_out, a.E, 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h_out + 9 * sizeof(double), a.res, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h_out + 9 * sizeof(double) + 2 * sizeof(int), a.mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  p->ess_n_hyp = n_hyp;
-  if (E) memcpy(E, h_out, 9 * sizeof(double));
-  memcpy(n_inliers, h_out + 9 * sizeof(double), sizeof(int));
-  memcpy(mask, h_out + 9 * sizeof(double) + 2 * sizeof(int), (size_t)n);
-  return XK_OK;
-}
-
-extern "C" int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n_cand, double *E, int *inliers) {
-  if (!p) return XK_EINVAL;
-  xk_handle *h = p->h;
-  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_pr_essential_hypotheses: negative range");
-  if (!p->d_ess || first + (long)count > p->ess_n_hyp)
-    return fail(h, XK_EINVAL, "xk_pr_essential_hypotheses: range outside the hypotheses of the last xk_pr_essential_ransac");
-  if (count == 0) return XK_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  const XkEssArgs a = ess_args(p);
-  if (n_cand) HIPCHK(h, hipMemcpyAsync(n_cand, a.ncand + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-  if (E)
-    HIPCHK(h, hipMemcpyAsync(E, a.cand + (size_t)first * XK_ESS_MAXC * 9, sizeof(double) * (size_t)count * XK_ESS_MAXC * 9,
-                             hipMemcpyDeviceToHost, h->stream));
-  if (inliers)
-    HIPCHK(h, hipMemcpyAsync(inliers, a.cnt + (size_t)first * XK_ESS_MAXC, sizeof(int) * (size_t)count * XK_ESS_MAXC,
-                             hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Fundamental-matrix RANSAC filter of the tracker's matches (tracker.cpp:233-293, camera.cpp:62-87), xk_fundamental.hip.h
-// ---------------------------------------------------------------------------
-#include "xk_fundamental.hip.h"
-
-struct xk_trk {
-  xk_handle *h;
-  int max_matches;
-  double fx, fy, cx, cy, s, s_term;
-  double *d_blk;              // distorted / undistorted / float-cast points, candidates, sums, key; then the result block
-  unsigned char *d_res;       // result block inside d_blk: F | kept previous | kept current | res | keep_idx | mask, packed per call
-  unsigned char *h_blk;       // pinned: points in (4 max_matches doubles), then the result block out
-  int n_hyp;                  // hypotheses of the last RANSAC (0: none yet)
-  struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
-};
-static void klt_free(xk_trk *t);
-
-// layout of d_blk in doubles: dist, und, pts [4 max_matches] each, then
-#define XK_FUND_OFF_SUM ((size_t)XK_FUND_MAX_HYP * XK_FUND_MAXC * 9)
-#define XK_FUND_OFF_KEY (XK_FUND_OFF_SUM + (size_t)XK_FUND_MAX_HYP * XK_FUND_MAXC)
-#define XK_FUND_DOUBLES (XK_FUND_OFF_KEY + 1)
-#define XK_FUND_INTS ((size_t)XK_FUND_MAX_HYP * (XK_FUND_MAXC + 2))   // cnt, ncand, bestc
-// the result block for n pairs: F [9] and the kept coordinates [2][n][2] in doubles, res [2] and keep_idx [n] in ints, mask [n]
-static size_t trk_res_bytes(int n) { return sizeof(double) * (9 + 4 * (size_t)n) + sizeof(int) * (2 + (size_t)n) + (size_t)n; }
-
-extern "C" void xk_trk_destroy(xk_trk *t) {
-  if (!t) return;
-  klt_free(t);
-  hipFree(t->d_blk);
-  if (t->h_blk) hipHostFree(t->h_blk);
-  free(t);
-}
-
-extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy, double cx, double cy, double s, xk_trk **out) {
-  if (!h || !out) return XK_EINVAL;
-  if (max_matches < 1) return fail(h, XK_EINVAL, "xk_trk_create: max_matches < 1");
-  if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(s))
-    return fail(h, XK_EINVAL, "xk_trk_create: focal lengths must be positive and the intrinsics finite");
-  HIPCHK(h, hipSetDevice(h->device));
-  xk_trk *t = (xk_trk *)calloc(1, sizeof(xk_trk));
-  if (!t) return XK_ENOMEM;
-  t->h = h; t->max_matches = max_matches;
-  t->fx = fx; t->fy = fy; t->cx = cx; t->cy = cy; t->s = s;
-  t->s_term = s != 0.0 ? 1.0 / (2.0 * std::tan(s / 2.0)) : 0.0;        // camera.cpp:39
-  const size_t pts = sizeof(double) * 4 * (size_t)max_matches;
-  const size_t head = 3 * pts + sizeof(double) * XK_FUND_DOUBLES + sizeof(int) * XK_FUND_INTS;   // (a multiple of 8)
-  void *d = nullptr, *hp = nullptr;
-  if (hipMalloc(&d, head + trk_res_bytes(max_matches)) != hipSuccess || hipHostMalloc(&hp, pts + trk_res_bytes(max_matches)) != hipSuccess) {
-    hipFree(d);
-    free(t);
-    return fail(h, XK_ENOMEM, "xk_trk_create: allocation failed");
-  }
-  t->d_blk = (double *)d;
-  t->d_res = (unsigned char *)d + head;
-  t->h_blk = (unsigned char *)hp;
-  *out = t;
-  return XK_OK;
-}
-
-static XkFundArgs trk_args(xk_trk *t, int n) {
-  XkFundArgs a{};
-  const size_t m4 = 4 * (size_t)t->max_matches;
-  a.dist = t->d_blk; a.und = t->d_blk + m4; a.pts = t->d_blk + 2 * m4;
-  a.cand = t->d_blk + 3 * m4;
-  a.sum = a.cand + XK_FUND_OFF_SUM;
-  a.key = (unsigned long long *)(a.cand + XK_FUND_OFF_KEY);
-  a.cnt = (int *)(a.cand + XK_FUND_DOUBLES);
-  a.ncand = a.cnt + (size_t)XK_FUND_MAX_HYP * XK_FUND_MAXC;
-  a.bestc = a.ncand + XK_FUND_MAX_HYP;
-  a.F = (double *)t->d_res;
-  a.kept_prev = a.F + 9; a.kept_cur = a.kept_prev + 2 * (size_t)n;
-  a.res = (int *)(a.kept_cur + 2 * (size_t)n);
-  a.keep_idx = a.res + 2;
-  a.mask = (unsigned char *)(a.keep_idx + n);
-  a.n = n; a.n_pts = 2 * n;
-  a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.s = t->s; a.s_term = t->s_term;
-  return a;
-}
-
-/* Camera::undistort (camera.cpp:62-87) */
-extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double *xy) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  if (n < 0 || (n > 0 && (!dist_xy || !xy))) return fail(h, XK_EINVAL, "xk_trk_undistort: null argument or negative n");
-  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_undistort: more points than max_matches");
-  if (n == 0) return XK_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  XkFundArgs a = trk_args(t, 0);
-  a.n_pts = n;
-  memcpy(t->h_blk, dist_xy, sizeof(double) * 2 * (size_t)n);
-  HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->h_blk, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(xk_fund_undistort, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "undistort launch", e);
-  HIPCHK(h, hipMemcpyAsync(t->h_blk, a.und, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  memcpy(xy, t->h_blk, sizeof(double) * 2 * (size_t)n);
-  return XK_OK;
-}
-
-// The launches behind both RANSAC entries: the points are in the pinned block (4n doubles: previous, then current), distorted
-// (undistort = true: they go through xk_fund_undistort) or already what the RANSAC sees.  One copy in, one copy out, one wait.
-static int trk_run(xk_trk *t, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
-  xk_handle *h = t->h;
-  const int n = a.n;
-  a.n_hyp = n_hyp;
-  a.t2 = threshold_px * threshold_px;
-  a.seed = (unsigned long long)seed;
-  if (!undistort) a.und = a.pts;
-  t->n_hyp = 0;
-  HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->h_blk, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * n + 255) / 256), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "fundamental RANSAC launch", e);
-  HIPCHK(h, hipMemcpyAsync(t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  t->n_hyp = n_hyp;
-  return XK_OK;
-}
-
-static int trk_check(xk_trk *t, const char *who, int n, double threshold_px, int n_hyp, bool nulls) {
-  xk_handle *h = t->h;
+// What the last RANSAC of a filter left for hypotheses first ... first+count-1, behind `who`: the three optional copies and one
+// wait.  n_hyp: hypotheses of that RANSAC (`last` names it in the error text), -1 before the scratch block exists.
+static int ransac_hypotheses(xk_handle *h, const char *who, const char *last, int n_hyp, const XkRansacScratch &s, int maxc, int first,
+                             int count, int *n_cand, double *cand, int *inliers) {
   char msg[160];
-  const char *what = nullptr;
-  int rc = XK_EINVAL;
-  if (nulls || n < 0) what = "null argument or negative n";
-  else if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) what = "threshold_px < 0";
-  else if (n_hyp < 1 || n_hyp > XK_FUND_MAX_HYP) what = "n_hyp outside 1...4096";
-  else if (n > t->max_matches) { what = "more point pairs than max_matches"; rc = XK_ECAPACITY; }
-  if (!what) return XK_OK;
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return fail(h, rc, msg);
-}
-
-/* cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) (tracker.cpp:243-260) */
-extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, double threshold_px, int n_hyp,
-                                         unsigned long seed, unsigned char *mask, double *F, int *n_inliers) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  int rc = trk_check(t, "xk_trk_fundamental_ransac", n, threshold_px, n_hyp, !mask || !n_inliers || (n > 0 && (!prev_xy || !cur_xy)));
-  if (rc != XK_OK) return rc;
-  *n_inliers = 0;
-  memset(mask, 0, (size_t)n);
-  if (F) memset(F, 0, 9 * sizeof(double));
-  if (n < 7) { t->n_hyp = 0; return XK_OK; }                 // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
-  HIPCHK(h, hipSetDevice(h->device));
-  XkFundArgs a = trk_args(t, n);
-  double *h_pts = (double *)t->h_blk;
-  for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
-  rc = trk_run(t, a, false, threshold_px, n_hyp, seed);
-  if (rc != XK_OK) return rc;
-  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
-  if (F) memcpy(F, r, 9 * sizeof(double));
-  memcpy(n_inliers, r + ((unsigned char *)a.res - t->d_res), sizeof(int));
-  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
-  return XK_OK;
-}
-
-/* What the last RANSAC of the tracker's matches (tracker.cpp:259-260) left for hypotheses first ... first+count-1 */
-extern "C" int xk_trk_fundamental_hypotheses(xk_trk *t, int first, int count, int *n_cand, double *F, int *inliers) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_trk_fundamental_hypotheses: negative range");
-  if (first + (long)count > t->n_hyp)
-    return fail(h, XK_EINVAL, "xk_trk_fundamental_hypotheses: range outside the hypotheses of the last RANSAC");
+  if (first < 0 || count < 0) {
+    snprintf(msg, sizeof msg, "%s: negative range", who);
+    return fail(h, XK_EINVAL, msg);
+  }
+  if (first + (long)count > n_hyp) {
+    snprintf(msg, sizeof msg, "%s: range outside the hypotheses of the last %s", who, last);
+    return fail(h, XK_EINVAL, msg);
+  }
   if (count == 0) return XK_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  const XkFundArgs a = trk_args(t, 0);
-  if (n_cand) HIPCHK(h, hipMemcpyAsync(n_cand, a.ncand + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-  if (F)
-    HIPCHK(h, hipMemcpyAsync(F, a.cand + (size_t)first * XK_FUND_MAXC * 9, sizeof(double) * (size_t)count * XK_FUND_MAXC * 9,
-                             hipMemcpyDeviceToHost, h->stream));
+  const size_t per = (size_t)maxc;
+  if (n_cand) HIPCHK(h, hipMemcpyAsync(n_cand, s.ncand + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  if (cand)
+    HIPCHK(h, hipMemcpyAsync(cand, s.cand + first * per * 9, sizeof(double) * count * per * 9, hipMemcpyDeviceToHost, h->stream));
   if (inliers)
-    HIPCHK(h, hipMemcpyAsync(inliers, a.cnt + (size_t)first * XK_FUND_MAXC, sizeof(int) * (size_t)count * XK_FUND_MAXC,
-                             hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(inliers, s.cnt + first * per, sizeof(int) * count * per, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
 }
 
-/* The outlier removal of Tracker::track (tracker.cpp:233-293): undistort both lists, RANSAC, keep the masked pairs */
-extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *cur_dist_xy, int n, double threshold_px,
-                                     int n_hyp, unsigned long seed, unsigned char *mask, int *keep_idx, double *prev_xy, double *cur_xy,
-                                     int *n_inliers) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  int rc = trk_check(t, "xk_trk_filter_matches", n, threshold_px, n_hyp,
-                     !mask || !keep_idx || !prev_xy || !cur_xy || !n_inliers || (n > 0 && (!prev_dist_xy || !cur_dist_xy)));
-  if (rc != XK_OK) return rc;
-  *n_inliers = 0;
-  memset(mask, 0, (size_t)n);
-  if (n < 7) { t->n_hyp = 0; return XK_OK; }
-  HIPCHK(h, hipSetDevice(h->device));
-  XkFundArgs a = trk_args(t, n);
-  memcpy(t->h_blk, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
-  memcpy(t->h_blk + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
-  rc = trk_run(t, a, true, threshold_px, n_hyp, seed);
-  if (rc != XK_OK) return rc;
-  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
-  int kept = 0;
-  memcpy(&kept, r + ((unsigned char *)a.res - t->d_res), sizeof(int));
-  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_filter_matches: inlier count out of range");
-  *n_inliers = kept;
-  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
-  memcpy(keep_idx, r + ((unsigned char *)a.keep_idx - t->d_res), sizeof(int) * (size_t)kept);
-  memcpy(prev_xy, r + ((unsigned char *)a.kept_prev - t->d_res), sizeof(double) * 2 * (size_t)kept);
-  memcpy(cur_xy, r + ((unsigned char *)a.kept_cur - t->d_res), sizeof(double) * 2 * (size_t)kept);
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Pyramidal Lucas-Kanade tracking of the tracker's features (tracker.cpp:623-690), xk_klt.hip.h
-// ---------------------------------------------------------------------------
-#include "xk_klt.hip.h"
-
-struct xk_klt {
-  int width, height, win_w, win_h, max_level, max_iter, levels;
-  double eps, min_eig_thr;
-  unsigned char *d_blk;       // slot 0 | slot 1 | previous points (floats) | result block
-  XkKltPyr slot[2];           // per slot and level: image, dIx, dIy at the level's pitch
-  int cur, pushed;            // the slot of the current image; images pushed since the setup, counted to 2
-  float *d_pts;
-  unsigned char *d_res;       // cur_xy | min_eig | kept previous | kept current | res [2] | keep_idx | status, packed per call
-  unsigned char *h_img;       // pinned: one image at level 0's pitch
-  unsigned char *h_blk;       // pinned: previous points in, then the result block out
-  hipEvent_t img_copied;      // the upload out of h_img: the next push waits for it before it refills the staging
-};
-
-// the result block for n features: cur_xy [n][2], min_eig [n], the kept coordinates [2][n][2] in doubles, res [2] and keep_idx [n]
-// in ints, status [n]
-static size_t klt_res_bytes(int n) { return sizeof(double) * 7 * (size_t)n + sizeof(int) * (2 + (size_t)n) + (size_t)n; }
-
-static void klt_release(xk_klt *k) {
-  hipFree(k->d_blk);
-  if (k->h_img) hipHostFree(k->h_img);
-  if (k->h_blk) hipHostFree(k->h_blk);
-  if (k->img_copied) hipEventDestroy(k->img_copied);
-  free(k);
-}
-
-static void klt_free(xk_trk *t) {
-  if (!t->klt) return;
-  hipStreamSynchronize(t->h->stream);
-  klt_release(t->klt);
-  t->klt = nullptr;
-}
-
-// Rule 1 of DESIGN 3.11: the largest l <= max_level with W_k > win_w and H_k > win_h for every k <= l; -1 if level 0 fails.
-static int klt_count_levels(int w, int h, int win_w, int win_h, int max_level) {
-  int lv = -1;
-  for (int l = 0; l <= max_level && w > win_w && h > win_h; ++l) { lv = l; w = (w + 1) / 2; h = (h + 1) / 2; }
-  return lv;
-}
-
-/* The parameters of cv::calcOpticalFlowPyrLK as Tracker holds them (tracker.h:234-261) and the device buffers of two images */
-extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int win_h, int max_level, int max_iter, double eps,
-                                double min_eig_thr) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  if (width < 16 || width > 4096 || height < 16 || height > 4096) return fail(h, XK_EINVAL, "xk_trk_klt_setup: image size outside 16...4096");
-  if (win_w < 3 || win_w > XK_KLT_MAX_WIN || win_h < 3 || win_h > XK_KLT_MAX_WIN) return fail(h, XK_EINVAL, "xk_trk_klt_setup: window outside 3...31");
-  if (max_level < 0 || max_level >= XK_KLT_MAX_LEVELS) return fail(h, XK_EINVAL, "xk_trk_klt_setup: max_level outside 0...4");
-  if (max_iter < 1 || max_iter > 100) return fail(h, XK_EINVAL, "xk_trk_klt_setup: max_iter outside 1...100");
-  if (!(eps > 0.0) || !(eps <= 10.0)) return fail(h, XK_EINVAL, "xk_trk_klt_setup: eps outside (0, 10]");
-  if (!(min_eig_thr >= 0.0) || !std::isfinite(min_eig_thr)) return fail(h, XK_EINVAL, "xk_trk_klt_setup: min_eig_thr < 0");
-  const int levels = klt_count_levels(width, height, win_w, win_h, max_level);
-  if (levels < 0) return fail(h, XK_EINVAL, "xk_trk_klt_setup: the window does not fit the image");
-  HIPCHK(h, hipSetDevice(h->device));
-  xk_klt *k = (xk_klt *)calloc(1, sizeof(xk_klt));      // (the new state is built whole before the old one goes: a failure leaves the old one in place)
-  if (!k) return XK_ENOMEM;
-  k->width = width; k->height = height; k->win_w = win_w; k->win_h = win_h; k->max_level = max_level; k->max_iter = max_iter;
-  k->levels = levels; k->eps = eps; k->min_eig_thr = min_eig_thr;
-  k->cur = 0; k->pushed = 0;
-  size_t slot_bytes = 0;                                          // per level: pitch h bytes of image, then two planes of shorts
-  for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) slot_bytes += 5 * (size_t)round_up(w, 16) * hh;
-  const size_t pts_bytes = (sizeof(float) * 2 * (size_t)t->max_matches + 15) / 16 * 16;
-  const size_t pitch0 = (size_t)round_up(width, 16);
-  // Every plane's rows are padded to the pitch.  NO kernel may read the padding columns [w, pitch): xk_klt_pyrdown takes four bytes
-  // at once only where x + 3 < w, xk_klt_track's plain taps only where the whole window lies inside the image, everything else goes
-  // through the mirror or a bounds test.  Nothing writes them either (level 0's come from the staging, which copies w bytes per row),
-  // so both blocks are zeroed once here: a later vectorised load that strays into the padding reads zeros, not what was there before.
-  const size_t dev_bytes = 2 * slot_bytes + pts_bytes + klt_res_bytes(t->max_matches);
-  void *d = nullptr, *hi = nullptr, *hb = nullptr;
-  if (hipMalloc(&d, dev_bytes) != hipSuccess || hipHostMalloc(&hi, pitch0 * height) != hipSuccess ||
-      hipHostMalloc(&hb, pts_bytes + klt_res_bytes(t->max_matches)) != hipSuccess ||
-      hipEventCreateWithFlags(&k->img_copied, hipEventDisableTiming) != hipSuccess ||
-      hipMemsetAsync(d, 0, dev_bytes, h->stream) != hipSuccess) {
-    k->d_blk = (unsigned char *)d; k->h_img = (unsigned char *)hi; k->h_blk = (unsigned char *)hb;
-    hipStreamSynchronize(h->stream);
-    klt_release(k);
-    return fail(h, XK_ENOMEM, "xk_trk_klt_setup: allocation failed");
-  }
-  memset(hi, 0, pitch0 * height);
-  k->d_blk = (unsigned char *)d; k->h_img = (unsigned char *)hi; k->h_blk = (unsigned char *)hb;
-  for (int s = 0; s < 2; ++s) {
-    unsigned char *p = k->d_blk + s * slot_bytes;
-    for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) {
-      XkKltLevel &L = k->slot[s].lv[l];
-      L.w = w; L.h = hh; L.pitch = round_up(w, 16);
-      const size_t plane = (size_t)L.pitch * hh;
-      L.img = p; L.dx = (short *)(p + plane); L.dy = (short *)(p + 3 * plane);
-      p += 5 * plane;
-    }
-  }
-  k->d_pts = (float *)(k->d_blk + 2 * slot_bytes);
-  k->d_res = k->d_blk + 2 * slot_bytes + pts_bytes;
-  klt_free(t);
-  t->klt = k;
-  return XK_OK;
-}
-
-/* levels of rule 1 (the pyramid has levels + 1 images), -1 before xk_trk_klt_setup */
-extern "C" int xk_trk_klt_levels(xk_trk *t) { return (t && t->klt) ? t->klt->levels : -1; }
-
-/* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
-extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  if (!k) return fail(h, XK_EINVAL, "xk_trk_push_image: before xk_trk_klt_setup");
-  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_push_image: null image or stride below the width");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int s = k->cur ^ 1;
-  const XkKltPyr &P = k->slot[s];
-  const size_t pitch0 = (size_t)P.lv[0].pitch;
-  if (k->pushed > 0) HIPCHK(h, hipEventSynchronize(k->img_copied));          // the staging is free again
-  for (int y = 0; y < k->height; ++y) memcpy(k->h_img + y * pitch0, img + (size_t)y * stride, (size_t)k->width);
-  HIPCHK(h, hipMemcpyAsync(P.lv[0].img, k->h_img, pitch0 * k->height, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(k->img_copied, h->stream));
-  for (int l = 0; l <= k->levels; ++l) {
-    const XkKltLevel &L = P.lv[l];
-    if (l > 0) {
-      const XkKltLevel &S = P.lv[l - 1];
-      hipLaunchKernelGGL(xk_klt_pyrdown, dim3((L.w + XK_KLT_PD_TW - 1) / XK_KLT_PD_TW, (L.h + XK_KLT_PD_TH - 1) / XK_KLT_PD_TH), dim3(256), 0,
-                         h->stream, S.img, S.w, S.h, S.pitch, L.img, L.w, L.h, L.pitch);
-    }
-    hipLaunchKernelGGL(xk_klt_scharr, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, h->stream, L.img, L.w, L.h, L.pitch, L.dx, L.dy);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "pyramid launch", e);
-  k->cur = s;
-  if (k->pushed < 2) ++k->pushed;
-  return XK_OK;
-}
-
-/* Tracker::featureTracking (tracker.cpp:623-690): cv::calcOpticalFlowPyrLK from the previous image to the current one, then the
- * pairs that were tracked and stayed inside the frame */
-extern "C" int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_xy, unsigned char *status, double *min_eig, int *keep_idx,
-                            double *kept_prev_xy, double *kept_cur_xy, int *n_kept) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  if (!k) return fail(h, XK_EINVAL, "xk_trk_track: before xk_trk_klt_setup");
-  if (n < 0 || !cur_xy || !status || !min_eig || !keep_idx || !kept_prev_xy || !kept_cur_xy || !n_kept || (n > 0 && !prev_xy))
-    return fail(h, XK_EINVAL, "xk_trk_track: null argument or negative n");
-  if (k->pushed < 2) return fail(h, XK_EINVAL, "xk_trk_track: fewer than two images pushed");
-  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_track: more features than max_matches");
-  *n_kept = 0;
-  if (n == 0) return XK_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  XkKltArgs a{};
-  a.prev = k->slot[k->cur ^ 1]; a.cur = k->slot[k->cur];
-  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
-  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
-  a.pts = k->d_pts;
-  a.cur_xy = (double *)k->d_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
-  a.kept_prev = a.min_eig + n; a.kept_cur = a.kept_prev + 2 * (size_t)n;
-  a.res = (int *)(a.kept_cur + 2 * (size_t)n);
-  a.keep_idx = a.res + 2;
-  a.status = (unsigned char *)(a.keep_idx + n);
-  const size_t pts_bytes = (sizeof(float) * 2 * (size_t)t->max_matches + 15) / 16 * 16;
-  memcpy(k->h_blk, prev_xy, sizeof(float) * 2 * (size_t)n);
-  HIPCHK(h, hipMemcpyAsync(k->d_pts, k->h_blk, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "feature tracking launch", e);
-  unsigned char *r = k->h_blk + pts_bytes;
-  HIPCHK(h, hipMemcpyAsync(r, k->d_res, klt_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  int kept = 0;
-  memcpy(&kept, r + ((unsigned char *)a.res - k->d_res), sizeof(int));
-  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_track: kept count out of range");
-  *n_kept = kept;
-  memcpy(cur_xy, r, sizeof(double) * 2 * (size_t)n);
-  memcpy(min_eig, r + ((unsigned char *)a.min_eig - k->d_res), sizeof(double) * (size_t)n);
-  memcpy(status, r + (a.status - k->d_res), (size_t)n);
-  memcpy(keep_idx, r + ((unsigned char *)a.keep_idx - k->d_res), sizeof(int) * (size_t)kept);
-  memcpy(kept_prev_xy, r + ((unsigned char *)a.kept_prev - k->d_res), sizeof(double) * 2 * (size_t)kept);
-  memcpy(kept_cur_xy, r + ((unsigned char *)a.kept_cur - k->d_res), sizeof(double) * 2 * (size_t)kept);
-  return XK_OK;
-}
-
-/* One pyramid level of the previous (which = 0) or the current (1) image as the device holds it: straight copies */
-extern "C" int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short *dIx, short *dIy, int *w, int *hgt) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  if (!k) return fail(h, XK_EINVAL, "xk_trk_klt_level: before xk_trk_klt_setup");
-  if (which < 0 || which > 1 || level < 0 || level > k->levels) return fail(h, XK_EINVAL, "xk_trk_klt_level: no such image or level");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_klt_level: that image has not been pushed");
-  HIPCHK(h, hipSetDevice(h->device));
-  const XkKltLevel &L = k->slot[which == 1 ? k->cur : k->cur ^ 1].lv[level];
-  if (w) *w = L.w;
-  if (hgt) *hgt = L.h;
-  if (img) HIPCHK(h, hipMemcpy2DAsync(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
-  if (dIx) HIPCHK(h, hipMemcpy2DAsync(dIx, 2 * (size_t)L.w, L.dx, 2 * (size_t)L.pitch, 2 * (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
-  if (dIy) HIPCHK(h, hipMemcpy2DAsync(dIy, 2 * (size_t)L.w, L.dy, 2 * (size_t)L.pitch, 2 * (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return XK_OK;
-}
+#include "xk_place_api.hip.h"
+#include "xk_tracker_api.hip.h"

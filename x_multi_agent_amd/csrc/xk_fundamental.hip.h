@@ -31,97 +31,32 @@
 //                                  them): the candidates are F1 and F2 themselves
 //        |c3| <= f m               a root at infinity: the candidate F1 - F2, and the roots of the polynomial deflated to its
 //                                  highest coefficient above f m
-//   4. real roots by xk_essential.hip.h's scheme: the roots of each derivative bracket the roots of the next, its safeguarded
-//      Newton inside each bracket (no trigonometric closed form)
+//   4. real roots by xk_ransac_real_roots: the roots of each derivative bracket the roots of the next, safeguarded Newton
+//      inside each bracket (no trigonometric closed form)
 //   5. per root F = l F1 + (1 - l) F2, unit Frobenius norm, K^-T F K^-1, unit norm again; ascending l, special candidates
 //      last; a non-finite candidate is dropped
 // There is NO collinearity or other degeneracy test of the sample: a degenerate sample yields candidates that score badly.
 //
-// Mapping: the 63 doubles of the system stay in registers (every loop below has constant bounds and is unrolled), one
-// thread per hypothesis, no LDS workspace.  The solver functions are __host__ __device__ so that the same text can be
+// Mapping: the 63 doubles of the system stay in registers (every loop of the solver with constant bounds is unrolled), one
+// thread per hypothesis, no LDS workspace.  Sampler, null space, root finder, score body, winner and compaction: xk_ransac.hip.h.  The solver functions are __host__ __device__ so that the same text can be
 // exercised on a CPU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "xk_essential.hip.h"     // xk_ess_mix (the sampler's stream), xk_ess_horner, xk_ess_bracket_root
+#include "xk_ransac.hip.h"
 
 #define XK_FUND_MAXC 3             // candidates per hypothesis
 #define XK_FUND_MAX_HYP 4096
 #define XK_FUND_COEF_FLOOR 1e-12   // relative: to max |c_k| for the leading coefficient, to the unit-norm pencil for all of them
 #define XK_FUND_SOLVE_T 64         // hypotheses per workgroup of the solve kernel: one wavefront
 
-// Hypothesis h draws values 7h .. 7h+6 of the stream of xk_ess_sample (value i = mix(seed + (i+1) golden)); draw k lands in
-// [0, n-k) and is shifted past the earlier picks in ascending order: seven distinct indices, no rejection loop.
-XK_ESS_HD void xk_fund_sample(unsigned long long seed, int h, int n, int pick[7]) {
-  unsigned int sorted[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const unsigned long long z = xk_ess_mix(seed + (unsigned long long)(7ll * h + k + 1) * 0x9E3779B97F4A7C15ull);
-    unsigned int r = (unsigned int)(((z >> 32) * (unsigned long long)(n - k)) >> 32);
-#pragma unroll
-    for (int m = 0; m < k; ++m)
-      if (r >= sorted[m]) ++r;
-    pick[k] = (int)r;
-    sorted[k] = r;
-#pragma unroll
-    for (int j = k; j > 0; --j)
-      if (sorted[j] < sorted[j - 1]) { const unsigned int t = sorted[j]; sorted[j] = sorted[j - 1]; sorted[j - 1] = t; }
-  }
-}
-
-XK_ESS_HD double xk_fund_triple(const double *x, const double *y, const double *z) {
+XK_RANSAC_HD double xk_fund_triple(const double *x, const double *y, const double *z) {
   return x[0] * (y[1] * z[2] - y[2] * z[1]) - x[1] * (y[0] * z[2] - y[2] * z[0]) + x[2] * (y[0] * z[1] - y[1] * z[0]);
 }
 
-// Real roots of c[0..D] (ascending powers, |c[D]| > 0), ascending; -1 where the bound on the roots is not finite.
-template <int D>
-XK_ESS_HD int xk_fund_real_roots(const double *c, double *roots) {
-  double prev[3] = {0.0, 0.0, 0.0}, cur[3] = {0.0, 0.0, 0.0}, pd[4];
-  int nprev = 0;
-#pragma unroll
-  for (int d = 1; d <= D; ++d) {
-    const int m = D - d;                       // pd = m-th derivative of c
-    double big = 0.0;
-#pragma unroll
-    for (int k = 0; k <= d; ++k) {
-      double f = c[k + m];
-#pragma unroll
-      for (int j = k + 1; j <= k + m; ++j) f *= (double)j;
-      pd[k] = f;
-    }
-#pragma unroll
-    for (int k = 0; k < d; ++k) big = fmax(big, fabs(pd[k] / pd[d]));
-    const double R = 1.0 + big;                // Cauchy's bound
-    if (!(R < 1e300)) return -1;
-    int nc = 0;
-    double lo = -R, flo = xk_ess_horner(pd, d, lo);
-#pragma unroll
-    for (int s = 0; s < d; ++s) {              // (at most d - 1 roots of the derivative: d brackets)
-      if (s <= nprev) {
-        const double hi = s < nprev ? prev[s] : R;
-        const double fhi = xk_ess_horner(pd, d, hi);
-        if ((flo < 0) != (fhi < 0)) {
-          const double r = xk_ess_bracket_root(pd, d, lo, hi, flo);
-#pragma unroll
-          for (int t = 0; t < 3; ++t)
-            if (t == nc) cur[t] = r;
-          ++nc;
-        }
-        lo = hi; flo = fhi;
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) prev[s] = cur[s];
-    nprev = nc;
-  }
-#pragma unroll
-  for (int s = 0; s < 3; ++s) roots[s] = prev[s];
-  return nprev;
-}
-
 // Fn (conditioned coordinates, any scale) -> unit norm, K^-T Fn K^-1, unit norm again, into out[9]; false if not finite.
-XK_ESS_HD bool xk_fund_to_pixels(const double *Fn, double fx, double fy, double cx, double cy, double *out) {
+XK_RANSAC_HD bool xk_fund_to_pixels(const double *Fn, double fx, double fy, double cx, double cy, double *out) {
   double nn = 0.0, F[9], G[9];
 #pragma unroll
   for (int e = 0; e < 9; ++e) nn += Fn[e] * Fn[e];
@@ -153,60 +88,13 @@ XK_ESS_HD bool xk_fund_to_pixels(const double *Fn, double fx, double fy, double 
 }
 
 // Seven conditioned pairs -> candidates Fout[<= 3][9] (row-major, pixel coordinates, unit Frobenius norm); returns their number.
-XK_ESS_HD int xk_fund_solve7(const double (*p1)[2], const double (*p2)[2], double fx, double fy, double cx, double cy,
+XK_RANSAC_HD int xk_fund_solve7(const double (*p1)[2], const double (*p2)[2], double fx, double fy, double cx, double cy,
                              double *Fout) {
   // 1. null space
-  double a[7][9], beta[7], F1[9], F2[9];
+  double Nt[9][2], F1[9], F2[9];
+  xk_ransac_null_space<7>(p1, p2, Nt);
 #pragma unroll
-  for (int p = 0; p < 7; ++p) {
-    const double u[3] = {p2[p][0], p2[p][1], 1.0}, v[3] = {p1[p][0], p1[p][1], 1.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) a[p][3 * i + j] = u[i] * v[j];
-  }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    double s = 0.0;
-#pragma unroll
-    for (int t = k; t < 9; ++t) s += a[k][t] * a[k][t];
-    const double nrm = sqrt(s);
-    beta[k] = 0.0;
-    if (nrm > 0.0) {
-      const double alpha = a[k][k] > 0 ? -nrm : nrm;
-      a[k][k] -= alpha;
-      double vv = 0.0;
-#pragma unroll
-      for (int t = k; t < 9; ++t) vv += a[k][t] * a[k][t];
-      beta[k] = 2.0 / vv;
-#pragma unroll
-      for (int j = k + 1; j < 7; ++j) {
-        double d = 0.0;
-#pragma unroll
-        for (int t = k; t < 9; ++t) d += a[k][t] * a[j][t];
-        d *= beta[k];
-#pragma unroll
-        for (int t = k; t < 9; ++t) a[j][t] -= d * a[k][t];
-      }
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < 2; ++v) {
-    double q[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) q[t] = (t == 7 + v) ? 1.0 : 0.0;
-#pragma unroll
-    for (int k = 6; k >= 0; --k) {
-      double d = 0.0;
-#pragma unroll
-      for (int t = k; t < 9; ++t) d += a[k][t] * q[t];
-      d *= beta[k];
-#pragma unroll
-      for (int t = k; t < 9; ++t) q[t] -= d * a[k][t];
-    }
-#pragma unroll
-    for (int t = 0; t < 9; ++t) (v == 0 ? F1 : F2)[t] = q[t];
-  }
+  for (int t = 0; t < 9; ++t) { F1[t] = Nt[t][0]; F2[t] = Nt[t][1]; }
   // 2. the cubic
   double D[9], c[4];
 #pragma unroll
@@ -229,9 +117,9 @@ XK_ESS_HD int xk_fund_solve7(const double (*p1)[2], const double (*p2)[2], doubl
   // 4. real roots
   double roots[3] = {0.0, 0.0, 0.0};
   int nr = 0;
-  if (deg == 3) nr = xk_fund_real_roots<3>(c, roots);
-  else if (deg == 2) nr = xk_fund_real_roots<2>(c, roots);
-  else if (deg == 1) nr = xk_fund_real_roots<1>(c, roots);
+  if (deg == 3) nr = xk_ransac_real_roots<3>(c, roots);
+  else if (deg == 2) nr = xk_ransac_real_roots<2>(c, roots);
+  else if (deg == 1) nr = xk_ransac_real_roots<1>(c, roots);
   if (nr < 0) nr = 0;
   // 5. candidates
 #pragma unroll
@@ -249,7 +137,7 @@ XK_ESS_HD int xk_fund_solve7(const double (*p1)[2], const double (*p2)[2], doubl
 
 // OpenCV's fundamental-matrix error of the pair (p1, p2) in pixels: the larger of the two squared point-to-epipolar-line
 // distances (not Sampson's).
-XK_ESS_HD double xk_fund_error(const double *F, double x1, double y1, double x2, double y2) {
+XK_RANSAC_HD double xk_fund_error(const double *F, double x1, double y1, double x2, double y2) {
   double a = F[0] * x1 + F[1] * y1 + F[2], b = F[3] * x1 + F[4] * y1 + F[5], c = F[6] * x1 + F[7] * y1 + F[8];
   const double e2 = x2 * a + y2 * b + c, s2 = a * a + b * b;
   a = F[0] * x2 + F[3] * y2 + F[6]; b = F[1] * x2 + F[4] * y2 + F[7]; c = F[2] * x2 + F[5] * y2 + F[8];
@@ -258,7 +146,7 @@ XK_ESS_HD double xk_fund_error(const double *F, double x1, double y1, double x2,
 }
 
 // camera.cpp:69-87 on one distorted pixel; s_term = 1 / (2 tan(s/2)) (camera.cpp:39), unused where s = 0.
-XK_ESS_HD void xk_fund_undistort1(double ud, double vd, double fx, double fy, double cx, double cy, double s, double s_term,
+XK_RANSAC_HD void xk_fund_undistort1(double ud, double vd, double fx, double fy, double cx, double cy, double s, double s_term,
                                   double *u, double *v) {
   const double x = (ud - cx) / fx, y = (vd - cy) / fy;
   const double r = sqrt(x * x + y * y);
@@ -276,17 +164,10 @@ struct XkFundArgs {
   int n, n_hyp;
   double fx, fy, cx, cy, s, s_term, t2;
   unsigned long long seed;
-  // scratch block
-  double *cand;                     // [XK_FUND_MAX_HYP][3][9]
-  double *sum;                      // [XK_FUND_MAX_HYP][3]
-  int *cnt;                         // [XK_FUND_MAX_HYP][3]
-  int *ncand, *bestc;               // [XK_FUND_MAX_HYP]
-  unsigned long long *key;
+  XkRansacScratch sc;               // XK_FUND_MAX_HYP hypotheses of XK_FUND_MAXC candidates
   // result
   double *F;                        // [9]
-  double *kept_prev, *kept_cur;     // [n][2] each, the first n_inliers rows written
-  int *res;                         // n_inliers, winner hypothesis
-  int *keep_idx;                    // [n]
+  XkKeptPairs kept;                 // res: n_inliers, winner hypothesis
   unsigned char *mask;              // [n]
 };
 
@@ -301,10 +182,10 @@ __global__ __launch_bounds__(256) void xk_fund_undistort(XkFundArgs a) {
 
 __global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {
   const int h = blockIdx.x * XK_FUND_SOLVE_T + threadIdx.x;
-  if (h == 0) *a.key = 0ull;
+  if (h == 0) *a.sc.key = 0ull;
   if (h >= a.n_hyp) return;
   int pick[7];
-  xk_fund_sample(a.seed, h, a.n, pick);
+  xk_ransac_sample<7>(a.seed, h, a.n, pick);
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
   double p1[7][2], p2[7][2];
 #pragma unroll
@@ -312,81 +193,39 @@ __global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {
     p1[k][0] = (P1[2 * pick[k]] - a.cx) / a.fx; p1[k][1] = (P1[2 * pick[k] + 1] - a.cy) / a.fy;
     p2[k][0] = (P2[2 * pick[k]] - a.cx) / a.fx; p2[k][1] = (P2[2 * pick[k] + 1] - a.cy) / a.fy;
   }
-  double *F = a.cand + (size_t)h * (XK_FUND_MAXC * 9);   // (written in place: a slot index in registers would be a runtime one)
+  double *F = a.sc.cand + (size_t)h * (XK_FUND_MAXC * 9);   // (written in place: a slot index in registers would be a runtime one)
   const int nc = xk_fund_solve7(p1, p2, a.fx, a.fy, a.cx, a.cy, F);
   for (int i = nc * 9; i < XK_FUND_MAXC * 9; ++i) F[i] = 0.0;
-  a.ncand[h] = nc;
+  a.sc.ncand[h] = nc;
 }
 
 __global__ __launch_bounds__(256) void xk_fund_score(XkFundArgs a) {
-  __shared__ int s_cnt[4];
-  __shared__ double s_sum[4];
-  const int h = blockIdx.x, nc = a.ncand[h];
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
-  int best_c = -1, best_cnt = -1;
-  double best_sum = 0.0;
-  for (int c = 0; c < XK_FUND_MAXC; ++c) {
-    int cnt = 0;
-    double sum = 0.0;
-    if (c < nc) {
-      const double *Fp = a.cand + ((size_t)h * XK_FUND_MAXC + c) * 9;
-      const double F[9] = {Fp[0], Fp[1], Fp[2], Fp[3], Fp[4], Fp[5], Fp[6], Fp[7], Fp[8]};
-      for (int i = threadIdx.x; i < a.n; i += 256) {
-        const double d = xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]);
-        if (d <= a.t2) { ++cnt; sum += d; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_down(cnt, o, 64); sum += __shfl_down(sum, o, 64); }
-      if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_sum[threadIdx.x >> 6] = sum; }
-      __syncthreads();
-      cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-      sum = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-      __syncthreads();
-      if (cnt > best_cnt || (cnt == best_cnt && sum < best_sum)) { best_cnt = cnt; best_sum = sum; best_c = c; }
-    }
-    if (threadIdx.x == 0) { a.cnt[h * XK_FUND_MAXC + c] = cnt; a.sum[h * XK_FUND_MAXC + c] = sum; }
-  }
-  if (threadIdx.x == 0) {
-    a.bestc[h] = best_c;
-    // count in the high word, inverted hypothesis index in the low word: the maximum is the highest count, then the lowest h
-    if (best_c >= 0) atomicMax(a.key, ((unsigned long long)best_cnt << 32) | (unsigned long long)(0xffffffffu - (unsigned int)h));
-  }
+  xk_ransac_score<XK_FUND_MAXC>(a.sc, a.n, a.t2, [&](const double *F, int i) {
+    return xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]);
+  });
 }
 
 __global__ __launch_bounds__(256) void xk_fund_mask(XkFundArgs a) {
-  __shared__ int s_w[4];
-  const unsigned long long key = *a.key;
-  const bool valid = key != 0ull;            // (false: no hypothesis produced a candidate)
-  const int h = valid ? (int)(0xffffffffu - (unsigned int)(key & 0xffffffffull)) : 0;
-  const double *Fp = a.cand + ((size_t)h * XK_FUND_MAXC + (valid ? a.bestc[h] : 0)) * 9;
+  const XkRansacWinner w = xk_ransac_winner(*a.sc.key);
+  const int h = w.valid ? w.h : 0;
+  const double *Fp = a.sc.cand + ((size_t)h * XK_FUND_MAXC + (w.valid ? a.sc.bestc[h] : 0)) * 9;
   const double F[9] = {Fp[0], Fp[1], Fp[2], Fp[3], Fp[4], Fp[5], Fp[6], Fp[7], Fp[8]};
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
   const double *U1 = a.und, *U2 = a.und + 2 * (size_t)a.n;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int base = 0;                              // pairs kept before this chunk of 256
-  for (int i0 = 0; i0 < a.n; i0 += 256) {
-    const int i = i0 + threadIdx.x;
-    bool keep = false;
-    if (i < a.n) {
-      keep = valid && xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]) <= a.t2;
-      a.mask[i] = keep ? 1 : 0;
-    }
-    const unsigned long long b = __ballot(keep);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[w] = __popcll(b);
-    __syncthreads();
-    int off = base;
-    for (int j = 0; j < w; ++j) off += s_w[j];
-    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    if (keep) {                              // (off + before < n: it counts kept pairs of index < i)
-      const int pos = off + before;
-      a.keep_idx[pos] = i;
-      a.kept_prev[2 * pos] = U1[2 * i]; a.kept_prev[2 * pos + 1] = U1[2 * i + 1];
-      a.kept_cur[2 * pos] = U2[2 * i]; a.kept_cur[2 * pos + 1] = U2[2 * i + 1];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 9) a.F[threadIdx.x] = valid ? Fp[threadIdx.x] : 0.0;
+  const int kept = xk_ransac_compact(
+      a.n,
+      [&](int i) {
+        const bool keep = w.valid && xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]) <= a.t2;
+        a.mask[i] = keep ? 1 : 0;
+        return keep;
+      },
+      [&](int i, int pos) {
+        a.kept.keep_idx[pos] = i;
+        a.kept.kept_prev[2 * pos] = U1[2 * i]; a.kept.kept_prev[2 * pos + 1] = U1[2 * i + 1];
+        a.kept.kept_cur[2 * pos] = U2[2 * i]; a.kept.kept_cur[2 * pos + 1] = U2[2 * i + 1];
+      });
+  if (threadIdx.x < 9) a.F[threadIdx.x] = w.valid ? Fp[threadIdx.x] : 0.0;
   // (the count is this kernel's own: the length of what it compacted, whatever the scoring kernel's rounding made of the same pairs)
-  if (threadIdx.x == 0) { a.res[0] = base; a.res[1] = valid ? h : -1; }
+  if (threadIdx.x == 0) { a.kept.res[0] = kept; a.kept.res[1] = w.valid ? h : -1; }
 }

@@ -20,12 +20,14 @@
 //                    their Iw, gx, gy stay in registers across the iterations.  Window sums: int32 per lane (<= 16 terms below
 //                    2^27), int64 across the wavefront by a butterfly of cross-lane moves, which leaves the total in every lane;
 //                    the 2 x 2 solve and every decision are then redundant and identical in all lanes.
-//   xk_klt_compact   one workgroup: the post-filter and the ORDERED compaction of the kept pairs, by the scheme of xk_fund_mask
-//                    (ballot + popcount per wavefront, wave totals through LDS, a running base over chunks of 256)
+//   xk_klt_compact   one workgroup: the post-filter and the ORDERED compaction of the kept pairs (xk_ransac_compact, as in
+//                    xk_fund_mask)
 // No atomics, no inline assembly.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include "xk_ransac.hip.h"     // the ordered compaction, XkKeptPairs
 
 #define XK_KLT_MAX_LEVELS 5        // levels 0 ... 4
 #define XK_KLT_MAX_WIN 31
@@ -51,9 +53,7 @@ struct XkKltArgs {
   double *cur_xy;                  // [n][2]
   double *min_eig;                 // [n]
   unsigned char *status;           // [n]
-  double *kept_prev, *kept_cur;    // [n][2] each, the first n_kept rows written
-  int *keep_idx;                   // [n]
-  int *res;                        // n_kept
+  XkKeptPairs kept;                // res: n_kept
 };
 
 // reflect-101 (-1 -> 1, n -> n - 2), then clamped: a caller that needs the value stays within one reflection, a tile's unused
@@ -266,32 +266,18 @@ __global__ __launch_bounds__(64 * XK_KLT_WAVES) void xk_klt_track(XkKltArgs a) {
 }
 
 __global__ __launch_bounds__(256) void xk_klt_compact(XkKltArgs a) {
-  __shared__ int s_w[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const double xmax = (double)a.cur.lv[0].w - 0.5, ymax = (double)a.cur.lv[0].h - 0.5;
-  int base = 0;                              // pairs kept before this chunk of 256
-  for (int i0 = 0; i0 < a.n; i0 += 256) {
-    const int i = i0 + threadIdx.x;
-    bool keep = false;
-    double x = 0.0, y = 0.0;
-    if (i < a.n) {
-      x = a.cur_xy[2 * i]; y = a.cur_xy[2 * i + 1];
-      keep = a.status[i] != 0 && x >= -0.5 && y >= -0.5 && x <= xmax && y <= ymax;
-    }
-    const unsigned long long b = __ballot(keep);
-    const int before = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[w] = __popcll(b);
-    __syncthreads();
-    int off = base;
-    for (int j = 0; j < w; ++j) off += s_w[j];
-    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    if (keep) {                              // (off + before < n: it counts kept pairs of index < i)
-      const int pos = off + before;
-      a.keep_idx[pos] = i;
-      a.kept_prev[2 * pos] = (double)a.pts[2 * i]; a.kept_prev[2 * pos + 1] = (double)a.pts[2 * i + 1];
-      a.kept_cur[2 * pos] = x; a.kept_cur[2 * pos + 1] = y;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.res[0] = base;
+  double x = 0.0, y = 0.0;                     // of this thread's index: loaded by the predicate, written by the writer
+  const int kept = xk_ransac_compact(
+      a.n,
+      [&](int i) {
+        x = a.cur_xy[2 * i]; y = a.cur_xy[2 * i + 1];
+        return a.status[i] != 0 && x >= -0.5 && y >= -0.5 && x <= xmax && y <= ymax;
+      },
+      [&](int i, int pos) {
+        a.kept.keep_idx[pos] = i;
+        a.kept.kept_prev[2 * pos] = (double)a.pts[2 * i]; a.kept.kept_prev[2 * pos + 1] = (double)a.pts[2 * i + 1];
+        a.kept.kept_cur[2 * pos] = x; a.kept.kept_cur[2 * pos + 1] = y;
+      });
+  if (threadIdx.x == 0) a.kept.res[0] = kept;
 }

@@ -1,0 +1,279 @@
+// xk_ransac.hip.h -- what the RANSAC filters share (gfx950): xk_essential.hip.h, xk_fundamental.hip.h and the ordered
+// compaction of xk_klt.hip.h.  One copy of each piece, so that the sampler's stream, the tie-break rule, the key packing and
+// the chunked scan cannot drift apart between the filters.
+//
+//   stream, sampler     splitmix64, M distinct indices per hypothesis without a rejection loop
+//   null space          of the M x 9 epipolar system, Householder on its transpose
+//   polynomials         Horner, the safeguarded bracket root, real roots by derivative bracketing
+//   score               per candidate inlier count + summed error, the hypothesis' best candidate, the packed atomicMax key
+//   winner              the key decoded
+//   ordered compaction  ballot + popcount per wavefront, wave totals through LDS, a running base over chunks of 256
+//   XkRansacScratch     the per-hypothesis scratch block; XkKeptPairs, the "kept pairs" tail of a result block
+//
+// What a model keeps to itself: its minimal solver past the null space, its error function, its kernels.  The solver pieces
+// are __host__ __device__ so that the same text can be exercised on a CPU.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#define XK_RANSAC_HD __host__ __device__ inline
+
+XK_RANSAC_HD unsigned long long xk_ransac_mix(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// Hypothesis h draws values M h .. M h + M - 1 of the stream (value i = mix(seed + (i+1) golden)); draw k lands in [0, n-k)
+// and is shifted past the earlier picks in ascending order: M distinct indices, no rejection loop.
+template <int M>
+XK_RANSAC_HD void xk_ransac_sample(unsigned long long seed, int h, int n, int pick[M]) {
+  unsigned int sorted[M];
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    const unsigned long long z = xk_ransac_mix(seed + (unsigned long long)((long long)M * h + k + 1) * 0x9E3779B97F4A7C15ull);
+    unsigned int r = (unsigned int)(((z >> 32) * (unsigned long long)(n - k)) >> 32);
+#pragma unroll
+    for (int m = 0; m < k; ++m)
+      if (r >= sorted[m]) ++r;
+    pick[k] = (int)r;
+    sorted[k] = r;
+#pragma unroll
+    for (int j = k; j > 0; --j)
+      if (sorted[j] < sorted[j - 1]) { const unsigned int t = sorted[j]; sorted[j] = sorted[j - 1]; sorted[j - 1] = t; }
+  }
+}
+
+// Null space of the M x 9 epipolar system of the pairs (p1, p2), row p: p2_i p1_j at 3i + j.  M Householder reflectors on its
+// transpose (beta = 0 for a zero column), applied backwards to e_M .. e_8: the last 9 - M columns of Q, orthonormal, entry by
+// entry in Nt[9][9 - M].
+template <int M>
+XK_RANSAC_HD void xk_ransac_null_space(const double (*p1)[2], const double (*p2)[2], double (*Nt)[9 - M]) {
+  double a[M][9], beta[M];
+#pragma unroll
+  for (int p = 0; p < M; ++p) {
+    const double u[3] = {p2[p][0], p2[p][1], 1.0}, v[3] = {p1[p][0], p1[p][1], 1.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) a[p][3 * i + j] = u[i] * v[j];
+  }
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    double s = 0.0;
+#pragma unroll
+    for (int t = k; t < 9; ++t) s += a[k][t] * a[k][t];
+    const double nrm = sqrt(s);
+    beta[k] = 0.0;
+    if (nrm > 0.0) {
+      const double alpha = a[k][k] > 0 ? -nrm : nrm;
+      a[k][k] -= alpha;
+      double vv = 0.0;
+#pragma unroll
+      for (int t = k; t < 9; ++t) vv += a[k][t] * a[k][t];
+      beta[k] = 2.0 / vv;
+#pragma unroll
+      for (int j = k + 1; j < M; ++j) {
+        double d = 0.0;
+#pragma unroll
+        for (int t = k; t < 9; ++t) d += a[k][t] * a[j][t];
+        d *= beta[k];
+#pragma unroll
+        for (int t = k; t < 9; ++t) a[j][t] -= d * a[k][t];
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 9 - M; ++v) {
+    double q[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) q[t] = (t == M + v) ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = M - 1; k >= 0; --k) {
+      double d = 0.0;
+#pragma unroll
+      for (int t = k; t < 9; ++t) d += a[k][t] * q[t];
+      d *= beta[k];
+#pragma unroll
+      for (int t = k; t < 9; ++t) q[t] -= d * a[k][t];
+    }
+#pragma unroll
+    for (int t = 0; t < 9; ++t) Nt[t][v] = q[t];
+  }
+}
+
+XK_RANSAC_HD double xk_ransac_horner(const double *c, int d, double x) {
+  double f = c[d];
+  for (int k = d - 1; k >= 0; --k) f = f * x + c[k];
+  return f;
+}
+
+// The root of the degree-d polynomial c in (lo, hi), f(lo) and f(hi) of opposite sign: Newton, bisection where it leaves
+// the bracket or stalls.
+XK_RANSAC_HD double xk_ransac_bracket_root(const double *c, int d, double lo, double hi, double flo) {
+  double xl = flo < 0 ? lo : hi, xh = flo < 0 ? hi : lo;
+  double x = 0.5 * (lo + hi), dxold = fabs(hi - lo), dx = dxold;
+  for (int it = 0; it < 200; ++it) {
+    double f = c[d], df = 0.0;
+    for (int k = d - 1; k >= 0; --k) { df = df * x + f; f = f * x + c[k]; }
+    if (f < 0) xl = x; else xh = x;
+    if (f == 0.0) return x;
+    double xn = x - f / df;
+    if (xn > fmin(xl, xh) && xn < fmax(xl, xh) && fabs(2.0 * f) <= fabs(dxold * df)) {
+      dxold = dx; dx = xn - x;
+    } else {                                   // (a non-finite Newton step lands here too)
+      dxold = dx; dx = 0.5 * (xh - xl); xn = xl + dx;
+    }
+    if (xn == x || fabs(dx) <= 1e-15 * fabs(xn)) return xn;
+    x = xn;
+  }
+  return x;
+}
+
+// Real roots of c[0..D] (ascending powers, |c[D]| > 0), ascending: the roots of each derivative bracket the roots of the next.
+// -1 where the bound on the roots is not finite.  Plain loops on purpose: unrolled into select chains this is 1.7x the code
+// at D = 10 (LAB).
+template <int D>
+XK_RANSAC_HD int xk_ransac_real_roots(const double *c, double *roots) {
+  double prev[D], cur[D], pd[D + 1];
+  int nprev = 0;
+  for (int d = 1; d <= D; ++d) {
+    const int m = D - d;                       // pd = m-th derivative of c
+    double big = 0.0;
+    for (int k = 0; k <= d; ++k) {
+      double f = c[k + m];
+      for (int j = k + 1; j <= k + m; ++j) f *= (double)j;
+      pd[k] = f;
+    }
+    for (int k = 0; k < d; ++k) big = fmax(big, fabs(pd[k] / pd[d]));
+    const double R = 1.0 + big;                // Cauchy's bound
+    if (!(R < 1e300)) return -1;
+    int nc = 0;
+    double lo = -R, flo = xk_ransac_horner(pd, d, lo);
+    for (int s = 0; s <= nprev; ++s) {
+      const double hi = s < nprev ? prev[s] : R;
+      const double fhi = xk_ransac_horner(pd, d, hi);
+      if ((flo < 0) != (fhi < 0) && nc < D) cur[nc++] = xk_ransac_bracket_root(pd, d, lo, hi, flo);
+      lo = hi; flo = fhi;
+    }
+    for (int s = 0; s < nc; ++s) prev[s] = cur[s];
+    nprev = nc;
+  }
+  for (int s = 0; s < nprev; ++s) roots[s] = prev[s];
+  return nprev;
+}
+
+// The scratch block of a filter with at most MAXC candidates per hypothesis and max_hyp hypotheses.
+struct XkRansacScratch {
+  double *cand;                     // [max_hyp][MAXC][9]
+  double *sum;                      // [max_hyp][MAXC]
+  int *cnt;                         // [max_hyp][MAXC]
+  int *ncand, *bestc;               // [max_hyp]
+  unsigned long long *key;
+};
+
+template <int MAXC>
+inline size_t xk_ransac_scratch_bytes(size_t max_hyp) {
+  return sizeof(double) * (max_hyp * MAXC * 10 + 1) + sizeof(int) * max_hyp * (MAXC + 2);
+}
+
+// base: 8-byte aligned; the doubles first, so everything stays aligned
+template <int MAXC>
+inline XkRansacScratch xk_ransac_scratch(void *base, size_t max_hyp) {
+  XkRansacScratch s;
+  s.cand = (double *)base;
+  s.sum = s.cand + max_hyp * MAXC * 9;
+  s.key = (unsigned long long *)(s.sum + max_hyp * MAXC);
+  s.cnt = (int *)(s.key + 1);
+  s.ncand = s.cnt + max_hyp * MAXC;
+  s.bestc = s.ncand + max_hyp;
+  return s;
+}
+
+// The body of a score kernel: workgroup blockIdx.x of 256 takes hypothesis blockIdx.x, lanes over the n points.  err(C, i) is
+// the squared error of point i under the candidate C[9].  Per candidate the inlier count (err <= t2) and the summed inlier
+// error; the hypothesis' best candidate (most inliers, then the smaller sum, then the lower index); and the filter's key.
+template <int MAXC, class Err>
+__device__ __forceinline__ void xk_ransac_score(const XkRansacScratch &s, int n, double t2, Err err) {
+  __shared__ int s_cnt[4];
+  __shared__ double s_sum[4];
+  const int h = blockIdx.x, nc = s.ncand[h];
+  int best_c = -1, best_cnt = -1;
+  double best_sum = 0.0;
+  for (int c = 0; c < MAXC; ++c) {
+    int cnt = 0;
+    double sum = 0.0;
+    if (c < nc) {
+      const double *Cp = s.cand + ((size_t)h * MAXC + c) * 9;
+      const double C[9] = {Cp[0], Cp[1], Cp[2], Cp[3], Cp[4], Cp[5], Cp[6], Cp[7], Cp[8]};
+      for (int i = threadIdx.x; i < n; i += 256) {
+        const double d = err(C, i);
+        if (d <= t2) { ++cnt; sum += d; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_down(cnt, o, 64); sum += __shfl_down(sum, o, 64); }
+      if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_sum[threadIdx.x >> 6] = sum; }
+      __syncthreads();
+      cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+      sum = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+      __syncthreads();
+      if (cnt > best_cnt || (cnt == best_cnt && sum < best_sum)) { best_cnt = cnt; best_sum = sum; best_c = c; }
+    }
+    if (threadIdx.x == 0) { s.cnt[h * MAXC + c] = cnt; s.sum[h * MAXC + c] = sum; }
+  }
+  if (threadIdx.x == 0) {
+    s.bestc[h] = best_c;
+    // count in the high word, inverted hypothesis index in the low word: the maximum is the highest count, then the lowest h
+    if (best_c >= 0) atomicMax(s.key, ((unsigned long long)best_cnt << 32) | (unsigned long long)(0xffffffffu - (unsigned int)h));
+  }
+}
+
+// The key decoded.  valid = false: no hypothesis produced a candidate (the solve kernel's thread 0 zeroes the key).
+struct XkRansacWinner { bool valid; int h, count; };
+__device__ __forceinline__ XkRansacWinner xk_ransac_winner(unsigned long long key) {
+  XkRansacWinner w;
+  w.valid = key != 0ull;
+  w.h = (int)(0xffffffffu - (unsigned int)(key & 0xffffffffull));
+  w.count = (int)(key >> 32);
+  return w;
+}
+
+// The "kept pairs" tail of a result block for n pairs: the doubles kept_prev [n][2], kept_cur [n][2], then the ints res [2],
+// keep_idx [n].  The first res[0] rows of each list are written.  The block's byte plane [n] follows at xk_kept_pairs_end.
+struct XkKeptPairs {
+  double *kept_prev, *kept_cur;
+  int *res, *keep_idx;
+};
+inline size_t xk_kept_pairs_bytes(size_t n) { return sizeof(double) * 4 * n + sizeof(int) * (2 + n); }
+inline XkKeptPairs xk_kept_pairs(double *at, size_t n) {
+  XkKeptPairs k;
+  k.kept_prev = at; k.kept_cur = at + 2 * n;
+  k.res = (int *)(at + 4 * n);
+  k.keep_idx = k.res + 2;
+  return k;
+}
+inline unsigned char *xk_kept_pairs_end(const XkKeptPairs &k, size_t n) { return (unsigned char *)(k.keep_idx + n); }
+
+// ORDERED compaction by ONE workgroup of 256: keep(i) is asked once for every i < n, put(i, pos) called for every kept i with
+// the number pos of kept indices below i; returns the total.  A thread's put(i, .) directly follows its keep(i), so the two
+// may share what keep loaded through the caller's locals.
+template <class Keep, class Put>
+__device__ __forceinline__ int xk_ransac_compact(int n, Keep keep, Put put) {
+  __shared__ int s_w[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int base = 0;                                // kept before this chunk of 256
+  for (int i0 = 0; i0 < n; i0 += 256) {
+    const int i = i0 + threadIdx.x;
+    const bool k = i < n && keep(i);
+    const unsigned long long b = __ballot(k);
+    const int before = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) s_w[w] = __popcll(b);
+    __syncthreads();
+    int off = base;
+    for (int j = 0; j < w; ++j) off += s_w[j];
+    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (k) put(i, off + before);               // (off + before < n: it counts kept indices below i)
+    __syncthreads();
+  }
+  return base;
+}

@@ -1,0 +1,387 @@
+// xk_tracker_api.hip.h -- host side of the tracker's front end (xk_trk_*): the fundamental-matrix RANSAC filter of the matches
+// (tracker.cpp:233-293, camera.cpp:62-87; xk_fundamental.hip.h) and the pyramidal Lucas-Kanade tracking in front of it
+// (tracker.cpp:623-690; xk_klt.hip.h).  Part of xk_api.hip's translation unit, included at its end.
+#pragma once
+#include "xk_fundamental.hip.h"
+#include "xk_klt.hip.h"
+
+struct xk_klt {
+  int width, height, win_w, win_h, max_level, max_iter, levels;
+  double eps, min_eig_thr;
+  unsigned char *d_blk;       // slot 0 | slot 1 | previous points (floats) | result block
+  XkKltPyr slot[2];           // per slot and level: image, dIx, dIy at the level's pitch
+  int cur, pushed;            // the slot of the current image; images pushed since the setup, counted to 2
+  float *d_pts;
+  unsigned char *d_res;       // cur_xy | min_eig | XkKeptPairs | status, packed per call
+  unsigned char *h_img;       // pinned: one image at level 0's pitch
+  unsigned char *h_blk;       // pinned: previous points in, then the result block out
+  hipEvent_t img_copied;      // the upload out of h_img: the next push waits for it before it refills the staging
+};
+
+struct xk_trk {
+  xk_handle *h;
+  int max_matches;
+  double fx, fy, cx, cy, s, s_term;
+  double *d_blk;              // distorted / undistorted / float-cast points [4 max_matches] each, XkRansacScratch; then the result block
+  unsigned char *d_res;       // result block inside d_blk: F | XkKeptPairs | mask, packed per call
+  unsigned char *h_blk;       // pinned: points in (4 max_matches doubles), then the result block out
+  int n_hyp;                  // hypotheses of the last RANSAC (0: none yet)
+  struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
+};
+
+// the result blocks for n pairs: F [9] | kept pairs | mask [n], and cur_xy [n][2] | min_eig [n] | kept pairs | status [n]
+static size_t trk_res_bytes(int n) { return sizeof(double) * 9 + xk_kept_pairs_bytes(n) + (size_t)n; }
+static size_t klt_res_bytes(int n) { return sizeof(double) * 3 * (size_t)n + xk_kept_pairs_bytes(n) + (size_t)n; }
+
+// The kept pairs of a result block out of its pinned copy r (the device block starts at d_res): 0 <= kept <= n or `range_msg`.
+static int kept_pairs_out(xk_handle *h, const XkKeptPairs &k, const unsigned char *d_res, const unsigned char *r, int n, const char *range_msg,
+                          int *keep_idx, double *prev_xy, double *cur_xy, int *n_kept) {
+  int kept = 0;
+  memcpy(&kept, r + ((unsigned char *)k.res - d_res), sizeof(int));
+  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, range_msg);
+  *n_kept = kept;
+  memcpy(keep_idx, r + ((unsigned char *)k.keep_idx - d_res), sizeof(int) * (size_t)kept);
+  memcpy(prev_xy, r + ((unsigned char *)k.kept_prev - d_res), sizeof(double) * 2 * (size_t)kept);
+  memcpy(cur_xy, r + ((unsigned char *)k.kept_cur - d_res), sizeof(double) * 2 * (size_t)kept);
+  return XK_OK;
+}
+
+static void klt_release(xk_klt *k) {
+  hipFree(k->d_blk);
+  if (k->h_img) hipHostFree(k->h_img);
+  if (k->h_blk) hipHostFree(k->h_blk);
+  if (k->img_copied) hipEventDestroy(k->img_copied);
+  free(k);
+}
+
+static void klt_free(xk_trk *t) {
+  if (!t->klt) return;
+  hipStreamSynchronize(t->h->stream);
+  klt_release(t->klt);
+  t->klt = nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// Fundamental-matrix RANSAC filter of the tracker's matches (tracker.cpp:233-293, camera.cpp:62-87), xk_fundamental.hip.h
+// ---------------------------------------------------------------------------
+extern "C" void xk_trk_destroy(xk_trk *t) {
+  if (!t) return;
+  klt_free(t);
+  hipFree(t->d_blk);
+  if (t->h_blk) hipHostFree(t->h_blk);
+  free(t);
+}
+
+extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy, double cx, double cy, double s, xk_trk **out) {
+  if (!h || !out) return XK_EINVAL;
+  if (max_matches < 1) return fail(h, XK_EINVAL, "xk_trk_create: max_matches < 1");
+  if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(s))
+    return fail(h, XK_EINVAL, "xk_trk_create: focal lengths must be positive and the intrinsics finite");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_trk *t = (xk_trk *)calloc(1, sizeof(xk_trk));
+  if (!t) return XK_ENOMEM;
+  t->h = h; t->max_matches = max_matches;
+  t->fx = fx; t->fy = fy; t->cx = cx; t->cy = cy; t->s = s;
+  t->s_term = s != 0.0 ? 1.0 / (2.0 * std::tan(s / 2.0)) : 0.0;        // camera.cpp:39
+  const size_t pts = sizeof(double) * 4 * (size_t)max_matches;
+  const size_t head = 3 * pts + xk_ransac_scratch_bytes<XK_FUND_MAXC>(XK_FUND_MAX_HYP);   // (a multiple of 8)
+  void *d = nullptr, *hp = nullptr;
+  if (hipMalloc(&d, head + trk_res_bytes(max_matches)) != hipSuccess || hipHostMalloc(&hp, pts + trk_res_bytes(max_matches)) != hipSuccess) {
+    hipFree(d);
+    free(t);
+    return fail(h, XK_ENOMEM, "xk_trk_create: allocation failed");
+  }
+  t->d_blk = (double *)d;
+  t->d_res = (unsigned char *)d + head;
+  t->h_blk = (unsigned char *)hp;
+  *out = t;
+  return XK_OK;
+}
+
+static XkFundArgs trk_args(xk_trk *t, int n) {
+  XkFundArgs a{};
+  const size_t m4 = 4 * (size_t)t->max_matches;
+  a.dist = t->d_blk; a.und = t->d_blk + m4; a.pts = t->d_blk + 2 * m4;
+  a.sc = xk_ransac_scratch<XK_FUND_MAXC>(t->d_blk + 3 * m4, XK_FUND_MAX_HYP);
+  a.F = (double *)t->d_res;
+  a.kept = xk_kept_pairs(a.F + 9, n);
+  a.mask = xk_kept_pairs_end(a.kept, n);
+  a.n = n; a.n_pts = 2 * n;
+  a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.s = t->s; a.s_term = t->s_term;
+  return a;
+}
+
+/* Camera::undistort (camera.cpp:62-87) */
+extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double *xy) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (n < 0 || (n > 0 && (!dist_xy || !xy))) return fail(h, XK_EINVAL, "xk_trk_undistort: null argument or negative n");
+  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_undistort: more points than max_matches");
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, 0);
+  a.n_pts = n;
+  memcpy(t->h_blk, dist_xy, sizeof(double) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->h_blk, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_fund_undistort, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "undistort launch", e);
+  HIPCHK(h, hipMemcpyAsync(t->h_blk, a.und, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  memcpy(xy, t->h_blk, sizeof(double) * 2 * (size_t)n);
+  return XK_OK;
+}
+
+// The launches behind both RANSAC entries: the points are in the pinned block (4n doubles: previous, then current), distorted
+// (undistort = true: they go through xk_fund_undistort) or already what the RANSAC sees.  One copy in, one copy out, one wait.
+static int trk_run(xk_trk *t, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
+  xk_handle *h = t->h;
+  const int n = a.n;
+  a.n_hyp = n_hyp;
+  a.t2 = threshold_px * threshold_px;
+  a.seed = (unsigned long long)seed;
+  if (!undistort) a.und = a.pts;
+  t->n_hyp = 0;
+  HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->h_blk, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "fundamental RANSAC launch", e);
+  HIPCHK(h, hipMemcpyAsync(t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  t->n_hyp = n_hyp;
+  return XK_OK;
+}
+
+static int trk_check(xk_trk *t, const char *who, int n, double threshold_px, int n_hyp, bool nulls) {
+  xk_handle *h = t->h;
+  char msg[160];
+  const char *what = nullptr;
+  int rc = XK_EINVAL;
+  if (nulls || n < 0) what = "null argument or negative n";
+  else if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) what = "threshold_px < 0";
+  else if (n_hyp < 1 || n_hyp > XK_FUND_MAX_HYP) what = "n_hyp outside 1...4096";
+  else if (n > t->max_matches) { what = "more point pairs than max_matches"; rc = XK_ECAPACITY; }
+  if (!what) return XK_OK;
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(h, rc, msg);
+}
+
+/* cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) (tracker.cpp:243-260) */
+extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, double threshold_px, int n_hyp,
+                                         unsigned long seed, unsigned char *mask, double *F, int *n_inliers) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  int rc = trk_check(t, "xk_trk_fundamental_ransac", n, threshold_px, n_hyp, !mask || !n_inliers || (n > 0 && (!prev_xy || !cur_xy)));
+  if (rc != XK_OK) return rc;
+  *n_inliers = 0;
+  memset(mask, 0, (size_t)n);
+  if (F) memset(F, 0, 9 * sizeof(double));
+  if (n < 7) { t->n_hyp = 0; return XK_OK; }                 // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, n);
+  double *h_pts = (double *)t->h_blk;
+  for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
+  rc = trk_run(t, a, false, threshold_px, n_hyp, seed);
+  if (rc != XK_OK) return rc;
+  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
+  if (F) memcpy(F, r, 9 * sizeof(double));
+  memcpy(n_inliers, r + ((unsigned char *)a.kept.res - t->d_res), sizeof(int));
+  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
+  return XK_OK;
+}
+
+/* What the last RANSAC of the tracker's matches (tracker.cpp:259-260) left for hypotheses first ... first+count-1 */
+extern "C" int xk_trk_fundamental_hypotheses(xk_trk *t, int first, int count, int *n_cand, double *F, int *inliers) {
+  if (!t) return XK_EINVAL;
+  return ransac_hypotheses(t->h, "xk_trk_fundamental_hypotheses", "RANSAC", t->n_hyp, trk_args(t, 0).sc, XK_FUND_MAXC, first, count,
+                           n_cand, F, inliers);
+}
+
+/* The outlier removal of Tracker::track (tracker.cpp:233-293): undistort both lists, RANSAC, keep the masked pairs */
+extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *cur_dist_xy, int n, double threshold_px,
+                                     int n_hyp, unsigned long seed, unsigned char *mask, int *keep_idx, double *prev_xy, double *cur_xy,
+                                     int *n_inliers) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  int rc = trk_check(t, "xk_trk_filter_matches", n, threshold_px, n_hyp,
+                     !mask || !keep_idx || !prev_xy || !cur_xy || !n_inliers || (n > 0 && (!prev_dist_xy || !cur_dist_xy)));
+  if (rc != XK_OK) return rc;
+  *n_inliers = 0;
+  memset(mask, 0, (size_t)n);
+  if (n < 7) { t->n_hyp = 0; return XK_OK; }
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, n);
+  memcpy(t->h_blk, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
+  memcpy(t->h_blk + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
+  rc = trk_run(t, a, true, threshold_px, n_hyp, seed);
+  if (rc != XK_OK) return rc;
+  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
+  rc = kept_pairs_out(h, a.kept, t->d_res, r, n, "xk_trk_filter_matches: inlier count out of range", keep_idx, prev_xy, cur_xy, n_inliers);
+  if (rc != XK_OK) return rc;
+  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
+  return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Pyramidal Lucas-Kanade tracking of the tracker's features (tracker.cpp:623-690), xk_klt.hip.h
+// ---------------------------------------------------------------------------
+// Rule 1 of DESIGN 3.11: the largest l <= max_level with W_k > win_w and H_k > win_h for every k <= l; -1 if level 0 fails.
+static int klt_count_levels(int w, int h, int win_w, int win_h, int max_level) {
+  int lv = -1;
+  for (int l = 0; l <= max_level && w > win_w && h > win_h; ++l) { lv = l; w = (w + 1) / 2; h = (h + 1) / 2; }
+  return lv;
+}
+
+/* The parameters of cv::calcOpticalFlowPyrLK as Tracker holds them (tracker.h:234-261) and the device buffers of two images */
+extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int win_h, int max_level, int max_iter, double eps,
+                                double min_eig_thr) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (width < 16 || width > 4096 || height < 16 || height > 4096) return fail(h, XK_EINVAL, "xk_trk_klt_setup: image size outside 16...4096");
+  if (win_w < 3 || win_w > XK_KLT_MAX_WIN || win_h < 3 || win_h > XK_KLT_MAX_WIN) return fail(h, XK_EINVAL, "xk_trk_klt_setup: window outside 3...31");
+  if (max_level < 0 || max_level >= XK_KLT_MAX_LEVELS) return fail(h, XK_EINVAL, "xk_trk_klt_setup: max_level outside 0...4");
+  if (max_iter < 1 || max_iter > 100) return fail(h, XK_EINVAL, "xk_trk_klt_setup: max_iter outside 1...100");
+  if (!(eps > 0.0) || !(eps <= 10.0)) return fail(h, XK_EINVAL, "xk_trk_klt_setup: eps outside (0, 10]");
+  if (!(min_eig_thr >= 0.0) || !std::isfinite(min_eig_thr)) return fail(h, XK_EINVAL, "xk_trk_klt_setup: min_eig_thr < 0");
+  const int levels = klt_count_levels(width, height, win_w, win_h, max_level);
+  if (levels < 0) return fail(h, XK_EINVAL, "xk_trk_klt_setup: the window does not fit the image");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_klt *k = (xk_klt *)calloc(1, sizeof(xk_klt));      // (the new state is built whole before the old one goes: a failure leaves the old one in place)
+  if (!k) return XK_ENOMEM;
+  k->width = width; k->height = height; k->win_w = win_w; k->win_h = win_h; k->max_level = max_level; k->max_iter = max_iter;
+  k->levels = levels; k->eps = eps; k->min_eig_thr = min_eig_thr;
+  k->cur = 0; k->pushed = 0;
+  size_t slot_bytes = 0;                                          // per level: pitch h bytes of image, then two planes of shorts
+  for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) slot_bytes += 5 * (size_t)round_up(w, 16) * hh;
+  const size_t pts_bytes = (sizeof(float) * 2 * (size_t)t->max_matches + 15) / 16 * 16;
+  const size_t pitch0 = (size_t)round_up(width, 16);
+  // Every plane's rows are padded to the pitch.  NO kernel may read the padding columns [w, pitch): xk_klt_pyrdown takes four bytes
+  // at once only where x + 3 < w, xk_klt_track's plain taps only where the whole window lies inside the image, everything else goes
+  // through the mirror or a bounds test.  Nothing writes them either (level 0's come from the staging, which copies w bytes per row),
+  // so both blocks are zeroed once here: a later vectorised load that strays into the padding reads zeros, not what was there before.
+  const size_t dev_bytes = 2 * slot_bytes + pts_bytes + klt_res_bytes(t->max_matches);
+  void *d = nullptr, *hi = nullptr, *hb = nullptr;
+  if (hipMalloc(&d, dev_bytes) != hipSuccess || hipHostMalloc(&hi, pitch0 * height) != hipSuccess ||
+      hipHostMalloc(&hb, pts_bytes + klt_res_bytes(t->max_matches)) != hipSuccess ||
+      hipEventCreateWithFlags(&k->img_copied, hipEventDisableTiming) != hipSuccess ||
+      hipMemsetAsync(d, 0, dev_bytes, h->stream) != hipSuccess) {
+    k->d_blk = (unsigned char *)d; k->h_img = (unsigned char *)hi; k->h_blk = (unsigned char *)hb;
+    hipStreamSynchronize(h->stream);
+    klt_release(k);
+    return fail(h, XK_ENOMEM, "xk_trk_klt_setup: allocation failed");
+  }
+  memset(hi, 0, pitch0 * height);
+  k->d_blk = (unsigned char *)d; k->h_img = (unsigned char *)hi; k->h_blk = (unsigned char *)hb;
+  for (int s = 0; s < 2; ++s) {
+    unsigned char *p = k->d_blk + s * slot_bytes;
+    for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) {
+      XkKltLevel &L = k->slot[s].lv[l];
+      L.w = w; L.h = hh; L.pitch = round_up(w, 16);
+      const size_t plane = (size_t)L.pitch * hh;
+      L.img = p; L.dx = (short *)(p + plane); L.dy = (short *)(p + 3 * plane);
+      p += 5 * plane;
+    }
+  }
+  k->d_pts = (float *)(k->d_blk + 2 * slot_bytes);
+  k->d_res = k->d_blk + 2 * slot_bytes + pts_bytes;
+  klt_free(t);
+  t->klt = k;
+  return XK_OK;
+}
+
+/* levels of rule 1 (the pyramid has levels + 1 images), -1 before xk_trk_klt_setup */
+extern "C" int xk_trk_klt_levels(xk_trk *t) { return (t && t->klt) ? t->klt->levels : -1; }
+
+/* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
+extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_push_image: before xk_trk_klt_setup");
+  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_push_image: null image or stride below the width");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int s = k->cur ^ 1;
+  const XkKltPyr &P = k->slot[s];
+  const size_t pitch0 = (size_t)P.lv[0].pitch;
+  if (k->pushed > 0) HIPCHK(h, hipEventSynchronize(k->img_copied));          // the staging is free again
+  for (int y = 0; y < k->height; ++y) memcpy(k->h_img + y * pitch0, img + (size_t)y * stride, (size_t)k->width);
+  HIPCHK(h, hipMemcpyAsync(P.lv[0].img, k->h_img, pitch0 * k->height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(k->img_copied, h->stream));
+  for (int l = 0; l <= k->levels; ++l) {
+    const XkKltLevel &L = P.lv[l];
+    if (l > 0) {
+      const XkKltLevel &S = P.lv[l - 1];
+      hipLaunchKernelGGL(xk_klt_pyrdown, dim3((L.w + XK_KLT_PD_TW - 1) / XK_KLT_PD_TW, (L.h + XK_KLT_PD_TH - 1) / XK_KLT_PD_TH), dim3(256), 0,
+                         h->stream, S.img, S.w, S.h, S.pitch, L.img, L.w, L.h, L.pitch);
+    }
+    hipLaunchKernelGGL(xk_klt_scharr, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, h->stream, L.img, L.w, L.h, L.pitch, L.dx, L.dy);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "pyramid launch", e);
+  k->cur = s;
+  if (k->pushed < 2) ++k->pushed;
+  return XK_OK;
+}
+
+/* Tracker::featureTracking (tracker.cpp:623-690): cv::calcOpticalFlowPyrLK from the previous image to the current one, then the
+ * pairs that were tracked and stayed inside the frame */
+extern "C" int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_xy, unsigned char *status, double *min_eig, int *keep_idx,
+                            double *kept_prev_xy, double *kept_cur_xy, int *n_kept) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_track: before xk_trk_klt_setup");
+  if (n < 0 || !cur_xy || !status || !min_eig || !keep_idx || !kept_prev_xy || !kept_cur_xy || !n_kept || (n > 0 && !prev_xy))
+    return fail(h, XK_EINVAL, "xk_trk_track: null argument or negative n");
+  if (k->pushed < 2) return fail(h, XK_EINVAL, "xk_trk_track: fewer than two images pushed");
+  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_track: more features than max_matches");
+  *n_kept = 0;
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkKltArgs a{};
+  a.prev = k->slot[k->cur ^ 1]; a.cur = k->slot[k->cur];
+  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
+  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
+  a.pts = k->d_pts;
+  a.cur_xy = (double *)k->d_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
+  a.kept = xk_kept_pairs(a.min_eig + n, n);
+  a.status = xk_kept_pairs_end(a.kept, n);
+  const size_t pts_bytes = (sizeof(float) * 2 * (size_t)t->max_matches + 15) / 16 * 16;
+  memcpy(k->h_blk, prev_xy, sizeof(float) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync(k->d_pts, k->h_blk, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "feature tracking launch", e);
+  unsigned char *r = k->h_blk + pts_bytes;
+  HIPCHK(h, hipMemcpyAsync(r, k->d_res, klt_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int rc = kept_pairs_out(h, a.kept, k->d_res, r, n, "xk_trk_track: kept count out of range", keep_idx, kept_prev_xy, kept_cur_xy, n_kept);
+  if (rc != XK_OK) return rc;
+  memcpy(cur_xy, r, sizeof(double) * 2 * (size_t)n);
+  memcpy(min_eig, r + ((unsigned char *)a.min_eig - k->d_res), sizeof(double) * (size_t)n);
+  memcpy(status, r + (a.status - k->d_res), (size_t)n);
+  return XK_OK;
+}
+
+/* One pyramid level of the previous (which = 0) or the current (1) image as the device holds it: straight copies */
+extern "C" int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short *dIx, short *dIy, int *w, int *hgt) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_klt_level: before xk_trk_klt_setup");
+  if (which < 0 || which > 1 || level < 0 || level > k->levels) return fail(h, XK_EINVAL, "xk_trk_klt_level: no such image or level");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_klt_level: that image has not been pushed");
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkKltLevel &L = k->slot[which == 1 ? k->cur : k->cur ^ 1].lv[level];
+  if (w) *w = L.w;
+  if (hgt) *hgt = L.h;
+  if (img) HIPCHK(h, hipMemcpy2DAsync(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
+  if (dIx) HIPCHK(h, hipMemcpy2DAsync(dIx, 2 * (size_t)L.w, L.dx, 2 * (size_t)L.pitch, 2 * (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
+  if (dIy) HIPCHK(h, hipMemcpy2DAsync(dIy, 2 * (size_t)L.w, L.dy, 2 * (size_t)L.pitch, 2 * (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
