@@ -150,6 +150,66 @@ def test_apply_ci_and_fuse(xk, oracle_c, sc):
     eng.close()
 
 
+def test_padded_leading_dimensions_change_nothing(xk):
+    """xk_fuse_ci_slam, xk_fuse_ci_msckf (k = 2) and xk_apply_ci through the raw C ABI, once with tight arrays and once with
+    ldp = n + 3, ldh = m + 2, lds = m + 1: the padding rows are NaN on input and a sentinel on output.  The live parts of the
+    outputs are byte-equal between the two calls and the outputs' padding is untouched (the engine always passes ld = rows)."""
+    import ctypes as C
+    c_dp = C.POINTER(C.c_double)
+    N, m, k, w, SENT = 10, 3, 2, 0.1, -12345.678
+    eng = xk.Engine(N, 0, 4)
+    n = eng.n                                               # 75
+    rng = np.random.default_rng(11)
+    P = synth.make_scenario(N, 4, 0, seed=323)["P"]
+    Pb = synth.make_scenario(N, 4, 0, seed=324)["P"]
+    H, Hb, Hc = (rng.standard_normal((m, n)) for _ in range(3))
+    res = 1e-2 * rng.standard_normal(m)
+    S_in = H @ P @ H.T + 1e-4 * np.eye(m)
+    Pj = P.copy()
+    Pj[15:18, 15:18] *= 1.25
+
+    def padded(a, ld, fill=np.nan):
+        out = np.full((ld, a.shape[1]), fill, order="F")
+        out[:a.shape[0]] = a
+        return out
+
+    ptr = lambda a: a.ctypes.data_as(c_dp)
+    Pb_t, Hb_t, Hc_t = (np.asfortranarray(x) for x in (Pb, Hb, Hc))   # xk_fuse_ci_msckf takes the other agents' arrays contiguous
+    Ps, Hs, ns = (c_dp * k)(ptr(Pb_t), ptr(Pb_t)), (c_dp * k)(ptr(Hb_t), ptr(Hc_t)), (C.c_int * k)(n, n)
+
+    def run(ldp, ldh, lds):
+        Pa, Pa2, Pjp = padded(P, ldp), padded(Pb, ldp), padded(Pj, ldp)
+        Ha, Ha2, Sp = padded(H, ldh), padded(Hb, ldh), padded(S_in, lds)
+        out = {}
+        for name in ("slam", "msckf"):
+            S = np.full((lds, m), SENT, order="F")
+            wr = C.c_double()
+            if name == "slam":
+                rc = eng.L.xk_fuse_ci_slam(eng.h, ptr(Pa), C.c_int(ldp), C.c_int(n), ptr(Ha), C.c_int(ldh), ptr(Pa2), C.c_int(ldp),
+                                           C.c_int(n), ptr(Ha2), C.c_int(ldh), C.c_int(m), C.c_double(w), ptr(S), C.c_int(lds),
+                                           C.byref(wr))
+            else:
+                rc = eng.L.xk_fuse_ci_msckf(eng.h, ptr(Pa), C.c_int(ldp), C.c_int(n), ptr(Ha), C.c_int(ldh), C.c_int(m), C.c_int(k),
+                                            Ps, ns, Hs, C.c_double(w), ptr(S), C.c_int(lds), C.byref(wr))
+            eng._chk(rc, "xk_fuse_ci_" + name)
+            out[name + "_S"], out[name + "_w"] = S, np.array([wr.value])
+        Po = np.full((ldp, n), SENT, order="F")
+        corr = np.full(n, SENT)
+        eng._chk(eng.L.xk_apply_ci(eng.h, ptr(Po), C.c_int(ldp), ptr(Pjp), C.c_int(ldp), C.c_int(n), ptr(Ha), C.c_int(ldh),
+                                   C.c_int(m), ptr(res), ptr(Sp), C.c_int(lds), ptr(corr)), "xk_apply_ci")
+        out["apply_P"], out["apply_corr"] = Po, corr
+        return out
+
+    a, b = run(n, m, m), run(n + 3, m + 2, m + 1)
+    eng.close()
+    live = {"slam_S": m, "msckf_S": m, "apply_P": n}         # rows that carry data; what is behind them is padding
+    for key in a:
+        rows = live.get(key, len(a[key]))
+        assert len(a[key]) == rows and np.isfinite(a[key]).all() and (a[key] != SENT).all(), key
+        assert np.ascontiguousarray(a[key]).tobytes() == np.ascontiguousarray(b[key][:rows]).tobytes(), key
+        assert (b[key][rows:] == SENT).all(), key
+
+
 def test_multi_slam_match_golden(xk):
     z = np.load(os.path.join(GOLDEN_DIR, "ci_two_agents.npz"))
     a = {k[2:]: z[k] for k in z.files if k.startswith("a_")}
@@ -329,6 +389,37 @@ def test_device_ci_round_matches_host_abi_round(xk, world):
     assert fused_d == fused_h and fused_h >= 1
     assert corr.shape == (fused_d, 15 + 6 * N) and np.isfinite(corr).all()
     assert rel(P_d, P_h) <= 1e-9, rel(P_d, P_h)
+
+
+def test_device_ci_round_one_shared_track(xk):
+    """A round with ONE shared track runs without side streams.  Every entry starts from the same prior and track 0 has the same
+    stream and workspace region whatever the number of tracks: its correction is byte-equal to the first one of a three-track round."""
+    import torch
+    from x_multi_agent_amd import fleet
+    world, N, K, M, w = 2, 10, 12, 0, 0.04
+    scs, lm = [], None
+    for r in range(world):
+        sc = synth.make_scenario(N, K, M, seed=4100 + r, agent_offset=0.03 * r, landmarks=lm, outlier_frac=0.0)
+        lm = sc["landmarks_true"] if lm is None else lm
+        scs.append(sc)
+    dyn = np.zeros(16); dyn[9] = 1.0
+    pays = np.stack([fleet.pack_payload_host(r, 0.0, dyn, scs[r]["C_q_G"], scs[r]["G_p_C"], None, None, scs[r]["P"], N, M)
+                     for r in range(world)])
+    rank = 1 % world
+    sc = scs[rank]
+    dp = torch.from_numpy(pays).cuda()
+    eng = xk.Engine(N, M, K)
+    got = {}
+    for n_tracks in (1, 3):
+        dt = torch.from_numpy(np.stack([fleet.pack_tracks(scs[r], n_tracks, N).ravel() for r in range(world)])).cuda()
+        torch.cuda.synchronize()
+        eng.stage(sc)                                       # resident P = the staged prior again
+        got[n_tracks] = fleet.ci_round_device(eng, sc, rank, world, dp, dt, n_tracks, w, want_corrections=True)
+    eng.close()
+    (fused1, corr1), (fused3, corr3) = got[1], got[3]
+    assert fused1 == 1 and fused3 >= 1
+    assert corr1.shape == (1, 15 + 6 * N) and np.isfinite(corr1).all() and np.abs(corr1).max() > 0.0
+    assert corr3[0].tobytes() == corr1[0].tobytes()
 
 
 @pytest.mark.parametrize("world", [4, 8])

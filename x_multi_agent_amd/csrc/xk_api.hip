@@ -293,7 +293,6 @@ extern "C" int xk_destroy(xk_handle *h) {
   if (h->d_ciwr) hipFree(h->d_ciwr);
   if (h->d_batch) hipFree(h->d_batch);
   if (h->h_batch) hipHostFree(h->h_batch);
-  if (h->h_ci_cols) hipHostFree(h->h_ci_cols);
   if (h->h_ci_w) hipHostFree(h->h_ci_w);
   free(h->h_trk_off);
   if (h->h_out) hipHostFree(h->h_out);
@@ -342,6 +341,20 @@ static char *stage_slot(xk_handle *h, size_t bytes) {
   const int s = h->stage_next;
   h->stage_next = (s + 1) % XK_STAGE_SLOTS;
   return h->h_stage[s];
+}
+
+// The completion markers kernels write into pinned host memory behind their results (xk_apply_update has the whole story).
+// XK_SPIN_DONE=0 (lab build): no marker is asked for, the stream's completion signal is waited for instead.
+static int spin_done() { static const int on = env_int("XK_SPIN_DONE", 1); return on; }
+// Polls *word (acquire) until it holds seq: true when it was seen.  False after ~1 s, or as soon as a kernel has left a status
+// word (a launch that gave up writes no marker): the caller then waits for the stream.
+static bool wait_marker(xk_handle *h, const unsigned long long *word, unsigned long long seq) {
+  bool seen = false;
+  for (long spins = 0; spins < 40000000L && !(seen = (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq)); ++spins) {
+    if ((spins & 255) == 255 && __atomic_load_n(&h->d_status[1], __ATOMIC_RELAXED) != 0) break;
+    __builtin_ia32_pause();
+  }
+  return seen;
 }
 
 // Staged window lists that no kernel has carried to the device yet: one host-to-device copy through the pinned ring.
@@ -1034,7 +1047,7 @@ static int build_compress_update_pass(xk_handle *h, double sigma_img, const doub
   if ((rc = cache_flags(h)) != XK_OK) return rc;
   UpdateSpec u = compressed_spec(h, dct, cov_update ? 1 : 0);
   u.corr = h->h_out;
-  static const int spin_env = env_int("XK_SPIN_DONE", 1);
+  const int spin_env = spin_done();
   if (spin_env) { u.done_flag = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2); u.done_seq = ++h->done_seq; }
   if ((rc = launch_compress(h, nullptr, &u)) != XK_OK) return rc;
   if (!h->last.fused && (rc = launch_update(h, u)) != XK_OK) return rc;
@@ -1156,7 +1169,7 @@ extern "C" int xk_apply_update(xk_handle *h, const double *corr_total, int cov_u
     // The kernels write the correction and (on failure) the status words into pinned host memory; the last workgroup of the
     // last launch then writes a sequence number next to them, which the host polls: the results are there ~5 us before the
     // runtime's completion signal says so (XK_SPIN_DONE=0: wait for that signal instead).  One wait per update, no copy.
-    static const int spin_env = env_int("XK_SPIN_DONE", 1);
+    const int spin_env = spin_done();
     unsigned long long *done = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2);
     if (waiting_only) u.done_seq = h->fused_seq;
     else {
@@ -1182,10 +1195,7 @@ extern "C" int xk_apply_update(xk_handle *h, const double *corr_total, int cov_u
       // their kernel boundaries, before that kernel started: whatever they wrote is visible by the time the marker is.
       // (a single launch that gave up before its Kalman role got going -- placement census -- writes no marker: the status word
       //  ends the wait)
-      for (long spins = 0; spins < 40000000L && !(seen = (__atomic_load_n(done, __ATOMIC_ACQUIRE) == u.done_seq)); ++spins) {
-        if ((spins & 255) == 255 && __atomic_load_n(&h->d_status[1], __ATOMIC_RELAXED) != 0) break;
-        __builtin_ia32_pause();   // (~1 s, then the signal)
-      }
+      seen = wait_marker(h, done, u.done_seq);
       if (seen) h->done_seen = u.done_seq;
     }
     if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1285,38 +1295,6 @@ extern "C" int xk_apply_update_dense(xk_handle *h, double *P, int ldp, int n, co
   return XK_OK;
 }
 
-extern "C" int xk_apply_ci(xk_handle *h, double *P_out, int ldp, const double *ci_P, int ldc, int n,
-                           const double *H, int ldh, int m, const double *res, const double *S, int lds,
-                           double *correction) {
-  if (!h || !P_out || !ci_P || !H || !res || !S || !correction || n != h->n || ldp < n || ldc < n || ldh < m ||
-      lds < m || m <= 0)
-    return XK_EINVAL;
-  if (m > h->CM) return fail(h, XK_ECAPACITY, "m exceeds the dense workspace");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, ci_P, sizeof(double) * ldc, sizeof(double) * n, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, H, sizeof(double) * ldh, sizeof(double) * m, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpS, sizeof(double) * m, S, sizeof(double) * lds, sizeof(double) * m, m,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_tmpz, res, sizeof(double) * m, hipMemcpyHostToDevice, h->stream));
-  UpdateSpec u;
-  memset(&u, 0, sizeof(u));
-  u.T = h->d_tmpH; u.str = 1; u.stc = m;
-  u.c = m; u.kdim = n; u.col0 = 0;
-  u.z = h->d_tmpz; u.sz = 1;
-  u.S = h->d_tmpS; u.ssr = 1; u.ssc = m;
-  u.Pin = h->d_tmpP; u.Pout = h->d_Pout; u.ct = nullptr; u.cov_update = 1;
-  int rc = launch_update(h, u);
-  if (rc != XK_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(correction, h->d_corr, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(P_out, sizeof(double) * ldp, h->d_Pout, sizeof(double) * n, sizeof(double) * n, n,
-                             hipMemcpyDeviceToHost, h->stream));
-  return read_status(h);
-}
-
-// applyCI on the RESIDENT covariance: P <- sym((I - K H) ci_P) replaces the handle's covariance and stays on the
-// device (the host mirror's resident mode; the compressed [T_H | z] of a pending xk_apply_update is not touched).
 // A build + compression queued by xk_build_compress_async whose single-launch CAQR gave up must be redone (multi-launch
 // schedule) while the covariance it was linearised at is still the resident one: BEFORE a CI entry replaces it.  After this
 // the compressed [T_H | z] is known to be good and xk_apply_update has nothing to retry.
@@ -1332,38 +1310,6 @@ static int settle_async(xk_handle *h) {
   }
   if (rc == XK_OK) h->async_pending = false;
   return rc;
-}
-
-extern "C" int xk_apply_ci_resident(xk_handle *h, const double *ci_P, int ldc, int n, const double *H, int ldh, int m,
-                                    const double *res, const double *S, int lds, double *correction) {
-  if (!h || !ci_P || !H || !res || !S || !correction || n != h->n || ldc < n || ldh < m || lds < m || m <= 0) return XK_EINVAL;
-  if (m > h->CM) return fail(h, XK_ECAPACITY, "m exceeds the dense workspace");
-  HIPCHK(h, hipSetDevice(h->device));
-  {
-    const int rs = settle_async(h);
-    if (rs != XK_OK) return rs;
-  }
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, ci_P, sizeof(double) * ldc, sizeof(double) * n, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, H, sizeof(double) * ldh, sizeof(double) * m, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpS, sizeof(double) * m, S, sizeof(double) * lds, sizeof(double) * m, m,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_tmpz, res, sizeof(double) * m, hipMemcpyHostToDevice, h->stream));
-  UpdateSpec u;
-  memset(&u, 0, sizeof(u));
-  u.T = h->d_tmpH; u.str = 1; u.stc = m;
-  u.c = m; u.kdim = n; u.col0 = 0;
-  u.z = h->d_tmpz; u.sz = 1;
-  u.S = h->d_tmpS; u.ssr = 1; u.ssc = m;
-  u.Pin = h->d_tmpP; u.Pout = h->d_Pout; u.ct = nullptr; u.cov_update = 1;
-  int rc = launch_update(h, u);
-  if (rc != XK_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(correction, h->d_corr, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  rc = read_status(h);
-  if (rc != XK_OK) return rc;
-  std::swap(h->d_P, h->d_Pout);
-  return XK_OK;
 }
 
 // Keeps / brings back a copy of the resident covariance on the device (restore = 0: save, 1: restore).  Benchmarks
@@ -1446,520 +1392,9 @@ extern "C" int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int s
 }
 
 // ---------------------------------------------------------------------------
-// covariance intersection: fixed weights, or searched ones (option "ci_weight_search", xk_ciw.hip.h)
+// covariance intersection: the fuse / match / track entries, applyCI, the device-resident round, the inter-agent payload
 // ---------------------------------------------------------------------------
-// 0: a fixed weight; 1: -1 <= w < 0 with the search switched on (ci.cpp:65-73,105-119); -1: what ci.cpp:59-62,98-101 throw on,
-// and every negative weight while the search is off
-static int check_w(const xk_handle *h, double w) {
-  if (w > 1.0 || w == 0 || w < -1) return -1;
-  if (w < 0.0) return h->opt_ci_search ? 1 : -1;
-  return 0;
-}
-
-// the entry's device-side weights, the start point of a search, its two result words, and per agent M_i and H_i P_i H_i^T
-static double *ciw_M(xk_handle *h, int i) { return h->d_ciw + 24 + (size_t)i * 576; }
-static double *ciw_T(xk_handle *h, int i) { return h->d_ciw + 24 + (size_t)(XK_CIW_MAXK1 + i) * 576; }
-
-static void ciw_set(xk_handle *h, double *slot, const double *v, int k1) {
-  XkCiwSetArgs s;
-  s.w = slot;
-  for (int i = 0; i < XK_CIW_MAXK1; ++i) s.v[i] = i < k1 ? v[i] : 0.0;
-  hipLaunchKernelGGL(xk_ciw_set, dim3(1), dim3(64), 0, h->stream, s);
-}
-
-// S (m x m in Sd) (+)= T / w_i with the weights of the entry's device slots (xk_ciw_sum)
-static void ciw_sum(xk_handle *h, const double *T, double *Sd, int m, int i, bool pair, bool first, bool add_diag, double diag,
-                    double *d_w_result) {
-  XkCiwSumArgs s{T, Sd, m, first ? 1 : 0, i, pair ? 1 : 0, add_diag ? 1 : 0, diag, h->d_ciw, d_w_result};
-  hipLaunchKernelGGL(xk_ciw_sum, dim3((m * m + 255) / 256), dim3(256), 0, h->stream, s);
-}
-
-// T (device, m x m, ld m) = Hd (m x nn col-major) * Pd (nn x nn) * Hd^T
-static void hpht(xk_handle *h, const double *Hd, const double *Pd, int m, int nn, double *T) {
-  XkGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = Hd; g.sar = 1; g.sac = m;
-  g.B = Pd; g.sbr = 1; g.sbc = nn;
-  g.C = h->d_Maug; g.scr = nn; g.scc = 1; g.D = g.C; g.sdr = nn; g.sdc = 1;
-  g.M = m; g.N = nn; g.K = nn; g.alpha = 1.0; g.beta = 0.0;
-  gemm(h, g);  // W = H P  (m x nn, row-major ld nn)
-  memset(&g, 0, sizeof(g));
-  g.A = h->d_Maug; g.sar = nn; g.sac = 1;
-  g.B = Hd; g.sbr = m; g.sbc = 1;  // B[k][j] = H[j][k]
-  g.C = T; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
-  g.M = m; g.N = m; g.K = nn; g.alpha = 1.0; g.beta = 0.0;
-  gemm(h, g);
-}
-
-// Information projection M = Hd Pd^-1 Hd^T (m x m, ld m) with the Kalman stage's factorisation: the system is [P | H^T],
-// xk_chol_whole per 192-row slab with the Schur-complement GEMM between slabs (launch_update), X = L^-1 H^T, M = X^T X.
-// ONE factorisation of Pd serves all m right-hand sides.  A pivot that is not positive sets the handle's status word.
-static int ci_info(xk_handle *h, const double *Hd, const double *Pd, int m, int nn, double *Mout) {
-  const int LDA = h->LDA, c = nn, ncols = nn + m;
-  if (nn > h->CM || ncols > LDA) return fail(h, XK_ECAPACITY, "CI weight search: covariance exceeds the workspace");
-  XkCopyArgs cp{Pd, h->d_Maug, nn, nn, 1, (long)nn, (long)LDA, 1};
-  hipLaunchKernelGGL(xk_copy2d, dim3((nn * nn + 255) / 256), dim3(256), 0, h->stream, cp);
-  XkCopyArgs ch{Hd, h->d_Maug + nn, nn, m, (long)m, 1, (long)LDA, 1};        // row r of the right-hand sides = column r of H
-  hipLaunchKernelGGL(xk_copy2d, dim3((nn * m + 255) / 256), dim3(256), 0, h->stream, ch);
-  const int B = 16 * XK_CHOLW_MAXB;
-  for (int off = 0; off < c;) {
-    const int cb = std::min(B, c - off);
-    XkCholWholeArgs d;
-    d.Maug = h->d_Maug + (size_t)off * LDA + off; d.ld = LDA; d.c = cb; d.ncols = ncols - off;
-    d.X = h->d_X + (size_t)off * LDA + off; d.status = h->d_status;
-#ifdef XK_CHOLW_PROBE
-    d.dbg = nullptr;
-#endif
-    xk_cholw_table((cb + 15) / 16, d.tab);
-    hipLaunchKernelGGL(xk_chol_whole, dim3((ncols - off - cb + 15) / 16), dim3(64 * XK_CHOLW_WAVES), 0, h->stream, d);
-    off += cb;
-    if (off < c) {
-      XkGemmArgs s;
-      memset(&s, 0, sizeof(s));
-      const double *Xs = h->d_X + (size_t)(off - cb) * LDA + off;
-      s.A = Xs; s.sar = 1; s.sac = LDA;
-      s.B = Xs; s.sbr = LDA; s.sbc = 1;
-      s.C = h->d_Maug + (size_t)off * LDA + off; s.scr = LDA; s.scc = 1;
-      s.D = s.C; s.sdr = LDA; s.sdc = 1;
-      s.M = c - off; s.N = ncols - off; s.K = cb; s.alpha = -1.0; s.beta = 1.0; s.mode = 0;
-      s.sym_cols = c - off;
-      gemm(h, s);
-    }
-  }
-  XkGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = h->d_X + nn; g.sar = 1; g.sac = LDA;       // A[i][k] = X[k][nn + i]
-  g.B = h->d_X + nn; g.sbr = LDA; g.sbc = 1;       // B[k][j] = X[k][nn + j]
-  g.C = Mout; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
-  g.M = m; g.N = m; g.K = nn; g.alpha = 1.0; g.beta = 0.0;
-  gemm(h, g);
-  return XK_OK;
-}
-
-// after the stream has been synchronised: did a factorisation of ci_info meet a pivot that is not positive?
-static int ciw_chol_status(xk_handle *h) {
-  if (h->d_status[0] == 0) return XK_OK;
-  h->d_status[0] = 0;
-  return fail(h, XK_ESINGULAR, "CI weight search: a covariance is not positive definite");
-}
-
-// queue the search over the k1 matrices in ciw_M (stride mstride); start = null: from the uniform point
-static void ciw_solve(xk_handle *h, int m, int k1, int mstride, const double *start) {
-  if (start) ciw_set(h, h->d_ciw + 8, start, k1);
-  XkCiwArgs a{ciw_M(h, 0), 0, mstride, m, k1, start ? h->d_ciw + 8 : nullptr, h->d_ciw, (int *)(h->d_ciw + 16), nullptr};
-  hipLaunchKernelGGL(xk_ci_weights, dim3(1), dim3(XK_CIW_THREADS), 0, h->stream, a);
-}
-
-// fetch the searched weights (synchronises), check both failure words, remember them for xk_ci_last_weights
-static int ciw_fetch(xk_handle *h, int k1, double *w) {
-  double buf[17];
-  HIPCHK(h, hipMemcpyAsync(buf, h->d_ciw, sizeof(buf), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (int rc = ciw_chol_status(h)) return rc;
-  int info[2];
-  memcpy(info, buf + 16, sizeof(info));
-  if (info[1] != 0)
-    return fail(h, XK_ESINGULAR, info[0] >= XK_CIW_MAXIT ? "CI weight search: no convergence within 50 Newton steps"
-                                                           : "CI weight search: sum w_i M_i is not positive definite");
-  for (int i = 0; i < 8; ++i) h->ci_last_w[i] = i < k1 ? buf[i] : 0.0;
-  h->ci_last_k1 = k1;
-  h->ci_last_iters = info[0];
-  if (w) memcpy(w, buf, sizeof(double) * k1);
-  return XK_OK;
-}
-
-// start points of the two forms.  The reference's own (ci.cpp:66-67,109-110) are infeasible for k agents resp. for w = -1 and make
-// NLopt give up; these are feasible, and the result does not depend on them.
-static void ciw_start_pair(double w, double *st) {
-  st[1] = std::min(std::max(-w, XK_CIW_LB), 1.0 - XK_CIW_LB);
-  st[0] = 1.0 - st[1];
-}
-static const double *ciw_start_multi(double w, int k, double *st) {
-  const double wo = -w, w0 = 1.0 - k * wo;
-  if (!(wo >= XK_CIW_LB) || !(w0 >= XK_CIW_LB)) return nullptr;      // uniform
-  st[0] = w0;
-  for (int i = 1; i <= k; ++i) st[i] = wo;
-  return st;
-}
-
-extern "C" int xk_fuse_ci_msckf(xk_handle *h, const double *P, int ldp, int n, const double *H, int ldh, int m,
-                                int k, const double *const *Ps, const int *ns, const double *const *Hs,
-                                double w_other, double *S, int lds, double *w_result) {
-  if (!h || !P || !H || !S || !w_result || k < 0 || m <= 0 || ldp < n || ldh < m || lds < m) return XK_EINVAL;
-  const int srch = check_w(h, w_other);
-  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
-  if (n > h->n || m > h->CM) return fail(h, XK_ECAPACITY, "fuse_ci dims exceed workspace");
-  if (srch && k < 1) return fail(h, XK_EINVAL, "CI weight search: no other agent");
-  if (srch && (m > XK_CIW_MAXM || k + 1 > XK_CIW_MAXK1)) return fail(h, XK_ECAPACITY, "CI weight search: at most 21 rows and 7 other agents");
-  HIPCHK(h, hipSetDevice(h->device));
-  const double w0 = 1.0 - (double)k * w_other;
-  if (!srch) {
-    const double v[2] = {w0, w_other};                                 // (every other agent has the same fixed weight: slot 1)
-    ciw_set(h, h->d_ciw, v, 2);
-  }
-  for (int i = 0; i <= k; ++i) {
-    const int n_i = i ? ns[i - 1] : n;
-    if (n_i > h->n) return fail(h, XK_ECAPACITY, "other agent's state larger than workspace");
-    if (i) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      HIPCHK(h, hipMemcpyAsync(h->d_tmpP, Ps[i - 1], sizeof(double) * (size_t)n_i * n_i, hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipMemcpyAsync(h->d_tmpH, Hs[i - 1], sizeof(double) * (size_t)m * n_i, hipMemcpyHostToDevice, h->stream));
-    } else {
-      HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
-                                 hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, H, sizeof(double) * ldh, sizeof(double) * m, n,
-                                 hipMemcpyHostToDevice, h->stream));
-    }
-    // fixed weights: the term joins the sum at once; searched: H_i P_i H_i^T and M_i are kept until the weights are known
-    double *T = srch ? ciw_T(h, i) : h->d_X;
-    hpht(h, h->d_tmpH, h->d_tmpP, m, n_i, T);
-    if (!srch) ciw_sum(h, T, h->d_tmpS, m, i ? 1 : 0, false, i == 0, false, 0.0, nullptr);
-    else if (int rc = ci_info(h, h->d_tmpH, h->d_tmpP, m, n_i, ciw_M(h, i))) return rc;
-  }
-  double wr = 1.0 / w0;
-  if (srch) {
-    double st[XK_CIW_MAXK1], w[XK_CIW_MAXK1];
-    ciw_solve(h, m, k + 1, 576, ciw_start_multi(w_other, k, st));
-    if (int rc = ciw_fetch(h, k + 1, w)) return rc;
-    for (int i = 0; i <= k; ++i) ciw_sum(h, ciw_T(h, i), h->d_tmpS, m, i, false, i == 0, false, 0.0, nullptr);
-    wr = 1.0 / w[0];                                                   // ci.cpp:78-90 with the searched w_0
-  }
-  HIPCHK(h, hipMemcpy2DAsync(S, sizeof(double) * lds, h->d_tmpS, sizeof(double) * m, sizeof(double) * m, m,
-                             hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  *w_result = wr;
-  return XK_OK;
-}
-
-extern "C" int xk_fuse_ci_slam(xk_handle *h, const double *Pa, int lda, int na, const double *Ha, int ldha,
-                               const double *Pb, int ldb, int nb, const double *Hb, int ldhb, int m,
-                               double w_other, double *S, int lds, double *w_result) {
-  if (!h || !Pa || !Ha || !Pb || !Hb || !S || !w_result || m <= 0 || lda < na || ldb < nb || ldha < m || ldhb < m ||
-      lds < m)
-    return XK_EINVAL;
-  const int srch = check_w(h, w_other);
-  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger than 0.0");
-  if (na > h->n || nb > h->n || m > h->CM) return fail(h, XK_ECAPACITY, "fuse_ci dims exceed workspace");
-  if (srch && m > XK_CIW_MAXM) return fail(h, XK_ECAPACITY, "CI weight search: at most 21 rows");
-  HIPCHK(h, hipSetDevice(h->device));
-  if (!srch) {
-    const double v[2] = {1.0 - w_other, w_other};
-    ciw_set(h, h->d_ciw, v, 2);
-  }
-  for (int i = 0; i < 2; ++i) {
-    const double *Pi = i ? Pb : Pa, *Hi = i ? Hb : Ha;
-    const int n_i = i ? nb : na, ldp_i = i ? ldb : lda, ldh_i = i ? ldhb : ldha;
-    if (i) HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n_i, Pi, sizeof(double) * ldp_i, sizeof(double) * n_i, n_i,
-                               hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, Hi, sizeof(double) * ldh_i, sizeof(double) * m, n_i,
-                               hipMemcpyHostToDevice, h->stream));
-    double *T = srch ? ciw_T(h, i) : h->d_X;
-    hpht(h, h->d_tmpH, h->d_tmpP, m, n_i, T);
-    if (!srch) ciw_sum(h, T, h->d_tmpS, m, i, true, i == 0, false, 0.0, nullptr);
-    else if (int rc = ci_info(h, h->d_tmpH, h->d_tmpP, m, n_i, ciw_M(h, i))) return rc;
-  }
-  double wr = 1.0 / (1.0 - w_other);
-  if (srch) {
-    double st[2], w[2];
-    ciw_start_pair(w_other, st);
-    ciw_solve(h, m, 2, 576, st);
-    if (int rc = ciw_fetch(h, 2, w)) return rc;
-    for (int i = 0; i < 2; ++i) ciw_sum(h, ciw_T(h, i), h->d_tmpS, m, i, true, i == 0, false, 0.0, nullptr);
-    wr = 1.0 / (1.0 - w[1]);                                           // ci.cpp:117-122 with the searched w_b
-  }
-  HIPCHK(h, hipMemcpy2DAsync(S, sizeof(double) * lds, h->d_tmpS, sizeof(double) * m, sizeof(double) * m, m,
-                             hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  *w_result = wr;
-  return XK_OK;
-}
-
-extern "C" int xk_multi_slam_match(xk_handle *h, const double *C_q_G, const double *G_p_C, int n_poses,
-                                   const double *feat, int anchor_idx, int feature_id, const double *P, int ldp,
-                                   int n, int n_poses_max, const double *o_C_q_G, const double *o_G_p_C,
-                                   int o_n_poses, const double *o_feat, int o_anchor_idx, int o_feature_id,
-                                   const double *o_P, int ldop, int no, int o_n_poses_max, double sigma_landmark,
-                                   double ci_slam_w, int *inlier, double *gamma, double *H, int ldh, double *res,
-                                   double *S, double *P_j, int ldpj) {
-  if (!h || !C_q_G || !G_p_C || !feat || !P || !o_C_q_G || !o_G_p_C || !o_feat || !o_P || !inlier || !gamma || !H ||
-      !res || !S || !P_j)
-    return XK_EINVAL;
-  if (anchor_idx < 0) return fail(h, XK_EINVAL, "anchor_idx < 0");       // throws, multi_slam_update.cpp:83-85
-  if (n != h->n || ldp < n || ldop < no || ldh < 3 || ldpj < n) return XK_EINVAL;
-  const int Mf = (n - XK_CORE - 6 * n_poses_max) / 3, oMf = (no - XK_CORE - 6 * o_n_poses_max) / 3;
-  if (feature_id < 0 || feature_id >= Mf || o_feature_id < 0 || o_feature_id >= oMf || anchor_idx >= n_poses ||
-      o_anchor_idx < 0 || o_anchor_idx >= o_n_poses)
-    return XK_EINVAL;
-  if (feat[3 * feature_id + 2] == 0) return fail(h, XK_EINVAL, "rho = 0");  // throws, :86-88
-  const int srch = check_w(h, ci_slam_w);
-  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger than 0.0");
-  if (no > h->n || n_poses > h->N || o_n_poses > h->N) return fail(h, XK_ECAPACITY, "match dims exceed workspace");
-  HIPCHK(h, hipSetDevice(h->device));
-  // scratch layout in d_ci
-  double *d = h->d_ci;
-  double *dq = d, *dp = dq + 4 * h->N, *df = dp + 3 * h->N, *doq = df + 3 * (Mf > 0 ? Mf : 1);
-  double *dop = doq + 4 * h->N, *dof = dop + 3 * h->N, *dH = dof + 3 * (oMf > 0 ? oMf : 1);
-  double *dout = dH + 3 * (size_t)n, *dcols_f = dout + 16, *doH = dcols_f + 2;
-  int *dcols = (int *)dcols_f;
-  double *doP = h->d_ci + 64 * (size_t)h->n + 1024;   // (the lists above end long before: < 11 n + 64 doubles)
-  HIPCHK(h, hipMemcpyAsync(dq, C_q_G, sizeof(double) * 4 * n_poses, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dp, G_p_C, sizeof(double) * 3 * n_poses, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(df, feat, sizeof(double) * 3 * Mf, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(doq, o_C_q_G, sizeof(double) * 4 * o_n_poses, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dop, o_G_p_C, sizeof(double) * 3 * o_n_poses, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dof, o_feat, sizeof(double) * 3 * oMf, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(doP, sizeof(double) * no, o_P, sizeof(double) * ldop, sizeof(double) * no, no,
-                             hipMemcpyHostToDevice, h->stream));
-  XkSlamMatchArgs a;
-  a.q = dq; a.p = dp; a.feat = df; a.P = h->d_tmpP; a.anchor = anchor_idx; a.fid = feature_id; a.n = n; a.npm = n_poses_max;
-  a.oq = doq; a.op = dop; a.ofeat = dof; a.oP = doP; a.oanchor = o_anchor_idx; a.ofid = o_feature_id; a.no = no;
-  a.onpm = o_n_poses_max;
-  a.var_l = sigma_landmark * sigma_landmark; a.w = h->d_ciw; a.chi = XK_CHI2_090[3];
-  a.H = dH; a.out = dout; a.cols = dcols; a.oH = nullptr; a.gate_only = 0;
-  if (!srch) {
-    const double v[2] = {1.0 - ci_slam_w, ci_slam_w};
-    ciw_set(h, h->d_ciw, v, 2);
-  } else {
-    // the Jacobians and the gate first (neither depends on the weights, multi_slam_update.cpp:216-220 precedes :222), then the two
-    // information projections and the search; the launch below reads the searched w_b
-    a.oH = doH; a.gate_only = 1;
-    hipLaunchKernelGGL(xk_slam_match, dim3(1), dim3(64), 0, h->stream, a);
-    a.oH = nullptr; a.gate_only = 0;
-    int rc = ci_info(h, dH, h->d_tmpP, 3, n, ciw_M(h, 0));
-    if (rc == XK_OK) rc = ci_info(h, doH, doP, 3, no, ciw_M(h, 1));
-    if (rc != XK_OK) return rc;
-    double st[2];
-    ciw_start_pair(ci_slam_w, st);
-    ciw_solve(h, 3, 2, 576, st);
-    if ((rc = ciw_fetch(h, 2, nullptr)) != XK_OK) return rc;
-  }
-  hipLaunchKernelGGL(xk_slam_match, dim3(1), dim3(64), 0, h->stream, a);
-  XkScaleArgs sc{h->d_tmpP, h->d_Pout, n, 3, dcols, dout + 14};
-  hipLaunchKernelGGL(xk_scale_blocks, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, sc);
-  double hout[16];
-  HIPCHK(h, hipMemcpyAsync(hout, dout, sizeof(double) * 16, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(H, sizeof(double) * ldh, dH, sizeof(double) * 3, sizeof(double) * 3, n,
-                             hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (int i = 0; i < 3; ++i) res[i] = hout[i];
-  *gamma = hout[12];
-  *inlier = hout[13] != 0.0;
-  if (*inlier) {
-    for (int i = 0; i < 9; ++i) S[i] = hout[3 + i];
-    HIPCHK(h, hipMemcpy2DAsync(P_j, sizeof(double) * ldpj, h->d_Pout, sizeof(double) * n, sizeof(double) * n, n,
-                               hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// MSCKF-MSCKF CI block (msckf_update.cpp:96-279) for one track
-// ---------------------------------------------------------------------------
-extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const double *C_q_G, const double *G_p_C,
-                                 int n_poses, const double *P, int ldp, int n, int n_poses_max, double sigma_img,
-                                 int k, const double *const *m_obs, const int *m_L, const double *const *m_q,
-                                 const double *const *m_p, const int *m_nposes, const double *const *m_P,
-                                 const int *m_n, double ci_msckf_w, int *self_inlier, double *self_gamma,
-                                 int *has_ci, double *ci_gamma, double *H, int ldh, double *res, double *S, int lds,
-                                 double *P_j, int ldpj) {
-  if (!h || !obs || !C_q_G || !G_p_C || !P || !self_inlier || !self_gamma || !has_ci || k < 0) return XK_EINVAL;
-  if (k > XK_CI_MAXK) return fail(h, XK_ECAPACITY, "more than 7 matched agents");
-  if (n != h->n || ldp < n || L < 2 || L > n_poses || n_poses > h->N || n_poses_max != h->N) return XK_EINVAL;
-  if (k > 0 && (!m_obs || !m_L || !m_q || !m_p || !m_nposes || !m_P || !m_n || !H || !res || !S || !P_j || !ci_gamma ||
-                ldh < 3 * k || lds < 3 * k || ldpj < n))
-    return XK_EINVAL;
-  const int srch = k > 0 ? check_w(h, ci_msckf_w) : 0;
-  if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
-  int Ltot = L, nmax = n;
-  for (int i = 0; i < k; ++i) {
-    if (m_L[i] < 2 || m_L[i] > m_nposes[i] || m_nposes[i] > 64 || m_n[i] < XK_CORE + 6 * m_nposes[i]) return XK_EINVAL;
-    Ltot += m_L[i];
-    nmax = std::max(nmax, m_n[i]);
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  *has_ci = 0;
-  const int m = 3 * k, k1 = k + 1;
-  // workspace (lazily sized): concatenated lists, per-agent window/obs/P, up rows, H blocks, S buffers
-  const size_t upsz = 3 * (size_t)nmax + 16;
-  const size_t need = 9 * (size_t)Ltot + 7 * 64 + 2 * 64 + (size_t)nmax * nmax + k1 * upsz + (size_t)std::max(m, 1) * k1 * nmax +
-                      4 * 24 * 24 + 1024;
-  double *ws = nullptr;
-  HIPCHK(h, hipMalloc((void **)&ws, sizeof(double) * need));
-  struct Guard { double *p; ~Guard() { if (p) hipFree(p); } } guard{ws};
-  double *dq = ws, *dp = dq + 4 * (size_t)Ltot, *dobs = dp + 3 * (size_t)Ltot;
-  double *aq = dobs + 2 * (size_t)Ltot, *ap = aq + 4 * 64, *aobs = ap + 3 * 64;   // one agent's window + track
-  double *aP = aobs + 2 * 64, *up = aP + (size_t)nmax * nmax, *Hs = up + k1 * upsz;
-  double *S1 = Hs + (size_t)std::max(m, 1) * k1 * nmax, *S2 = S1 + 24 * 24, *dres = S2 + 24 * 24, *dgpf = dres + 24;
-  double *dscal = dgpf + 8;  // [0] ci gamma, [1] w_result
-  int *dint = (int *)(dscal + 8);  // [0] gn iters, [1] inlier, [2] tile rows, [3..] block columns
-  // concatenated lists: matched agents first, self last (:113-149)
-  size_t at = 0;
-  for (int i = 0; i < k; ++i) {
-    HIPCHK(h, hipMemcpyAsync(dq + 4 * at, m_q[i] + 4 * (size_t)(m_nposes[i] - m_L[i]), sizeof(double) * 4 * m_L[i], hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dp + 3 * at, m_p[i] + 3 * (size_t)(m_nposes[i] - m_L[i]), sizeof(double) * 3 * m_L[i], hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dobs + 2 * at, m_obs[i], sizeof(double) * 2 * m_L[i], hipMemcpyHostToDevice, h->stream));
-    at += m_L[i];
-  }
-  HIPCHK(h, hipMemcpyAsync(dq + 4 * at, C_q_G + 4 * (size_t)(n_poses - L), sizeof(double) * 4 * L, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dp + 3 * at, G_p_C + 3 * (size_t)(n_poses - L), sizeof(double) * 3 * L, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(dobs + 2 * at, obs, sizeof(double) * 2 * L, hipMemcpyHostToDevice, h->stream));
-  XkTriMultiArgs ta{dq, dp, dobs, Ltot, dgpf, dint, nullptr, 0};
-  hipLaunchKernelGGL(xk_triangulate_multi, dim3(1), dim3(64), 0, h->stream, ta);
-  // per-agent column-space rows (self first = row block 0, then the matched agents, :168-204)
-  const int offs[2] = {0, 0};
-  (void)offs;
-  for (int i = 0; i < k1; ++i) {
-    const bool self = (i == 0);
-    const double *hq = self ? C_q_G : m_q[i - 1], *hp = self ? G_p_C : m_p[i - 1], *hobs = self ? obs : m_obs[i - 1];
-    const double *hP = self ? P : m_P[i - 1];
-    const int np_i = self ? n_poses : m_nposes[i - 1], L_i = self ? L : m_L[i - 1], n_i = self ? n : m_n[i - 1];
-    const int ld_i = self ? ldp : n_i, npm_i = self ? n_poses_max : m_nposes[i - 1];
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // scratch reuse across agents
-    HIPCHK(h, hipMemcpyAsync(aq, hq, sizeof(double) * 4 * np_i, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ap, hp, sizeof(double) * 3 * np_i, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(aobs, hobs, sizeof(double) * 2 * L_i, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpy2DAsync(aP, sizeof(double) * n_i, hP, sizeof(double) * ld_i, sizeof(double) * n_i, n_i, hipMemcpyHostToDevice, h->stream));
-    const int toff[2] = {0, L_i};
-    HIPCHK(h, hipMemcpyAsync(dint + 8, toff, sizeof(int) * 2, hipMemcpyHostToDevice, h->stream));
-    XkFeatArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = aq; a.p = ap; a.n_poses = np_i; a.n_poses_max = npm_i; a.trk_off = dint + 8; a.obs = aobs; a.K = 1;
-    a.P = aP; a.n = n_i; a.var_img = sigma_img * sigma_img; a.chi95 = h->d_chi95;
-    a.A = nullptr; a.DB = 0; a.C1P = 0; a.na = n_i - XK_CORE;
-    a.tile_rows = dint + 2; a.inlier = dint + 1; a.gamma = dscal + 2; a.gpf = dgpf + 4; a.gn_iters = dint + 3;
-    a.gpf_in = dgpf; a.up_out = up + i * upsz; a.batch = nullptr; a.dbg = nullptr; a.inlier_h = nullptr; a.gamma_h = nullptr;
-    hipLaunchKernelGGL(xk_msckf_feature, dim3(1), dim3(XK_FEAT_THREADS), xk_feature_lds_bytes(np_i), h->stream, a);
-    if (self) {
-      int inl = 0;
-      double g = 0;
-      HIPCHK(h, hipMemcpyAsync(&inl, dint + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(&g, dscal + 2, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      *self_inlier = inl;
-      *self_gamma = g;
-      if (!inl || k == 0) return XK_OK;  // proceed_with_multi_ false (:180)
-    }
-  }
-  // null-space projection of the landmark and split into per-agent Jacobians (:207-223)
-  XkCiProjArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.k1 = k1;
-  pa.res = dres;
-  for (int i = 0; i < k1; ++i) {
-    pa.up[i] = up + i * upsz;
-    pa.n[i] = (i == 0) ? n : m_n[i - 1];
-    pa.H[i] = Hs + (size_t)m * nmax * i;
-  }
-  hipLaunchKernelGGL(xk_ci_project, dim3(k1), dim3(256), 0, h->stream, pa);
-  // S_gate = sum H_i P_i H_i^T + sigma^2 I (:217-237) and the CI-weighted S (ci.cpp:78-85 + :255)
-  const double w0 = 1.0 - (double)k * ci_msckf_w, var_img = sigma_img * sigma_img;
-  for (int i = 0; i < k1; ++i) {
-    const double *hP = (i == 0) ? P : m_P[i - 1];
-    const int n_i = (i == 0) ? n : m_n[i - 1], ld_i = (i == 0) ? ldp : n_i;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy2DAsync(aP, sizeof(double) * n_i, hP, sizeof(double) * ld_i, sizeof(double) * n_i, n_i, hipMemcpyHostToDevice, h->stream));
-    XkGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = pa.H[i]; g.sar = 1; g.sac = m; g.B = aP; g.sbr = 1; g.sbc = n_i;
-    g.C = h->d_Maug; g.scr = n_i; g.scc = 1; g.D = g.C; g.sdr = n_i; g.sdc = 1;
-    g.M = m; g.N = n_i; g.K = n_i; g.alpha = 1.0; g.beta = 0.0;
-    gemm(h, g);  // W = H_i P_i
-    for (int pass = 0; pass < 2; ++pass) {  // 0: the gate's sum (weights play no part in it); 1: H_i P_i H_i^T on its own, weighted below
-      memset(&g, 0, sizeof(g));
-      g.A = h->d_Maug; g.sar = n_i; g.sac = 1; g.B = pa.H[i]; g.sbr = m; g.sbc = 1;
-      g.C = pass ? ciw_T(h, i) : S1; g.scr = 1; g.scc = m; g.D = g.C; g.sdr = 1; g.sdc = m;
-      g.M = m; g.N = m; g.K = n_i;
-      g.alpha = 1.0;
-      g.beta = (i == 0 || pass) ? 0.0 : 1.0;
-      g.mode = (i == k && !pass) ? 1 : 0;   // noise once, on the last term
-      g.diag = nullptr; g.diag_scalar = var_img;
-      gemm(h, g);
-    }
-    // searched weights: M_i = H_i P_i^-1 H_i^T while P_i is on the device -- one factorisation per agent
-    if (srch)
-      if (int rc = ci_info(h, pa.H[i], aP, m, n_i, ciw_M(h, i))) return rc;
-  }
-  hipLaunchKernelGGL(xk_small_gamma, dim3(1), dim3(1), 0, h->stream, S1, dres, m, dscal);
-  double g_ci = 0;
-  HIPCHK(h, hipMemcpyAsync(&g_ci, dscal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (srch)
-    if (int rc = ciw_chol_status(h)) return rc;
-  *ci_gamma = g_ci;
-  const int dof = 2 * Ltot - 3;
-  if (dof >= XK_CHI2_LEN) return fail(h, XK_ECAPACITY, "chi-square table too short");
-  if (!(g_ci < XK_CHI2_095[dof])) return XK_OK;   // :243-250
-  // the CI-weighted S (ci.cpp:78-85 + :255): the weights sit in the entry's device slots, the host's constants or the searched ones
-  if (!srch) {
-    double v[XK_CIW_MAXK1] = {w0};
-    for (int i = 1; i <= k; ++i) v[i] = ci_msckf_w;
-    ciw_set(h, h->d_ciw, v, k1);
-  } else {
-    double st[XK_CIW_MAXK1];
-    ciw_solve(h, m, k1, 576, ciw_start_multi(ci_msckf_w, k, st));
-    if (int rc = ciw_fetch(h, k1, nullptr)) return rc;
-  }
-  for (int i = 0; i < k1; ++i) ciw_sum(h, ciw_T(h, i), S2, m, i, false, i == 0, i == k, var_img, i == 0 ? dscal + 1 : nullptr);
-  // P_j: diagonal 3x3 blocks of the L observed poses scaled by w_result = 1/w0 (:256-267)
-  std::vector<int> cols(2 * L);
-  for (int i = 0; i < L; ++i) {
-    const int pos = n_poses - L + i;
-    cols[2 * i] = XK_CORE + 3 * pos;
-    cols[2 * i + 1] = XK_CORE + 3 * pos + 3 * n_poses_max;
-  }
-  int *dcols = dint + 16;   // (dscal[1] = w_result = 1 / w_0 was left there by xk_ciw_sum)
-  HIPCHK(h, hipMemcpyAsync(dcols, cols.data(), sizeof(int) * 2 * L, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n, hipMemcpyHostToDevice, h->stream));
-  XkScaleArgs sc{h->d_tmpP, h->d_Pout, n, 2 * L, dcols, dscal + 1};
-  hipLaunchKernelGGL(xk_scale_blocks, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, sc);
-  HIPCHK(h, hipMemcpy2DAsync(H, sizeof(double) * ldh, pa.H[0], sizeof(double) * m, sizeof(double) * m, n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(res, dres, sizeof(double) * m, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(S, sizeof(double) * lds, S2, sizeof(double) * m, sizeof(double) * m, m, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(P_j, sizeof(double) * ldpj, h->d_Pout, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  *has_ci = 1;
-  return XK_OK;
-}
-
-// The search alone, on matrices the caller supplies (include/xk.h).
-extern "C" int xk_ci_solve_weights(xk_handle *h, const double *M, int m, int k1, const double *w_start, double *w, int *iters) {
-  if (!h || !M || !w) return XK_EINVAL;
-  if (m < 1 || m > XK_CIW_MAXM || k1 < 2 || k1 > XK_CIW_MAXK1) return fail(h, XK_EINVAL, "xk_ci_solve_weights: 1 <= m <= 21, 2 <= k1 <= 8");
-  if (w_start) {
-    double sum = 0.0;
-    for (int i = 0; i < k1; ++i) {
-      if (!(w_start[i] >= XK_CIW_LB)) return fail(h, XK_EINVAL, "xk_ci_solve_weights: every start weight must be at least 1e-4");
-      sum += w_start[i];
-    }
-    if (!(fabs(sum - 1.0) <= 1e-12)) return fail(h, XK_EINVAL, "xk_ci_solve_weights: the start weights must sum to one");
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(ciw_M(h, 0), M, sizeof(double) * (size_t)k1 * m * m, hipMemcpyHostToDevice, h->stream));
-  ciw_solve(h, m, k1, m * m, w_start);
-  if (int rc = ciw_fetch(h, k1, w)) return rc;
-  if (iters) *iters = h->ci_last_iters;
-  return XK_OK;
-}
-
-extern "C" int xk_ci_round_weights(const xk_handle *h, int track, double *w, int *k1, int *iters) {
-  if (!h || !w || track < 0 || track >= h->ci_round_tracks) return XK_EINVAL;
-  for (int i = 0; i < 8; ++i) w[i] = h->ci_round_w[track][i];
-  if (k1) *k1 = h->ci_round_k1[track];
-  if (iters) *iters = h->ci_round_iters[track];
-  return XK_OK;
-}
-
-extern "C" int xk_ci_last_weights(const xk_handle *h, double *w, int *k1, int *iters) {
-  if (!h || !w) return XK_EINVAL;
-  for (int i = 0; i < 8; ++i) w[i] = h->ci_last_w[i];
-  if (k1) *k1 = h->ci_last_k1;
-  if (iters) *iters = h->ci_last_iters;
-  return XK_OK;
-}
+#include "xk_ci_api.hip.h"
 
 // ---------------------------------------------------------------------------
 // StateManager::manage on the resident covariance
@@ -2026,385 +1461,6 @@ extern "C" int xk_cov_propagate(xk_handle *h, const double *f_d, int ldf, const 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, XK_EDEVICE, "propagate launch", e);
   h->have_rows = h->have_R = false;
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Device-resident CI round: the gathered SimpleState payloads (and the observations of the shared
-// tracks) stay where RCCL put them.  Same arithmetic as xk_msckf_ci_track + xk_apply_ci per shared
-// track, with every per-agent stage batched over the agents and no host staging of the n x n
-// covariances.  One host synchronisation per track (the two gate decisions).
-// ---------------------------------------------------------------------------
-extern "C" int xk_ci_round_device(xk_handle *h, const double *d_payloads, long payload_stride, int world, int self_rank,
-                                  const double *d_tracks, int n_tracks, const int *track_len, const int *n_poses_valid,
-                                  const int *self_track, double sigma_img, double ci_msckf_w, int *n_fused,
-                                  double *corrections) {
-  if (!h || !d_payloads || !d_tracks || !track_len || !n_poses_valid || !self_track || !n_fused) return XK_EINVAL;
-  const int k = world - 1, k1 = world, N = h->N, n = h->n, m = 3 * k;
-  *n_fused = 0;
-  if (world < 2) return XK_OK;
-  if (k > XK_CI_MAXK) return fail(h, XK_ECAPACITY, "more than 7 matched agents");
-  if (self_rank < 0 || self_rank >= world || n_tracks < 0 || n_tracks > 8) return XK_EINVAL;
-  if (payload_stride != xk_payload_doubles(N, h->Mmax)) return fail(h, XK_EINVAL, "payload layout differs from this handle's (N, M)");
-  if (h->n_poses < 2) return fail(h, XK_EINVAL, "window not staged");
-  const int srch = check_w(h, ci_msckf_w);
-  if (srch < 0)
-    return fail(h, XK_EINVAL, (ci_msckf_w < 0 && ci_msckf_w >= -1 && !h->opt_ci_search)
-                                  ? "xk_ci_round_device: a negative CI weight asks for the weight search, which is switched off (xk_set_option \"ci_weight_search\", 1)"
-                                  : "The CI weights must be lower than 1.0 and larger 0.0");
-  if (m > h->CM) return fail(h, XK_ECAPACITY, "m exceeds the dense workspace");
-  HIPCHK(h, hipSetDevice(h->device));
-  // searched weights: per agent [P_i | H_i^T of all tracks] and the solve's output, then the solver's operands and results
-  const int ciwr_ld = n + XK_CIWR_MAXRHS;
-  const size_t ciwr_agent = 2 * (size_t)n * ciwr_ld;
-  if (srch && !h->d_ciwr)
-    HIPCHK(h, hipMalloc((void **)&h->d_ciwr, sizeof(double) * (XK_CIW_MAXK1 * ciwr_agent + 64 * 576 + 64 + 64 + 8 + 8 + 4)));
-  const size_t upsz = 3 * (size_t)n + 16;
-  const size_t Lcap = (size_t)k1 * 64;
-  const size_t ci_ws_doubles = (size_t)9 * 8 * 64 + 8 * upsz + (size_t)21 * 8 * n + 8 * XK_CI_MAXCHUNK * 576 + 2 * 576 + 512;
-    if (!h->d_ciws) {
-    HIPCHK(h, hipMalloc((void **)&h->d_ciws, sizeof(double) * 8 * ci_ws_doubles));   // one region per shared track
-    HIPCHK(h, hipMalloc((void **)&h->d_batch, sizeof(XkFeatBatch) * 64));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_batch, sizeof(XkFeatBatch) * 64));
-    HIPCHK(h, hipHostMalloc((void **)&h->h_ci_cols, sizeof(int) * (8 * 128 + 8)));   // + the per-track own-gate flags
-    // [0..7] 1/w0, [8..15] joint gamma; [16 + 4 j ..] track j: own verdict, joint gamma, marker; a searched round adds
-    // [48 + 8 j ..] track j's weights, [112 ..] the solver's two info words per track (ints), [120 ..] the pivot status per agent (ints)
-    HIPCHK(h, hipHostMalloc((void **)&h->h_ci_w, sizeof(double) * 128));
-    memset(h->h_ci_w, 0, sizeof(double) * 128);
-    hipFuncSetAttribute((const void *)xk_ci_hph, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    HIPCHK(h, hipEventCreateWithFlags(&h->ci_fork, hipEventDisableTiming));
-    for (int j = 1; j < 8; ++j) {
-      HIPCHK(h, hipStreamCreateWithFlags(&h->ci_stream[j], hipStreamNonBlocking));
-      HIPCHK(h, hipEventCreateWithFlags(&h->ci_join[j], hipEventDisableTiming));
-    }
-  }
-  // per-track workspace (the stages before the gate of every shared track are queued back to back, then ONE
-  // synchronisation fetches all the gate results)
-  struct CiWs { double *dq, *dp, *dobs, *up, *Hs, *Si, *S1, *S2, *dres, *dgpf, *dscal; int *dint; };
-  auto ci_ws = [&](int j) {
-    CiWs w;
-    double *ws = h->d_ciws + (size_t)j * ci_ws_doubles;
-    w.dq = ws; w.dp = w.dq + 4 * Lcap; w.dobs = w.dp + 3 * Lcap; w.up = w.dobs + 2 * Lcap;
-    w.Hs = w.up + k1 * upsz; w.Si = w.Hs + (size_t)std::max(m, 1) * k1 * n; w.S1 = w.Si + (size_t)k1 * XK_CI_MAXCHUNK * 576; w.S2 = w.S1 + 576;
-    w.dres = w.S2 + 576; w.dgpf = w.dres + 24; w.dscal = w.dgpf + 8;   // dscal[0] ci gamma, [1] w_result, [2..] per-agent gamma
-    w.dint = (int *)(w.dscal + 16);   // [0..7] inlier per agent, [8..15] tile rows, [16..31] gn iters, [32..159] block columns, [192..] landmarks
-    return w;
-  };
-  // payload layout (fleet.py / xk_pack_payload): hdr[8] dyn[16] pos[3N] att[4N] feat[3M] anchors[M] cov[n*n]
-  const size_t o_pos = 24, o_att = o_pos + 3 * (size_t)N, o_cov = o_att + 4 * (size_t)N + 4 * (size_t)h->Mmax;
-  const size_t trk_stride = 1 + 2 * (size_t)N;
-  // (searched: xk_ci_combine's own S_ci is formed with unit weights and replaced by xk_ciwr_finish)
-  const double w0 = srch ? 1.0 : 1.0 - (double)k * ci_msckf_w, w_oth = srch ? 1.0 : ci_msckf_w, var_img = sigma_img * sigma_img;
-  { int rcw = flush_window(h); if (rcw != XK_OK) return rcw; }
-  int fused = 0;
-  int trk_L0[8], trk_dof[8];
-  // Every track is validated BEFORE anything is queued or forked: an early return below this point would leave side streams
-  // running into workspace and pinned words the next call reuses.
-  for (int j = 0; j < n_tracks; ++j) {
-    const int st = self_track[j];
-    if (st < 0 || st >= h->K) return fail(h, XK_EINVAL, "shared track index outside the staged tracks");
-    int Ltot = h->h_trk_off[st + 1] - h->h_trk_off[st];
-    for (int r = 0; r < world; ++r) {
-      if (r == self_rank) continue;
-      const int np_r = n_poses_valid[r], L_r = track_len[r * n_tracks + j];
-      if (L_r < 2 || L_r > np_r || np_r > N) return fail(h, XK_EINVAL, "received track / window lengths inconsistent");
-      Ltot += L_r;
-    }
-    if (2 * Ltot - 3 >= XK_CHI2_LEN) return fail(h, XK_ECAPACITY, "chi-square table too short");
-  }
-  // (a HIP error after the fork: the side streams are joined before the error is returned)
-  auto bail = [&](int rc) {
-    for (int j = 1; j < 8; ++j)
-      if (h->ci_stream[j]) hipStreamSynchronize(h->ci_stream[j]);
-    hipStreamSynchronize(h->stream);
-    return rc;
-  };
-#define CI_CHK(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) return bail(fail(h, XK_EDEVICE, #call, e_));                \
-  } while (0)
-  // The shared tracks are independent until applyCI (every P_j is built from the same prior), and a track's stages are a chain of
-  // seven small launches (~160 us at 8 agents): track j >= 1 runs its chain on a side stream next to track 0's.
-  const unsigned long long ci_seq = ++h->done_seq;
-  static const int side_env = env_int("XK_CI_SIDE_STREAMS", 1);
-  const bool side = side_env && n_tracks > 1;
-  double *ciwr_M = nullptr, *ciwr_start = nullptr, *ciwr_w = nullptr, *ciwr_winv = nullptr;
-  int *ciwr_info = nullptr, *ciwr_status = nullptr;
-  if (srch) {
-    ciwr_M = h->d_ciwr + XK_CIW_MAXK1 * ciwr_agent; ciwr_start = ciwr_M + 64 * 576; ciwr_w = ciwr_start + 64; ciwr_winv = ciwr_w + 64;
-    ciwr_info = (int *)(ciwr_winv + 8); ciwr_status = ciwr_info + 16;
-  }
-  XkCiwrAssembleArgs ciwr_as;
-  XkCiwrFinishArgs ciwr_fin;
-  memset(&ciwr_as, 0, sizeof(ciwr_as));
-  memset(&ciwr_fin, 0, sizeof(ciwr_fin));
-  if (side) CI_CHK(hipEventRecord(h->ci_fork, h->stream));
-  // Round 6: the launches of a track's chain are PREPARED here and issued stage by stage over all tracks below.  The round was bound by
-  // the host issuing 2 x 8 launches one track after the other (~7 us each: the second track's chain started 60 us after the first
-  // one's, tools/exp/ci_round_kernels.sh); stage-major, both chains are in flight from the first launch on.
-  std::vector<std::function<hipError_t()>> ci_stage[8];
-  for (int j = 0; j < n_tracks; ++j) {
-    hipStream_t sj = (side && j > 0) ? h->ci_stream[j] : h->stream;
-    if (side && j > 0) CI_CHK(hipStreamWaitEvent(sj, h->ci_fork, 0));
-    const CiWs w = ci_ws(j);
-    double *dq = w.dq, *dp = w.dp, *dobs = w.dobs, *up = w.up, *Hs = w.Hs, *Si = w.Si, *S1 = w.S1, *S2 = w.S2;
-    double *dres = w.dres, *dgpf = w.dgpf, *dscal = w.dscal;
-    int *dint = w.dint;
-    const int st = self_track[j];
-    // agent order: index 0 = self, 1.. = the others by rank
-    const double *aq[XK_CI_MAXK + 1], *ap[XK_CI_MAXK + 1], *aobs[XK_CI_MAXK + 1], *aP[XK_CI_MAXK + 1];
-    int anp[XK_CI_MAXK + 1], aL[XK_CI_MAXK + 1], Ltot = 0;
-    aq[0] = h->d_q; ap[0] = h->d_p; aobs[0] = h->d_obs + 2 * (size_t)h->h_trk_off[st]; aP[0] = h->d_P;
-    anp[0] = h->n_poses; aL[0] = h->h_trk_off[st + 1] - h->h_trk_off[st];
-    for (int r = 0, i = 1; r < world; ++r) {
-      if (r == self_rank) continue;
-      const double *base = d_payloads + (size_t)r * payload_stride;
-      aq[i] = base + o_att; ap[i] = base + o_pos; aP[i] = base + o_cov;
-      aobs[i] = d_tracks + ((size_t)r * n_tracks + j) * trk_stride + 1;
-      anp[i] = n_poses_valid[r]; aL[i] = track_len[r * n_tracks + j];
-      ++i;
-    }
-    for (int i = 0; i < k1; ++i) Ltot += aL[i];
-    // joint triangulation over the concatenated lists: matched agents first, self last (:113-149)
-    XkCiGatherArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.k1 = k1; ga.dq = dq; ga.dp = dp; ga.dobs = dobs;
-    for (int i = 0; i < k1; ++i) {
-      const int src = (i < k) ? i + 1 : 0;
-      ga.q[i] = aq[src]; ga.p[i] = ap[src]; ga.obs[i] = aobs[src]; ga.np[i] = anp[src]; ga.L[i] = aL[src];
-    }
-    ci_stage[0].push_back([=]() { hipLaunchKernelGGL(xk_ci_gather, dim3(k1), dim3(64), 0, sj, ga); return hipSuccess; });
-    XkTriMultiArgs ta{dq, dp, dobs, Ltot, dgpf, dint + 16, nullptr, 0};
-    ci_stage[1].push_back([=]() { hipLaunchKernelGGL(xk_triangulate_multi, dim3(1), dim3(64), 0, sj, ta); return hipSuccess; });
-    // per-agent column-space rows, one workgroup per agent (:168-204)
-    XkFeatBatch *hb = h->h_batch + 8 * j, *db = h->d_batch + 8 * j;
-    int npmax = 0;
-    for (int i = 0; i < k1; ++i) {
-      hb[i].q = aq[i]; hb[i].p = ap[i]; hb[i].obs = aobs[i]; hb[i].P = aP[i];
-      hb[i].n_poses = anp[i]; hb[i].n_poses_max = N; hb[i].n = n; hb[i].L = aL[i]; hb[i].up_out = up + i * upsz;
-      npmax = std::max(npmax, anp[i]);
-    }
-    ci_stage[2].push_back([=]() { return hipMemcpyAsync(db, hb, sizeof(XkFeatBatch) * k1, hipMemcpyHostToDevice, sj); });
-    XkFeatArgs a;
-    memset(&a, 0, sizeof(a));
-    a.K = k1; a.var_img = var_img; a.chi95 = h->d_chi95; a.n = n; a.na = n - XK_CORE; a.n_poses = npmax; a.n_poses_max = N;
-    a.tile_rows = dint + 8; a.inlier = dint; a.gamma = dscal + 2; a.gpf = (double *)(dint + 192); a.gn_iters = dint + 24;
-    a.gpf_in = dgpf; a.batch = db;
-    ci_stage[3].push_back([=]() { hipLaunchKernelGGL(xk_msckf_feature, dim3(k1), dim3(XK_FEAT_THREADS), xk_feature_lds_bytes(npmax), sj, a); return hipSuccess; });
-    // null-space projection of the landmark and split into per-agent Jacobians (:207-223)
-    XkCiProjArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.k1 = k1; pa.res = dres;
-    for (int i = 0; i < k1; ++i) { pa.up[i] = up + i * upsz; pa.n[i] = n; pa.H[i] = Hs + (size_t)m * n * i; }
-    ci_stage[4].push_back([=]() { hipLaunchKernelGGL(xk_ci_project, dim3(k1), dim3(256), 0, sj, pa); return hipSuccess; });
-    // S_i = H_i P_i H_i^T for all agents, then the gate / CI combinations and gamma
-    XkCiHphArgs ha;
-    memset(&ha, 0, sizeof(ha));
-    ha.m = m; ha.S = Si;
-    for (int i = 0; i < k1; ++i) { ha.H[i] = pa.H[i]; ha.P[i] = aP[i]; ha.n[i] = n; }
-    const int nchunk = (n + XK_CI_CHUNK - 1) / XK_CI_CHUNK;
-    ci_stage[5].push_back([=]() { hipLaunchKernelGGL(xk_ci_hph, dim3(k1, nchunk), dim3(256), sizeof(double) * ((size_t)m * n + 24 * 33), sj, ha); return hipSuccess; });
-    // the two gate decisions (own chi-square test :180, joint test :243-250) come back per track: written by the kernel into
-    // pinned host memory, a marker behind them
-    // (searched: the gate words and the marker come from the last kernel of the searched chain instead)
-    XkCiCombineArgs ca{k1, m, Si, nchunk, w0, w_oth, var_img, dres, S1, S2, dscal,
-                       dint, h->h_ci_w + 16 + 4 * j, srch ? nullptr : reinterpret_cast<unsigned long long *>(h->h_ci_w + 16 + 4 * j + 2), ci_seq};
-    if (srch) {
-      ciwr_as.H[j] = Hs;
-      if (j == 0)
-        for (int i = 0; i < k1; ++i) ciwr_as.P[i] = aP[i];
-      ciwr_fin.Si[j] = Si; ciwr_fin.S_ci[j] = S2; ciwr_fin.own_inlier[j] = dint; ciwr_fin.gamma[j] = dscal;
-    }
-    ci_stage[6].push_back([=]() { hipLaunchKernelGGL(xk_ci_combine, dim3(1), dim3(512), 0, sj, ca); return hipSuccess; });
-    if (side && j > 0) {
-      hipEvent_t ej = h->ci_join[j];
-      hipStream_t s0 = h->stream;
-      ci_stage[7].push_back([=]() { hipError_t e = hipEventRecord(ej, sj); return e != hipSuccess ? e : hipStreamWaitEvent(s0, ej, 0); });
-    }
-    trk_L0[j] = aL[0];
-    trk_dof[j] = 2 * Ltot - 3;
-  }
-  for (auto &stage : ci_stage)
-    for (auto &issue : stage) CI_CHK(issue());
-  if (srch && n_tracks > 0) {
-    // The searched chain, on the engine's stream behind the join of the side streams (it needs every track's Jacobians): the
-    // information projections of all agents and tracks with ONE factorisation per agent, the search per track, the weighted S_ci.
-    XkCiwrAgents ag;
-    memset(&ag, 0, sizeof(ag));
-    ag.ld = ciwr_ld;
-    for (int i = 0; i < k1; ++i) { ag.Maug[i] = h->d_ciwr + (size_t)i * ciwr_agent; ag.X[i] = ag.Maug[i] + (size_t)n * ciwr_ld; }
-    const int ncols = n + n_tracks * m;
-    double st[XK_CIW_MAXK1];
-    const double *start = ciw_start_multi(ci_msckf_w, k, st);
-    ciwr_as.ag = ag; ciwr_as.n = n; ciwr_as.m = m; ciwr_as.k1 = k1; ciwr_as.nt = n_tracks;
-    ciwr_as.start = start ? ciwr_start : nullptr; ciwr_as.status = ciwr_status;
-    for (int i = 0; i < XK_CIW_MAXK1; ++i) ciwr_as.st[i] = (start && i < k1) ? st[i] : 0.0;
-    hipLaunchKernelGGL(xk_ciwr_assemble, dim3((unsigned)(((size_t)n * ncols + 255) / 256), k1), dim3(256), 0, h->stream, ciwr_as);
-    const int B = 16 * XK_CHOLW_MAXB;
-    for (int off = 0; off < n;) {
-      const int cb = std::min(B, n - off);
-      XkCiwrCholArgs d;
-      d.ag = ag; d.off = off; d.c = cb; d.ncols = ncols - off; d.status = ciwr_status;
-      xk_cholw_table((cb + 15) / 16, d.tab);
-      hipLaunchKernelGGL(xk_ciwr_chol, dim3((ncols - off - cb + 15) / 16, k1), dim3(64 * XK_CHOLW_WAVES), 0, h->stream, d);
-      off += cb;
-      if (off < n) {
-        XkCiwrSchurArgs sa{ag, off, cb, n - off, ncols - off};
-        hipLaunchKernelGGL(xk_ciwr_schur, dim3((ncols - off + 15) / 16, (n - off + 15) / 16, k1), dim3(64), 0, h->stream, sa);
-      }
-    }
-    XkCiwrXtxArgs xa{ag, n, m, ciwr_M};
-    hipLaunchKernelGGL(xk_ciwr_xtx, dim3(n_tracks, k1), dim3(256), 0, h->stream, xa);
-    // (no handle status word: a failing problem on a track the gates reject must not poison the handle)
-    XkCiwArgs wa{ciwr_M, (long)XK_CIW_MAXK1 * 576, 576, m, k1, start ? ciwr_start : nullptr, ciwr_w, ciwr_info, nullptr, 1};
-    hipLaunchKernelGGL(xk_ci_weights, dim3(n_tracks), dim3(XK_CIW_THREADS), 0, h->stream, wa);
-    ciwr_fin.nt = n_tracks; ciwr_fin.k1 = k1; ciwr_fin.m = m; ciwr_fin.nchunk = (n + XK_CI_CHUNK - 1) / XK_CI_CHUNK;
-    ciwr_fin.var_img = var_img; ciwr_fin.w = ciwr_w; ciwr_fin.info = ciwr_info; ciwr_fin.status = ciwr_status;
-    ciwr_fin.winv = ciwr_winv; ciwr_fin.host = h->h_ci_w; ciwr_fin.seq = ci_seq;
-    hipLaunchKernelGGL(xk_ciwr_finish, dim3(1), dim3(512), 0, h->stream, ciwr_fin);
-    CI_CHK(hipGetLastError());
-  }
-#undef CI_CHK
-  if (n_tracks > 0) {
-    // wait for the markers of all tracks (XK_SPIN_DONE=0, or a marker that does not come within ~1 s: the runtime's signal)
-    static const int spin_env = env_int("XK_SPIN_DONE", 1);
-    bool seen = spin_env != 0;
-    for (int j = 0; j < n_tracks && seen; ++j) {
-      const unsigned long long *mk = reinterpret_cast<const unsigned long long *>(h->h_ci_w + 16 + 4 * j + 2);
-      seen = false;
-      for (long spins = 0; spins < 40000000L && !(seen = (__atomic_load_n(mk, __ATOMIC_ACQUIRE) == ci_seq)); ++spins) {
-        if ((spins & 255) == 255 && __atomic_load_n(&h->d_status[1], __ATOMIC_RELAXED) != 0) break;
-        __builtin_ia32_pause();
-      }
-    }
-    if (!seen) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      for (int j = 1; j < n_tracks && side; ++j) HIPCHK(h, hipStreamSynchronize(h->ci_stream[j]));
-    }
-  }
-  int last_fused = -1;
-  for (int j = 0; j < n_tracks; ++j)
-    if (h->h_ci_w[16 + 4 * j] != 0.0 && h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]]) last_fused = j;
-  if (srch && n_tracks > 0) {
-    // what the searched chain left in pinned memory with the gate words.  No silent fallback: a covariance that is not positive
-    // definite fails the round whatever the gates say (as the host route, which checks before the gate decision), and so does a
-    // failed search on a track that passes both gates.  Nothing has been applied at this point.
-    const int *pst = reinterpret_cast<const int *>(h->h_ci_w + 120), *pinfo = reinterpret_cast<const int *>(h->h_ci_w + 112);
-    for (int i = 0; i < k1; ++i)
-      if (pst[i] != 0) {
-        const int rank = i == 0 ? self_rank : (i - 1 < self_rank ? i - 1 : i);
-        char msg[128];
-        snprintf(msg, sizeof(msg), "CI weight search: the covariance of the agent of rank %d is not positive definite", rank);
-        return fail(h, XK_ESINGULAR, msg);
-      }
-    for (int j = 0; j < n_tracks; ++j) {
-      const bool pass = h->h_ci_w[16 + 4 * j] != 0.0 && h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]];
-      if (pass && pinfo[2 * j + 1] != 0)
-        return fail(h, XK_ESINGULAR, pinfo[2 * j] >= XK_CIW_MAXIT ? "CI weight search: no convergence within 50 Newton steps"
-                                                                   : "CI weight search: sum w_i M_i is not positive definite");
-    }
-    h->ci_round_tracks = n_tracks;
-    for (int j = 0; j < n_tracks; ++j) {
-      const bool pass = h->h_ci_w[16 + 4 * j] != 0.0 && h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]];
-      for (int i = 0; i < 8; ++i) h->ci_round_w[j][i] = (pass && i < k1) ? h->h_ci_w[48 + 8 * j + i] : 0.0;
-      h->ci_round_k1[j] = pass ? k1 : 0;
-      h->ci_round_iters[j] = pass ? pinfo[2 * j] : 0;
-    }
-    if (last_fused >= 0) {
-      memcpy(h->ci_last_w, h->ci_round_w[last_fused], sizeof(h->ci_last_w));
-      h->ci_last_k1 = k1;
-      h->ci_last_iters = h->ci_round_iters[last_fused];
-    }
-  }
-  static const int spin_done = env_int("XK_SPIN_DONE", 1);
-  unsigned long long *done = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2);
-  unsigned long long wait_seq = 0;
-  for (int j = 0; j < n_tracks; ++j) {
-    if (h->h_ci_w[16 + 4 * j] == 0.0 || !(h->h_ci_w[16 + 4 * j + 1] < XK_CHI2_095[trk_dof[j]])) continue;
-    const CiWs w = ci_ws(j);
-    double *Hs = w.Hs, *S2 = w.S2, *dres = w.dres, *dscal = w.dscal;
-    int *dint = w.dint;
-    // P_j: diagonal 3x3 blocks of the observed poses scaled by 1/w0 (:256-267), then applyCI (updater.cpp:144-161)
-    const int L = trk_L0[j];
-    // (the blocks are those of the last L window poses: the kernel works their columns out itself -- no staging copies)
-    // (searched: the factor is the device word 1 / w_0 the searched chain left for this track)
-    XkScaleArgs sc{h->d_P, h->d_tmpP, n, 2 * L, nullptr, nullptr, 1, h->n_poses - L, L, N, 1.0 / w0, srch ? ciwr_winv + j : nullptr};
-    (void)dint; (void)dscal;
-    hipLaunchKernelGGL(xk_scale_blocks, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, sc);
-    UpdateSpec u;
-    memset(&u, 0, sizeof(u));
-    u.T = Hs; u.str = 1; u.stc = m;      // H of agent 0 (self)
-    u.c = m; u.kdim = n; u.col0 = 0;
-    u.z = dres; u.sz = 1;
-    u.S = S2; u.ssr = 1; u.ssc = m;
-    u.Pin = h->d_tmpP; u.Pout = h->d_Pout; u.ct = nullptr; u.cov_update = 1;   // every entry starts from the same prior
-    if (j == last_fused && !corrections && spin_done) { u.done_flag = done; u.done_seq = wait_seq = ++h->done_seq; }   // the round's last launch marks its end
-    int rc = launch_update(h, u);
-    if (rc != XK_OK) return rc;
-    if (corrections) HIPCHK(h, hipMemcpyAsync(corrections + (size_t)fused * n, h->d_corr, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    ++fused;                                       // (the next track's gate decision, or read_status below, waits)
-  }
-  if (fused) {
-    bool seen = false;
-    if (wait_seq) {   // (as xk_apply_update: the marker is the last store of the last kernel; a status word ends the wait early)
-      for (long spins = 0; spins < 40000000L && !(seen = (__atomic_load_n(done, __ATOMIC_ACQUIRE) == wait_seq)); ++spins) {
-        if ((spins & 255) == 255 && __atomic_load_n(&h->d_status[1], __ATOMIC_RELAXED) != 0) break;
-        __builtin_ia32_pause();
-      }
-      if (seen) h->done_seen = wait_seq;
-    }
-    int rc;
-    if (seen) { stage_stream_idle(h); rc = eval_status(h, h->d_status[0], h->d_status[1], false); }
-    else rc = read_status(h);
-    if (rc != XK_OK) return rc;
-    std::swap(h->d_P, h->d_Pout);   // applyCI overwrites P: the last fused entry is the resident covariance
-    h->have_rows = h->have_R = false;
-  }
-  *n_fused = fused;
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// inter-agent payload
-// ---------------------------------------------------------------------------
-extern "C" long xk_payload_doubles(int N, int M) {
-  const long n = XK_CORE + 6L * N + 3L * M;
-  return 8 + 16 + 3L * N + 4L * N + 3L * M + M + n * n;
-}
-
-__global__ void xk_pack_small(const double *hdr_dyn /*24*/, const double *p, const double *q, int n_poses,
-                              const double *feat, const int *anchors, int Mcur, int N, int M, double *out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int o_pos = 24, o_att = o_pos + 3 * N, o_feat = o_att + 4 * N, o_anc = o_feat + 3 * M, o_cov = o_anc + M;
-  if (i >= o_cov) return;
-  double v = 0.0;
-  if (i < 24) v = hdr_dyn[i];
-  else if (i < o_att) { const int t = i - o_pos; v = (t < 3 * n_poses) ? p[t] : 0.0; }
-  else if (i < o_feat) { const int t = i - o_att; v = (t < 4 * n_poses) ? q[t] : 0.0; }
-  else if (i < o_anc) { const int t = i - o_feat; v = (t < 3 * Mcur) ? feat[t] : 0.0; }
-  else { const int t = i - o_anc; v = (t < Mcur) ? (double)anchors[t] : -1.0; }
-  out[i] = v;
-}
-
-extern "C" int xk_pack_payload(xk_handle *h, double agent_id, double timestamp, const double *dyn16,
-                               double *d_dst, double **d_payload) {
-  if (!h || !dyn16) return XK_EINVAL;
-  double *dst = d_dst ? d_dst : h->d_payload;
-  HIPCHK(h, hipSetDevice(h->device));
-  { int rcw = flush_window(h); if (rcw != XK_OK) return rcw; }
-  double *hd = h->h_pin;
-  hd[0] = agent_id; hd[1] = timestamp; hd[2] = h->N; hd[3] = h->Mmax; hd[4] = h->n; hd[5] = h->n_poses;
-  hd[6] = 0.0; hd[7] = 0.0;
-  for (int i = 0; i < 16; ++i) hd[8 + i] = dyn16[i];
-  HIPCHK(h, hipMemcpyAsync(h->d_ci, hd, sizeof(double) * 24, hipMemcpyHostToDevice, h->stream));
-  const int small = 24 + 7 * h->N + 4 * h->Mmax;
-  hipLaunchKernelGGL(xk_pack_small, dim3((small + 255) / 256), dim3(256), 0, h->stream, h->d_ci, h->d_p, h->d_q,
-                     h->n_poses, h->d_feat, h->d_anchor, h->M, h->N, h->Mmax, dst);
-  HIPCHK(h, hipMemcpyAsync(dst + small, h->d_P, sizeof(double) * (size_t)h->n * h->n,
-                           hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (d_payload) *d_payload = dst;
   return XK_OK;
 }
 

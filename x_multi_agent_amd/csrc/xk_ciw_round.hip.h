@@ -23,6 +23,20 @@
 #define XK_CIWR_MAXT 8                                   // shared tracks of a round
 #define XK_CIWR_MAXRHS (XK_CIW_MAXM * XK_CIWR_MAXT)      // 168 right-hand sides
 
+// The round's pinned words (xk_handle::h_ci_w, XK_CIP_DOUBLES doubles of host memory the kernels write and the host polls), defined
+// here once for xk_ciwr_finish and for the host (xk_ci_api.hip.h: xk_ci_combine's host_gate / host_marker, the waits, the readers).
+//   gate words of track j   [0] the own chi-square verdict, [1] the joint gamma, [2] the marker (unsigned long long): xk_ci_combine
+//                           with fixed weights, xk_ciwr_finish with searched ones
+//   weights of track j      eight doubles, searched rounds only
+//   info words              ints, per track [2 j] Newton steps, [2 j + 1] the solver's failure word
+//   status words            ints, per agent the pivot status of its factorisation
+#define XK_CIP_DOUBLES 128
+__host__ __device__ __forceinline__ double *xk_cip_gate(double *w, int j) { return w + 16 + 4 * j; }
+__host__ __device__ __forceinline__ unsigned long long *xk_cip_marker(double *w, int j) { return reinterpret_cast<unsigned long long *>(xk_cip_gate(w, j) + 2); }
+__host__ __device__ __forceinline__ double *xk_cip_weights(double *w, int j) { return w + 48 + 8 * j; }
+__host__ __device__ __forceinline__ int *xk_cip_info(double *w) { return reinterpret_cast<int *>(w + 112); }
+__host__ __device__ __forceinline__ int *xk_cip_status(double *w) { return reinterpret_cast<int *>(w + 120); }
+
 // per-agent workspace: Maug_i and X_i, n x ld row-major each, ld = n + 168
 struct XkCiwrAgents {
   double *Maug[XK_CIW_MAXK1], *X[XK_CIW_MAXK1];
@@ -253,7 +267,7 @@ struct XkCiwrFinishArgs {
   const int *info;                      // [track][2]
   const int *status;                    // [8] per-agent pivot status
   double *winv;                         // out [track]: 1 / w_0
-  double *host;                         // pinned: the layout of h_ci_w (xk_api.hip)
+  double *host;                         // pinned: h_ci_w, the XK_CIP words above
   unsigned long long seq;
 };
 __global__ __launch_bounds__(512) void xk_ciwr_finish(XkCiwrFinishArgs a) {
@@ -277,16 +291,14 @@ __global__ __launch_bounds__(512) void xk_ciwr_finish(XkCiwrFinishArgs a) {
     }
   }
   if (t < a.nt) a.winv[t] = 1.0 / a.w[8 * t];
-  // pinned: [16 + 4 j] own verdict, [+1] joint gamma; [48 + 8 j ..] weights; [112 + j] the two info words; [120 ..] pivot status
-  if (t < 8 * a.nt) __hip_atomic_store(a.host + 48 + t, a.w[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (t < 2 * a.nt) __hip_atomic_store(reinterpret_cast<int *>(a.host + 112) + t, a.info[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (t < 8) __hip_atomic_store(reinterpret_cast<int *>(a.host + 120) + t, a.status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (t < 8 * a.nt) __hip_atomic_store(xk_cip_weights(a.host, 0) + t, a.w[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (t < 2 * a.nt) __hip_atomic_store(xk_cip_info(a.host) + t, a.info[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (t < 8) __hip_atomic_store(xk_cip_status(a.host) + t, a.status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (t < a.nt) {
-    __hip_atomic_store(a.host + 16 + 4 * t, (double)*a.own_inlier[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(a.host + 16 + 4 * t + 1, *a.gamma[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(xk_cip_gate(a.host, t), (double)*a.own_inlier[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(xk_cip_gate(a.host, t) + 1, *a.gamma[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   __threadfence_system();
   __syncthreads();
-  if (t < a.nt)
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(a.host + 16 + 4 * t + 2), a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (t < a.nt) __hip_atomic_store(xk_cip_marker(a.host, t), a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }

@@ -135,14 +135,14 @@ struct xk_handle {
   // CI / payload
   double *d_payload;
   double *d_ci;  // scratch for the CI kernels
-  double *d_ciws;          // workspace of the device-resident CI round (lazily allocated)
+  double *d_ciws;          // workspace of the device-resident CI round (lazily allocated): eight regions of ci_track_ws (xk_ci_api.hip.h)
   // CI weight search (xk_ciw.hip.h): option "ci_weight_search"; d_ciw = [8 weights | 8 start | 2 info words | 8 M_i | 8 H_i P_i H_i^T]
   int opt_ci_search;
   double *d_ciw;
   double ci_last_w[8];     // what xk_ci_last_weights hands out: the weights of the last searched entry,
   int ci_last_k1, ci_last_iters;   // how many there were and the Newton steps they took
   // searched device round (xk_ciw_round.hip.h), allocated by the first searched round:
-  // d_ciwr = per agent [Maug | X] (n x (n + 168) each), then M [8 tracks][8 agents][576], start [8][8], weights [8][8], 1/w0 [8], info [8][2], status [8]
+  // d_ciwr = per agent [Maug | X] (n x (n + 168) each), then the solver's operands and results: ciwr_layout (xk_ci_api.hip.h)
   double *d_ciwr;
   int ci_round_tracks;             // shared tracks of the last searched round (0 before the first one)
   double ci_round_w[8][8];         // what xk_ci_round_weights hands out
@@ -151,8 +151,7 @@ struct xk_handle {
   hipEvent_t ci_fork, ci_join[8];   // next to track 0 on the engine's stream (forked and joined with events)
   XkFeatBatch *d_batch;    // per-agent descriptors of the batched feature launch, [8 tracks][8 agents]
   XkFeatBatch *h_batch;    // pinned staging of the same
-  int *h_ci_cols;          // pinned: per shared track, the block columns of xk_scale_blocks [8][128]
-  double *h_ci_w;          // pinned: per shared track, 1/w0 [8]; the gate words; from [48] on what a searched round reports
+  double *h_ci_w;          // pinned: what the round's kernels report to the host (the XK_CIP_* words of xk_ciw_round.hip.h)
   int *h_trk_off;          // host copy of the staged track offsets
   // MSCKF-SLAM tracks (features being initialised this frame)
   int anchor_max;          // largest staged SLAM anchor index (rechecked against the staged window at build time)
