@@ -32,8 +32,20 @@ class TrackedFeature : public Feature {
   double getYDist() const { return y_dist_; }
   void setXDist(double x_dist) { x_dist_ = x_dist; }
   void setYDist(double y_dist) { y_dist_ = y_dist; }
+  // what the detection and the tile bookkeeping attach (feature.h: fast_score_, pyramid_level_, tile_row_, tile_col_).  They
+  // live here, not in Feature: the update path copies whole tracks as pairs of doubles.
+  double getFastScore() const { return fast_score_; }
+  void setFastScore(double fast_score) { fast_score_ = fast_score; }
+  unsigned int getPyramidLevel() const { return pyramid_level_; }
+  void setPyramidLevel(unsigned int pyramid_level) { pyramid_level_ = pyramid_level; }
+  int getTileRow() const { return tile_row_; }
+  int getTileCol() const { return tile_col_; }
+  void setTile(int row, int col) { tile_row_ = row; tile_col_ = col; }
  private:
   double x_dist_ = 0, y_dist_ = 0;
+  double fast_score_ = 0;
+  unsigned int pyramid_level_ = 0;
+  int tile_row_ = 0, tile_col_ = 0;
 };
 using FeatureList = std::vector<TrackedFeature>;      // the tracker's lists (types.h:49)
 struct Match { TrackedFeature previous, current; };   // types.h:39-42, :57

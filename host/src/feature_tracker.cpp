@@ -1,6 +1,8 @@
-// Mirror of Tracker::featureTracking, src/x/vision/tracker.cpp:623-690; the arithmetic runs in libxk.so.
+// Mirror of Tracker::featureTracking and Tracker::featureDetection, src/x/vision/tracker.cpp:623-690 and :390-590; the arithmetic
+// runs in libxk.so.  The tile bookkeeping (tiled_image.cpp:139-158, tracker.cpp:592-620) is host code, as in the reference.
 #include "x/vision/feature_tracker.h"
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -12,11 +14,12 @@ static void check(xk_handle *h, int rc, const char *what) {
 
 FeatureTracker::FeatureTracker(xk_handle *xk, const Camera &camera, int max_features, int win_w, int win_h, int max_level, int max_iter,
                                double eps, double min_eig_thr)
-    : xk_(xk) {
+    : xk_(xk), max_features_(max_features) {
   if (max_features < 1) throw std::runtime_error("FeatureTracker: max_features < 1");
   const size_t m = (size_t)max_features;                      // (the staging first: nothing below can throw once the handle exists)
   prev_in_.resize(2 * m); cur_.resize(2 * m); min_eig_.resize(m); kept_prev_.resize(2 * m); kept_cur_.resize(2 * m);
   status_.resize(m); keep_.resize(m);
+  old_in_.resize(2 * m); det_xy_.resize(2 * m); det_score_.resize(m);
   check(xk_, xk_trk_create(xk_, max_features, camera.getFx(), camera.getFy(), camera.getCx(), camera.getCy(), camera.getS(), &trk_),
         "xk_trk_create");
   const int rc = xk_trk_klt_setup(trk_, (int)camera.getWidth(), (int)camera.getHeight(), win_w, win_h, max_level, max_iter, eps, min_eig_thr);
@@ -45,7 +48,82 @@ std::pair<FeatureList, FeatureList> FeatureTracker::track(const FeatureList &pre
   for (int k = 0; k < n_kept; ++k) {
     out.first.push_back(previous[(size_t)keep_[k]]);
     out.second.emplace_back(0.0, 0.0, kept_cur_[2 * k], kept_cur_[2 * k + 1]);
+    out.second.back().setPyramidLevel(out.first.back().getPyramidLevel());   // :670-678: level and score of the previous feature
+    out.second.back().setFastScore(out.first.back().getFastScore());
   }
   if (kept_indices) kept_indices->assign(keep_.begin(), keep_.begin() + n_kept);
   return out;
+}
+
+void FeatureTracker::setDetection(int threshold, bool non_max_supp, int block_half_length, int margin, int max_candidates) {
+  check(xk_, xk_trk_detect_setup(trk_, threshold, non_max_supp ? 1 : 0, block_half_length, margin, max_candidates), "xk_trk_detect_setup");
+}
+
+FeatureList FeatureTracker::detect(const FeatureList &old_features, bool current_image) {
+  const size_t n_old = old_features.size();
+  if (n_old > (size_t)max_features_) throw std::runtime_error("FeatureTracker::detect: more old features than max_features");
+  for (size_t i = 0; i < n_old; ++i) { old_in_[2 * i] = old_features[i].getXDist(); old_in_[2 * i + 1] = old_features[i].getYDist(); }
+  int n_found = 0, n_candidates = 0;
+  check(xk_, xk_trk_detect(trk_, current_image ? 1 : 0, n_old ? old_in_.data() : nullptr, (int)n_old, det_xy_.data(), det_score_.data(),
+                           &n_found, &n_candidates),
+        "xk_trk_detect");
+  FeatureList out;
+  out.reserve((size_t)n_found);
+  for (int k = 0; k < n_found; ++k) {                          // Feature(..., pt.x * scale_factor, pt.y * scale_factor, level, response), :464-467
+    out.emplace_back(0.0, 0.0, (double)det_xy_[2 * k], (double)det_xy_[2 * k + 1]);
+    out.back().setPyramidLevel(0);
+    out.back().setFastScore((double)det_score_[k]);
+  }
+  return out;
+}
+
+TileGrid::TileGrid(unsigned int width, unsigned int height, unsigned int n_tiles_h, unsigned int n_tiles_w, unsigned int max_feat_per_tile)
+    : rows_(height), n_tiles_h_(n_tiles_h), n_tiles_w_(n_tiles_w), max_feat_per_tile_(max_feat_per_tile) {
+  if (n_tiles_h < 1 || n_tiles_w < 1) throw std::runtime_error("TileGrid: no tiles");
+  tile_height_ = (double)height / n_tiles_h;                   // tiled_image.cpp:104-105
+  tile_width_ = (double)width / n_tiles_w;
+  tiles_.assign((size_t)n_tiles_h * n_tiles_w, 0u);
+}
+
+void TileGrid::setTileForFeature(TrackedFeature &feature) const {
+  double c = feature.getXDist() - tile_width_ - 0.5;           // tiled_image.cpp:141-146
+  int col = 0;
+  while (c > 0) {
+    col += 1;
+    c -= tile_width_;
+  }
+  double r = rows_ - feature.getYDist() - 0.5;                 // :149-154
+  int row = static_cast<int>(n_tiles_h_) - 1;
+  while (r > tile_height_) {
+    row -= 1;
+    r -= tile_height_;
+  }
+  feature.setTile(row, col);
+}
+
+void TileGrid::resetFeatureCounts() { std::fill(tiles_.begin(), tiles_.end(), 0u); }
+
+void TileGrid::incrementFeatureCountAtTile(int row, int col) {
+  if (row >= 0 && row < (int)n_tiles_h_ && col >= 0 && col < (int)n_tiles_w_) tiles_[(size_t)row * n_tiles_w_ + col] += 1;
+}
+
+unsigned int TileGrid::getFeatureCountAtTile(int row, int col) const {
+  return (row >= 0 && row < (int)n_tiles_h_ && col >= 0 && col < (int)n_tiles_w_) ? tiles_[(size_t)row * n_tiles_w_ + col] : 0u;
+}
+
+void FeatureTracker::removeOverflow(TileGrid &grid, FeatureList &features1, FeatureList &features2) {
+  if (features1.size() != features2.size()) throw std::runtime_error("FeatureTracker::removeOverflow: lists differ in length");
+  grid.resetFeatureCounts();
+  for (auto i = features2.size(); i >= 1; i--) {               // tracker.cpp:598-606
+    grid.setTileForFeature(features1[i - 1]);
+    grid.setTileForFeature(features2[i - 1]);
+    grid.incrementFeatureCountAtTile(features2[i - 1].getTileRow(), features2[i - 1].getTileCol());
+  }
+  for (int i = (int)features2.size() - 1; i >= 1; i--) {       // :610-619
+    const unsigned int count = grid.getFeatureCountAtTile(features2[i - 1].getTileRow(), features2[i - 1].getTileCol());
+    if (count > grid.getMaxFeatPerTile()) {
+      features1.erase(features1.begin() + i - 1);
+      features2.erase(features2.begin() + i - 1);
+    }
+  }
 }

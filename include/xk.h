@@ -466,6 +466,52 @@ int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_xy, unsigne
  * above levels, an image that has not been pushed. */
 int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short *dIx, short *dIy, int *w, int *h);
 
+/* ---- detection of the features that are tracked (Tracker::featureDetection, tracker.cpp:390-590) -----------------
+ * On the first frame, and again whenever too few features survive (tracker.cpp:160-167, :204-228), the reference runs
+ * cv::FAST(img, keypoints, fast_detection_delta_, non_max_supp_) (:441-448), keeps the keypoints inside the border
+ * (isFeatureInsideBorder, :536-552), sorts them by score (:483-486) and appends, best first, those that do not lie in
+ * the neighbourhood of an old feature or of one appended before (computeNeighborhoodMask :494-534,
+ * appendNonNeighborFeatures :564-590).  The same xk_trk does that on the device, on level 0 of an image slot that
+ * xk_trk_push_image filled.  The algorithm is this project's statement of those calls; every quantity is an
+ * integer and the result is defined bit for bit:
+ *   score      s(x, y) = max over the 16 arcs of 9 contiguous circle pixels of the arc's smallest I(circle) - I(x, y), and
+ *              of the same with the sign turned, - 1 (OpenCV's cornerScore); a corner has s >= threshold; 3 <= x < W - 3,
+ *              3 <= y < H - 3
+ *   keypoint   non_max_supp: the corner's s is strictly greater than s at its eight neighbours (0 where no corner)
+ *   candidate  margin <= x <= W - margin - 1, margin <= y <= H - margin - 1
+ *   order      ascending key ((255 - s) << 24) | (y W + x): score descending, raster order within a score (std::sort
+ *              leaves that open)
+ *   selection  in that order a candidate is accepted iff no old feature (round half away from zero; a non-finite one
+ *              blocks nothing) and no candidate accepted before lies within Chebyshev distance block_half_length of it:
+ *              the painted mask with every box clipped to the image, defined also where the reference's unclipped
+ *              cv::Rect would assert.
+ * Level 0 only (pyramid_depth_ is 1), no descriptors, no photometric intensity. */
+
+/* The parameters Tracker holds (tracker.h:245-255: fast_detection_delta_ 9, non_max_supp_ true, block_half_length_ 20,
+ * margin_ 20) and max_candidates (1...32768), the most candidates one image may have.  Called after xk_trk_klt_setup, whose
+ * image size it takes; allocates the score image, the key list, the blocked mask and the pinned staging of the result.
+ * XK_EINVAL: before xk_trk_klt_setup, threshold outside 1...254, non_max_supp not 0 or 1, block_half_length or margin
+ * outside 0...4096, max_candidates outside 1...32768.  A call that fails leaves an earlier detection setup as it was.  A
+ * later xk_trk_klt_setup that succeeds DROPS the detection setup with the images: call this again after it. */
+int xk_trk_detect_setup(xk_trk *t, int threshold, int non_max_supp, int block_half_length, int margin, int max_candidates);
+
+/* Tracker::featureDetection (tracker.cpp:390-590) on the previous (which = 0) or the current (1) image, as in
+ * xk_trk_klt_level -- the reference's re-detection names previous_img_ (:214): old_xy HOST [n_old][2] fp64, the old
+ * features' distorted pixels (may be NULL when n_old = 0) -> xy HOST [max_matches][2] (the first *n_found rows: the accepted
+ * pixels x, y in ascending key), score HOST [max_matches] (their s), *n_found, *n_candidates (candidates before the
+ * selection).  One copy in, three launches, one copy out, one synchronisation.  Every output is required.
+ * XK_EINVAL: null outputs, n_old < 0, which not 0 or 1, no detection setup, a slot that has not been pushed.
+ * XK_ECAPACITY: n_old > max_matches (both counts 0); more than max_candidates candidates (*n_candidates is the true
+ * count, *n_found = 0: nothing was selected); more than max_matches accepted (both counts true).  The lists are then
+ * untouched.  Nothing found: XK_OK with *n_found = 0. */
+int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_old, int *xy, int *score, int *n_found, int *n_candidates);
+
+/* What the last xk_trk_detect left on the device: scores HOST [height][width] uint8, the score image (s at corners, 0
+ * elsewhere -- before non-maximum suppression and the border test); keys HOST [max_candidates] (the first *n_candidates
+ * entries: the candidates' keys, ascending; not written after a detection that overflowed max_candidates).  Any output
+ * may be NULL.  An inspection path, not part of a frame: straight copies.  XK_EINVAL before a detection. */
+int xk_trk_detect_stage(xk_trk *t, unsigned char *scores, unsigned int *keys, int *n_candidates);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and

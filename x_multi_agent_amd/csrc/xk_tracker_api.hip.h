@@ -1,9 +1,25 @@
 // xk_tracker_api.hip.h -- host side of the tracker's front end (xk_trk_*): the fundamental-matrix RANSAC filter of the matches
 // (tracker.cpp:233-293, camera.cpp:62-87; xk_fundamental.hip.h) and the pyramidal Lucas-Kanade tracking in front of it
-// (tracker.cpp:623-690; xk_klt.hip.h).  Part of xk_api.hip's translation unit, included at its end.
+// (tracker.cpp:623-690; xk_klt.hip.h), and the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h).
+// Part of xk_api.hip's translation unit, included at its end.
 #pragma once
+#include "xk_fast.hip.h"
 #include "xk_fundamental.hip.h"
 #include "xk_klt.hip.h"
+
+// The detection setup of an image size (xk_trk_detect_setup): it belongs to the xk_klt whose level-0 images it scans.
+struct xk_det {
+  int threshold, nms, b, margin, max_candidates;
+  int key_cap, wpr;
+  size_t lds_bytes;           // of xk_fast_select: the keys, and the blocked mask behind them when both fit
+  unsigned char *d_blk;       // S | keys | counter | old features | result block | blocked mask (when it does not fit the LDS)
+  unsigned char *S;
+  unsigned int *keys, *mask_g;
+  int *count, *res;
+  double *old_xy;
+  unsigned char *h_blk;       // pinned: old features in (2 max_matches doubles), then the result block out
+  int n_cand;                 // candidates of the last detection (-1: none yet)
+};
 
 struct xk_klt {
   int width, height, win_w, win_h, max_level, max_iter, levels;
@@ -16,6 +32,7 @@ struct xk_klt {
   unsigned char *h_img;       // pinned: one image at level 0's pitch
   unsigned char *h_blk;       // pinned: previous points in, then the result block out
   hipEvent_t img_copied;      // the upload out of h_img: the next push waits for it before it refills the staging
+  struct xk_det *det;         // xk_trk_detect_setup; NULL before.  It goes with this setup
 };
 
 struct xk_trk {
@@ -46,7 +63,15 @@ static int kept_pairs_out(xk_handle *h, const XkKeptPairs &k, const unsigned cha
   return XK_OK;
 }
 
+static void det_release(xk_det *d) {
+  if (!d) return;
+  hipFree(d->d_blk);
+  if (d->h_blk) hipHostFree(d->h_blk);
+  free(d);
+}
+
 static void klt_release(xk_klt *k) {
+  det_release(k->det);
   hipFree(k->d_blk);
   if (k->h_img) hipHostFree(k->h_img);
   if (k->h_blk) hipHostFree(k->h_blk);
@@ -382,6 +407,130 @@ extern "C" int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *
   if (img) HIPCHK(h, hipMemcpy2DAsync(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
   if (dIx) HIPCHK(h, hipMemcpy2DAsync(dIx, 2 * (size_t)L.w, L.dx, 2 * (size_t)L.pitch, 2 * (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
   if (dIy) HIPCHK(h, hipMemcpy2DAsync(dIy, 2 * (size_t)L.w, L.dy, 2 * (size_t)L.pitch, 2 * (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// FAST detection and neighbourhood selection of new features (tracker.cpp:390-590), xk_fast.hip.h
+// ---------------------------------------------------------------------------
+static size_t det_res_bytes(int n) { return sizeof(int) * (4 + 3 * (size_t)n); }
+
+/* The parameters of Tracker::featureDetection as Tracker holds them (tracker.h:245-255) and the device buffers of one detection */
+extern "C" int xk_trk_detect_setup(xk_trk *t, int threshold, int non_max_supp, int block_half_length, int margin, int max_candidates) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_detect_setup: before xk_trk_klt_setup");
+  if (threshold < 1 || threshold > 254) return fail(h, XK_EINVAL, "xk_trk_detect_setup: threshold outside 1...254");
+  if (non_max_supp < 0 || non_max_supp > 1) return fail(h, XK_EINVAL, "xk_trk_detect_setup: non_max_supp is 0 or 1");
+  if (block_half_length < 0 || block_half_length > 4096) return fail(h, XK_EINVAL, "xk_trk_detect_setup: block_half_length outside 0...4096");
+  if (margin < 0 || margin > 4096) return fail(h, XK_EINVAL, "xk_trk_detect_setup: margin outside 0...4096");
+  if (max_candidates < 1 || max_candidates > XK_FAST_MAX_CAND) return fail(h, XK_EINVAL, "xk_trk_detect_setup: max_candidates outside 1...32768");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_det *d = (xk_det *)calloc(1, sizeof(xk_det));      // (built whole before the old one goes, as in xk_trk_klt_setup)
+  if (!d) return XK_ENOMEM;
+  d->threshold = threshold; d->nms = non_max_supp; d->b = block_half_length; d->margin = margin; d->max_candidates = max_candidates;
+  d->n_cand = -1;
+  d->key_cap = 64;
+  while (d->key_cap < max_candidates) d->key_cap <<= 1;
+  d->wpr = (k->width + 31) / 32;
+  const size_t key_lds = sizeof(unsigned int) * (size_t)d->key_cap, mask_bytes = sizeof(unsigned int) * (size_t)d->wpr * k->height;
+  const bool mask_in_lds = key_lds + mask_bytes <= XK_FAST_LDS_MAX;
+  d->lds_bytes = key_lds + (mask_in_lds ? mask_bytes : 0);
+  const size_t pitch0 = (size_t)round_up(k->width, 16);
+  const size_t s_bytes = pitch0 * k->height;                                     // (a multiple of 16, as every offset below)
+  const size_t keys_bytes = sizeof(unsigned int) * (size_t)round_up(max_candidates, 4);
+  const size_t old_bytes = sizeof(double) * 2 * (size_t)t->max_matches;
+  const size_t res_bytes = (det_res_bytes(t->max_matches) + 15) / 16 * 16;
+  const size_t dev_bytes = s_bytes + keys_bytes + 16 + old_bytes + res_bytes + (mask_in_lds ? 0 : mask_bytes);
+  void *dv = nullptr, *hb = nullptr;
+  if (hipMalloc(&dv, dev_bytes) != hipSuccess || hipHostMalloc(&hb, old_bytes + res_bytes) != hipSuccess ||
+      hipMemsetAsync(dv, 0, dev_bytes, h->stream) != hipSuccess ||
+      hipFuncSetAttribute((const void *)xk_fast_select, hipFuncAttributeMaxDynamicSharedMemorySize, XK_FAST_LDS_MAX) != hipSuccess) {
+    d->d_blk = (unsigned char *)dv; d->h_blk = (unsigned char *)hb;
+    hipStreamSynchronize(h->stream);
+    det_release(d);
+    return fail(h, XK_ENOMEM, "xk_trk_detect_setup: allocation failed");
+  }
+  d->d_blk = (unsigned char *)dv; d->h_blk = (unsigned char *)hb;
+  unsigned char *p = d->d_blk;
+  d->S = p; p += s_bytes;
+  d->keys = (unsigned int *)p; p += keys_bytes;
+  d->count = (int *)p; p += 16;
+  d->old_xy = (double *)p; p += old_bytes;
+  d->res = (int *)p; p += res_bytes;
+  d->mask_g = mask_in_lds ? nullptr : (unsigned int *)p;
+  if (k->det) {
+    hipStreamSynchronize(h->stream);
+    det_release(k->det);
+  }
+  k->det = d;
+  return XK_OK;
+}
+
+/* Tracker::featureDetection (tracker.cpp:390-590) on level 0 of the previous (which = 0) or the current (1) image */
+extern "C" int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_old, int *xy, int *score, int *n_found, int *n_candidates) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_det *d = k ? k->det : nullptr;
+  if (!d) return fail(h, XK_EINVAL, "xk_trk_detect: before xk_trk_detect_setup");
+  if (!xy || !score || !n_found || !n_candidates || n_old < 0 || (n_old > 0 && !old_xy))
+    return fail(h, XK_EINVAL, "xk_trk_detect: null argument or negative n_old");
+  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_detect: which is 0 or 1");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_detect: that image has not been pushed");
+  *n_found = 0; *n_candidates = 0;
+  if (n_old > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_detect: more old features than max_matches");
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkKltLevel &L = k->slot[which == 1 ? k->cur : k->cur ^ 1].lv[0];
+  XkFastArgs a{};
+  a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
+  a.S = d->S; a.keys = d->keys; a.count = d->count; a.mask_g = d->mask_g; a.key_cap = d->key_cap; a.wpr = d->wpr;
+  a.old_xy = d->old_xy; a.n_old = n_old;
+  a.threshold = d->threshold; a.nms = d->nms; a.b = d->b; a.margin = d->margin; a.max_candidates = d->max_candidates;
+  a.max_matches = t->max_matches;
+  a.res = d->res;
+  d->n_cand = -1;
+  if (n_old > 0) {
+    memcpy(d->h_blk, old_xy, sizeof(double) * 2 * (size_t)n_old);
+    HIPCHK(h, hipMemcpyAsync(d->old_xy, d->h_blk, sizeof(double) * 2 * (size_t)n_old, hipMemcpyHostToDevice, h->stream));
+  }
+  hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fast_select, dim3(1), dim3(XK_FAST_SEL_T), d->lds_bytes, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "detection launch", e);
+  // accepted points are pairwise more than b apart: at most ceil(W / (b + 1)) ceil(H / (b + 1)) of them come back
+  const long long bound = (long long)((a.w + d->b) / (d->b + 1)) * ((a.h + d->b) / (d->b + 1));
+  const int cap = (int)std::min<long long>(bound, t->max_matches);
+  int *r = (int *)(d->h_blk + sizeof(double) * 2 * (size_t)t->max_matches);
+  HIPCHK(h, hipMemcpyAsync(r, d->res, det_res_bytes(t->max_matches), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int found = r[0], cand = r[1];
+  if (found < 0 || cand < 0 || (cand <= d->max_candidates && found > cand)) return fail(h, XK_EDEVICE, "xk_trk_detect: counts out of range");
+  d->n_cand = cand;
+  *n_found = found; *n_candidates = cand;
+  if (cand > d->max_candidates) return fail(h, XK_ECAPACITY, "xk_trk_detect: more candidates than max_candidates");
+  if (found > cap) return fail(h, XK_ECAPACITY, "xk_trk_detect: more features accepted than max_matches");
+  memcpy(xy, r + 4, sizeof(int) * 2 * (size_t)found);
+  memcpy(score, r + 4 + 2 * (size_t)t->max_matches, sizeof(int) * (size_t)found);
+  return XK_OK;
+}
+
+/* What the last detection left: the score image and the sorted keys.  Straight copies */
+extern "C" int xk_trk_detect_stage(xk_trk *t, unsigned char *scores, unsigned int *keys, int *n_candidates) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_det *d = k ? k->det : nullptr;
+  if (!d || d->n_cand < 0) return fail(h, XK_EINVAL, "xk_trk_detect_stage: before a detection");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (n_candidates) *n_candidates = d->n_cand;
+  const size_t pitch0 = (size_t)round_up(k->width, 16);
+  if (scores) HIPCHK(h, hipMemcpy2DAsync(scores, (size_t)k->width, d->S, pitch0, (size_t)k->width, (size_t)k->height, hipMemcpyDeviceToHost, h->stream));
+  if (keys && d->n_cand > 0 && d->n_cand <= d->max_candidates)
+    HIPCHK(h, hipMemcpyAsync(keys, d->keys, sizeof(unsigned int) * (size_t)d->n_cand, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
 }

@@ -39,6 +39,7 @@ SYMBOLS = [
     "xk_trk_create", "xk_trk_destroy", "xk_trk_undistort", "xk_trk_fundamental_ransac", "xk_trk_fundamental_hypotheses",
     "xk_trk_filter_matches",
     "xk_trk_klt_setup", "xk_trk_klt_levels", "xk_trk_push_image", "xk_trk_track", "xk_trk_klt_level",
+    "xk_trk_detect_setup", "xk_trk_detect", "xk_trk_detect_stage",
 ]
 
 

@@ -4,9 +4,10 @@
 manager sees it.
 
 `Klt` is the step in front of it: the pyramidal Lucas-Kanade tracking of `Tracker::featureTracking` (tracker.cpp:623-690),
-from two images and the previous features to the pairs that filter takes.
+from two images and the previous features to the pairs that filter takes.  `Klt.detect` produces those features:
+`Tracker::featureDetection` (tracker.cpp:390-590), FAST and the neighbourhood selection on a pushed image.
 
-No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h)."""
+No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h, csrc/xk_fast.hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -179,3 +180,34 @@ class Klt:
         self._chk(self.L.xk_trk_klt_level(self.p, C.c_int(which), C.c_int(level), img.ctypes.data_as(c_ub), dx.ctypes.data_as(c_sp),
                                           dy.ctypes.data_as(c_sp), None, None), "xk_trk_klt_level")
         return img, dx, dy
+
+    def detect_setup(self, threshold=9, non_max_supp=True, block_half_length=20, margin=20, max_candidates=8192):
+        """xk_trk_detect_setup: the parameters of Tracker::featureDetection (tracker.h:245-255) for the set-up image size.  A
+        later setup() drops it."""
+        self._chk(self.L.xk_trk_detect_setup(self.p, C.c_int(threshold), C.c_int(int(non_max_supp)), C.c_int(block_half_length),
+                                             C.c_int(margin), C.c_int(max_candidates)), "xk_trk_detect_setup")
+        self.max_candidates = int(max_candidates)
+
+    def detect(self, which=1, old_xy=None):
+        """Tracker::featureDetection (tracker.cpp:390-590) on the previous (which = 0) or current (1) image: FAST, the border,
+        the order by score and the selection outside the neighbourhood of old_xy (fp64 pixels [n_old, 2]) and of one another
+        -> dict of xy int32 [n, 2], score int32 [n] (ascending key), n_candidates."""
+        old = np.zeros((0, 2)) if old_xy is None else np.ascontiguousarray(old_xy, np.float64).reshape(-1, 2)
+        xy, score = np.zeros((self.max_features, 2), np.int32), np.zeros(self.max_features, np.int32)
+        nf, nc = C.c_int(0), C.c_int(0)
+        rc = self.L.xk_trk_detect(self.p, C.c_int(which), old.ctypes.data_as(c_dp) if len(old) else None, C.c_int(len(old)),
+                                  xy.ctypes.data_as(c_ip), score.ctypes.data_as(c_ip), C.byref(nf), C.byref(nc))
+        if rc != 0:
+            err = XkError(rc, "xk_trk_detect", (self.L.xk_last_error(self.eng.h) or b"").decode())
+            err.n_found, err.n_candidates = nf.value, nc.value
+            raise err
+        return dict(xy=xy[:nf.value].copy(), score=score[:nf.value].copy(), n_candidates=nc.value)
+
+    def detect_stage(self):
+        """What the last detect left -> (score image uint8 [height, width], the candidates' keys uint32, ascending)."""
+        n = C.c_int(0)
+        self._chk(self.L.xk_trk_detect_stage(self.p, None, None, C.byref(n)), "xk_trk_detect_stage")
+        S, keys = np.zeros((self.height, self.width), np.uint8), np.zeros(max(self.max_candidates, 1), np.uint32)
+        self._chk(self.L.xk_trk_detect_stage(self.p, S.ctypes.data_as(c_ub), keys.ctypes.data_as(C.POINTER(C.c_uint)), None),
+                  "xk_trk_detect_stage")
+        return S, keys[:min(n.value, self.max_candidates)].copy()
