@@ -7,11 +7,14 @@
 // features' neighbourhoods -- runs on the GPU too, behind xk_trk_detect.  The tile bookkeeping around it,
 // TiledImage::setTileForFeature (tiled_image.cpp:139-158) and Tracker::removeOverflowFeatures (tracker.cpp:592-620), is host
 // code here as it is there: list walks over a few hundred items.
+// PlaceRecognition::compute (place_recognition.cpp:72-94), the cv::ORB::compute a MULTI_UAV build runs on the keypoints of every
+// detection (tracker.cpp:440-444), runs on the GPU behind xk_trk_describe.
 #pragma once
 #include <cstdint>
 #include <utility>
 #include <vector>
 
+#include "x/place_recognition/database.h"
 #include "x/vision/camera.h"
 #include "xk.h"
 
@@ -62,7 +65,24 @@ class FeatureTracker {
   // size - 1, so the last pair is never examined; the counts are the current list's, against max_feat_per_tile.
   static void removeOverflow(TileGrid &grid, FeatureList &previous, FeatureList &current);
 
+  // The description of detected features (xk_trk_describe_setup): centroid_orientation false takes every descriptor at the fixed
+  // angle_deg -- what cv::ORB::compute sees on cv::FAST keypoints, whose angle is -1 -- true at the intensity centroid's; edge is
+  // OpenCV's edgeThreshold; pattern [256][4] (x1 y1 x2 y2), nullptr: the project's default; max_descriptors the most keypoints one
+  // describe() takes.  The reference drops the keypoints within edge of the border BEFORE the selection.  So that the features
+  // detect() returns are the same ones, the detection's margin is RAISED to edge from here on (now, if setDetection was called,
+  // and in every later setDetection): with margin >= edge the description drops nothing, and describing the accepted features
+  // equals the reference's order, describe all and then select, because descriptors do not influence the selection.
+  // From then on detect() fills getDescriptor() of what it returns and track() hands it from the previous to the current feature
+  // (tracker.cpp:675-679).
+  void setDescription(bool centroid_orientation = false, double angle_deg = -1.0, int edge = 31, const signed char *pattern = nullptr,
+                      int max_descriptors = 8192);
+  // cv::ORB::compute on pixels of the caller's choice, e.g. every candidate of a detection, the reference's descriptros_
+  // (place_recognition.cpp:92): the rows of the keypoints at least edge inside the image, in input order; kept_indices
+  // (optional): their positions in the input list.
+  Descriptors describe(const std::vector<std::pair<int, int>> &pixels, bool current_image = true, std::vector<int> *kept_indices = nullptr);
+
  private:
+  void applyDetection();
   xk_handle *xk_;
   xk_trk *trk_ = nullptr;
   int max_features_ = 0;
@@ -73,5 +93,10 @@ class FeatureTracker {
   std::vector<int> keep_;
   std::vector<double> old_in_;
   std::vector<int> det_xy_, det_score_;
+  bool detection_set_ = false;
+  int det_threshold_ = 9, det_nms_ = 1, det_b_ = 20, det_margin_ = 20, det_max_candidates_ = 8192;
+  int desc_edge_ = 0, max_descriptors_ = 0;   // 0: no description set up
+  std::vector<int> desc_xy_, desc_keep_, desc_dir_, desc_mom_;
+  std::vector<unsigned char> desc_out_;
 };
 }  // namespace x

@@ -3,6 +3,8 @@
 // the match records the multi-agent updates consume (MsckfMatch / SlamMatch, types.h:83-116), and what the tracker's
 // outlier removal reads and writes: TrackedFeature (a Feature with its distorted pixels), FeatureList, Match / MatchList (types.h:39-57).
 #pragma once
+#include <array>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -41,11 +43,18 @@ class TrackedFeature : public Feature {
   int getTileRow() const { return tile_row_; }
   int getTileCol() const { return tile_col_; }
   void setTile(int row, int col) { tile_row_ = row; tile_col_ = col; }
+  // the rotated-BRIEF descriptor the description attaches (feature.h: descriptor_, one row of a cv::Mat of CV_8U) and whether
+  // there is one.  Here for the same reason: vio_updater.cpp asserts the size of Feature.
+  bool hasDescriptor() const { return has_descriptor_; }
+  const std::array<unsigned char, 32> &getDescriptor() const { return descriptor_; }
+  void setDescriptor(const unsigned char *bytes32) { std::memcpy(descriptor_.data(), bytes32, 32); has_descriptor_ = true; }
  private:
   double x_dist_ = 0, y_dist_ = 0;
   double fast_score_ = 0;
   unsigned int pyramid_level_ = 0;
   int tile_row_ = 0, tile_col_ = 0;
+  std::array<unsigned char, 32> descriptor_{};
+  bool has_descriptor_ = false;
 };
 using FeatureList = std::vector<TrackedFeature>;      // the tracker's lists (types.h:49)
 struct Match { TrackedFeature previous, current; };   // types.h:39-42, :57

@@ -50,13 +50,52 @@ std::pair<FeatureList, FeatureList> FeatureTracker::track(const FeatureList &pre
     out.second.emplace_back(0.0, 0.0, kept_cur_[2 * k], kept_cur_[2 * k + 1]);
     out.second.back().setPyramidLevel(out.first.back().getPyramidLevel());   // :670-678: level and score of the previous feature
     out.second.back().setFastScore(out.first.back().getFastScore());
+    if (out.first.back().hasDescriptor()) out.second.back().setDescriptor(out.first.back().getDescriptor().data());   // :675-679
   }
   if (kept_indices) kept_indices->assign(keep_.begin(), keep_.begin() + n_kept);
   return out;
 }
 
 void FeatureTracker::setDetection(int threshold, bool non_max_supp, int block_half_length, int margin, int max_candidates) {
-  check(xk_, xk_trk_detect_setup(trk_, threshold, non_max_supp ? 1 : 0, block_half_length, margin, max_candidates), "xk_trk_detect_setup");
+  const int keep[5] = {det_threshold_, det_nms_, det_b_, det_margin_, det_max_candidates_};
+  det_threshold_ = threshold; det_nms_ = non_max_supp ? 1 : 0; det_b_ = block_half_length; det_margin_ = margin; det_max_candidates_ = max_candidates;
+  try {
+    applyDetection();
+  } catch (...) {                                               // (the device kept its earlier setup: so do the members)
+    det_threshold_ = keep[0]; det_nms_ = keep[1]; det_b_ = keep[2]; det_margin_ = keep[3]; det_max_candidates_ = keep[4];
+    throw;
+  }
+  detection_set_ = true;
+}
+
+// the detection setup as asked for, its margin raised to the description's edge
+void FeatureTracker::applyDetection() {
+  check(xk_, xk_trk_detect_setup(trk_, det_threshold_, det_nms_, det_b_, std::max(det_margin_, desc_edge_), det_max_candidates_),
+        "xk_trk_detect_setup");
+}
+
+void FeatureTracker::setDescription(bool centroid_orientation, double angle_deg, int edge, const signed char *pattern, int max_descriptors) {
+  check(xk_, xk_trk_describe_setup(trk_, centroid_orientation ? 1 : 0, angle_deg, edge, pattern, max_descriptors), "xk_trk_describe_setup");
+  desc_edge_ = edge; max_descriptors_ = max_descriptors;
+  const size_t m = (size_t)max_descriptors;
+  desc_xy_.resize(2 * m); desc_keep_.resize(m); desc_dir_.resize(2 * m); desc_mom_.resize(2 * m); desc_out_.resize(32 * m);
+  if (detection_set_) applyDetection();
+}
+
+Descriptors FeatureTracker::describe(const std::vector<std::pair<int, int>> &pixels, bool current_image, std::vector<int> *kept_indices) {
+  if (max_descriptors_ == 0) throw std::runtime_error("FeatureTracker::describe: before setDescription");
+  const size_t n = pixels.size();
+  if (n > (size_t)max_descriptors_) throw std::runtime_error("FeatureTracker::describe: more keypoints than max_descriptors");
+  for (size_t i = 0; i < n; ++i) { desc_xy_[2 * i] = pixels[i].first; desc_xy_[2 * i + 1] = pixels[i].second; }
+  int n_kept = 0;
+  check(xk_, xk_trk_describe(trk_, current_image ? 1 : 0, n ? desc_xy_.data() : nullptr, (int)n, desc_out_.data(), desc_keep_.data(),
+                             desc_dir_.data(), desc_mom_.data(), &n_kept),
+        "xk_trk_describe");
+  Descriptors out;
+  out.rows = n_kept; out.cols = 32;
+  out.data.assign(desc_out_.begin(), desc_out_.begin() + 32 * (size_t)n_kept);
+  if (kept_indices) kept_indices->assign(desc_keep_.begin(), desc_keep_.begin() + n_kept);
+  return out;
 }
 
 FeatureList FeatureTracker::detect(const FeatureList &old_features, bool current_image) {
@@ -73,6 +112,13 @@ FeatureList FeatureTracker::detect(const FeatureList &old_features, bool current
     out.emplace_back(0.0, 0.0, (double)det_xy_[2 * k], (double)det_xy_[2 * k + 1]);
     out.back().setPyramidLevel(0);
     out.back().setFastScore((double)det_score_[k]);
+  }
+  if (max_descriptors_ > 0 && n_found > 0) {                   // PlaceRecognition::compute of the keypoints, tracker.cpp:440-444
+    std::vector<std::pair<int, int>> pixels((size_t)n_found);
+    for (int k = 0; k < n_found; ++k) pixels[(size_t)k] = {det_xy_[2 * k], det_xy_[2 * k + 1]};
+    const Descriptors d = describe(pixels, current_image);
+    if (d.rows != n_found) throw std::runtime_error("FeatureTracker::detect: the description dropped a detected feature");   // (margin >= edge)
+    for (int k = 0; k < n_found; ++k) out[(size_t)k].setDescriptor(d.data.data() + 32 * (size_t)k);
   }
   return out;
 }

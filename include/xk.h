@@ -512,6 +512,49 @@ int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_old, int *xy
  * may be NULL.  An inspection path, not part of a frame: straight copies.  XK_EINVAL before a detection. */
 int xk_trk_detect_stage(xk_trk *t, unsigned char *scores, unsigned int *keys, int *n_candidates);
 
+/* ---- description of the detected features (PlaceRecognition::compute, place_recognition.cpp:72-94) ----------------
+ * A MULTI_UAV build describes every FAST keypoint at each detection (tracker.cpp:440-444 -> cv::ORB::compute), hands each
+ * feature's descriptor on through the tracking (:675-679) and keeps the whole block as the source of the request's VLAD
+ * (descriptros_, place_recognition.cpp:92, :690-692).  The same xk_trk does that on the device, on level 0 of an image slot
+ * that xk_trk_push_image filled (cv::FAST keypoints have octave 0).  The algorithm is this project's statement of the call
+ * (DESIGN 3.13), defined bit for bit; agreement with OpenCV's own bits is not claimed:
+ *   blur       G = the image under the separable taps {18, 34, 49, 54, 49, 34, 18} / 256 (sigma 2), unrounded between the
+ *              passes, (sum + 32768) >> 16 once; borders reflect without repeating the edge pixel
+ *   filter     a keypoint is kept iff edge <= x < W - edge and edge <= y < H - edge (KeyPointsFilter::runByImageBorder);
+ *              kept keypoints keep their input order
+ *   direction  (A, B) = 16384 (cos, sin), rounded to integers: of a fixed angle (cv::FAST leaves KeyPoint::angle at -1 and
+ *              cv::ORB::compute takes the angle as it finds it: the default, -1 degree), or of the intensity centroid
+ *              (m10, m01) of the unblurred image over the disc of radius 15 ((16384, 0) where both moments are 0)
+ *   tests      bit i & 7 of byte i >> 3 is G[y + r(x1 B + y1 A)][x + r(x1 A - y1 B)] < the same at (x2, y2) for row i =
+ *              (x1, y1, x2, y2) of the pattern; r = division by 16384 rounded half away from zero
+ * Level 0 only, WTA_K = 2, no Harris score. */
+
+/* orientation 0: the fixed angle angle_deg; 1: the intensity centroid (angle_deg is ignored but must be finite).  edge
+ * (25...4096; OpenCV's edgeThreshold 31).  pattern HOST [256][4] int8, x1 y1 x2 y2 per test, every coordinate within -15
+ * ... 15: OpenCV's ORB is the first 256 rows of bit_pattern_31_ in its orb.cpp, which a binding that links OpenCV passes
+ * here; NULL selects this project's default, whose descriptors match no vocabulary trained on OpenCV's.
+ * max_desc (1...32768): the most keypoints one call may pass, independent of max_matches.  Called after xk_trk_klt_setup,
+ * whose image size it takes; allocates the two blurred images, the result block and its pinned staging.
+ * XK_EINVAL: before xk_trk_klt_setup, orientation not 0 or 1, angle_deg not finite, edge or max_desc out of range, a
+ * pattern coordinate outside -15...15, a pattern row whose two points coincide.  A call that fails leaves an earlier
+ * description setup as it was.  A later xk_trk_klt_setup that succeeds DROPS it with the images: call this again after it. */
+int xk_trk_describe_setup(xk_trk *t, int orientation, double angle_deg, int edge, const signed char *pattern, int max_desc);
+
+/* cv::ORB::compute (place_recognition.cpp:83-88) on the previous (which = 0) or the current (1) image: xy HOST [n][2]
+ * int32, the keypoints' pixels (any values: the filter decides) -> desc HOST [n][32] (the first *n_kept rows), keep_idx
+ * HOST [n] (their positions in xy, ascending), dir HOST [n][2] (A, B of the kept), moments HOST [n][2] (m10, m01 of the
+ * kept; zeros with a fixed angle), *n_kept.  The slot's blur is queued by its first description after the push.  One copy
+ * in, two launches (three with the blur), one copy out, one synchronisation.  Every output is required.
+ * XK_EINVAL: null outputs, n < 0, which not 0 or 1, no description setup, a slot that has not been pushed.
+ * XK_ECAPACITY: n > max_desc; the outputs are then untouched.  n = 0 or nothing kept (an image smaller than 2 edge + 1
+ * keeps nothing): XK_OK with *n_kept = 0. */
+int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsigned char *desc, int *keep_idx, int *dir, int *moments, int *n_kept);
+
+/* blurred HOST [height][width] uint8: G of the previous (which = 0) or the current (1) image, computed now if no
+ * description of that slot did; pattern HOST [256][4]: the pattern in use, as the device holds it.  Either may be NULL.
+ * An inspection path, not part of a frame: straight copies.  XK_EINVAL as for xk_trk_describe. */
+int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed char *pattern);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and

@@ -1,11 +1,13 @@
 // xk_tracker_api.hip.h -- host side of the tracker's front end (xk_trk_*): the fundamental-matrix RANSAC filter of the matches
 // (tracker.cpp:233-293, camera.cpp:62-87; xk_fundamental.hip.h) and the pyramidal Lucas-Kanade tracking in front of it
-// (tracker.cpp:623-690; xk_klt.hip.h), and the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h).
+// (tracker.cpp:623-690; xk_klt.hip.h), the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h) and their
+// rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h).
 // Part of xk_api.hip's translation unit, included at its end.
 #pragma once
 #include "xk_fast.hip.h"
 #include "xk_fundamental.hip.h"
 #include "xk_klt.hip.h"
+#include "xk_orb.hip.h"
 
 // The detection setup of an image size (xk_trk_detect_setup): it belongs to the xk_klt whose level-0 images it scans.
 struct xk_det {
@@ -21,6 +23,18 @@ struct xk_det {
   int n_cand;                 // candidates of the last detection (-1: none yet)
 };
 
+// The description setup of an image size (xk_trk_describe_setup): it belongs to the xk_klt whose level-0 images it describes.
+struct xk_orb {
+  int centroid, A, B, edge, max_desc;
+  unsigned char *d_blk;       // G of slot 0 | G of slot 1 | pattern | keypoints in | kept keypoints | result block
+  unsigned char *G[2];        // by slot, as xk_klt::slot: a push swaps the roles of the slots, not their buffers
+  int blurred[2];             // G[s] holds the blur of the image in slot s.  xk_trk_push_image clears the flag of the slot it fills
+  signed char *pattern;
+  int *xy, *kept_xy, *res;
+  unsigned char *h_blk;       // pinned: keypoints in (2 max_desc ints), then the result block out
+  signed char h_pattern[1024];
+};
+
 struct xk_klt {
   int width, height, win_w, win_h, max_level, max_iter, levels;
   double eps, min_eig_thr;
@@ -33,6 +47,7 @@ struct xk_klt {
   unsigned char *h_blk;       // pinned: previous points in, then the result block out
   hipEvent_t img_copied;      // the upload out of h_img: the next push waits for it before it refills the staging
   struct xk_det *det;         // xk_trk_detect_setup; NULL before.  It goes with this setup
+  struct xk_orb *orb;         // xk_trk_describe_setup; likewise
 };
 
 struct xk_trk {
@@ -70,8 +85,16 @@ static void det_release(xk_det *d) {
   free(d);
 }
 
+static void orb_release(xk_orb *o) {
+  if (!o) return;
+  hipFree(o->d_blk);
+  if (o->h_blk) hipHostFree(o->h_blk);
+  free(o);
+}
+
 static void klt_release(xk_klt *k) {
   det_release(k->det);
+  orb_release(k->orb);
   hipFree(k->d_blk);
   if (k->h_img) hipHostFree(k->h_img);
   if (k->h_blk) hipHostFree(k->h_blk);
@@ -331,6 +354,7 @@ extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride
   const int s = k->cur ^ 1;
   const XkKltPyr &P = k->slot[s];
   const size_t pitch0 = (size_t)P.lv[0].pitch;
+  if (k->orb) k->orb->blurred[s] = 0;                                        // (the other slot's blur stays with its slot)
   if (k->pushed > 0) HIPCHK(h, hipEventSynchronize(k->img_copied));          // the staging is free again
   for (int y = 0; y < k->height; ++y) memcpy(k->h_img + y * pitch0, img + (size_t)y * stride, (size_t)k->width);
   HIPCHK(h, hipMemcpyAsync(P.lv[0].img, k->h_img, pitch0 * k->height, hipMemcpyHostToDevice, h->stream));
@@ -531,6 +555,163 @@ extern "C" int xk_trk_detect_stage(xk_trk *t, unsigned char *scores, unsigned in
   if (scores) HIPCHK(h, hipMemcpy2DAsync(scores, (size_t)k->width, d->S, pitch0, (size_t)k->width, (size_t)k->height, hipMemcpyDeviceToHost, h->stream));
   if (keys && d->n_cand > 0 && d->n_cand <= d->max_candidates)
     HIPCHK(h, hipMemcpyAsync(keys, d->keys, sizeof(unsigned int) * (size_t)d->n_cand, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Rotated-BRIEF descriptors of keypoints (place_recognition.cpp:72-94, tracker.cpp:440-444), xk_orb.hip.h
+// ---------------------------------------------------------------------------
+// The default pattern: candidate row r takes values 4r ... 4r + 3 of the splitmix64 stream of seed "ORB" (value i =
+// mix(seed + (i + 1) golden), as the RANSAC sampler's), each mapped to -15 ... 15 by the high word's product with 31; a row
+// whose two points coincide is skipped; the first 256 accepted rows.
+static void orb_default_pattern(signed char *p) {
+  const unsigned long long seed = 0x4F5242ull;
+  for (unsigned long long row = 0, got = 0; got < 256; ++row) {
+    int c[4];
+    for (int k = 0; k < 4; ++k) {
+      const unsigned long long z = xk_ransac_mix(seed + (4 * row + k + 1) * 0x9E3779B97F4A7C15ull);
+      c[k] = (int)(((z >> 32) * 31ull) >> 32) - XK_ORB_HALF;
+    }
+    if (c[0] == c[2] && c[1] == c[3]) continue;
+    for (int k = 0; k < 4; ++k) p[4 * got + k] = (signed char)c[k];
+    ++got;
+  }
+}
+
+/* The parameters of cv::ORB::compute as PlaceRecognition holds them (place_recognition.cpp:72-94) and the device buffers of one call */
+extern "C" int xk_trk_describe_setup(xk_trk *t, int orientation, double angle_deg, int edge, const signed char *pattern, int max_desc) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_describe_setup: before xk_trk_klt_setup");
+  if (orientation < 0 || orientation > 1) return fail(h, XK_EINVAL, "xk_trk_describe_setup: orientation is 0 (fixed angle) or 1 (intensity centroid)");
+  if (!std::isfinite(angle_deg)) return fail(h, XK_EINVAL, "xk_trk_describe_setup: angle_deg is not finite");
+  if (edge < 25 || edge > 4096) return fail(h, XK_EINVAL, "xk_trk_describe_setup: edge outside 25...4096");
+  if (max_desc < 1 || max_desc > XK_ORB_MAX_DESC) return fail(h, XK_EINVAL, "xk_trk_describe_setup: max_desc outside 1...32768");
+  if (pattern)
+    for (int i = 0; i < 256; ++i) {
+      const signed char *r = pattern + 4 * i;
+      for (int c = 0; c < 4; ++c)
+        if (r[c] < -XK_ORB_HALF || r[c] > XK_ORB_HALF) return fail(h, XK_EINVAL, "xk_trk_describe_setup: a pattern coordinate outside -15...15");
+      if (r[0] == r[2] && r[1] == r[3]) return fail(h, XK_EINVAL, "xk_trk_describe_setup: a pattern row whose two points coincide");
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_orb *o = (xk_orb *)calloc(1, sizeof(xk_orb));      // (built whole before the old one goes, as in xk_trk_klt_setup)
+  if (!o) return XK_ENOMEM;
+  o->centroid = orientation; o->edge = edge; o->max_desc = max_desc;
+  const double th = angle_deg * (M_PI / 180.0);
+  o->A = (int)std::rint(16384.0 * std::cos(th)); o->B = (int)std::rint(16384.0 * std::sin(th));
+  if (pattern) memcpy(o->h_pattern, pattern, sizeof o->h_pattern);
+  else orb_default_pattern(o->h_pattern);
+  const size_t g_bytes = (size_t)round_up(k->width, 16) * k->height;              // (a multiple of 16, as every offset below)
+  const size_t xy_bytes = (sizeof(int) * 2 * (size_t)max_desc + 15) / 16 * 16;
+  const size_t res_bytes = (xk_orb_res_bytes((size_t)max_desc) + 15) / 16 * 16;
+  const size_t dev_bytes = 2 * g_bytes + sizeof o->h_pattern + 2 * xy_bytes + res_bytes;
+  void *dv = nullptr, *hb = nullptr;
+  const size_t pin_bytes = std::max(xy_bytes + res_bytes, sizeof o->h_pattern);   // (the pattern goes up through it, below)
+  bool ok = hipMalloc(&dv, dev_bytes) == hipSuccess && hipHostMalloc(&hb, pin_bytes) == hipSuccess &&
+            hipMemsetAsync(dv, 0, dev_bytes, h->stream) == hipSuccess;            // (G's padding columns are never written: zeros)
+  o->d_blk = (unsigned char *)dv; o->h_blk = (unsigned char *)hb;
+  if (ok) {
+    memcpy(o->h_blk, o->h_pattern, sizeof o->h_pattern);
+    ok = hipMemcpyAsync(o->d_blk + 2 * g_bytes, o->h_blk, sizeof o->h_pattern, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess) ok = false;                  // (the staging is free again; an old setup idle)
+  if (!ok) {
+    orb_release(o);
+    return fail(h, XK_ENOMEM, "xk_trk_describe_setup: allocation failed");
+  }
+  unsigned char *p = o->d_blk;
+  o->G[0] = p; p += g_bytes;
+  o->G[1] = p; p += g_bytes;
+  o->pattern = (signed char *)p; p += sizeof o->h_pattern;
+  o->xy = (int *)p; p += xy_bytes;
+  o->kept_xy = (int *)p; p += xy_bytes;
+  o->res = (int *)p;
+  orb_release(k->orb);
+  k->orb = o;
+  return XK_OK;
+}
+
+// The slot of the previous (which = 0) or the current (1) image as XkOrbArgs, its blur queued if this is the slot's first
+// description since its push.
+static int orb_slot(xk_trk *t, int which, XkOrbArgs &a) {
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_orb *o = k->orb;
+  const int s = which == 1 ? k->cur : k->cur ^ 1;
+  const XkKltLevel &L = k->slot[s].lv[0];
+  a.img = L.img; a.G = o->G[s]; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
+  a.edge = o->edge; a.centroid = o->centroid; a.A = o->A; a.B = o->B;
+  a.pattern = o->pattern; a.xy = o->xy; a.kept_xy = o->kept_xy; a.res = o->res;
+  if (!o->blurred[s]) {
+    hipLaunchKernelGGL(xk_orb_blur, dim3((a.w + XK_ORB_TW - 1) / XK_ORB_TW, (a.h + XK_ORB_TH - 1) / XK_ORB_TH), dim3(256), 0, h->stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, XK_EDEVICE, "blur launch", e);
+    o->blurred[s] = 1;
+  }
+  return XK_OK;
+}
+
+/* cv::ORB::compute(img, keypoints, descriptors) (place_recognition.cpp:72-94) on the previous (which = 0) or the current (1) image */
+extern "C" int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsigned char *desc, int *keep_idx, int *dir, int *moments,
+                               int *n_kept) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_orb *o = k ? k->orb : nullptr;
+  if (!o) return fail(h, XK_EINVAL, "xk_trk_describe: before xk_trk_describe_setup");
+  if (!desc || !keep_idx || !dir || !moments || !n_kept || n < 0 || (n > 0 && !xy)) return fail(h, XK_EINVAL, "xk_trk_describe: null argument or negative n");
+  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_describe: which is 0 or 1");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_describe: that image has not been pushed");
+  if (n > o->max_desc) return fail(h, XK_ECAPACITY, "xk_trk_describe: more keypoints than max_desc");
+  *n_kept = 0;
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkOrbArgs a{};
+  a.n = n;
+  memcpy(o->h_blk, xy, sizeof(int) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync(o->xy, o->h_blk, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  const int rc = orb_slot(t, which, a);
+  if (rc != XK_OK) return rc;
+  hipLaunchKernelGGL(xk_orb_filter, dim3(1), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_orb_describe, dim3(std::min((n + XK_ORB_WAVES - 1) / XK_ORB_WAVES, XK_ORB_MAX_GRID)), dim3(64 * XK_ORB_WAVES), 0,
+                     h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "description launch", e);
+  const unsigned char *r = o->h_blk + (sizeof(int) * 2 * (size_t)o->max_desc + 15) / 16 * 16;
+  HIPCHK(h, hipMemcpyAsync((void *)r, o->res, xk_orb_res_bytes((size_t)n), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int kept = 0;
+  memcpy(&kept, r, sizeof(int));
+  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_describe: kept count out of range");
+  *n_kept = kept;
+  const int *ri = (const int *)r;
+  memcpy(keep_idx, ri + 4, sizeof(int) * (size_t)kept);
+  memcpy(dir, ri + 4 + n, sizeof(int) * 2 * (size_t)kept);
+  memcpy(moments, ri + 4 + 3 * (size_t)n, sizeof(int) * 2 * (size_t)kept);
+  memcpy(desc, r + xk_orb_desc_off((size_t)n), 32 * (size_t)kept);
+  return XK_OK;
+}
+
+/* The blurred image of a slot and the pattern in use.  Straight copies */
+extern "C" int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed char *pattern) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_orb *o = k ? k->orb : nullptr;
+  if (!o) return fail(h, XK_EINVAL, "xk_trk_describe_stage: before xk_trk_describe_setup");
+  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_describe_stage: which is 0 or 1");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_describe_stage: that image has not been pushed");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pattern) HIPCHK(h, hipMemcpyAsync(pattern, o->pattern, sizeof o->h_pattern, hipMemcpyDeviceToHost, h->stream));   // (the kernels' copy)
+  if (blurred) {
+    XkOrbArgs a{};
+    const int rc = orb_slot(t, which, a);
+    if (rc != XK_OK) return rc;
+    HIPCHK(h, hipMemcpy2DAsync(blurred, (size_t)a.w, a.G, (size_t)a.pitch, (size_t)a.w, (size_t)a.h, hipMemcpyDeviceToHost, h->stream));
+  }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
 }

@@ -40,6 +40,7 @@ SYMBOLS = [
     "xk_trk_filter_matches",
     "xk_trk_klt_setup", "xk_trk_klt_levels", "xk_trk_push_image", "xk_trk_track", "xk_trk_klt_level",
     "xk_trk_detect_setup", "xk_trk_detect", "xk_trk_detect_stage",
+    "xk_trk_describe_setup", "xk_trk_describe", "xk_trk_describe_stage",
 ]
 
 

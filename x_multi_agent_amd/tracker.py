@@ -5,9 +5,12 @@ manager sees it.
 
 `Klt` is the step in front of it: the pyramidal Lucas-Kanade tracking of `Tracker::featureTracking` (tracker.cpp:623-690),
 from two images and the previous features to the pairs that filter takes.  `Klt.detect` produces those features:
-`Tracker::featureDetection` (tracker.cpp:390-590), FAST and the neighbourhood selection on a pushed image.
+`Tracker::featureDetection` (tracker.cpp:390-590), FAST and the neighbourhood selection on a pushed image, and
+`Klt.describe` their rotated-BRIEF descriptors (`PlaceRecognition::compute`, place_recognition.cpp:72-94), which is what
+place.Database takes.
 
-No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h, csrc/xk_fast.hip.h)."""
+No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h, csrc/xk_fast.hip.h,
+csrc/xk_orb.hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -17,6 +20,7 @@ from .engine import XkError, c_dp, c_ip
 c_ub = C.POINTER(C.c_ubyte)
 c_fp = C.POINTER(C.c_float)
 c_sp = C.POINTER(C.c_short)
+c_sb = C.POINTER(C.c_byte)
 
 
 class MatchFilter:
@@ -211,3 +215,37 @@ class Klt:
         self._chk(self.L.xk_trk_detect_stage(self.p, S.ctypes.data_as(c_ub), keys.ctypes.data_as(C.POINTER(C.c_uint)), None),
                   "xk_trk_detect_stage")
         return S, keys[:min(n.value, self.max_candidates)].copy()
+
+    def describe_setup(self, orientation=0, angle_deg=-1.0, edge=31, pattern=None, max_desc=8192):
+        """xk_trk_describe_setup: orientation 0 = the fixed angle angle_deg (what cv::ORB::compute sees on cv::FAST keypoints:
+        -1), 1 = the intensity centroid; edge = OpenCV's edgeThreshold; pattern int8 [256, 4] (x1 y1 x2 y2 within -15...15;
+        OpenCV's is the first 256 rows of its bit_pattern_31_), None: the project's default.  A later setup()
+        drops it."""
+        pp = None
+        if pattern is not None:
+            pat = np.ascontiguousarray(pattern, np.int8)
+            if pat.shape != (256, 4):
+                raise ValueError("describe_setup: the pattern is int8 [256, 4]")
+            pp = pat.ctypes.data_as(c_sb)
+        self._chk(self.L.xk_trk_describe_setup(self.p, C.c_int(int(orientation)), C.c_double(angle_deg), C.c_int(edge), pp, C.c_int(max_desc)),
+                  "xk_trk_describe_setup")
+
+    def describe(self, xy, which=1):
+        """cv::ORB::compute (place_recognition.cpp:83-88) of the keypoints xy (int32 pixels [n, 2]) on the previous (which = 0)
+        or current (1) image -> dict of desc uint8 [m, 32], keep_idx int32 [m] (the keypoints at least `edge` inside the image,
+        input order), dir int32 [m, 2] (16384 cos, 16384 sin), moments int32 [m, 2] (m10, m01; zeros with a fixed angle)."""
+        pts = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n, m = len(pts), max(len(pts), 1)
+        desc, keep, dirs, mom, nk = np.zeros((m, 32), np.uint8), np.zeros(m, np.int32), np.zeros((m, 2), np.int32), np.zeros((m, 2), np.int32), C.c_int(0)
+        self._chk(self.L.xk_trk_describe(self.p, C.c_int(which), pts.ctypes.data_as(c_ip), C.c_int(n), desc.ctypes.data_as(c_ub),
+                                         keep.ctypes.data_as(c_ip), dirs.ctypes.data_as(c_ip), mom.ctypes.data_as(c_ip), C.byref(nk)),
+                  "xk_trk_describe")
+        k = nk.value
+        return dict(desc=desc[:k].copy(), keep_idx=keep[:k].copy(), dir=dirs[:k].copy(), moments=mom[:k].copy())
+
+    def describe_stage(self, which=1):
+        """-> (the blurred image uint8 [height, width] of the previous (which = 0) or current (1) image, the pattern in use
+        int8 [256, 4])."""
+        G, pat = np.zeros((self.height, self.width), np.uint8), np.zeros((256, 4), np.int8)
+        self._chk(self.L.xk_trk_describe_stage(self.p, C.c_int(which), G.ctypes.data_as(c_ub), pat.ctypes.data_as(c_sb)), "xk_trk_describe_stage")
+        return G, pat
