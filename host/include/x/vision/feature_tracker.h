@@ -9,6 +9,8 @@
 // code here as it is there: list walks over a few hundred items.
 // PlaceRecognition::compute (place_recognition.cpp:72-94), the cv::ORB::compute a MULTI_UAV build runs on the keypoints of every
 // detection (tracker.cpp:440-444), runs on the GPU behind xk_trk_describe.
+// Tracker::calibrateImage (tracker.cpp:761-858), the photometric calibration a PHOTOMETRIC_CALI build runs on every frame after the
+// first, runs on the GPU behind xk_trk_photo_calibrate.
 #pragma once
 #include <cstdint>
 #include <utility>
@@ -81,11 +83,31 @@ class FeatureTracker {
   // (optional): their positions in the input list.
   Descriptors describe(const std::vector<std::pair<int, int>> &pixels, bool current_image = true, std::vector<int> *kept_indices = nullptr);
 
+  // The photometric calibration (xk_trk_photo_setup): kernel_size is intensities_kernel_size_ (tracker.h:366), epsilon_gap and
+  // epsilon_base the drift parameters of IRPhotoCalib, n_hyp the most hypotheses of a gain estimate (a frame evaluates
+  // min(features, n_hyp); the reference runs as many as it has features).  From then on detect() fills getIntensity() from the
+  // working image (tracker.cpp:461) and track() from the raw current image (:666).
+  void setPhotometric(int kernel_size = 30, double epsilon_gap = 0.0, double epsilon_base = 0.0, int n_hyp = 512);
+  struct Calibration {
+    bool estimated = false;              // gains were estimated by this call
+    int kept = 0, support = 0;           // features the raw tracking kept, inliers of the estimate
+    double a_rel = 1.0, b_rel = 0.0;     // the estimate against the previous frame
+    double frame_ab[4] = {0, 0, 0, 0};   // the pair after the drift adjustments, the frame's origin pair
+  };
+  // Tracker::calibrateImage (tracker.cpp:761-858) on the features of the previous image (getXDist / getYDist, getIntensity):
+  // call it between pushImage and track, as tracker.cpp:186-195 orders them.  The current image is corrected on the device.
+  Calibration calibrate(const FeatureList &previous, unsigned long seed = 0);
+  // level 0 of the current (or previous) image as the device holds it, height rows of width bytes: the working image, which the
+  // tracking, the detection and the description read, or with raw = true (after setPhotometric) the image as pushed
+  std::vector<uint8_t> image(bool current_image = true, bool raw = false);
+
  private:
+  void fillIntensity(FeatureList &features, bool current_image, bool raw_plane);
   void applyDetection();
   xk_handle *xk_;
   xk_trk *trk_ = nullptr;
   int max_features_ = 0;
+  int width_ = 0, height_ = 0;
   // staging for one call, sized once by max_features: points in, everything xk_trk_track reports out
   std::vector<float> prev_in_;
   std::vector<double> cur_, min_eig_, kept_prev_, kept_cur_;
@@ -98,5 +120,8 @@ class FeatureTracker {
   int desc_edge_ = 0, max_descriptors_ = 0;   // 0: no description set up
   std::vector<int> desc_xy_, desc_keep_, desc_dir_, desc_mom_;
   std::vector<unsigned char> desc_out_;
+  int photo_hyp_ = 0;                         // 0: no photometric calibration set up
+  std::vector<double> photo_val_, photo_in_;
+  std::vector<int> photo_xy_, photo_sum_, photo_cnt_;
 };
 }  // namespace x

@@ -48,6 +48,10 @@ class TrackedFeature : public Feature {
   bool hasDescriptor() const { return has_descriptor_; }
   const std::array<unsigned char, 32> &getDescriptor() const { return descriptor_; }
   void setDescriptor(const unsigned char *bytes32) { std::memcpy(descriptor_.data(), bytes32, 32); has_descriptor_ = true; }
+  // the box-mean intensity a PHOTOMETRIC_CALI build attaches (feature.h: intensity_; tracker.cpp:461, :666).  fp64 here: the
+  // exact integer sum over 255 count
+  double getIntensity() const { return intensity_; }
+  void setIntensity(double intensity) { intensity_ = intensity; }
  private:
   double x_dist_ = 0, y_dist_ = 0;
   double fast_score_ = 0;
@@ -55,6 +59,7 @@ class TrackedFeature : public Feature {
   int tile_row_ = 0, tile_col_ = 0;
   std::array<unsigned char, 32> descriptor_{};
   bool has_descriptor_ = false;
+  double intensity_ = 0;
 };
 using FeatureList = std::vector<TrackedFeature>;      // the tracker's lists (types.h:49)
 struct Match { TrackedFeature previous, current; };   // types.h:39-42, :57

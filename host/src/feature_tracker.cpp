@@ -1,5 +1,5 @@
-// Mirror of Tracker::featureTracking and Tracker::featureDetection, src/x/vision/tracker.cpp:623-690 and :390-590; the arithmetic
-// runs in libxk.so.  The tile bookkeeping (tiled_image.cpp:139-158, tracker.cpp:592-620) is host code, as in the reference.
+// Mirror of Tracker::featureTracking, Tracker::featureDetection and Tracker::calibrateImage, src/x/vision/tracker.cpp:623-690,
+// :390-590 and :761-858; the arithmetic runs in libxk.so.  The tile bookkeeping (tiled_image.cpp:139-158, tracker.cpp:592-620) is host code, as in the reference.
 #include "x/vision/feature_tracker.h"
 
 #include <algorithm>
@@ -14,7 +14,7 @@ static void check(xk_handle *h, int rc, const char *what) {
 
 FeatureTracker::FeatureTracker(xk_handle *xk, const Camera &camera, int max_features, int win_w, int win_h, int max_level, int max_iter,
                                double eps, double min_eig_thr)
-    : xk_(xk), max_features_(max_features) {
+    : xk_(xk), max_features_(max_features), width_((int)camera.getWidth()), height_((int)camera.getHeight()) {
   if (max_features < 1) throw std::runtime_error("FeatureTracker: max_features < 1");
   const size_t m = (size_t)max_features;                      // (the staging first: nothing below can throw once the handle exists)
   prev_in_.resize(2 * m); cur_.resize(2 * m); min_eig_.resize(m); kept_prev_.resize(2 * m); kept_cur_.resize(2 * m);
@@ -53,6 +53,50 @@ std::pair<FeatureList, FeatureList> FeatureTracker::track(const FeatureList &pre
     if (out.first.back().hasDescriptor()) out.second.back().setDescriptor(out.first.back().getDescriptor().data());   // :675-679
   }
   if (kept_indices) kept_indices->assign(keep_.begin(), keep_.begin() + n_kept);
+  if (photo_hyp_ > 0) fillIntensity(out.second, true, true);   // computeIntensity(img2, ...) of the raw current image, :666
+  return out;
+}
+
+void FeatureTracker::setPhotometric(int kernel_size, double epsilon_gap, double epsilon_base, int n_hyp) {
+  check(xk_, xk_trk_photo_setup(trk_, kernel_size, epsilon_gap, epsilon_base, n_hyp), "xk_trk_photo_setup");
+  photo_hyp_ = n_hyp;
+  const size_t m = (size_t)max_features_;
+  photo_val_.resize(m); photo_in_.resize(m); photo_xy_.resize(2 * m); photo_sum_.resize(m); photo_cnt_.resize(m);
+}
+
+// computeIntensity at static_cast<int> of the distorted pixels (tracker.cpp:461, :666)
+void FeatureTracker::fillIntensity(FeatureList &features, bool current_image, bool raw_plane) {
+  const size_t n = features.size();
+  if (n == 0) return;
+  for (size_t i = 0; i < n; ++i) { photo_xy_[2 * i] = (int)features[i].getXDist(); photo_xy_[2 * i + 1] = (int)features[i].getYDist(); }
+  check(xk_, xk_trk_photo_intensity(trk_, current_image ? 1 : 0, raw_plane ? 0 : 1, photo_xy_.data(), (int)n, photo_val_.data(),
+                                    photo_sum_.data(), photo_cnt_.data()),
+        "xk_trk_photo_intensity");
+  for (size_t i = 0; i < n; ++i) features[i].setIntensity(photo_val_[i]);
+}
+
+FeatureTracker::Calibration FeatureTracker::calibrate(const FeatureList &previous, unsigned long seed) {
+  if (photo_hyp_ == 0) throw std::runtime_error("FeatureTracker::calibrate: before setPhotometric");
+  const size_t n = previous.size();
+  if (n > (size_t)max_features_) throw std::runtime_error("FeatureTracker::calibrate: more features than max_features");
+  for (size_t i = 0; i < n; ++i) {
+    prev_in_[2 * i] = (float)previous[i].getXDist(); prev_in_[2 * i + 1] = (float)previous[i].getYDist();
+    photo_in_[i] = previous[i].getIntensity();
+  }
+  Calibration c;
+  int estimated = 0;
+  const int n_hyp = std::max(1, std::min((int)n, photo_hyp_));
+  check(xk_, xk_trk_photo_calibrate(trk_, prev_in_.data(), photo_in_.data(), (int)n, n_hyp, seed, keep_.data(), photo_val_.data(),
+                                    photo_sum_.data(), photo_cnt_.data(), &c.kept, &c.a_rel, &c.b_rel, &c.support, c.frame_ab, &estimated),
+        "xk_trk_photo_calibrate");
+  c.estimated = estimated != 0;
+  return c;
+}
+
+std::vector<uint8_t> FeatureTracker::image(bool current_image, bool raw) {
+  std::vector<uint8_t> out((size_t)width_ * height_);
+  if (raw) check(xk_, xk_trk_photo_raw(trk_, current_image ? 1 : 0, out.data()), "xk_trk_photo_raw");
+  else check(xk_, xk_trk_klt_level(trk_, current_image ? 1 : 0, 0, out.data(), nullptr, nullptr, nullptr, nullptr), "xk_trk_klt_level");
   return out;
 }
 
@@ -120,6 +164,7 @@ FeatureList FeatureTracker::detect(const FeatureList &old_features, bool current
     if (d.rows != n_found) throw std::runtime_error("FeatureTracker::detect: the description dropped a detected feature");   // (margin >= edge)
     for (int k = 0; k < n_found; ++k) out[(size_t)k].setDescriptor(d.data.data() + 32 * (size_t)k);
   }
+  if (photo_hyp_ > 0) fillIntensity(out, current_image, false);   // computeIntensity of the (corrected) image, tracker.cpp:461
   return out;
 }
 

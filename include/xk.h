@@ -485,7 +485,8 @@ int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short 
  *              blocks nothing) and no candidate accepted before lies within Chebyshev distance block_half_length of it:
  *              the painted mask with every box clipped to the image, defined also where the reference's unclipped
  *              cv::Rect would assert.
- * Level 0 only (pyramid_depth_ is 1), no descriptors, no photometric intensity. */
+ * Level 0 only (pyramid_depth_ is 1), no descriptors; the intensity a PHOTOMETRIC_CALI build attaches
+ * to a detected feature (tracker.cpp:461) is xk_trk_photo_intensity, below. */
 
 /* The parameters Tracker holds (tracker.h:245-255: fast_detection_delta_ 9, non_max_supp_ true, block_half_length_ 20,
  * margin_ 20) and max_candidates (1...32768), the most candidates one image may have.  Called after xk_trk_klt_setup, whose
@@ -554,6 +555,101 @@ int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsigned char *d
  * description of that slot did; pattern HOST [256][4]: the pattern in use, as the device holds it.  Either may be NULL.
  * An inspection path, not part of a frame: straight copies.  XK_EINVAL as for xk_trk_describe. */
 int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed char *pattern);
+
+/* ---- photometric calibration of the images (Tracker::calibrateImage, tracker.cpp:761-877; irPhotoCalib.cpp) ---------
+ * A PHOTOMETRIC_CALI build passes every frame after the first through calibrateImage (tracker.cpp:186-190) before it is
+ * tracked: a Lucas-Kanade pass between the UNCORRECTED images, a box-mean intensity per feature, a RANSAC estimate of the
+ * affine gain between the frames chained into a 15-frame history, and a rewrite of every pixel of the current image, which
+ * is what featureTracking, featureDetection and PlaceRecognition::compute then see.  The same xk_trk does that on the
+ * device.  With a photo setup every image slot has two planes: the RAW one, as pushed, and the WORKING one, which every
+ * other xk_trk_* entry reads and which equals the raw one until a correction.  The algorithm is this project's statement
+ * of those calls:
+ *   intensity  hk = kernel_size / 2; the window of (x, y) is rows y - hk ... y + hk - 1, columns x - hk ... x + hk - 1
+ *              (tracker.cpp:866-867), clipped to the image; sum = the EXACT integer sum of its pixels, count their number,
+ *              value = (double)sum / (255.0 * (double)count) in fp64, 0 where count is 0 (the reference accumulates
+ *              pixel / 255.f in float and divides 0 by 0)
+ *   gains      per group: hypothesis h fits four distinct points drawn by the sampler of the RANSAC filters above from
+ *              seed + g; the fit is the CLOSED-FORM minimum of the cost of photoetricOptimization.h:57-100 (its 2 x 2 normal
+ *              equations by Cramer's rule in fp64) -- the minimum Ceres iterates toward; agreement with Ceres' last iterate
+ *              is NOT claimed; a point is an inlier iff |o - (p (a - b) + b)| < 8e-3 (irPhotoCalib.cpp:270-278); most
+ *              inliers win, ties to the lowest hypothesis; the refit over the winner's inliers is the same closed form.
+ *              ALL n_hyp hypotheses are evaluated (the reference runs as many as the group has points from an unseeded
+ *              shuffle).  A group of 4 or fewer points contributes nothing (:116)
+ *   chain      irPhotoCalib.cpp:104-160, :212-218 in fp64, operation by operation
+ *   correction in float32, every operation rounded once: f = v * (1.f/255.f); c = ((f * (float)(a - b) + (float)b) -
+ *              PS[y][x]) * 255.f; x = c truncated toward zero (0 where c is not finite or |c| >= 2^31); m = x % 256 with
+ *              C's sign rule; u = max(m, 0); out = u < 128 ? 2u : (u == 128 ? 255 : 512 - 2u) (the table of :42-51)
+ * Out of scope: the estimation of the spatial parameters (:162-210, :314-420; the correction takes the caller's map), the
+ * second Lucas-Kanade parameter set and FAST threshold (tracker.cpp:641-645, :848; the caller re-runs the setups),
+ * keyframe mode, the detached thread of refinePhotometricParams, pyramid levels above 0. */
+
+/* intensities_kernel_size_ (2...64; tracker.h:366: 30), epsilon_gap and epsilon_base of IRPhotoCalib (finite, in [0, 1]),
+ * max_hyp (1...4096): the most hypotheses a gain estimate may evaluate.  Called after xk_trk_klt_setup, whose image size it
+ * takes; allocates the raw plane of both slots (images already pushed are copied into it), the spatial map (zeros), the
+ * parameter ring (one entry (1, 0), irPhotoCalib.cpp:25), one RANSAC scratch block per group and the pinned staging.  From
+ * then on xk_trk_push_image builds the pyramid in the raw plane and copies the slot's block into the working plane, device
+ * to device.  XK_EINVAL: before xk_trk_klt_setup, a parameter out of range.  A call that fails leaves an earlier photo
+ * setup as it was.  A later xk_trk_klt_setup that succeeds DROPS it with the images: call this again after it. */
+int xk_trk_photo_setup(xk_trk *t, int kernel_size, double epsilon_gap, double epsilon_base, int max_hyp);
+
+/* Tracker::computeIntensity (tracker.cpp:860-877) on level 0 of the previous (which = 0) or the current (1) image, its
+ * raw (plane = 0) or working (1) plane: xy HOST [n][2] int32 (any values) -> value HOST [n] fp64, sum, count HOST [n]
+ * int32.  XK_EINVAL: null pointers, n < 0, which or plane not 0 or 1, no photo setup, a slot that has not been pushed.
+ * XK_ECAPACITY: n > max_matches. */
+int xk_trk_photo_intensity(xk_trk *t, int which, int plane, const int *xy, int n, double *value, int *sum, int *count);
+
+/* One call of IRPhotoCalib::ProcessCurrentFrame (irPhotoCalib.cpp:95-160, :212-218) with EstimateGainsRansac (:221-312)
+ * per group: G groups (1...14), group g = points off[g] ... off[g+1] - 1 (off HOST [G + 1], off[0] = 0, ascending) of
+ * o_hist (the intensities in the frame frame_back[g] frames back) and o_cur (in the current frame), both HOST fp64.
+ * Calibrate-per-frame passes G = 1, frame_back = {1} (tracker.cpp:832-839); refinePhotometricParams (:698-754) one group
+ * per history frame.  -> a_rel, b_rel HOST [G]: each group's refit ((1, 0) for a group of <= 4 points or without an
+ * inlier), support HOST [G]: its inlier count, frame_ab HOST [4]: the support-weighted pair relative to the previous frame
+ * after the drift adjustments, then the frame's origin pair, which is appended to the ring (the oldest entry is dropped
+ * beyond 15).  One copy in, three launches per group and one for the chain, one copy out, one synchronisation.
+ * XK_EINVAL: null pointers, G, n_hyp (1...max_hyp) or off out of range, no photo setup, frame_back[g] outside 1 ... the
+ * ring's size (the reference would index out of bounds); the ring is then untouched.  XK_ECAPACITY: a group of more than
+ * max_matches points. */
+int xk_trk_photo_gains(xk_trk *t, int G, const int *off, const double *o_hist, const double *o_cur, const int *frame_back, int n_hyp,
+                       unsigned long seed, double *a_rel, double *b_rel, int *support, double *frame_ab);
+
+/* What the last gain estimate (xk_trk_photo_gains or xk_trk_photo_calibrate) left for hypotheses first ... first+count-1
+ * of group g: ab HOST [count][2], inliers HOST [count].  Either may be NULL.  Straight copies.  XK_EINVAL outside the last
+ * call's range (a group of <= 4 points has no hypotheses). */
+int xk_trk_photo_hypotheses(xk_trk *t, int g, int first, int count, double *ab, int *inliers);
+
+/* params_PT_ (irPhotoCalib.cpp:25, :213-218): a, b HOST [15], the ring's pairs, oldest first; *count of them are written. */
+int xk_trk_photo_params(xk_trk *t, double *a, double *b, int *count);
+
+/* The ring back to its one entry (1, 0); no gains estimated yet (CALIBRATION_DONE false). */
+int xk_trk_photo_reset(xk_trk *t);
+
+/* params_PS_ (irPhotoCalib.cpp:36): ps HOST [height][width] float32, NULL: zeros.  Waits for the upload. */
+int xk_trk_photo_set_spatial(xk_trk *t, const float *ps);
+
+/* IRPhotoCalib::getCorrectedImage (irPhotoCalib.cpp:442-472) of the previous (which = 0) or the current (1) image with
+ * the ring's last pair: level 0 of the working plane recomputed from level 0 of the RAW plane (so a repeated call gives
+ * the same image), then the working plane's pyramid and Scharr derivatives; the slot's blur of xk_trk_describe is redone
+ * at the next description.  Queued, no synchronisation.  XK_EINVAL: no photo setup, which not 0 or 1, a slot not pushed. */
+int xk_trk_photo_correct(xk_trk *t, int which);
+
+/* img HOST [height][width] uint8: level 0 of a slot's raw plane, the image as pushed.  A straight copy. */
+int xk_trk_photo_raw(xk_trk *t, int which, unsigned char *img);
+
+/* Tracker::calibrateImage (tracker.cpp:761-858) whole, between xk_trk_push_image and xk_trk_track (tracker.cpp:186-195):
+ *   1. xk_trk_track's two launches from the RAW previous to the RAW current plane on prev_xy (HOST [n][2] float32), with
+ *      the post-filter of :803-806
+ *   2. the intensities of the kept points on the raw current plane at the truncated pixel (:807-808)
+ *   3. the gain estimate with one group, frame_back 1, against the kept rows of prev_intensity (HOST [n] fp64, :810)
+ *   4. the correction of the current image
+ * -> keep_idx, intensity, sum, count HOST [n] (the first *n_kept rows), a_rel, b_rel, support (one each), frame_ab HOST
+ * [4], *estimated.  With n < 4 or fewer than 4 kept points (:763, :795, :826) *estimated = 0, the ring does not advance
+ * and the image is corrected (with the ring's last pair) only if an earlier call estimated gains; the gain outputs are
+ * then (1, 0), 0 and zeros.  One copy in, one copy out, one synchronisation; the lists stay on the device between the
+ * steps.  XK_EINVAL: null pointers, n < 0, n_hyp outside 1...max_hyp, no photo setup, fewer than two images pushed.
+ * XK_ECAPACITY: n > max_matches. */
+int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const double *prev_intensity, int n, int n_hyp, unsigned long seed,
+                           int *keep_idx, double *intensity, int *sum, int *count, int *n_kept, double *a_rel, double *b_rel,
+                           int *support, double *frame_ab, int *estimated);
 
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance

@@ -1,13 +1,15 @@
 // xk_tracker_api.hip.h -- host side of the tracker's front end (xk_trk_*): the fundamental-matrix RANSAC filter of the matches
 // (tracker.cpp:233-293, camera.cpp:62-87; xk_fundamental.hip.h) and the pyramidal Lucas-Kanade tracking in front of it
 // (tracker.cpp:623-690; xk_klt.hip.h), the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h) and their
-// rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h).
+// rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h), and the photometric calibration of the images in front of
+// all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).
 // Part of xk_api.hip's translation unit, included at its end.
 #pragma once
 #include "xk_fast.hip.h"
 #include "xk_fundamental.hip.h"
 #include "xk_klt.hip.h"
 #include "xk_orb.hip.h"
+#include "xk_photo.hip.h"
 
 // The detection setup of an image size (xk_trk_detect_setup): it belongs to the xk_klt whose level-0 images it scans.
 struct xk_det {
@@ -35,6 +37,26 @@ struct xk_orb {
   signed char h_pattern[1024];
 };
 
+// The photometric setup of an image size (xk_trk_photo_setup): it belongs to the xk_klt whose images it calibrates.
+struct xk_photo {
+  int kernel_size, max_hyp;
+  double eps_gap, eps_base;
+  unsigned char *d_blk;       // raw slot 0 | raw slot 1 | PS | the i/o block | one XkRansacScratch per group
+  XkKltPyr raw[2];            // by slot, as xk_klt::slot: the images as pushed.  xk_klt::slot holds the working (corrected) ones
+  float *PS;                  // [height][pitch of level 0]
+  unsigned char *d_io;        // out: state | value | sum | count | the tracking's result block; in: previous intensities |
+  unsigned char *h_io;        //   previous points | pixels | o_hist | o_cur | off | frame_back.  Pinned, the same layout
+  size_t io_bytes, in_off;    // the in part starts at in_off
+  XkPhotoState *st;
+  double *value, *prev_int, *o_hist, *o_cur;
+  int *sum, *count, *ixy, *off, *frame_back;
+  float *pts;
+  unsigned char *klt_res;
+  XkRansacScratch sc[XK_PHOTO_MAX_GROUPS];
+  int ring_n, done;           // host mirrors of the state
+  int n_hyp[XK_PHOTO_MAX_GROUPS];   // hypotheses per group of the last call (0: none, or a group of <= 4)
+};
+
 struct xk_klt {
   int width, height, win_w, win_h, max_level, max_iter, levels;
   double eps, min_eig_thr;
@@ -48,6 +70,8 @@ struct xk_klt {
   hipEvent_t img_copied;      // the upload out of h_img: the next push waits for it before it refills the staging
   struct xk_det *det;         // xk_trk_detect_setup; NULL before.  It goes with this setup
   struct xk_orb *orb;         // xk_trk_describe_setup; likewise
+  struct xk_photo *photo;     // xk_trk_photo_setup; likewise
+  size_t slot_bytes;          // of one slot: its levels are one contiguous block
 };
 
 struct xk_trk {
@@ -92,9 +116,20 @@ static void orb_release(xk_orb *o) {
   free(o);
 }
 
+static void photo_release(xk_photo *p) {
+  if (!p) return;
+  hipFree(p->d_blk);
+  if (p->h_io) hipHostFree(p->h_io);
+  free(p);
+}
+
+// The slot's plane that a push fills first: the raw one with a photo setup, the only one without.
+static const XkKltPyr &photo_raw_slot(const xk_klt *k, int s) { return k->photo ? k->photo->raw[s] : k->slot[s]; }
+
 static void klt_release(xk_klt *k) {
   det_release(k->det);
   orb_release(k->orb);
+  photo_release(k->photo);
   hipFree(k->d_blk);
   if (k->h_img) hipHostFree(k->h_img);
   if (k->h_blk) hipHostFree(k->h_blk);
@@ -333,6 +368,7 @@ extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int
       p += 5 * plane;
     }
   }
+  k->slot_bytes = slot_bytes;
   k->d_pts = (float *)(k->d_blk + 2 * slot_bytes);
   k->d_res = k->d_blk + 2 * slot_bytes + pts_bytes;
   klt_free(t);
@@ -343,22 +379,8 @@ extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int
 /* levels of rule 1 (the pyramid has levels + 1 images), -1 before xk_trk_klt_setup */
 extern "C" int xk_trk_klt_levels(xk_trk *t) { return (t && t->klt) ? t->klt->levels : -1; }
 
-/* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
-extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  if (!k) return fail(h, XK_EINVAL, "xk_trk_push_image: before xk_trk_klt_setup");
-  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_push_image: null image or stride below the width");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int s = k->cur ^ 1;
-  const XkKltPyr &P = k->slot[s];
-  const size_t pitch0 = (size_t)P.lv[0].pitch;
-  if (k->orb) k->orb->blurred[s] = 0;                                        // (the other slot's blur stays with its slot)
-  if (k->pushed > 0) HIPCHK(h, hipEventSynchronize(k->img_copied));          // the staging is free again
-  for (int y = 0; y < k->height; ++y) memcpy(k->h_img + y * pitch0, img + (size_t)y * stride, (size_t)k->width);
-  HIPCHK(h, hipMemcpyAsync(P.lv[0].img, k->h_img, pitch0 * k->height, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(k->img_copied, h->stream));
+// Levels 1 ... of a slot from its level 0, and the Scharr derivatives of every level.
+static int klt_pyramid(xk_handle *h, const xk_klt *k, const XkKltPyr &P) {
   for (int l = 0; l <= k->levels; ++l) {
     const XkKltLevel &L = P.lv[l];
     if (l > 0) {
@@ -370,6 +392,29 @@ extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, XK_EDEVICE, "pyramid launch", e);
+  return XK_OK;
+}
+
+/* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
+extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_push_image: before xk_trk_klt_setup");
+  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_push_image: null image or stride below the width");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int s = k->cur ^ 1;
+  const XkKltPyr &P = k->slot[s];
+  const XkKltPyr &B = photo_raw_slot(k, s);                                  // where the pyramid is built: the raw plane with a photo setup
+  const size_t pitch0 = (size_t)P.lv[0].pitch;
+  if (k->orb) k->orb->blurred[s] = 0;                                        // (the other slot's blur stays with its slot)
+  if (k->pushed > 0) HIPCHK(h, hipEventSynchronize(k->img_copied));          // the staging is free again
+  for (int y = 0; y < k->height; ++y) memcpy(k->h_img + y * pitch0, img + (size_t)y * stride, (size_t)k->width);
+  HIPCHK(h, hipMemcpyAsync(B.lv[0].img, k->h_img, pitch0 * k->height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(k->img_copied, h->stream));
+  int rc = klt_pyramid(h, k, B);
+  if (rc != XK_OK) return rc;
+  if (k->photo) HIPCHK(h, hipMemcpyAsync(P.lv[0].img, B.lv[0].img, k->slot_bytes, hipMemcpyDeviceToDevice, h->stream));   // raw -> working
   k->cur = s;
   if (k->pushed < 2) ++k->pushed;
   return XK_OK;
@@ -714,4 +759,392 @@ extern "C" int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurre
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Photometric calibration of the images (tracker.cpp:761-877, irPhotoCalib.cpp), xk_photo.hip.h
+// ---------------------------------------------------------------------------
+static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+// The state as a reset leaves it, through the pinned block (the stream is idle afterwards).
+static int photo_state_reset(xk_handle *h, xk_photo *p) {
+  XkPhotoState *s = (XkPhotoState *)p->h_io;
+  memset(s, 0, sizeof *s);
+  s->ring[0] = 1.0; s->ring[1] = 0.0;                                             // irPhotoCalib.cpp:25
+  s->ring_n = 1;
+  HIPCHK(h, hipMemcpyAsync(p->st, s, sizeof *s, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  p->ring_n = 1; p->done = 0;
+  memset(p->n_hyp, 0, sizeof p->n_hyp);
+  return XK_OK;
+}
+
+/* The parameters of IRPhotoCalib and of Tracker::computeIntensity as Tracker holds them (tracker.h:366, irPhotoCalib.cpp:15-25), the
+ * raw planes, the spatial map and the parameter ring */
+extern "C" int xk_trk_photo_setup(xk_trk *t, int kernel_size, double epsilon_gap, double epsilon_base, int max_hyp) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_photo_setup: before xk_trk_klt_setup");
+  if (kernel_size < 2 || kernel_size > 64) return fail(h, XK_EINVAL, "xk_trk_photo_setup: kernel_size outside 2...64");
+  if (!(epsilon_gap >= 0.0 && epsilon_gap <= 1.0) || !(epsilon_base >= 0.0 && epsilon_base <= 1.0))
+    return fail(h, XK_EINVAL, "xk_trk_photo_setup: epsilon_gap or epsilon_base outside [0, 1]");
+  if (max_hyp < 1 || max_hyp > XK_PHOTO_MAX_HYP) return fail(h, XK_EINVAL, "xk_trk_photo_setup: max_hyp outside 1...4096");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_photo *p = (xk_photo *)calloc(1, sizeof(xk_photo));   // (built whole before the old one goes, as in xk_trk_klt_setup)
+  if (!p) return XK_ENOMEM;
+  p->kernel_size = kernel_size; p->max_hyp = max_hyp; p->eps_gap = epsilon_gap; p->eps_base = epsilon_base;
+  const size_t mm = (size_t)round_up(t->max_matches, 4), gm = XK_PHOTO_MAX_GROUPS * mm;
+  const size_t ps_bytes = sizeof(float) * (size_t)round_up(k->width, 16) * k->height;
+  const size_t sc_bytes = up16(xk_ransac_scratch_bytes<1>((size_t)max_hyp));
+  // the i/o block: every piece a multiple of 16 bytes
+  const size_t o_state = 0, o_value = up16(sizeof(XkPhotoState)), o_sum = o_value + 8 * mm, o_count = o_sum + 4 * mm,
+               o_klt = o_count + 4 * mm, o_prev = o_klt + up16(klt_res_bytes(t->max_matches)), o_pts = o_prev + 8 * mm, o_ixy = o_pts + 8 * mm,
+               o_hist = o_ixy + 8 * mm, o_cur = o_hist + 8 * gm, o_off = o_cur + 8 * gm, o_fb = o_off + 64, io_bytes = o_fb + 64;
+  const size_t dev_bytes = 2 * k->slot_bytes + ps_bytes + io_bytes + XK_PHOTO_MAX_GROUPS * sc_bytes;
+  void *dv = nullptr, *hb = nullptr;
+  bool ok = hipMalloc(&dv, dev_bytes) == hipSuccess && hipHostMalloc(&hb, io_bytes) == hipSuccess &&
+            hipMemsetAsync(dv, 0, dev_bytes, h->stream) == hipSuccess;               // (the raw planes' padding columns and PS: zeros)
+  p->d_blk = (unsigned char *)dv; p->h_io = (unsigned char *)hb;
+  if (ok) {
+    for (int s = 0; s < 2; ++s) {
+      p->raw[s] = k->slot[s];
+      for (int l = 0; l <= k->levels; ++l) {                                          // the same layout at another base
+        XkKltLevel &L = p->raw[s].lv[l];
+        const XkKltLevel &W = k->slot[s].lv[l];
+        unsigned char *base = p->d_blk + s * k->slot_bytes + (W.img - k->slot[s].lv[0].img);
+        const size_t plane = (size_t)W.pitch * W.h;
+        L.img = base; L.dx = (short *)(base + plane); L.dy = (short *)(base + 3 * plane);
+      }
+      // images pushed before this call are raw and working at once
+      ok = ok && hipMemcpyAsync(p->raw[s].lv[0].img, k->slot[s].lv[0].img, k->slot_bytes, hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
+    }
+    p->PS = (float *)(p->d_blk + 2 * k->slot_bytes);
+    p->d_io = p->d_blk + 2 * k->slot_bytes + ps_bytes;
+    p->io_bytes = io_bytes; p->in_off = o_prev;
+    p->st = (XkPhotoState *)(p->d_io + o_state);
+    p->value = (double *)(p->d_io + o_value); p->sum = (int *)(p->d_io + o_sum); p->count = (int *)(p->d_io + o_count);
+    p->klt_res = p->d_io + o_klt;
+    p->prev_int = (double *)(p->d_io + o_prev); p->pts = (float *)(p->d_io + o_pts); p->ixy = (int *)(p->d_io + o_ixy);
+    p->o_hist = (double *)(p->d_io + o_hist); p->o_cur = (double *)(p->d_io + o_cur);
+    p->off = (int *)(p->d_io + o_off); p->frame_back = (int *)(p->d_io + o_fb);
+    for (int g = 0; g < XK_PHOTO_MAX_GROUPS; ++g) p->sc[g] = xk_ransac_scratch<1>(p->d_io + io_bytes + g * sc_bytes, (size_t)max_hyp);
+    memset(p->h_io, 0, io_bytes);
+    ok = ok && photo_state_reset(h, p) == XK_OK;
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess) ok = false;                      // (an old setup is idle now)
+  if (!ok) {
+    photo_release(p);
+    return fail(h, XK_ENOMEM, "xk_trk_photo_setup: allocation failed");
+  }
+  photo_release(k->photo);
+  k->photo = p;
+  return XK_OK;
+}
+
+// the pinned mirror of a device pointer into the i/o block
+template <class T>
+static T *photo_host(const xk_photo *p, const T *dev) { return (T *)(p->h_io + ((const unsigned char *)dev - p->d_io)); }
+
+static xk_photo *photo_of(xk_trk *t, const char *who) {
+  xk_photo *p = t->klt ? t->klt->photo : nullptr;
+  if (!p) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s: before xk_trk_photo_setup", who);
+    fail(t->h, XK_EINVAL, msg);
+  }
+  return p;
+}
+
+static XkPhotoIntArgs photo_int_args(const xk_photo *p, const XkKltLevel &L, int n) {
+  XkPhotoIntArgs a{};
+  a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch; a.hk = p->kernel_size / 2;
+  a.xy = p->ixy; a.n = n; a.value = p->value; a.sum = p->sum; a.count = p->count;
+  return a;
+}
+
+/* Tracker::computeIntensity (tracker.cpp:860-877) of n pixels on level 0 of a slot's raw (plane = 0) or working (1) image */
+extern "C" int xk_trk_photo_intensity(xk_trk *t, int which, int plane, const int *xy, int n, double *value, int *sum, int *count) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_intensity");
+  if (!p) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (n < 0 || !value || !sum || !count || (n > 0 && !xy)) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: null argument or negative n");
+  if (which < 0 || which > 1 || plane < 0 || plane > 1) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: which and plane are 0 or 1");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: that image has not been pushed");
+  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_photo_intensity: more points than max_matches");
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int s = which == 1 ? k->cur : k->cur ^ 1;
+  const XkPhotoIntArgs a = photo_int_args(p, (plane == 0 ? p->raw[s] : k->slot[s]).lv[0], n);
+  memcpy(photo_host(p, p->ixy), xy, sizeof(int) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync(p->ixy, photo_host(p, p->ixy), sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_photo_intensity, dim3((n + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "intensity launch", e);
+  const size_t out_bytes = (size_t)((unsigned char *)p->klt_res - (unsigned char *)p->value);     // value | sum | count
+  HIPCHK(h, hipMemcpyAsync(photo_host(p, p->value), p->value, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  memcpy(value, photo_host(p, p->value), sizeof(double) * (size_t)n);
+  memcpy(sum, photo_host(p, p->sum), sizeof(int) * (size_t)n);
+  memcpy(count, photo_host(p, p->count), sizeof(int) * (size_t)n);
+  return XK_OK;
+}
+
+// The solve, score and refit of group g and, after the last group, the chain: queued, no wait.
+static int photo_queue_gains(xk_handle *h, xk_photo *p, XkPhotoGainArgs &a) {
+  for (int g = 0; g < a.G; ++g) {
+    a.g = g; a.sc = p->sc[g];
+    hipLaunchKernelGGL(xk_photo_solve, dim3((a.n_hyp + XK_PHOTO_SOLVE_T - 1) / XK_PHOTO_SOLVE_T), dim3(XK_PHOTO_SOLVE_T), 0, h->stream, a);
+    hipLaunchKernelGGL(xk_photo_score, dim3(a.n_hyp), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(xk_photo_refit, dim3(1), dim3(256), 0, h->stream, a);
+  }
+  hipLaunchKernelGGL(xk_photo_chain, dim3(1), dim3(64), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "gain estimation launch", e);
+  return XK_OK;
+}
+
+static XkPhotoGainArgs photo_gain_args(const xk_photo *p, int G, int n_hyp, unsigned long seed, int per_frame) {
+  XkPhotoGainArgs a{};
+  a.o_hist = p->o_hist; a.o_cur = per_frame ? p->value : p->o_cur;
+  a.off = p->off; a.frame_back = p->frame_back;
+  a.G = G; a.n_hyp = n_hyp; a.per_frame = per_frame; a.seed = (unsigned long long)seed;
+  a.eps_gap = p->eps_gap; a.eps_base = p->eps_base; a.st = p->st;
+  return a;
+}
+
+// the state out of the pinned block after a wait
+static int photo_state_out(xk_handle *h, xk_photo *p, int G, double *a_rel, double *b_rel, int *support, double *frame_ab) {
+  const XkPhotoState *s = (const XkPhotoState *)p->h_io;
+  if (s->ring_n < 1 || s->ring_n > XK_PHOTO_RING) return fail(h, XK_EDEVICE, "photometric state: ring size out of range");
+  p->ring_n = s->ring_n; p->done = s->done;
+  if (a_rel) memcpy(a_rel, s->a_rel, sizeof(double) * (size_t)G);
+  if (b_rel) memcpy(b_rel, s->b_rel, sizeof(double) * (size_t)G);
+  if (support) memcpy(support, s->support, sizeof(int) * (size_t)G);
+  if (frame_ab) memcpy(frame_ab, s->frame_ab, sizeof s->frame_ab);
+  return XK_OK;
+}
+
+/* IRPhotoCalib::ProcessCurrentFrame (irPhotoCalib.cpp:95-160, :212-218) with EstimateGainsRansac (:221-312) per group */
+extern "C" int xk_trk_photo_gains(xk_trk *t, int G, const int *off, const double *o_hist, const double *o_cur, const int *frame_back, int n_hyp,
+                                  unsigned long seed, double *a_rel, double *b_rel, int *support, double *frame_ab) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_gains");
+  if (!p) return XK_EINVAL;
+  if (G < 1 || G > XK_PHOTO_MAX_GROUPS) return fail(h, XK_EINVAL, "xk_trk_photo_gains: G outside 1...14");
+  if (!off || !frame_back || !a_rel || !b_rel || !support || !frame_ab) return fail(h, XK_EINVAL, "xk_trk_photo_gains: null argument");
+  if (n_hyp < 1 || n_hyp > p->max_hyp) return fail(h, XK_EINVAL, "xk_trk_photo_gains: n_hyp outside 1...max_hyp");
+  if (off[0] != 0) return fail(h, XK_EINVAL, "xk_trk_photo_gains: off[0] is not 0");
+  for (int g = 0; g < G; ++g) {
+    if (off[g + 1] < off[g]) return fail(h, XK_EINVAL, "xk_trk_photo_gains: off is not ascending");
+    if (off[g + 1] - off[g] > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_photo_gains: a group of more points than max_matches");
+    if (frame_back[g] < 1 || frame_back[g] > p->ring_n) return fail(h, XK_EINVAL, "xk_trk_photo_gains: frame_back outside 1...the ring's size");
+  }
+  const int total = off[G];
+  if (total > 0 && (!o_hist || !o_cur)) return fail(h, XK_EINVAL, "xk_trk_photo_gains: null argument");
+  HIPCHK(h, hipSetDevice(h->device));
+  // one copy in: o_hist | o_cur | off | frame_back are adjacent, the lists at their full stride
+  memcpy(photo_host(p, p->o_hist), o_hist, sizeof(double) * (size_t)total);
+  memcpy(photo_host(p, p->o_cur), o_cur, sizeof(double) * (size_t)total);
+  memcpy(photo_host(p, p->off), off, sizeof(int) * (size_t)(G + 1));
+  memcpy(photo_host(p, p->frame_back), frame_back, sizeof(int) * (size_t)G);
+  const size_t in_at = (size_t)((unsigned char *)p->o_hist - p->d_io);
+  HIPCHK(h, hipMemcpyAsync(p->o_hist, p->h_io + in_at, p->io_bytes - in_at, hipMemcpyHostToDevice, h->stream));
+  XkPhotoGainArgs a = photo_gain_args(p, G, n_hyp, seed, 0);
+  memset(p->n_hyp, 0, sizeof p->n_hyp);
+  int rc = photo_queue_gains(h, p, a);
+  if (rc != XK_OK) return rc;
+  HIPCHK(h, hipMemcpyAsync(p->h_io, p->st, sizeof(XkPhotoState), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int g = 0; g < G; ++g) p->n_hyp[g] = off[g + 1] - off[g] > 4 ? n_hyp : 0;
+  return photo_state_out(h, p, G, a_rel, b_rel, support, frame_ab);
+}
+
+/* What the last gain estimate left for hypotheses first ... first+count-1 of group g.  Straight copies */
+extern "C" int xk_trk_photo_hypotheses(xk_trk *t, int g, int first, int count, double *ab, int *inliers) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_hypotheses");
+  if (!p) return XK_EINVAL;
+  if (g < 0 || g >= XK_PHOTO_MAX_GROUPS) return fail(h, XK_EINVAL, "xk_trk_photo_hypotheses: no such group");
+  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_trk_photo_hypotheses: negative range");
+  if (first + (long)count > p->n_hyp[g]) return fail(h, XK_EINVAL, "xk_trk_photo_hypotheses: range outside the hypotheses of the last estimate");
+  if (count == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkRansacScratch &s = p->sc[g];
+  if (ab) HIPCHK(h, hipMemcpy2DAsync(ab, 2 * sizeof(double), s.cand + 9 * (size_t)first, 9 * sizeof(double), 2 * sizeof(double), (size_t)count,
+                                    hipMemcpyDeviceToHost, h->stream));
+  if (inliers) HIPCHK(h, hipMemcpyAsync(inliers, s.cnt + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+/* params_PT_ (irPhotoCalib.cpp:25, :213-218): the ring's pairs, oldest first.  A straight copy */
+extern "C" int xk_trk_photo_params(xk_trk *t, double *a, double *b, int *count) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_params");
+  if (!p) return XK_EINVAL;
+  if (!count) return fail(h, XK_EINVAL, "xk_trk_photo_params: null argument");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(p->h_io, p->st, sizeof(XkPhotoState), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const XkPhotoState *s = (const XkPhotoState *)p->h_io;
+  if (s->ring_n < 1 || s->ring_n > XK_PHOTO_RING) return fail(h, XK_EDEVICE, "xk_trk_photo_params: ring size out of range");
+  *count = s->ring_n;
+  for (int i = 0; i < s->ring_n; ++i) {
+    if (a) a[i] = s->ring[2 * i];
+    if (b) b[i] = s->ring[2 * i + 1];
+  }
+  return XK_OK;
+}
+
+/* The ring back to its one entry (1, 0), no gains estimated yet */
+extern "C" int xk_trk_photo_reset(xk_trk *t) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_reset");
+  if (!p) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));                                       // (the pinned block is free)
+  return photo_state_reset(h, p);
+}
+
+/* params_PS_ (irPhotoCalib.cpp:36): the caller's spatial map, float32 [height][width]; NULL: zeros */
+extern "C" int xk_trk_photo_set_spatial(xk_trk *t, const float *ps) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_set_spatial");
+  if (!p) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t pitch = sizeof(float) * (size_t)round_up(k->width, 16);
+  if (ps) HIPCHK(h, hipMemcpy2DAsync(p->PS, pitch, ps, sizeof(float) * (size_t)k->width, sizeof(float) * (size_t)k->width, (size_t)k->height,
+                                    hipMemcpyHostToDevice, h->stream));
+  else HIPCHK(h, hipMemsetAsync(p->PS, 0, pitch * k->height, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));                                       // (the caller's array is free again)
+  return XK_OK;
+}
+
+// The correction of slot s queued: level 0 of the working plane from the raw one, then its pyramid and derivatives.
+static int photo_queue_correct(xk_handle *h, xk_klt *k, int s, int per_frame) {
+  xk_photo *p = k->photo;
+  const XkKltLevel &R = p->raw[s].lv[0], &W = k->slot[s].lv[0];
+  XkPhotoCorrectArgs a{};
+  a.raw = R.img; a.out = W.img; a.PS = p->PS; a.w = W.w; a.h = W.h; a.pitch = W.pitch; a.per_frame = per_frame; a.st = p->st;
+  const int threads = (W.pitch / 16) * W.h;
+  hipLaunchKernelGGL(xk_photo_correct, dim3((threads + 255) / 256), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "correction launch", e);
+  if (k->orb) k->orb->blurred[s] = 0;
+  return klt_pyramid(h, k, k->slot[s]);
+}
+
+/* IRPhotoCalib::getCorrectedImage (irPhotoCalib.cpp:442-472) of the previous (which = 0) or the current (1) image, with the ring's
+ * last pair */
+extern "C" int xk_trk_photo_correct(xk_trk *t, int which) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_correct");
+  if (!p) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_photo_correct: which is 0 or 1");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_photo_correct: that image has not been pushed");
+  HIPCHK(h, hipSetDevice(h->device));
+  return photo_queue_correct(h, k, which == 1 ? k->cur : k->cur ^ 1, 0);
+}
+
+/* Level 0 of a slot's raw plane: the image as pushed.  A straight copy */
+extern "C" int xk_trk_photo_raw(xk_trk *t, int which, unsigned char *img) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_raw");
+  if (!p) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (which < 0 || which > 1 || !img) return fail(h, XK_EINVAL, "xk_trk_photo_raw: which is 0 or 1, img not NULL");
+  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_photo_raw: that image has not been pushed");
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkKltLevel &L = p->raw[which == 1 ? k->cur : k->cur ^ 1].lv[0];
+  HIPCHK(h, hipMemcpy2DAsync(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+/* Tracker::calibrateImage (tracker.cpp:761-858): track the previous features between the RAW images, their intensities in the
+ * current one, the gain estimate against the previous intensities, the correction of the current image */
+extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const double *prev_intensity, int n, int n_hyp, unsigned long seed,
+                                      int *keep_idx, double *intensity, int *sum, int *count, int *n_kept, double *a_rel, double *b_rel,
+                                      int *support, double *frame_ab, int *estimated) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = photo_of(t, "xk_trk_photo_calibrate");
+  if (!p) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (n < 0 || !keep_idx || !intensity || !sum || !count || !n_kept || !a_rel || !b_rel || !support || !frame_ab || !estimated ||
+      (n > 0 && (!prev_xy || !prev_intensity)))
+    return fail(h, XK_EINVAL, "xk_trk_photo_calibrate: null argument or negative n");
+  if (n_hyp < 1 || n_hyp > p->max_hyp) return fail(h, XK_EINVAL, "xk_trk_photo_calibrate: n_hyp outside 1...max_hyp");
+  if (k->pushed < 2) return fail(h, XK_EINVAL, "xk_trk_photo_calibrate: fewer than two images pushed");
+  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_photo_calibrate: more features than max_matches");
+  *n_kept = 0; *estimated = 0;
+  *a_rel = 1.0; *b_rel = 0.0; *support = 0;
+  memset(frame_ab, 0, 4 * sizeof(double));
+  memset(p->n_hyp, 0, sizeof p->n_hyp);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (n < 4) {                                                   // tracker.cpp:763: corrected only after an earlier estimate
+    if (!p->done) return XK_OK;
+    const int rc = photo_queue_correct(h, k, k->cur, 1);
+    if (rc != XK_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return XK_OK;
+  }
+  XkKltArgs a{};
+  a.prev = p->raw[k->cur ^ 1]; a.cur = p->raw[k->cur];
+  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
+  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
+  a.pts = p->pts;
+  a.cur_xy = (double *)p->klt_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
+  a.kept = xk_kept_pairs(a.min_eig + n, n);
+  a.status = xk_kept_pairs_end(a.kept, n);
+  // one copy in: previous intensities | previous points
+  memcpy(photo_host(p, p->prev_int), prev_intensity, sizeof(double) * (size_t)n);
+  memcpy(photo_host(p, p->pts), prev_xy, sizeof(float) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync(p->prev_int, photo_host(p, p->prev_int), (size_t)((unsigned char *)p->ixy - (unsigned char *)p->prev_int),
+                           hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
+  XkPhotoGatherArgs ga{};
+  ga.kept = a.kept; ga.prev_intensity = p->prev_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
+  hipLaunchKernelGGL(xk_photo_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, ga);
+  XkPhotoIntArgs ia = photo_int_args(p, p->raw[k->cur].lv[0], n);
+  ia.n_dev = a.kept.res;
+  hipLaunchKernelGGL(xk_photo_intensity, dim3((n + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, ia);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "calibration launch", e);
+  XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp, seed, 1);
+  int rc = photo_queue_gains(h, p, g);
+  if (rc != XK_OK) return rc;
+  rc = photo_queue_correct(h, k, k->cur, 1);
+  if (rc != XK_OK) return rc;
+  // one copy out: state | value | sum | count | the tracking's result block
+  const size_t out_bytes = (size_t)(p->klt_res - p->d_io) + klt_res_bytes(n);
+  HIPCHK(h, hipMemcpyAsync(p->h_io, p->d_io, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const unsigned char *r = photo_host(p, p->klt_res);
+  int kept = 0;
+  memcpy(&kept, r + ((unsigned char *)a.kept.res - p->klt_res), sizeof(int));
+  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_photo_calibrate: kept count out of range");
+  *n_kept = kept;
+  memcpy(keep_idx, r + ((unsigned char *)a.kept.keep_idx - p->klt_res), sizeof(int) * (size_t)kept);
+  memcpy(intensity, photo_host(p, p->value), sizeof(double) * (size_t)kept);
+  memcpy(sum, photo_host(p, p->sum), sizeof(int) * (size_t)kept);
+  memcpy(count, photo_host(p, p->count), sizeof(int) * (size_t)kept);
+  const XkPhotoState *s = (const XkPhotoState *)p->h_io;
+  *estimated = s->estimated;
+  if (kept > 4) p->n_hyp[0] = n_hyp;
+  if (!s->estimated) return photo_state_out(h, p, 0, nullptr, nullptr, nullptr, nullptr);
+  return photo_state_out(h, p, 1, a_rel, b_rel, support, frame_ab);
 }

@@ -7,10 +7,11 @@ manager sees it.
 from two images and the previous features to the pairs that filter takes.  `Klt.detect` produces those features:
 `Tracker::featureDetection` (tracker.cpp:390-590), FAST and the neighbourhood selection on a pushed image, and
 `Klt.describe` their rotated-BRIEF descriptors (`PlaceRecognition::compute`, place_recognition.cpp:72-94), which is what
-place.Database takes.
+place.Database takes.  `Klt.photo_*` is the photometric calibration a PHOTOMETRIC_CALI build runs in front of all of them
+(`Tracker::calibrateImage`, tracker.cpp:761-877, and IRPhotoCalib): photo_calibrate between push_image and track.
 
 No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h, csrc/xk_fast.hip.h,
-csrc/xk_orb.hip.h)."""
+csrc/xk_orb.hip.h, csrc/xk_photo.hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -249,3 +250,106 @@ class Klt:
         G, pat = np.zeros((self.height, self.width), np.uint8), np.zeros((256, 4), np.int8)
         self._chk(self.L.xk_trk_describe_stage(self.p, C.c_int(which), G.ctypes.data_as(c_ub), pat.ctypes.data_as(c_sb)), "xk_trk_describe_stage")
         return G, pat
+
+    # ---- photometric calibration (Tracker::calibrateImage, tracker.cpp:761-877; irPhotoCalib.cpp), csrc/xk_photo.hip.h ----
+    def photo_setup(self, kernel_size=30, epsilon_gap=0.0, epsilon_base=0.0, max_hyp=512):
+        """xk_trk_photo_setup: the raw plane of both image slots, the spatial map (zeros), the parameter ring (one entry (1, 0))
+        and the scratch of a gain estimate of up to max_hyp hypotheses.  A later setup() drops it."""
+        self._chk(self.L.xk_trk_photo_setup(self.p, C.c_int(kernel_size), C.c_double(epsilon_gap), C.c_double(epsilon_base), C.c_int(max_hyp)),
+                  "xk_trk_photo_setup")
+        self.photo_max_hyp = int(max_hyp)
+
+    def photo_intensity(self, xy, which=1, plane=1):
+        """Tracker::computeIntensity (tracker.cpp:860-877) at the pixels xy (int32 [n, 2]) of the previous (which = 0) or current
+        (1) image, its raw (plane = 0) or working (1) plane -> (value fp64 [n], sum int32 [n], count int32 [n])."""
+        pts = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n, m = len(pts), max(len(pts), 1)
+        value, s, c = np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        self._chk(self.L.xk_trk_photo_intensity(self.p, C.c_int(which), C.c_int(plane), pts.ctypes.data_as(c_ip), C.c_int(n),
+                                                value.ctypes.data_as(c_dp), s.ctypes.data_as(c_ip), c.ctypes.data_as(c_ip)),
+                  "xk_trk_photo_intensity")
+        return value[:n], s[:n], c[:n]
+
+    def photo_gains(self, o_hist, o_cur, frame_back=(1,), n_hyp=None, seed=0):
+        """IRPhotoCalib::ProcessCurrentFrame (irPhotoCalib.cpp:95-160, :212-218): o_hist, o_cur are lists of G arrays (or one
+        array: one group), frame_back one int per group; n_hyp None: min(the largest group, max_hyp), at least 1 -> dict of
+        a_rel, b_rel fp64 [G], support int32 [G], frame_ab fp64 [4]."""
+        if not isinstance(o_hist, (list, tuple)):
+            o_hist, o_cur = [o_hist], [o_cur]
+        oh = [np.ascontiguousarray(v, np.float64).ravel() for v in o_hist]
+        oc = [np.ascontiguousarray(v, np.float64).ravel() for v in o_cur]
+        if len(oh) != len(oc) or len(oh) != len(frame_back) or any(len(a) != len(b) for a, b in zip(oh, oc)):
+            raise ValueError("photo_gains: o_hist, o_cur and frame_back differ in length")
+        G = len(oh)
+        off = np.zeros(G + 1, np.int32)
+        off[1:] = np.cumsum([len(v) for v in oh])
+        H = np.concatenate(oh + [np.zeros(1)])
+        Cu = np.concatenate(oc + [np.zeros(1)])
+        fb = np.ascontiguousarray(frame_back, np.int32)
+        if n_hyp is None:
+            n_hyp = max(1, min(max(len(v) for v in oh), self.photo_max_hyp))
+        a, b, sup, fab = np.zeros(max(G, 1)), np.zeros(max(G, 1)), np.zeros(max(G, 1), np.int32), np.zeros(4)
+        self._chk(self.L.xk_trk_photo_gains(self.p, C.c_int(G), off.ctypes.data_as(c_ip), H.ctypes.data_as(c_dp), Cu.ctypes.data_as(c_dp),
+                                            fb.ctypes.data_as(c_ip), C.c_int(n_hyp), C.c_ulong(seed), a.ctypes.data_as(c_dp),
+                                            b.ctypes.data_as(c_dp), sup.ctypes.data_as(c_ip), fab.ctypes.data_as(c_dp)), "xk_trk_photo_gains")
+        return dict(a_rel=a[:G], b_rel=b[:G], support=sup[:G], frame_ab=fab)
+
+    def photo_hypotheses(self, g, first, count):
+        """What the last gain estimate left for hypotheses first ... first+count-1 of group g -> (ab fp64 [count, 2], inliers
+        int32 [count])."""
+        ab, inl = np.zeros((max(count, 1), 2)), np.zeros(max(count, 1), np.int32)
+        self._chk(self.L.xk_trk_photo_hypotheses(self.p, C.c_int(g), C.c_int(first), C.c_int(count), ab.ctypes.data_as(c_dp),
+                                                 inl.ctypes.data_as(c_ip)), "xk_trk_photo_hypotheses")
+        return ab[:count], inl[:count]
+
+    def photo_params(self):
+        """The parameter ring, oldest first -> fp64 [count, 2] of (a, b)."""
+        a, b, n = np.zeros(15), np.zeros(15), C.c_int(0)
+        self._chk(self.L.xk_trk_photo_params(self.p, a.ctypes.data_as(c_dp), b.ctypes.data_as(c_dp), C.byref(n)), "xk_trk_photo_params")
+        return np.stack([a[:n.value], b[:n.value]], axis=1)
+
+    def photo_reset(self):
+        """The ring back to (1, 0)."""
+        self._chk(self.L.xk_trk_photo_reset(self.p), "xk_trk_photo_reset")
+
+    def photo_set_spatial(self, ps=None):
+        """The spatial map params_PS_: float32 [height, width], None: zeros."""
+        pp = None
+        if ps is not None:
+            ps = np.ascontiguousarray(ps, np.float32)
+            if ps.shape != (self.height, self.width):
+                raise ValueError("photo_set_spatial: the map is float32 [height, width]")
+            pp = ps.ctypes.data_as(c_fp)
+        self._chk(self.L.xk_trk_photo_set_spatial(self.p, pp), "xk_trk_photo_set_spatial")
+
+    def photo_correct(self, which=1):
+        """IRPhotoCalib::getCorrectedImage of the previous (which = 0) or current (1) image with the ring's last pair."""
+        self._chk(self.L.xk_trk_photo_correct(self.p, C.c_int(which)), "xk_trk_photo_correct")
+
+    def photo_raw(self, which=1):
+        """Level 0 of the raw plane -> uint8 [height, width], the image as pushed."""
+        img = np.zeros((self.height, self.width), np.uint8)
+        self._chk(self.L.xk_trk_photo_raw(self.p, C.c_int(which), img.ctypes.data_as(c_ub)), "xk_trk_photo_raw")
+        return img
+
+    def photo_calibrate(self, prev_xy, prev_intensity, n_hyp=None, seed=0):
+        """Tracker::calibrateImage (tracker.cpp:761-858), between push_image and track: float32 pixels [n, 2] of the previous
+        features and their intensities fp64 [n] -> dict of keep_idx int32 [m], intensity fp64 [m], sum, count int32 [m] (the
+        kept features in the raw current image), a_rel, b_rel, support, frame_ab fp64 [4], estimated (bool).  n_hyp None:
+        min(n, max_hyp), at least 1."""
+        prev = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+        pin = np.ascontiguousarray(prev_intensity, np.float64).ravel()
+        if len(prev) != len(pin):
+            raise ValueError("photo_calibrate: prev_xy and prev_intensity differ in length")
+        n, m = len(prev), max(len(prev), 1)
+        if n_hyp is None:
+            n_hyp = max(1, min(n, self.photo_max_hyp))
+        keep, val, s, c = np.zeros(m, np.int32), np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        nk, a, b, sup, est, fab = C.c_int(0), C.c_double(0), C.c_double(0), C.c_int(0), C.c_int(0), np.zeros(4)
+        self._chk(self.L.xk_trk_photo_calibrate(self.p, prev.ctypes.data_as(c_fp), pin.ctypes.data_as(c_dp), C.c_int(n), C.c_int(n_hyp),
+                                                C.c_ulong(seed), keep.ctypes.data_as(c_ip), val.ctypes.data_as(c_dp), s.ctypes.data_as(c_ip),
+                                                c.ctypes.data_as(c_ip), C.byref(nk), C.byref(a), C.byref(b), C.byref(sup),
+                                                fab.ctypes.data_as(c_dp), C.byref(est)), "xk_trk_photo_calibrate")
+        k = nk.value
+        return dict(keep_idx=keep[:k].copy(), intensity=val[:k].copy(), sum=s[:k].copy(), count=c[:k].copy(), a_rel=a.value, b_rel=b.value,
+                    support=sup.value, frame_ab=fab, estimated=bool(est.value))
