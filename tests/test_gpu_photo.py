@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fast_cases as fc
 import klt_cases as kc
 import klt_np as knp
 import orb_np as onp
@@ -369,3 +370,49 @@ def test_without_a_photo_setup_nothing_changes(eng):
     for a, b in zip(l0, l1):
         for x, y in zip(a, b):
             assert x.tobytes() == y.tobytes()
+
+
+def test_replacing_each_setup_leaves_the_others_working(eng):
+    """The detection, description and photo setups alive on one xk_trk while each is replaced by one of the same parameters: every
+    entry returns the bytes it returned before.  By design one thing changes: a new photo setup starts its ring over at (1, 0).
+    A new xk_trk_klt_setup then drops all three."""
+    im = fc.dots_image()
+    k = make(eng, (96, 48), 32, (5, 5), 0)
+    setups = dict(detect=lambda: k.detect_setup(9, True, 5, 4, 2048), describe=lambda: k.describe_setup(0, -1.0, 25, None, 64),
+                  photo=lambda: k.photo_setup(30, 0.0, 0.0, 8))
+
+    def blobs(v):
+        if isinstance(v, dict):
+            return [blobs(v[key]) for key in sorted(v)]
+        if isinstance(v, (tuple, list)):
+            return [blobs(x) for x in v]
+        return np.asarray(v).tobytes()
+
+    def calls():
+        det = k.detect(1)
+        xy = det["xy"]
+        return xy, blobs([det, k.describe(xy, 0), k.describe(xy, 1), k.track(xy.astype(np.float32)), k.photo_intensity(xy, 1, 0),
+                          k.photo_intensity(xy, 1, 1), k.photo_raw(1), k.describe_stage(0), k.describe_stage(1)])
+
+    try:
+        for f in setups.values():
+            f()
+        k.push_image(im)
+        k.push_image(im)
+        o, p, _ = pc.gain_data(4, 1)
+        k.photo_gains(o, p, (1,), 4, 0)                                          # the ring advances: two entries
+        assert len(k.photo_params()) == 2
+        xy, record = calls()
+        assert len(xy) == len(fc.restated("dots")["xy"]) > 0                     # (the calls had something to return)
+        for name, f in setups.items():
+            f()
+            assert calls()[1] == record, name
+            assert len(k.photo_params()) == (1 if name == "photo" else 2), name
+        assert k.photo_params().tobytes() == np.array([[1.0, 0.0]]).tobytes()   # the exception: the new photo setup's ring
+        k.setup(96, 48, (5, 5), 0)
+        for entry in (lambda: k.detect(1), lambda: k.describe(xy, 1), lambda: k.photo_raw(1)):
+            with pytest.raises(tracker.XkError) as e:
+                entry()
+            assert e.value.status == XK_EINVAL
+    finally:
+        k.close()

@@ -3,6 +3,9 @@
 // (tracker.cpp:623-690; xk_klt.hip.h), the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h) and their
 // rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h), and the photometric calibration of the images in front of
 // all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).
+// Every stage keeps its buffers in one xk_block (a device block and its pinned mirror, carved once by the stage's setup, which stores
+// every pointer an entry needs) and reaches them through the same helpers: sub_of (the stage's setup or XK_EINVAL), img_slot (the
+// slot of the previous or the current image or XK_EINVAL), launched (the check behind a group of launches), kept_count_out, setup_install.
 // Part of xk_api.hip's translation unit, included at its end.
 #pragma once
 #include "xk_fast.hip.h"
@@ -11,29 +14,86 @@
 #include "xk_orb.hip.h"
 #include "xk_photo.hip.h"
 
+#define XKCHK(call)                          \
+  do {                                       \
+    const int rc_ = (call);                  \
+    if (rc_ != XK_OK) return rc_;            \
+  } while (0)
+
+static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+// "<who>: <what>" as the handle's message
+static int fail_at(xk_handle *h, int code, const char *who, const char *what) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return fail(h, code, msg);
+}
+
+// the check behind a group of launches
+static int launched(xk_handle *h, const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? XK_OK : fail(h, XK_EDEVICE, what, e);
+}
+
+// A device block and its pinned mirror: what every stage below allocates once per setup and carves into its buffers.
+struct xk_block {
+  unsigned char *d, *h;
+  size_t d_bytes, h_bytes;
+};
+
+static void blk_free(xk_block &b) {
+  hipFree(b.d);
+  if (b.h) hipHostFree(b.h);
+  b = xk_block{};
+}
+
+// Both blocks of `who`, zeroed: the pinned one here, the device one on the handle's stream (queued, not waited for).
+// The images in these blocks have their rows padded to a pitch.  NO kernel may read the padding columns [w, pitch): xk_klt_pyrdown
+// takes four bytes at once only where x + 3 < w, xk_klt_track's plain taps only where the whole window lies inside the image,
+// everything else goes through the mirror or a bounds test.  Nothing writes them either (level 0's come from the staging, which copies
+// w bytes per row; the blur and the correction write w columns), so they are zeroed once here: a later vectorised load that strays
+// into the padding reads zeros, not what was there before.  The same holds for the padding between the pieces of a block.
+static int blk_alloc(xk_handle *h, xk_block &b, size_t d_bytes, size_t h_bytes, const char *who) {
+  b = xk_block{nullptr, nullptr, d_bytes, h_bytes};
+  if (hipMalloc((void **)&b.d, d_bytes) == hipSuccess && hipHostMalloc((void **)&b.h, h_bytes) == hipSuccess &&
+      hipMemsetAsync(b.d, 0, d_bytes, h->stream) == hipSuccess) {
+    memset(b.h, 0, h_bytes);
+    return XK_OK;
+  }
+  blk_free(b);
+  return fail_at(h, XK_ENOMEM, who, "allocation failed");
+}
+
+// The next piece of a block: `bytes` at base + off, and off moves on by them rounded up to 16.
+template <class T>
+static T *carve(unsigned char *base, size_t &off, size_t bytes) {
+  T *p = (T *)(base + off);
+  off += up16(bytes);
+  return p;
+}
+
 // The detection setup of an image size (xk_trk_detect_setup): it belongs to the xk_klt whose level-0 images it scans.
 struct xk_det {
   int threshold, nms, b, margin, max_candidates;
   int key_cap, wpr;
   size_t lds_bytes;           // of xk_fast_select: the keys, and the blocked mask behind them when both fit
-  unsigned char *d_blk;       // S | keys | counter | old features | result block | blocked mask (when it does not fit the LDS)
-  unsigned char *S;
+  xk_block blk;                 // device: S | keys | counter | old features | result block | blocked mask (when it does not fit the LDS)
+  unsigned char *S;           // pinned: old features in (2 max_matches doubles), then the result block out, at h_res
   unsigned int *keys, *mask_g;
-  int *count, *res;
+  int *count, *res, *h_res;
   double *old_xy;
-  unsigned char *h_blk;       // pinned: old features in (2 max_matches doubles), then the result block out
   int n_cand;                 // candidates of the last detection (-1: none yet)
 };
 
 // The description setup of an image size (xk_trk_describe_setup): it belongs to the xk_klt whose level-0 images it describes.
 struct xk_orb {
   int centroid, A, B, edge, max_desc;
-  unsigned char *d_blk;       // G of slot 0 | G of slot 1 | pattern | keypoints in | kept keypoints | result block
+  xk_block blk;                 // device: G of slot 0 | G of slot 1 | pattern | keypoints in | kept keypoints | result block
   unsigned char *G[2];        // by slot, as xk_klt::slot: a push swaps the roles of the slots, not their buffers
   int blurred[2];             // G[s] holds the blur of the image in slot s.  xk_trk_push_image clears the flag of the slot it fills
   signed char *pattern;
   int *xy, *kept_xy, *res;
-  unsigned char *h_blk;       // pinned: keypoints in (2 max_desc ints), then the result block out
+  unsigned char *h_res;       // pinned: keypoints in (2 max_desc ints), then the result block out, at h_res
   signed char h_pattern[1024];
 };
 
@@ -41,12 +101,11 @@ struct xk_orb {
 struct xk_photo {
   int kernel_size, max_hyp;
   double eps_gap, eps_base;
-  unsigned char *d_blk;       // raw slot 0 | raw slot 1 | PS | the i/o block | one XkRansacScratch per group
+  xk_block blk;                 // device: raw slot 0 | raw slot 1 | PS | the i/o block | one XkRansacScratch per group
   XkKltPyr raw[2];            // by slot, as xk_klt::slot: the images as pushed.  xk_klt::slot holds the working (corrected) ones
   float *PS;                  // [height][pitch of level 0]
   unsigned char *d_io;        // out: state | value | sum | count | the tracking's result block; in: previous intensities |
-  unsigned char *h_io;        //   previous points | pixels | o_hist | o_cur | off | frame_back.  Pinned, the same layout
-  size_t io_bytes, in_off;    // the in part starts at in_off
+                              //   previous points | pixels | o_hist | o_cur | off | frame_back.  blk.h is its mirror, the same layout
   XkPhotoState *st;
   double *value, *prev_int, *o_hist, *o_cur;
   int *sum, *count, *ixy, *off, *frame_back;
@@ -60,13 +119,13 @@ struct xk_photo {
 struct xk_klt {
   int width, height, win_w, win_h, max_level, max_iter, levels;
   double eps, min_eig_thr;
-  unsigned char *d_blk;       // slot 0 | slot 1 | previous points (floats) | result block
+  xk_block blk;                 // device: slot 0 | slot 1 | previous points (floats) | result block
   XkKltPyr slot[2];           // per slot and level: image, dIx, dIy at the level's pitch
   int cur, pushed;            // the slot of the current image; images pushed since the setup, counted to 2
   float *d_pts;
   unsigned char *d_res;       // cur_xy | min_eig | XkKeptPairs | status, packed per call
+  unsigned char *h_res;       // pinned: previous points in, then the result block out, at h_res
   unsigned char *h_img;       // pinned: one image at level 0's pitch
-  unsigned char *h_blk;       // pinned: previous points in, then the result block out
   hipEvent_t img_copied;      // the upload out of h_img: the next push waits for it before it refills the staging
   struct xk_det *det;         // xk_trk_detect_setup; NULL before.  It goes with this setup
   struct xk_orb *orb;         // xk_trk_describe_setup; likewise
@@ -78,9 +137,11 @@ struct xk_trk {
   xk_handle *h;
   int max_matches;
   double fx, fy, cx, cy, s, s_term;
-  double *d_blk;              // distorted / undistorted / float-cast points [4 max_matches] each, XkRansacScratch; then the result block
-  unsigned char *d_res;       // result block inside d_blk: F | XkKeptPairs | mask, packed per call
-  unsigned char *h_blk;       // pinned: points in (4 max_matches doubles), then the result block out
+  xk_block blk;                 // device: distorted / undistorted / float-cast points [4 max_matches doubles] each, XkRansacScratch, result block
+  double *dist, *und, *pts;
+  XkRansacScratch sc;
+  unsigned char *d_res;       // the result block: F | XkKeptPairs | mask, packed per call
+  unsigned char *h_res;       // pinned: points in (4 max_matches doubles), then the result block out, at h_res
   int n_hyp;                  // hypotheses of the last RANSAC (0: none yet)
   struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
 };
@@ -89,69 +150,91 @@ struct xk_trk {
 static size_t trk_res_bytes(int n) { return sizeof(double) * 9 + xk_kept_pairs_bytes(n) + (size_t)n; }
 static size_t klt_res_bytes(int n) { return sizeof(double) * 3 * (size_t)n + xk_kept_pairs_bytes(n) + (size_t)n; }
 
-// The kept pairs of a result block out of its pinned copy r (the device block starts at d_res): 0 <= kept <= n or `range_msg`.
-static int kept_pairs_out(xk_handle *h, const XkKeptPairs &k, const unsigned char *d_res, const unsigned char *r, int n, const char *range_msg,
-                          int *keep_idx, double *prev_xy, double *cur_xy, int *n_kept) {
+// The count at `at` in a result block's pinned copy: 0 <= count <= n, or XK_EDEVICE.
+static int kept_count_out(xk_handle *h, const char *who, const void *at, int n, int *n_kept) {
   int kept = 0;
-  memcpy(&kept, r + ((unsigned char *)k.res - d_res), sizeof(int));
-  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, range_msg);
+  memcpy(&kept, at, sizeof(int));
+  if (kept < 0 || kept > n) return fail_at(h, XK_EDEVICE, who, "kept count out of range");
   *n_kept = kept;
-  memcpy(keep_idx, r + ((unsigned char *)k.keep_idx - d_res), sizeof(int) * (size_t)kept);
-  memcpy(prev_xy, r + ((unsigned char *)k.kept_prev - d_res), sizeof(double) * 2 * (size_t)kept);
-  memcpy(cur_xy, r + ((unsigned char *)k.kept_cur - d_res), sizeof(double) * 2 * (size_t)kept);
   return XK_OK;
 }
 
-static void det_release(xk_det *d) {
-  if (!d) return;
-  hipFree(d->d_blk);
-  if (d->h_blk) hipHostFree(d->h_blk);
-  free(d);
+// The kept pairs of a result block out of its pinned copy r (the device block starts at d_res).
+static int kept_pairs_out(xk_handle *h, const char *who, const XkKeptPairs &k, const unsigned char *d_res, const unsigned char *r, int n,
+                          int *keep_idx, double *prev_xy, double *cur_xy, int *n_kept) {
+  XKCHK(kept_count_out(h, who, r + ((unsigned char *)k.res - d_res), n, n_kept));
+  memcpy(keep_idx, r + ((unsigned char *)k.keep_idx - d_res), sizeof(int) * (size_t)*n_kept);
+  memcpy(prev_xy, r + ((unsigned char *)k.kept_prev - d_res), sizeof(double) * 2 * (size_t)*n_kept);
+  memcpy(cur_xy, r + ((unsigned char *)k.kept_cur - d_res), sizeof(double) * 2 * (size_t)*n_kept);
+  return XK_OK;
 }
 
-static void orb_release(xk_orb *o) {
-  if (!o) return;
-  hipFree(o->d_blk);
-  if (o->h_blk) hipHostFree(o->h_blk);
-  free(o);
-}
-
-static void photo_release(xk_photo *p) {
+// xk_det, xk_orb, xk_photo: a block and nothing else to give back
+template <class T>
+static void setup_free(T *p) {
   if (!p) return;
-  hipFree(p->d_blk);
-  if (p->h_io) hipHostFree(p->h_io);
+  blk_free(p->blk);
   free(p);
 }
 
-// The slot's plane that a push fills first: the raw one with a photo setup, the only one without.
-static const XkKltPyr &photo_raw_slot(const xk_klt *k, int s) { return k->photo ? k->photo->raw[s] : k->slot[s]; }
-
-static void klt_release(xk_klt *k) {
-  det_release(k->det);
-  orb_release(k->orb);
-  photo_release(k->photo);
-  hipFree(k->d_blk);
+static void setup_free(xk_klt *k) {
+  if (!k) return;
+  setup_free(k->det);
+  setup_free(k->orb);
+  setup_free(k->photo);
+  blk_free(k->blk);
   if (k->h_img) hipHostFree(k->h_img);
-  if (k->h_blk) hipHostFree(k->h_blk);
   if (k->img_copied) hipEventDestroy(k->img_copied);
   free(k);
 }
 
-static void klt_free(xk_trk *t) {
-  if (!t->klt) return;
-  hipStreamSynchronize(t->h->stream);
-  klt_release(t->klt);
-  t->klt = nullptr;
+// The end of every setup.  The new state was built whole (rc says how that went); one wait, after which the staging is free and the
+// old state idle; then the old one goes and the new one takes its place.  A failure leaves the old one where it is.
+template <class T>
+static int setup_install(xk_handle *h, int rc, const char *who, T *&old, T *fresh) {
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == XK_OK) rc = fail_at(h, XK_ENOMEM, who, "allocation failed");
+  if (rc != XK_OK) {
+    setup_free(fresh);
+    return rc;
+  }
+  setup_free(old);
+  old = fresh;
+  return XK_OK;
 }
+
+// The setup of entry `who` that `setup` makes (xk_klt::det, orb or photo), or nullptr after fail(XK_EINVAL).
+template <class T>
+static T *sub_of(xk_trk *t, T *xk_klt::*sub, const char *who, const char *setup) {
+  T *p = t->klt ? t->klt->*sub : nullptr;
+  if (!p) {
+    char what[64];
+    snprintf(what, sizeof what, "before %s", setup);
+    fail_at(t->h, XK_EINVAL, who, what);
+  }
+  return p;
+}
+
+// The slot of the previous (which = 0) or the current (1) image for entry `who`, or -1 after fail(XK_EINVAL).
+static int img_slot(xk_trk *t, const char *who, int which) {
+  const xk_klt *k = t->klt;
+  const char *what = !k ? "before xk_trk_klt_setup" : which < 0 || which > 1 ? "which is 0 or 1" :
+                     k->pushed < 2 - which ? "that image has not been pushed" : nullptr;
+  if (!what) return which == 1 ? k->cur : k->cur ^ 1;
+  fail_at(t->h, XK_EINVAL, who, what);
+  return -1;
+}
+
+// The slot's plane that a push fills first: the raw one with a photo setup, the only one without.
+static const XkKltPyr &photo_raw_slot(const xk_klt *k, int s) { return k->photo ? k->photo->raw[s] : k->slot[s]; }
 
 // ---------------------------------------------------------------------------
 // Fundamental-matrix RANSAC filter of the tracker's matches (tracker.cpp:233-293, camera.cpp:62-87), xk_fundamental.hip.h
 // ---------------------------------------------------------------------------
 extern "C" void xk_trk_destroy(xk_trk *t) {
   if (!t) return;
-  klt_free(t);
-  hipFree(t->d_blk);
-  if (t->h_blk) hipHostFree(t->h_blk);
+  if (t->klt) hipStreamSynchronize(t->h->stream);
+  setup_free(t->klt);
+  blk_free(t->blk);
   free(t);
 }
 
@@ -167,25 +250,24 @@ extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy
   t->fx = fx; t->fy = fy; t->cx = cx; t->cy = cy; t->s = s;
   t->s_term = s != 0.0 ? 1.0 / (2.0 * std::tan(s / 2.0)) : 0.0;        // camera.cpp:39
   const size_t pts = sizeof(double) * 4 * (size_t)max_matches;
-  const size_t head = 3 * pts + xk_ransac_scratch_bytes<XK_FUND_MAXC>(XK_FUND_MAX_HYP);   // (a multiple of 8)
-  void *d = nullptr, *hp = nullptr;
-  if (hipMalloc(&d, head + trk_res_bytes(max_matches)) != hipSuccess || hipHostMalloc(&hp, pts + trk_res_bytes(max_matches)) != hipSuccess) {
-    hipFree(d);
+  const size_t head = 3 * pts + xk_ransac_scratch_bytes<XK_FUND_MAXC>(XK_FUND_MAX_HYP);
+  const int rc = blk_alloc(h, t->blk, head + trk_res_bytes(max_matches), pts + trk_res_bytes(max_matches), "xk_trk_create");
+  if (rc != XK_OK) {
     free(t);
-    return fail(h, XK_ENOMEM, "xk_trk_create: allocation failed");
+    return rc;
   }
-  t->d_blk = (double *)d;
-  t->d_res = (unsigned char *)d + head;
-  t->h_blk = (unsigned char *)hp;
+  size_t off = 0;
+  t->dist = carve<double>(t->blk.d, off, pts); t->und = carve<double>(t->blk.d, off, pts); t->pts = carve<double>(t->blk.d, off, pts);
+  t->sc = xk_ransac_scratch<XK_FUND_MAXC>(t->blk.d + off, XK_FUND_MAX_HYP);
+  t->d_res = t->blk.d + head;                                            // (a multiple of 8: doubles first, and the scratch is not padded)
+  t->h_res = t->blk.h + pts;
   *out = t;
   return XK_OK;
 }
 
 static XkFundArgs trk_args(xk_trk *t, int n) {
   XkFundArgs a{};
-  const size_t m4 = 4 * (size_t)t->max_matches;
-  a.dist = t->d_blk; a.und = t->d_blk + m4; a.pts = t->d_blk + 2 * m4;
-  a.sc = xk_ransac_scratch<XK_FUND_MAXC>(t->d_blk + 3 * m4, XK_FUND_MAX_HYP);
+  a.dist = t->dist; a.und = t->und; a.pts = t->pts; a.sc = t->sc;
   a.F = (double *)t->d_res;
   a.kept = xk_kept_pairs(a.F + 9, n);
   a.mask = xk_kept_pairs_end(a.kept, n);
@@ -204,14 +286,13 @@ extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double 
   HIPCHK(h, hipSetDevice(h->device));
   XkFundArgs a = trk_args(t, 0);
   a.n_pts = n;
-  memcpy(t->h_blk, dist_xy, sizeof(double) * 2 * (size_t)n);
-  HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->h_blk, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  memcpy(t->blk.h, dist_xy, sizeof(double) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->blk.h, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(xk_fund_undistort, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "undistort launch", e);
-  HIPCHK(h, hipMemcpyAsync(t->h_blk, a.und, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  XKCHK(launched(h, "undistort launch"));
+  HIPCHK(h, hipMemcpyAsync(t->blk.h, a.und, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  memcpy(xy, t->h_blk, sizeof(double) * 2 * (size_t)n);
+  memcpy(xy, t->blk.h, sizeof(double) * 2 * (size_t)n);
   return XK_OK;
 }
 
@@ -225,31 +306,26 @@ static int trk_run(xk_trk *t, XkFundArgs &a, bool undistort, double threshold_px
   a.seed = (unsigned long long)seed;
   if (!undistort) a.und = a.pts;
   t->n_hyp = 0;
-  HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->h_blk, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->blk.h, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * n + 255) / 256), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "fundamental RANSAC launch", e);
-  HIPCHK(h, hipMemcpyAsync(t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
+  XKCHK(launched(h, "fundamental RANSAC launch"));
+  HIPCHK(h, hipMemcpyAsync(t->h_res, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   t->n_hyp = n_hyp;
   return XK_OK;
 }
 
 static int trk_check(xk_trk *t, const char *who, int n, double threshold_px, int n_hyp, bool nulls) {
-  xk_handle *h = t->h;
-  char msg[160];
   const char *what = nullptr;
   int rc = XK_EINVAL;
   if (nulls || n < 0) what = "null argument or negative n";
   else if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) what = "threshold_px < 0";
   else if (n_hyp < 1 || n_hyp > XK_FUND_MAX_HYP) what = "n_hyp outside 1...4096";
   else if (n > t->max_matches) { what = "more point pairs than max_matches"; rc = XK_ECAPACITY; }
-  if (!what) return XK_OK;
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return fail(h, rc, msg);
+  return what ? fail_at(t->h, rc, who, what) : XK_OK;
 }
 
 /* cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) (tracker.cpp:243-260) */
@@ -257,19 +333,17 @@ extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const 
                                          unsigned long seed, unsigned char *mask, double *F, int *n_inliers) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  int rc = trk_check(t, "xk_trk_fundamental_ransac", n, threshold_px, n_hyp, !mask || !n_inliers || (n > 0 && (!prev_xy || !cur_xy)));
-  if (rc != XK_OK) return rc;
+  XKCHK(trk_check(t, "xk_trk_fundamental_ransac", n, threshold_px, n_hyp, !mask || !n_inliers || (n > 0 && (!prev_xy || !cur_xy))));
   *n_inliers = 0;
   memset(mask, 0, (size_t)n);
   if (F) memset(F, 0, 9 * sizeof(double));
   if (n < 7) { t->n_hyp = 0; return XK_OK; }                 // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
   HIPCHK(h, hipSetDevice(h->device));
   XkFundArgs a = trk_args(t, n);
-  double *h_pts = (double *)t->h_blk;
+  double *h_pts = (double *)t->blk.h;
   for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
-  rc = trk_run(t, a, false, threshold_px, n_hyp, seed);
-  if (rc != XK_OK) return rc;
-  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
+  XKCHK(trk_run(t, a, false, threshold_px, n_hyp, seed));
+  const unsigned char *r = t->h_res;
   if (F) memcpy(F, r, 9 * sizeof(double));
   memcpy(n_inliers, r + ((unsigned char *)a.kept.res - t->d_res), sizeof(int));
   memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
@@ -289,21 +363,18 @@ extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, cons
                                      int *n_inliers) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  int rc = trk_check(t, "xk_trk_filter_matches", n, threshold_px, n_hyp,
-                     !mask || !keep_idx || !prev_xy || !cur_xy || !n_inliers || (n > 0 && (!prev_dist_xy || !cur_dist_xy)));
-  if (rc != XK_OK) return rc;
+  XKCHK(trk_check(t, "xk_trk_filter_matches", n, threshold_px, n_hyp,
+                     !mask || !keep_idx || !prev_xy || !cur_xy || !n_inliers || (n > 0 && (!prev_dist_xy || !cur_dist_xy))));
   *n_inliers = 0;
   memset(mask, 0, (size_t)n);
   if (n < 7) { t->n_hyp = 0; return XK_OK; }
   HIPCHK(h, hipSetDevice(h->device));
   XkFundArgs a = trk_args(t, n);
-  memcpy(t->h_blk, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
-  memcpy(t->h_blk + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
-  rc = trk_run(t, a, true, threshold_px, n_hyp, seed);
-  if (rc != XK_OK) return rc;
-  const unsigned char *r = t->h_blk + sizeof(double) * 4 * (size_t)t->max_matches;
-  rc = kept_pairs_out(h, a.kept, t->d_res, r, n, "xk_trk_filter_matches: inlier count out of range", keep_idx, prev_xy, cur_xy, n_inliers);
-  if (rc != XK_OK) return rc;
+  memcpy(t->blk.h, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
+  memcpy(t->blk.h + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
+  XKCHK(trk_run(t, a, true, threshold_px, n_hyp, seed));
+  const unsigned char *r = t->h_res;
+  XKCHK(kept_pairs_out(h, "xk_trk_filter_matches", a.kept, t->d_res, r, n, keep_idx, prev_xy, cur_xy, n_inliers));
   memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
   return XK_OK;
 }
@@ -311,6 +382,16 @@ extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, cons
 // ---------------------------------------------------------------------------
 // Pyramidal Lucas-Kanade tracking of the tracker's features (tracker.cpp:623-690), xk_klt.hip.h
 // ---------------------------------------------------------------------------
+// The planes of a slot's levels (w, h and pitch are set) from `base` on: per level the image, then dIx and dIy.
+static void klt_place(XkKltPyr &P, int levels, unsigned char *base) {
+  for (int l = 0; l <= levels; ++l) {
+    XkKltLevel &L = P.lv[l];
+    const size_t plane = (size_t)L.pitch * L.h;
+    L.img = base; L.dx = (short *)(base + plane); L.dy = (short *)(base + 3 * plane);
+    base += 5 * plane;
+  }
+}
+
 // Rule 1 of DESIGN 3.11: the largest l <= max_level with W_k > win_w and H_k > win_h for every k <= l; -1 if level 0 fails.
 static int klt_count_levels(int w, int h, int win_w, int win_h, int max_level) {
   int lv = -1;
@@ -332,48 +413,34 @@ extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int
   const int levels = klt_count_levels(width, height, win_w, win_h, max_level);
   if (levels < 0) return fail(h, XK_EINVAL, "xk_trk_klt_setup: the window does not fit the image");
   HIPCHK(h, hipSetDevice(h->device));
-  xk_klt *k = (xk_klt *)calloc(1, sizeof(xk_klt));      // (the new state is built whole before the old one goes: a failure leaves the old one in place)
+  xk_klt *k = (xk_klt *)calloc(1, sizeof(xk_klt));
   if (!k) return XK_ENOMEM;
   k->width = width; k->height = height; k->win_w = win_w; k->win_h = win_h; k->max_level = max_level; k->max_iter = max_iter;
   k->levels = levels; k->eps = eps; k->min_eig_thr = min_eig_thr;
   k->cur = 0; k->pushed = 0;
-  size_t slot_bytes = 0;                                          // per level: pitch h bytes of image, then two planes of shorts
-  for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) slot_bytes += 5 * (size_t)round_up(w, 16) * hh;
-  const size_t pts_bytes = (sizeof(float) * 2 * (size_t)t->max_matches + 15) / 16 * 16;
-  const size_t pitch0 = (size_t)round_up(width, 16);
-  // Every plane's rows are padded to the pitch.  NO kernel may read the padding columns [w, pitch): xk_klt_pyrdown takes four bytes
-  // at once only where x + 3 < w, xk_klt_track's plain taps only where the whole window lies inside the image, everything else goes
-  // through the mirror or a bounds test.  Nothing writes them either (level 0's come from the staging, which copies w bytes per row),
-  // so both blocks are zeroed once here: a later vectorised load that strays into the padding reads zeros, not what was there before.
-  const size_t dev_bytes = 2 * slot_bytes + pts_bytes + klt_res_bytes(t->max_matches);
-  void *d = nullptr, *hi = nullptr, *hb = nullptr;
-  if (hipMalloc(&d, dev_bytes) != hipSuccess || hipHostMalloc(&hi, pitch0 * height) != hipSuccess ||
-      hipHostMalloc(&hb, pts_bytes + klt_res_bytes(t->max_matches)) != hipSuccess ||
-      hipEventCreateWithFlags(&k->img_copied, hipEventDisableTiming) != hipSuccess ||
-      hipMemsetAsync(d, 0, dev_bytes, h->stream) != hipSuccess) {
-    k->d_blk = (unsigned char *)d; k->h_img = (unsigned char *)hi; k->h_blk = (unsigned char *)hb;
-    hipStreamSynchronize(h->stream);
-    klt_release(k);
-    return fail(h, XK_ENOMEM, "xk_trk_klt_setup: allocation failed");
+  XkKltPyr P{};                                                   // per level: pitch h bytes of image, then two planes of shorts
+  for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) {
+    P.lv[l].w = w; P.lv[l].h = hh; P.lv[l].pitch = round_up(w, 16);
+    k->slot_bytes += 5 * (size_t)P.lv[l].pitch * hh;
   }
-  memset(hi, 0, pitch0 * height);
-  k->d_blk = (unsigned char *)d; k->h_img = (unsigned char *)hi; k->h_blk = (unsigned char *)hb;
-  for (int s = 0; s < 2; ++s) {
-    unsigned char *p = k->d_blk + s * slot_bytes;
-    for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) {
-      XkKltLevel &L = k->slot[s].lv[l];
-      L.w = w; L.h = hh; L.pitch = round_up(w, 16);
-      const size_t plane = (size_t)L.pitch * hh;
-      L.img = p; L.dx = (short *)(p + plane); L.dy = (short *)(p + 3 * plane);
-      p += 5 * plane;
+  const size_t pts_bytes = up16(sizeof(float) * 2 * (size_t)t->max_matches), res_bytes = klt_res_bytes(t->max_matches);
+  const size_t img_bytes = (size_t)P.lv[0].pitch * height;
+  int rc = blk_alloc(h, k->blk, 2 * k->slot_bytes + pts_bytes + res_bytes, pts_bytes + res_bytes, "xk_trk_klt_setup");
+  if (rc == XK_OK && (hipHostMalloc((void **)&k->h_img, img_bytes) != hipSuccess ||
+                      hipEventCreateWithFlags(&k->img_copied, hipEventDisableTiming) != hipSuccess))
+    rc = fail(h, XK_ENOMEM, "xk_trk_klt_setup: allocation failed");
+  if (rc == XK_OK) {
+    memset(k->h_img, 0, img_bytes);                               // (the staging's padding columns, as blk_alloc's)
+    size_t off = 0;
+    for (int s = 0; s < 2; ++s) {
+      k->slot[s] = P;
+      klt_place(k->slot[s], levels, carve<unsigned char>(k->blk.d, off, k->slot_bytes));
     }
+    k->d_pts = carve<float>(k->blk.d, off, pts_bytes);
+    k->d_res = k->blk.d + off;
+    k->h_res = k->blk.h + pts_bytes;
   }
-  k->slot_bytes = slot_bytes;
-  k->d_pts = (float *)(k->d_blk + 2 * slot_bytes);
-  k->d_res = k->d_blk + 2 * slot_bytes + pts_bytes;
-  klt_free(t);
-  t->klt = k;
-  return XK_OK;
+  return setup_install(h, rc, "xk_trk_klt_setup", t->klt, k);             // (the old setup's detection, description and photo setups go with it)
 }
 
 /* levels of rule 1 (the pyramid has levels + 1 images), -1 before xk_trk_klt_setup */
@@ -390,9 +457,7 @@ static int klt_pyramid(xk_handle *h, const xk_klt *k, const XkKltPyr &P) {
     }
     hipLaunchKernelGGL(xk_klt_scharr, dim3((L.w + 63) / 64, (L.h + 3) / 4), dim3(256), 0, h->stream, L.img, L.w, L.h, L.pitch, L.dx, L.dy);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "pyramid launch", e);
-  return XK_OK;
+  return launched(h, "pyramid launch");
 }
 
 /* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
@@ -412,12 +477,27 @@ extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride
   for (int y = 0; y < k->height; ++y) memcpy(k->h_img + y * pitch0, img + (size_t)y * stride, (size_t)k->width);
   HIPCHK(h, hipMemcpyAsync(B.lv[0].img, k->h_img, pitch0 * k->height, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(k->img_copied, h->stream));
-  int rc = klt_pyramid(h, k, B);
-  if (rc != XK_OK) return rc;
+  XKCHK(klt_pyramid(h, k, B));
   if (k->photo) HIPCHK(h, hipMemcpyAsync(P.lv[0].img, B.lv[0].img, k->slot_bytes, hipMemcpyDeviceToDevice, h->stream));   // raw -> working
   k->cur = s;
   if (k->pushed < 2) ++k->pushed;
   return XK_OK;
+}
+
+// The tracking of the n points at d_pts from pyramid `prev` to `cur`, queued: the result block (klt_res_bytes(n)) goes to d_res.
+static int klt_queue_track(xk_handle *h, const xk_klt *k, const XkKltPyr &prev, const XkKltPyr &cur, const float *d_pts, unsigned char *d_res,
+                           int n, XkKltArgs &a) {
+  a = XkKltArgs{};
+  a.prev = prev; a.cur = cur;
+  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
+  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
+  a.pts = d_pts;
+  a.cur_xy = (double *)d_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
+  a.kept = xk_kept_pairs(a.min_eig + n, n);
+  a.status = xk_kept_pairs_end(a.kept, n);
+  hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
+  return launched(h, "feature tracking launch");
 }
 
 /* Tracker::featureTracking (tracker.cpp:623-690): cv::calcOpticalFlowPyrLK from the previous image to the current one, then the
@@ -435,26 +515,14 @@ extern "C" int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_
   *n_kept = 0;
   if (n == 0) return XK_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  XkKltArgs a{};
-  a.prev = k->slot[k->cur ^ 1]; a.cur = k->slot[k->cur];
-  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
-  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
-  a.pts = k->d_pts;
-  a.cur_xy = (double *)k->d_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
-  a.kept = xk_kept_pairs(a.min_eig + n, n);
-  a.status = xk_kept_pairs_end(a.kept, n);
-  const size_t pts_bytes = (sizeof(float) * 2 * (size_t)t->max_matches + 15) / 16 * 16;
-  memcpy(k->h_blk, prev_xy, sizeof(float) * 2 * (size_t)n);
-  HIPCHK(h, hipMemcpyAsync(k->d_pts, k->h_blk, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "feature tracking launch", e);
-  unsigned char *r = k->h_blk + pts_bytes;
-  HIPCHK(h, hipMemcpyAsync(r, k->d_res, klt_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
+  memcpy(k->blk.h, prev_xy, sizeof(float) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync(k->d_pts, k->blk.h, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  XkKltArgs a;
+  XKCHK(klt_queue_track(h, k, k->slot[k->cur ^ 1], k->slot[k->cur], k->d_pts, k->d_res, n, a));
+  const unsigned char *r = k->h_res;
+  HIPCHK(h, hipMemcpyAsync(k->h_res, k->d_res, klt_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int rc = kept_pairs_out(h, a.kept, k->d_res, r, n, "xk_trk_track: kept count out of range", keep_idx, kept_prev_xy, kept_cur_xy, n_kept);
-  if (rc != XK_OK) return rc;
+  XKCHK(kept_pairs_out(h, "xk_trk_track", a.kept, k->d_res, r, n, keep_idx, kept_prev_xy, kept_cur_xy, n_kept));
   memcpy(cur_xy, r, sizeof(double) * 2 * (size_t)n);
   memcpy(min_eig, r + ((unsigned char *)a.min_eig - k->d_res), sizeof(double) * (size_t)n);
   memcpy(status, r + (a.status - k->d_res), (size_t)n);
@@ -465,12 +533,11 @@ extern "C" int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_
 extern "C" int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short *dIx, short *dIy, int *w, int *hgt) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  if (!k) return fail(h, XK_EINVAL, "xk_trk_klt_level: before xk_trk_klt_setup");
-  if (which < 0 || which > 1 || level < 0 || level > k->levels) return fail(h, XK_EINVAL, "xk_trk_klt_level: no such image or level");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_klt_level: that image has not been pushed");
+  const int s = img_slot(t, "xk_trk_klt_level", which);
+  if (s < 0) return XK_EINVAL;
+  if (level < 0 || level > t->klt->levels) return fail(h, XK_EINVAL, "xk_trk_klt_level: no such level");
   HIPCHK(h, hipSetDevice(h->device));
-  const XkKltLevel &L = k->slot[which == 1 ? k->cur : k->cur ^ 1].lv[level];
+  const XkKltLevel &L = t->klt->slot[s].lv[level];
   if (w) *w = L.w;
   if (hgt) *hgt = L.h;
   if (img) HIPCHK(h, hipMemcpy2DAsync(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
@@ -497,7 +564,7 @@ extern "C" int xk_trk_detect_setup(xk_trk *t, int threshold, int non_max_supp, i
   if (margin < 0 || margin > 4096) return fail(h, XK_EINVAL, "xk_trk_detect_setup: margin outside 0...4096");
   if (max_candidates < 1 || max_candidates > XK_FAST_MAX_CAND) return fail(h, XK_EINVAL, "xk_trk_detect_setup: max_candidates outside 1...32768");
   HIPCHK(h, hipSetDevice(h->device));
-  xk_det *d = (xk_det *)calloc(1, sizeof(xk_det));      // (built whole before the old one goes, as in xk_trk_klt_setup)
+  xk_det *d = (xk_det *)calloc(1, sizeof(xk_det));
   if (!d) return XK_ENOMEM;
   d->threshold = threshold; d->nms = non_max_supp; d->b = block_half_length; d->margin = margin; d->max_candidates = max_candidates;
   d->n_cand = -1;
@@ -507,52 +574,39 @@ extern "C" int xk_trk_detect_setup(xk_trk *t, int threshold, int non_max_supp, i
   const size_t key_lds = sizeof(unsigned int) * (size_t)d->key_cap, mask_bytes = sizeof(unsigned int) * (size_t)d->wpr * k->height;
   const bool mask_in_lds = key_lds + mask_bytes <= XK_FAST_LDS_MAX;
   d->lds_bytes = key_lds + (mask_in_lds ? mask_bytes : 0);
-  const size_t pitch0 = (size_t)round_up(k->width, 16);
-  const size_t s_bytes = pitch0 * k->height;                                     // (a multiple of 16, as every offset below)
-  const size_t keys_bytes = sizeof(unsigned int) * (size_t)round_up(max_candidates, 4);
-  const size_t old_bytes = sizeof(double) * 2 * (size_t)t->max_matches;
-  const size_t res_bytes = (det_res_bytes(t->max_matches) + 15) / 16 * 16;
-  const size_t dev_bytes = s_bytes + keys_bytes + 16 + old_bytes + res_bytes + (mask_in_lds ? 0 : mask_bytes);
-  void *dv = nullptr, *hb = nullptr;
-  if (hipMalloc(&dv, dev_bytes) != hipSuccess || hipHostMalloc(&hb, old_bytes + res_bytes) != hipSuccess ||
-      hipMemsetAsync(dv, 0, dev_bytes, h->stream) != hipSuccess ||
-      hipFuncSetAttribute((const void *)xk_fast_select, hipFuncAttributeMaxDynamicSharedMemorySize, XK_FAST_LDS_MAX) != hipSuccess) {
-    d->d_blk = (unsigned char *)dv; d->h_blk = (unsigned char *)hb;
-    hipStreamSynchronize(h->stream);
-    det_release(d);
-    return fail(h, XK_ENOMEM, "xk_trk_detect_setup: allocation failed");
+  const size_t s_bytes = (size_t)k->slot[0].lv[0].pitch * k->height, keys_bytes = up16(sizeof(unsigned int) * (size_t)max_candidates);
+  const size_t old_bytes = sizeof(double) * 2 * (size_t)t->max_matches, res_bytes = up16(det_res_bytes(t->max_matches));
+  int rc = blk_alloc(h, d->blk, s_bytes + keys_bytes + 16 + old_bytes + res_bytes + (mask_in_lds ? 0 : mask_bytes), old_bytes + res_bytes,
+                     "xk_trk_detect_setup");
+  if (rc == XK_OK && hipFuncSetAttribute((const void *)xk_fast_select, hipFuncAttributeMaxDynamicSharedMemorySize, XK_FAST_LDS_MAX) != hipSuccess)
+    rc = fail(h, XK_ENOMEM, "xk_trk_detect_setup: allocation failed");
+  if (rc == XK_OK) {
+    size_t off = 0;
+    d->S = carve<unsigned char>(d->blk.d, off, s_bytes);
+    d->keys = carve<unsigned int>(d->blk.d, off, keys_bytes);
+    d->count = carve<int>(d->blk.d, off, sizeof(int));
+    d->old_xy = carve<double>(d->blk.d, off, old_bytes);
+    d->res = carve<int>(d->blk.d, off, res_bytes);
+    d->mask_g = mask_in_lds ? nullptr : carve<unsigned int>(d->blk.d, off, mask_bytes);
+    d->h_res = (int *)(d->blk.h + old_bytes);
   }
-  d->d_blk = (unsigned char *)dv; d->h_blk = (unsigned char *)hb;
-  unsigned char *p = d->d_blk;
-  d->S = p; p += s_bytes;
-  d->keys = (unsigned int *)p; p += keys_bytes;
-  d->count = (int *)p; p += 16;
-  d->old_xy = (double *)p; p += old_bytes;
-  d->res = (int *)p; p += res_bytes;
-  d->mask_g = mask_in_lds ? nullptr : (unsigned int *)p;
-  if (k->det) {
-    hipStreamSynchronize(h->stream);
-    det_release(k->det);
-  }
-  k->det = d;
-  return XK_OK;
+  return setup_install(h, rc, "xk_trk_detect_setup", k->det, d);
 }
 
 /* Tracker::featureDetection (tracker.cpp:390-590) on level 0 of the previous (which = 0) or the current (1) image */
 extern "C" int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_old, int *xy, int *score, int *n_found, int *n_candidates) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  xk_det *d = k ? k->det : nullptr;
-  if (!d) return fail(h, XK_EINVAL, "xk_trk_detect: before xk_trk_detect_setup");
+  xk_det *d = sub_of(t, &xk_klt::det, "xk_trk_detect", "xk_trk_detect_setup");
+  if (!d) return XK_EINVAL;
   if (!xy || !score || !n_found || !n_candidates || n_old < 0 || (n_old > 0 && !old_xy))
     return fail(h, XK_EINVAL, "xk_trk_detect: null argument or negative n_old");
-  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_detect: which is 0 or 1");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_detect: that image has not been pushed");
+  const int s = img_slot(t, "xk_trk_detect", which);
+  if (s < 0) return XK_EINVAL;
   *n_found = 0; *n_candidates = 0;
   if (n_old > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_detect: more old features than max_matches");
   HIPCHK(h, hipSetDevice(h->device));
-  const XkKltLevel &L = k->slot[which == 1 ? k->cur : k->cur ^ 1].lv[0];
+  const XkKltLevel &L = t->klt->slot[s].lv[0];
   XkFastArgs a{};
   a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
   a.S = d->S; a.keys = d->keys; a.count = d->count; a.mask_g = d->mask_g; a.key_cap = d->key_cap; a.wpr = d->wpr;
@@ -562,19 +616,18 @@ extern "C" int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_o
   a.res = d->res;
   d->n_cand = -1;
   if (n_old > 0) {
-    memcpy(d->h_blk, old_xy, sizeof(double) * 2 * (size_t)n_old);
-    HIPCHK(h, hipMemcpyAsync(d->old_xy, d->h_blk, sizeof(double) * 2 * (size_t)n_old, hipMemcpyHostToDevice, h->stream));
+    memcpy(d->blk.h, old_xy, sizeof(double) * 2 * (size_t)n_old);
+    HIPCHK(h, hipMemcpyAsync(d->old_xy, d->blk.h, sizeof(double) * 2 * (size_t)n_old, hipMemcpyHostToDevice, h->stream));
   }
   hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fast_select, dim3(1), dim3(XK_FAST_SEL_T), d->lds_bytes, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "detection launch", e);
+  XKCHK(launched(h, "detection launch"));
   // accepted points are pairwise more than b apart: at most ceil(W / (b + 1)) ceil(H / (b + 1)) of them come back
   const long long bound = (long long)((a.w + d->b) / (d->b + 1)) * ((a.h + d->b) / (d->b + 1));
   const int cap = (int)std::min<long long>(bound, t->max_matches);
-  int *r = (int *)(d->h_blk + sizeof(double) * 2 * (size_t)t->max_matches);
-  HIPCHK(h, hipMemcpyAsync(r, d->res, det_res_bytes(t->max_matches), hipMemcpyDeviceToHost, h->stream));
+  const int *r = d->h_res;
+  HIPCHK(h, hipMemcpyAsync(d->h_res, d->res, det_res_bytes(t->max_matches), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const int found = r[0], cand = r[1];
   if (found < 0 || cand < 0 || (cand <= d->max_candidates && found > cand)) return fail(h, XK_EDEVICE, "xk_trk_detect: counts out of range");
@@ -591,13 +644,13 @@ extern "C" int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_o
 extern "C" int xk_trk_detect_stage(xk_trk *t, unsigned char *scores, unsigned int *keys, int *n_candidates) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  xk_det *d = k ? k->det : nullptr;
-  if (!d || d->n_cand < 0) return fail(h, XK_EINVAL, "xk_trk_detect_stage: before a detection");
+  xk_det *d = sub_of(t, &xk_klt::det, "xk_trk_detect_stage", "xk_trk_detect_setup");
+  if (!d) return XK_EINVAL;
+  if (d->n_cand < 0) return fail(h, XK_EINVAL, "xk_trk_detect_stage: before a detection");
   HIPCHK(h, hipSetDevice(h->device));
   if (n_candidates) *n_candidates = d->n_cand;
-  const size_t pitch0 = (size_t)round_up(k->width, 16);
-  if (scores) HIPCHK(h, hipMemcpy2DAsync(scores, (size_t)k->width, d->S, pitch0, (size_t)k->width, (size_t)k->height, hipMemcpyDeviceToHost, h->stream));
+  const XkKltLevel &L = t->klt->slot[0].lv[0];
+  if (scores) HIPCHK(h, hipMemcpy2DAsync(scores, (size_t)L.w, d->S, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
   if (keys && d->n_cand > 0 && d->n_cand <= d->max_candidates)
     HIPCHK(h, hipMemcpyAsync(keys, d->keys, sizeof(unsigned int) * (size_t)d->n_cand, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -642,58 +695,45 @@ extern "C" int xk_trk_describe_setup(xk_trk *t, int orientation, double angle_de
       if (r[0] == r[2] && r[1] == r[3]) return fail(h, XK_EINVAL, "xk_trk_describe_setup: a pattern row whose two points coincide");
     }
   HIPCHK(h, hipSetDevice(h->device));
-  xk_orb *o = (xk_orb *)calloc(1, sizeof(xk_orb));      // (built whole before the old one goes, as in xk_trk_klt_setup)
+  xk_orb *o = (xk_orb *)calloc(1, sizeof(xk_orb));
   if (!o) return XK_ENOMEM;
   o->centroid = orientation; o->edge = edge; o->max_desc = max_desc;
   const double th = angle_deg * (M_PI / 180.0);
   o->A = (int)std::rint(16384.0 * std::cos(th)); o->B = (int)std::rint(16384.0 * std::sin(th));
   if (pattern) memcpy(o->h_pattern, pattern, sizeof o->h_pattern);
   else orb_default_pattern(o->h_pattern);
-  const size_t g_bytes = (size_t)round_up(k->width, 16) * k->height;              // (a multiple of 16, as every offset below)
-  const size_t xy_bytes = (sizeof(int) * 2 * (size_t)max_desc + 15) / 16 * 16;
-  const size_t res_bytes = (xk_orb_res_bytes((size_t)max_desc) + 15) / 16 * 16;
-  const size_t dev_bytes = 2 * g_bytes + sizeof o->h_pattern + 2 * xy_bytes + res_bytes;
-  void *dv = nullptr, *hb = nullptr;
-  const size_t pin_bytes = std::max(xy_bytes + res_bytes, sizeof o->h_pattern);   // (the pattern goes up through it, below)
-  bool ok = hipMalloc(&dv, dev_bytes) == hipSuccess && hipHostMalloc(&hb, pin_bytes) == hipSuccess &&
-            hipMemsetAsync(dv, 0, dev_bytes, h->stream) == hipSuccess;            // (G's padding columns are never written: zeros)
-  o->d_blk = (unsigned char *)dv; o->h_blk = (unsigned char *)hb;
-  if (ok) {
-    memcpy(o->h_blk, o->h_pattern, sizeof o->h_pattern);
-    ok = hipMemcpyAsync(o->d_blk + 2 * g_bytes, o->h_blk, sizeof o->h_pattern, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+  const size_t g_bytes = (size_t)k->slot[0].lv[0].pitch * k->height;
+  const size_t xy_bytes = up16(sizeof(int) * 2 * (size_t)max_desc), res_bytes = up16(xk_orb_res_bytes((size_t)max_desc));
+  int rc = blk_alloc(h, o->blk, 2 * g_bytes + sizeof o->h_pattern + 2 * xy_bytes + res_bytes,
+                     std::max(xy_bytes + res_bytes, sizeof o->h_pattern), "xk_trk_describe_setup");   // (the pattern goes up through the mirror)
+  if (rc == XK_OK) {
+    size_t off = 0;
+    o->G[0] = carve<unsigned char>(o->blk.d, off, g_bytes);
+    o->G[1] = carve<unsigned char>(o->blk.d, off, g_bytes);
+    o->pattern = carve<signed char>(o->blk.d, off, sizeof o->h_pattern);
+    o->xy = carve<int>(o->blk.d, off, xy_bytes);
+    o->kept_xy = carve<int>(o->blk.d, off, xy_bytes);
+    o->res = carve<int>(o->blk.d, off, res_bytes);
+    o->h_res = o->blk.h + xy_bytes;
+    memcpy(o->blk.h, o->h_pattern, sizeof o->h_pattern);
+    if (hipMemcpyAsync(o->pattern, o->blk.h, sizeof o->h_pattern, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+      rc = fail(h, XK_ENOMEM, "xk_trk_describe_setup: allocation failed");
   }
-  if (hipStreamSynchronize(h->stream) != hipSuccess) ok = false;                  // (the staging is free again; an old setup idle)
-  if (!ok) {
-    orb_release(o);
-    return fail(h, XK_ENOMEM, "xk_trk_describe_setup: allocation failed");
-  }
-  unsigned char *p = o->d_blk;
-  o->G[0] = p; p += g_bytes;
-  o->G[1] = p; p += g_bytes;
-  o->pattern = (signed char *)p; p += sizeof o->h_pattern;
-  o->xy = (int *)p; p += xy_bytes;
-  o->kept_xy = (int *)p; p += xy_bytes;
-  o->res = (int *)p;
-  orb_release(k->orb);
-  k->orb = o;
-  return XK_OK;
+  return setup_install(h, rc, "xk_trk_describe_setup", k->orb, o);
 }
 
-// The slot of the previous (which = 0) or the current (1) image as XkOrbArgs, its blur queued if this is the slot's first
-// description since its push.
-static int orb_slot(xk_trk *t, int which, XkOrbArgs &a) {
+// The slot s as XkOrbArgs, its blur queued if this is the slot's first description since its push.
+static int orb_slot(xk_trk *t, int s, XkOrbArgs &a) {
   xk_handle *h = t->h;
   xk_klt *k = t->klt;
   xk_orb *o = k->orb;
-  const int s = which == 1 ? k->cur : k->cur ^ 1;
   const XkKltLevel &L = k->slot[s].lv[0];
   a.img = L.img; a.G = o->G[s]; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
   a.edge = o->edge; a.centroid = o->centroid; a.A = o->A; a.B = o->B;
   a.pattern = o->pattern; a.xy = o->xy; a.kept_xy = o->kept_xy; a.res = o->res;
   if (!o->blurred[s]) {
     hipLaunchKernelGGL(xk_orb_blur, dim3((a.w + XK_ORB_TW - 1) / XK_ORB_TW, (a.h + XK_ORB_TH - 1) / XK_ORB_TH), dim3(256), 0, h->stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, XK_EDEVICE, "blur launch", e);
+    XKCHK(launched(h, "blur launch"));
     o->blurred[s] = 1;
   }
   return XK_OK;
@@ -704,34 +744,29 @@ extern "C" int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsig
                                int *n_kept) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  xk_orb *o = k ? k->orb : nullptr;
-  if (!o) return fail(h, XK_EINVAL, "xk_trk_describe: before xk_trk_describe_setup");
+  xk_orb *o = sub_of(t, &xk_klt::orb, "xk_trk_describe", "xk_trk_describe_setup");
+  if (!o) return XK_EINVAL;
   if (!desc || !keep_idx || !dir || !moments || !n_kept || n < 0 || (n > 0 && !xy)) return fail(h, XK_EINVAL, "xk_trk_describe: null argument or negative n");
-  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_describe: which is 0 or 1");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_describe: that image has not been pushed");
+  const int s = img_slot(t, "xk_trk_describe", which);
+  if (s < 0) return XK_EINVAL;
   if (n > o->max_desc) return fail(h, XK_ECAPACITY, "xk_trk_describe: more keypoints than max_desc");
   *n_kept = 0;
   if (n == 0) return XK_OK;
   HIPCHK(h, hipSetDevice(h->device));
   XkOrbArgs a{};
   a.n = n;
-  memcpy(o->h_blk, xy, sizeof(int) * 2 * (size_t)n);
-  HIPCHK(h, hipMemcpyAsync(o->xy, o->h_blk, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  const int rc = orb_slot(t, which, a);
-  if (rc != XK_OK) return rc;
+  memcpy(o->blk.h, xy, sizeof(int) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync(o->xy, o->blk.h, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  XKCHK(orb_slot(t, s, a));
   hipLaunchKernelGGL(xk_orb_filter, dim3(1), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_orb_describe, dim3(std::min((n + XK_ORB_WAVES - 1) / XK_ORB_WAVES, XK_ORB_MAX_GRID)), dim3(64 * XK_ORB_WAVES), 0,
                      h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "description launch", e);
-  const unsigned char *r = o->h_blk + (sizeof(int) * 2 * (size_t)o->max_desc + 15) / 16 * 16;
-  HIPCHK(h, hipMemcpyAsync((void *)r, o->res, xk_orb_res_bytes((size_t)n), hipMemcpyDeviceToHost, h->stream));
+  XKCHK(launched(h, "description launch"));
+  const unsigned char *r = o->h_res;
+  HIPCHK(h, hipMemcpyAsync(o->h_res, o->res, xk_orb_res_bytes((size_t)n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  int kept = 0;
-  memcpy(&kept, r, sizeof(int));
-  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_describe: kept count out of range");
-  *n_kept = kept;
+  XKCHK(kept_count_out(h, "xk_trk_describe", r, n, n_kept));
+  const size_t kept = (size_t)*n_kept;
   const int *ri = (const int *)r;
   memcpy(keep_idx, ri + 4, sizeof(int) * (size_t)kept);
   memcpy(dir, ri + 4 + n, sizeof(int) * 2 * (size_t)kept);
@@ -744,17 +779,15 @@ extern "C" int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsig
 extern "C" int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed char *pattern) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  xk_orb *o = k ? k->orb : nullptr;
-  if (!o) return fail(h, XK_EINVAL, "xk_trk_describe_stage: before xk_trk_describe_setup");
-  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_describe_stage: which is 0 or 1");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_describe_stage: that image has not been pushed");
+  xk_orb *o = sub_of(t, &xk_klt::orb, "xk_trk_describe_stage", "xk_trk_describe_setup");
+  if (!o) return XK_EINVAL;
+  const int s = img_slot(t, "xk_trk_describe_stage", which);
+  if (s < 0) return XK_EINVAL;
   HIPCHK(h, hipSetDevice(h->device));
   if (pattern) HIPCHK(h, hipMemcpyAsync(pattern, o->pattern, sizeof o->h_pattern, hipMemcpyDeviceToHost, h->stream));   // (the kernels' copy)
   if (blurred) {
     XkOrbArgs a{};
-    const int rc = orb_slot(t, which, a);
-    if (rc != XK_OK) return rc;
+    XKCHK(orb_slot(t, s, a));
     HIPCHK(h, hipMemcpy2DAsync(blurred, (size_t)a.w, a.G, (size_t)a.pitch, (size_t)a.w, (size_t)a.h, hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -764,16 +797,13 @@ extern "C" int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurre
 // ---------------------------------------------------------------------------
 // Photometric calibration of the images (tracker.cpp:761-877, irPhotoCalib.cpp), xk_photo.hip.h
 // ---------------------------------------------------------------------------
-static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
-// The state as a reset leaves it, through the pinned block (the stream is idle afterwards).
+// The state as a reset leaves it, queued through the pinned block: the caller waits.
 static int photo_state_reset(xk_handle *h, xk_photo *p) {
-  XkPhotoState *s = (XkPhotoState *)p->h_io;
+  XkPhotoState *s = (XkPhotoState *)p->blk.h;
   memset(s, 0, sizeof *s);
   s->ring[0] = 1.0; s->ring[1] = 0.0;                                             // irPhotoCalib.cpp:25
   s->ring_n = 1;
   HIPCHK(h, hipMemcpyAsync(p->st, s, sizeof *s, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   p->ring_n = 1; p->done = 0;
   memset(p->n_hyp, 0, sizeof p->n_hyp);
   return XK_OK;
@@ -791,70 +821,43 @@ extern "C" int xk_trk_photo_setup(xk_trk *t, int kernel_size, double epsilon_gap
     return fail(h, XK_EINVAL, "xk_trk_photo_setup: epsilon_gap or epsilon_base outside [0, 1]");
   if (max_hyp < 1 || max_hyp > XK_PHOTO_MAX_HYP) return fail(h, XK_EINVAL, "xk_trk_photo_setup: max_hyp outside 1...4096");
   HIPCHK(h, hipSetDevice(h->device));
-  xk_photo *p = (xk_photo *)calloc(1, sizeof(xk_photo));   // (built whole before the old one goes, as in xk_trk_klt_setup)
+  xk_photo *p = (xk_photo *)calloc(1, sizeof(xk_photo));
   if (!p) return XK_ENOMEM;
   p->kernel_size = kernel_size; p->max_hyp = max_hyp; p->eps_gap = epsilon_gap; p->eps_base = epsilon_base;
   const size_t mm = (size_t)round_up(t->max_matches, 4), gm = XK_PHOTO_MAX_GROUPS * mm;
-  const size_t ps_bytes = sizeof(float) * (size_t)round_up(k->width, 16) * k->height;
+  const size_t ps_bytes = sizeof(float) * (size_t)k->slot[0].lv[0].pitch * k->height;
   const size_t sc_bytes = up16(xk_ransac_scratch_bytes<1>((size_t)max_hyp));
-  // the i/o block: every piece a multiple of 16 bytes
-  const size_t o_state = 0, o_value = up16(sizeof(XkPhotoState)), o_sum = o_value + 8 * mm, o_count = o_sum + 4 * mm,
-               o_klt = o_count + 4 * mm, o_prev = o_klt + up16(klt_res_bytes(t->max_matches)), o_pts = o_prev + 8 * mm, o_ixy = o_pts + 8 * mm,
-               o_hist = o_ixy + 8 * mm, o_cur = o_hist + 8 * gm, o_off = o_cur + 8 * gm, o_fb = o_off + 64, io_bytes = o_fb + 64;
-  const size_t dev_bytes = 2 * k->slot_bytes + ps_bytes + io_bytes + XK_PHOTO_MAX_GROUPS * sc_bytes;
-  void *dv = nullptr, *hb = nullptr;
-  bool ok = hipMalloc(&dv, dev_bytes) == hipSuccess && hipHostMalloc(&hb, io_bytes) == hipSuccess &&
-            hipMemsetAsync(dv, 0, dev_bytes, h->stream) == hipSuccess;               // (the raw planes' padding columns and PS: zeros)
-  p->d_blk = (unsigned char *)dv; p->h_io = (unsigned char *)hb;
-  if (ok) {
+  // the i/o block, every piece a multiple of 16 bytes: state | value | sum, count | the tracking's result block | previous intensities,
+  // previous points, pixels | o_hist, o_cur | off | frame_back
+  const size_t io_bytes = up16(sizeof(XkPhotoState)) + 8 * mm + 2 * 4 * mm + up16(klt_res_bytes(t->max_matches)) + 3 * 8 * mm + 2 * 8 * gm + 64 + 64;
+  int rc = blk_alloc(h, p->blk, 2 * k->slot_bytes + ps_bytes + io_bytes + XK_PHOTO_MAX_GROUPS * sc_bytes, io_bytes, "xk_trk_photo_setup");
+  if (rc == XK_OK) {
+    size_t off = 0;
+    bool ok = true;
     for (int s = 0; s < 2; ++s) {
-      p->raw[s] = k->slot[s];
-      for (int l = 0; l <= k->levels; ++l) {                                          // the same layout at another base
-        XkKltLevel &L = p->raw[s].lv[l];
-        const XkKltLevel &W = k->slot[s].lv[l];
-        unsigned char *base = p->d_blk + s * k->slot_bytes + (W.img - k->slot[s].lv[0].img);
-        const size_t plane = (size_t)W.pitch * W.h;
-        L.img = base; L.dx = (short *)(base + plane); L.dy = (short *)(base + 3 * plane);
-      }
+      p->raw[s] = k->slot[s];                                                           // the same layout at another base
+      klt_place(p->raw[s], k->levels, carve<unsigned char>(p->blk.d, off, k->slot_bytes));
       // images pushed before this call are raw and working at once
       ok = ok && hipMemcpyAsync(p->raw[s].lv[0].img, k->slot[s].lv[0].img, k->slot_bytes, hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
     }
-    p->PS = (float *)(p->d_blk + 2 * k->slot_bytes);
-    p->d_io = p->d_blk + 2 * k->slot_bytes + ps_bytes;
-    p->io_bytes = io_bytes; p->in_off = o_prev;
-    p->st = (XkPhotoState *)(p->d_io + o_state);
-    p->value = (double *)(p->d_io + o_value); p->sum = (int *)(p->d_io + o_sum); p->count = (int *)(p->d_io + o_count);
-    p->klt_res = p->d_io + o_klt;
-    p->prev_int = (double *)(p->d_io + o_prev); p->pts = (float *)(p->d_io + o_pts); p->ixy = (int *)(p->d_io + o_ixy);
-    p->o_hist = (double *)(p->d_io + o_hist); p->o_cur = (double *)(p->d_io + o_cur);
-    p->off = (int *)(p->d_io + o_off); p->frame_back = (int *)(p->d_io + o_fb);
-    for (int g = 0; g < XK_PHOTO_MAX_GROUPS; ++g) p->sc[g] = xk_ransac_scratch<1>(p->d_io + io_bytes + g * sc_bytes, (size_t)max_hyp);
-    memset(p->h_io, 0, io_bytes);
-    ok = ok && photo_state_reset(h, p) == XK_OK;
+    p->PS = carve<float>(p->blk.d, off, ps_bytes);
+    unsigned char *io = p->d_io = carve<unsigned char>(p->blk.d, off, io_bytes);
+    for (int g = 0; g < XK_PHOTO_MAX_GROUPS; ++g) p->sc[g] = xk_ransac_scratch<1>(carve<unsigned char>(p->blk.d, off, sc_bytes), (size_t)max_hyp);
+    off = 0;
+    p->st = carve<XkPhotoState>(io, off, sizeof(XkPhotoState));
+    p->value = carve<double>(io, off, 8 * mm); p->sum = carve<int>(io, off, 4 * mm); p->count = carve<int>(io, off, 4 * mm);
+    p->klt_res = carve<unsigned char>(io, off, klt_res_bytes(t->max_matches));
+    p->prev_int = carve<double>(io, off, 8 * mm); p->pts = carve<float>(io, off, 8 * mm); p->ixy = carve<int>(io, off, 8 * mm);
+    p->o_hist = carve<double>(io, off, 8 * gm); p->o_cur = carve<double>(io, off, 8 * gm);
+    p->off = carve<int>(io, off, 64); p->frame_back = carve<int>(io, off, 64);
+    if (!ok || photo_state_reset(h, p) != XK_OK) rc = fail(h, XK_ENOMEM, "xk_trk_photo_setup: allocation failed");
   }
-  if (hipStreamSynchronize(h->stream) != hipSuccess) ok = false;                      // (an old setup is idle now)
-  if (!ok) {
-    photo_release(p);
-    return fail(h, XK_ENOMEM, "xk_trk_photo_setup: allocation failed");
-  }
-  photo_release(k->photo);
-  k->photo = p;
-  return XK_OK;
+  return setup_install(h, rc, "xk_trk_photo_setup", k->photo, p);
 }
 
 // the pinned mirror of a device pointer into the i/o block
 template <class T>
-static T *photo_host(const xk_photo *p, const T *dev) { return (T *)(p->h_io + ((const unsigned char *)dev - p->d_io)); }
-
-static xk_photo *photo_of(xk_trk *t, const char *who) {
-  xk_photo *p = t->klt ? t->klt->photo : nullptr;
-  if (!p) {
-    char msg[96];
-    snprintf(msg, sizeof msg, "%s: before xk_trk_photo_setup", who);
-    fail(t->h, XK_EINVAL, msg);
-  }
-  return p;
-}
+static T *photo_host(const xk_photo *p, const T *dev) { return (T *)(p->blk.h + ((const unsigned char *)dev - p->d_io)); }
 
 static XkPhotoIntArgs photo_int_args(const xk_photo *p, const XkKltLevel &L, int n) {
   XkPhotoIntArgs a{};
@@ -867,22 +870,21 @@ static XkPhotoIntArgs photo_int_args(const xk_photo *p, const XkKltLevel &L, int
 extern "C" int xk_trk_photo_intensity(xk_trk *t, int which, int plane, const int *xy, int n, double *value, int *sum, int *count) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_intensity");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_intensity", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   xk_klt *k = t->klt;
   if (n < 0 || !value || !sum || !count || (n > 0 && !xy)) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: null argument or negative n");
-  if (which < 0 || which > 1 || plane < 0 || plane > 1) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: which and plane are 0 or 1");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: that image has not been pushed");
+  if (plane < 0 || plane > 1) return fail(h, XK_EINVAL, "xk_trk_photo_intensity: plane is 0 or 1");
+  const int s = img_slot(t, "xk_trk_photo_intensity", which);
+  if (s < 0) return XK_EINVAL;
   if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_photo_intensity: more points than max_matches");
   if (n == 0) return XK_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  const int s = which == 1 ? k->cur : k->cur ^ 1;
   const XkPhotoIntArgs a = photo_int_args(p, (plane == 0 ? p->raw[s] : k->slot[s]).lv[0], n);
   memcpy(photo_host(p, p->ixy), xy, sizeof(int) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync(p->ixy, photo_host(p, p->ixy), sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(xk_photo_intensity, dim3((n + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "intensity launch", e);
+  XKCHK(launched(h, "intensity launch"));
   const size_t out_bytes = (size_t)((unsigned char *)p->klt_res - (unsigned char *)p->value);     // value | sum | count
   HIPCHK(h, hipMemcpyAsync(photo_host(p, p->value), p->value, out_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -901,9 +903,7 @@ static int photo_queue_gains(xk_handle *h, xk_photo *p, XkPhotoGainArgs &a) {
     hipLaunchKernelGGL(xk_photo_refit, dim3(1), dim3(256), 0, h->stream, a);
   }
   hipLaunchKernelGGL(xk_photo_chain, dim3(1), dim3(64), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "gain estimation launch", e);
-  return XK_OK;
+  return launched(h, "gain estimation launch");
 }
 
 static XkPhotoGainArgs photo_gain_args(const xk_photo *p, int G, int n_hyp, unsigned long seed, int per_frame) {
@@ -917,7 +917,7 @@ static XkPhotoGainArgs photo_gain_args(const xk_photo *p, int G, int n_hyp, unsi
 
 // the state out of the pinned block after a wait
 static int photo_state_out(xk_handle *h, xk_photo *p, int G, double *a_rel, double *b_rel, int *support, double *frame_ab) {
-  const XkPhotoState *s = (const XkPhotoState *)p->h_io;
+  const XkPhotoState *s = (const XkPhotoState *)p->blk.h;
   if (s->ring_n < 1 || s->ring_n > XK_PHOTO_RING) return fail(h, XK_EDEVICE, "photometric state: ring size out of range");
   p->ring_n = s->ring_n; p->done = s->done;
   if (a_rel) memcpy(a_rel, s->a_rel, sizeof(double) * (size_t)G);
@@ -932,7 +932,7 @@ extern "C" int xk_trk_photo_gains(xk_trk *t, int G, const int *off, const double
                                   unsigned long seed, double *a_rel, double *b_rel, int *support, double *frame_ab) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_gains");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_gains", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   if (G < 1 || G > XK_PHOTO_MAX_GROUPS) return fail(h, XK_EINVAL, "xk_trk_photo_gains: G outside 1...14");
   if (!off || !frame_back || !a_rel || !b_rel || !support || !frame_ab) return fail(h, XK_EINVAL, "xk_trk_photo_gains: null argument");
@@ -952,12 +952,11 @@ extern "C" int xk_trk_photo_gains(xk_trk *t, int G, const int *off, const double
   memcpy(photo_host(p, p->off), off, sizeof(int) * (size_t)(G + 1));
   memcpy(photo_host(p, p->frame_back), frame_back, sizeof(int) * (size_t)G);
   const size_t in_at = (size_t)((unsigned char *)p->o_hist - p->d_io);
-  HIPCHK(h, hipMemcpyAsync(p->o_hist, p->h_io + in_at, p->io_bytes - in_at, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->o_hist, p->blk.h + in_at, p->blk.h_bytes - in_at, hipMemcpyHostToDevice, h->stream));
   XkPhotoGainArgs a = photo_gain_args(p, G, n_hyp, seed, 0);
   memset(p->n_hyp, 0, sizeof p->n_hyp);
-  int rc = photo_queue_gains(h, p, a);
-  if (rc != XK_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(p->h_io, p->st, sizeof(XkPhotoState), hipMemcpyDeviceToHost, h->stream));
+  XKCHK(photo_queue_gains(h, p, a));
+  HIPCHK(h, hipMemcpyAsync(p->blk.h, p->st, sizeof(XkPhotoState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int g = 0; g < G; ++g) p->n_hyp[g] = off[g + 1] - off[g] > 4 ? n_hyp : 0;
   return photo_state_out(h, p, G, a_rel, b_rel, support, frame_ab);
@@ -967,7 +966,7 @@ extern "C" int xk_trk_photo_gains(xk_trk *t, int G, const int *off, const double
 extern "C" int xk_trk_photo_hypotheses(xk_trk *t, int g, int first, int count, double *ab, int *inliers) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_hypotheses");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_hypotheses", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   if (g < 0 || g >= XK_PHOTO_MAX_GROUPS) return fail(h, XK_EINVAL, "xk_trk_photo_hypotheses: no such group");
   if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_trk_photo_hypotheses: negative range");
@@ -986,13 +985,13 @@ extern "C" int xk_trk_photo_hypotheses(xk_trk *t, int g, int first, int count, d
 extern "C" int xk_trk_photo_params(xk_trk *t, double *a, double *b, int *count) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_params");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_params", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   if (!count) return fail(h, XK_EINVAL, "xk_trk_photo_params: null argument");
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(p->h_io, p->st, sizeof(XkPhotoState), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->blk.h, p->st, sizeof(XkPhotoState), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const XkPhotoState *s = (const XkPhotoState *)p->h_io;
+  const XkPhotoState *s = (const XkPhotoState *)p->blk.h;
   if (s->ring_n < 1 || s->ring_n > XK_PHOTO_RING) return fail(h, XK_EDEVICE, "xk_trk_photo_params: ring size out of range");
   *count = s->ring_n;
   for (int i = 0; i < s->ring_n; ++i) {
@@ -1006,22 +1005,24 @@ extern "C" int xk_trk_photo_params(xk_trk *t, double *a, double *b, int *count) 
 extern "C" int xk_trk_photo_reset(xk_trk *t) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_reset");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_reset", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));                                       // (the pinned block is free)
-  return photo_state_reset(h, p);
+  XKCHK(photo_state_reset(h, p));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
 }
 
 /* params_PS_ (irPhotoCalib.cpp:36): the caller's spatial map, float32 [height][width]; NULL: zeros */
 extern "C" int xk_trk_photo_set_spatial(xk_trk *t, const float *ps) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_set_spatial");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_set_spatial", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   xk_klt *k = t->klt;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t pitch = sizeof(float) * (size_t)round_up(k->width, 16);
+  const size_t pitch = sizeof(float) * (size_t)k->slot[0].lv[0].pitch;
   if (ps) HIPCHK(h, hipMemcpy2DAsync(p->PS, pitch, ps, sizeof(float) * (size_t)k->width, sizeof(float) * (size_t)k->width, (size_t)k->height,
                                     hipMemcpyHostToDevice, h->stream));
   else HIPCHK(h, hipMemsetAsync(p->PS, 0, pitch * k->height, h->stream));
@@ -1037,8 +1038,7 @@ static int photo_queue_correct(xk_handle *h, xk_klt *k, int s, int per_frame) {
   a.raw = R.img; a.out = W.img; a.PS = p->PS; a.w = W.w; a.h = W.h; a.pitch = W.pitch; a.per_frame = per_frame; a.st = p->st;
   const int threads = (W.pitch / 16) * W.h;
   hipLaunchKernelGGL(xk_photo_correct, dim3((threads + 255) / 256), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "correction launch", e);
+  XKCHK(launched(h, "correction launch"));
   if (k->orb) k->orb->blurred[s] = 0;
   return klt_pyramid(h, k, k->slot[s]);
 }
@@ -1048,26 +1048,25 @@ static int photo_queue_correct(xk_handle *h, xk_klt *k, int s, int per_frame) {
 extern "C" int xk_trk_photo_correct(xk_trk *t, int which) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_correct");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_correct", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
-  xk_klt *k = t->klt;
-  if (which < 0 || which > 1) return fail(h, XK_EINVAL, "xk_trk_photo_correct: which is 0 or 1");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_photo_correct: that image has not been pushed");
+  const int s = img_slot(t, "xk_trk_photo_correct", which);
+  if (s < 0) return XK_EINVAL;
   HIPCHK(h, hipSetDevice(h->device));
-  return photo_queue_correct(h, k, which == 1 ? k->cur : k->cur ^ 1, 0);
+  return photo_queue_correct(h, t->klt, s, 0);
 }
 
 /* Level 0 of a slot's raw plane: the image as pushed.  A straight copy */
 extern "C" int xk_trk_photo_raw(xk_trk *t, int which, unsigned char *img) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_raw");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_raw", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
-  xk_klt *k = t->klt;
-  if (which < 0 || which > 1 || !img) return fail(h, XK_EINVAL, "xk_trk_photo_raw: which is 0 or 1, img not NULL");
-  if (k->pushed < (which == 0 ? 2 : 1)) return fail(h, XK_EINVAL, "xk_trk_photo_raw: that image has not been pushed");
+  if (!img) return fail(h, XK_EINVAL, "xk_trk_photo_raw: null argument");
+  const int s = img_slot(t, "xk_trk_photo_raw", which);
+  if (s < 0) return XK_EINVAL;
   HIPCHK(h, hipSetDevice(h->device));
-  const XkKltLevel &L = p->raw[which == 1 ? k->cur : k->cur ^ 1].lv[0];
+  const XkKltLevel &L = p->raw[s].lv[0];
   HIPCHK(h, hipMemcpy2DAsync(img, (size_t)L.w, L.img, (size_t)L.pitch, (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
@@ -1080,7 +1079,7 @@ extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const dou
                                       int *support, double *frame_ab, int *estimated) {
   if (!t) return XK_EINVAL;
   xk_handle *h = t->h;
-  xk_photo *p = photo_of(t, "xk_trk_photo_calibrate");
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_calibrate", "xk_trk_photo_setup");
   if (!p) return XK_EINVAL;
   xk_klt *k = t->klt;
   if (n < 0 || !keep_idx || !intensity || !sum || !count || !n_kept || !a_rel || !b_rel || !support || !frame_ab || !estimated ||
@@ -1096,53 +1095,39 @@ extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const dou
   HIPCHK(h, hipSetDevice(h->device));
   if (n < 4) {                                                   // tracker.cpp:763: corrected only after an earlier estimate
     if (!p->done) return XK_OK;
-    const int rc = photo_queue_correct(h, k, k->cur, 1);
-    if (rc != XK_OK) return rc;
+    XKCHK(photo_queue_correct(h, k, k->cur, 1));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return XK_OK;
   }
-  XkKltArgs a{};
-  a.prev = p->raw[k->cur ^ 1]; a.cur = p->raw[k->cur];
-  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
-  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
-  a.pts = p->pts;
-  a.cur_xy = (double *)p->klt_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
-  a.kept = xk_kept_pairs(a.min_eig + n, n);
-  a.status = xk_kept_pairs_end(a.kept, n);
   // one copy in: previous intensities | previous points
   memcpy(photo_host(p, p->prev_int), prev_intensity, sizeof(double) * (size_t)n);
   memcpy(photo_host(p, p->pts), prev_xy, sizeof(float) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync(p->prev_int, photo_host(p, p->prev_int), (size_t)((unsigned char *)p->ixy - (unsigned char *)p->prev_int),
                            hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
+  XkKltArgs a;
+  XKCHK(klt_queue_track(h, k, p->raw[k->cur ^ 1], p->raw[k->cur], p->pts, p->klt_res, n, a));
   XkPhotoGatherArgs ga{};
   ga.kept = a.kept; ga.prev_intensity = p->prev_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
   hipLaunchKernelGGL(xk_photo_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, ga);
   XkPhotoIntArgs ia = photo_int_args(p, p->raw[k->cur].lv[0], n);
   ia.n_dev = a.kept.res;
   hipLaunchKernelGGL(xk_photo_intensity, dim3((n + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, ia);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "calibration launch", e);
+  XKCHK(launched(h, "calibration launch"));
   XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp, seed, 1);
-  int rc = photo_queue_gains(h, p, g);
-  if (rc != XK_OK) return rc;
-  rc = photo_queue_correct(h, k, k->cur, 1);
-  if (rc != XK_OK) return rc;
+  XKCHK(photo_queue_gains(h, p, g));
+  XKCHK(photo_queue_correct(h, k, k->cur, 1));
   // one copy out: state | value | sum | count | the tracking's result block
   const size_t out_bytes = (size_t)(p->klt_res - p->d_io) + klt_res_bytes(n);
-  HIPCHK(h, hipMemcpyAsync(p->h_io, p->d_io, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->blk.h, p->d_io, out_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const unsigned char *r = photo_host(p, p->klt_res);
-  int kept = 0;
-  memcpy(&kept, r + ((unsigned char *)a.kept.res - p->klt_res), sizeof(int));
-  if (kept < 0 || kept > n) return fail(h, XK_EDEVICE, "xk_trk_photo_calibrate: kept count out of range");
-  *n_kept = kept;
+  XKCHK(kept_count_out(h, "xk_trk_photo_calibrate", r + ((unsigned char *)a.kept.res - p->klt_res), n, n_kept));
+  const int kept = *n_kept;
   memcpy(keep_idx, r + ((unsigned char *)a.kept.keep_idx - p->klt_res), sizeof(int) * (size_t)kept);
   memcpy(intensity, photo_host(p, p->value), sizeof(double) * (size_t)kept);
   memcpy(sum, photo_host(p, p->sum), sizeof(int) * (size_t)kept);
   memcpy(count, photo_host(p, p->count), sizeof(int) * (size_t)kept);
-  const XkPhotoState *s = (const XkPhotoState *)p->h_io;
+  const XkPhotoState *s = (const XkPhotoState *)p->blk.h;
   *estimated = s->estimated;
   if (kept > 4) p->n_hyp[0] = n_hyp;
   if (!s->estimated) return photo_state_out(h, p, 0, nullptr, nullptr, nullptr, nullptr);

@@ -24,26 +24,25 @@ c_sp = C.POINTER(C.c_short)
 c_sb = C.POINTER(C.c_byte)
 
 
-class MatchFilter:
-    """The camera model and the RANSAC of x::Tracker on one agent's GPU.  K = (fx, fy, cx, cy) in pixels or a 3 x 3 camera
-    matrix, s = the FOV distortion parameter (0: none)."""
+class _Trk:
+    """What MatchFilter and Klt share: an xk_trk (its own, or its owner's), the status check and the release."""
+    owner = None
 
-    def __init__(self, eng, max_matches, K, s=0.0):
-        self.eng, self.L = eng, eng.L
-        K = np.asarray(K, np.float64)
-        self.K = tuple(float(v) for v in ((K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.ravel()))
-        self.s = float(s)
-        self.max_matches = int(max_matches)
-        self.p = C.c_void_p()
-        rc = self.L.xk_trk_create(eng.h, C.c_int(self.max_matches), *(C.c_double(v) for v in self.K), C.c_double(self.s),
-                                  C.byref(self.p))
+    def _create(self, eng, max_matches, K=(1.0, 1.0, 0.0, 0.0), s=0.0):
+        self.eng, self.L, self.p = eng, eng.L, C.c_void_p()
+        self._chk(self.L.xk_trk_create(eng.h, C.c_int(max_matches), *(C.c_double(v) for v in K), C.c_double(s), C.byref(self.p)), "xk_trk_create")
+
+    def _error(self, rc, what):
+        return XkError(rc, what, (self.L.xk_last_error(self.eng.h) or b"").decode())
+
+    def _chk(self, rc, what):
         if rc != 0:
-            raise XkError(rc, "xk_trk_create", (self.L.xk_last_error(eng.h) or b"").decode())
+            raise self._error(rc, what)
 
     def close(self):
-        if self.p:
+        if self.owner is None and self.p:
             self.L.xk_trk_destroy(self.p)
-            self.p = C.c_void_p()
+        self.p = C.c_void_p()
 
     def __del__(self):
         try:
@@ -51,9 +50,17 @@ class MatchFilter:
         except Exception:
             pass
 
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise XkError(rc, what, (self.L.xk_last_error(self.eng.h) or b"").decode())
+
+class MatchFilter(_Trk):
+    """The camera model and the RANSAC of x::Tracker on one agent's GPU.  K = (fx, fy, cx, cy) in pixels or a 3 x 3 camera
+    matrix, s = the FOV distortion parameter (0: none)."""
+
+    def __init__(self, eng, max_matches, K, s=0.0):
+        K = np.asarray(K, np.float64)
+        self.K = tuple(float(v) for v in ((K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.ravel()))
+        self.s = float(s)
+        self.max_matches = int(max_matches)
+        self._create(eng, self.max_matches, self.K, self.s)
 
     def undistort(self, dist_xy):
         """Camera::undistort (camera.cpp:62-87): distorted pixels [n, 2] -> undistorted pixels [n, 2], fp64."""
@@ -105,7 +112,7 @@ class MatchFilter:
         return mask[:n], keep[:m], pxy[:m], cxy[:m]
 
 
-class Klt:
+class Klt(_Trk):
     """cv::calcOpticalFlowPyrLK as x::Tracker calls it (tracker.cpp:642-651, parameters tracker.h:234-261) and the post-filter
     behind it (:658-686) on one agent's GPU: push_image per frame, track per frame.  match_filter: an existing MatchFilter
     whose xk_trk this object shares, so that one device object serves both steps of a frame (max_features is then its
@@ -113,17 +120,12 @@ class Klt:
 
     def __init__(self, eng, max_features, width, height, win=(31, 31), max_level=2, max_iter=30, eps=0.01, min_eig_thr=0.003,
                  match_filter=None):
-        self.eng, self.L = eng, eng.L
         self.owner = match_filter
         if match_filter is not None:
-            self.p, self.max_features = match_filter.p, match_filter.max_matches
+            self.eng, self.L, self.p, self.max_features = eng, eng.L, match_filter.p, match_filter.max_matches
         else:
             self.max_features = int(max_features)
-            self.p = C.c_void_p()
-            rc = self.L.xk_trk_create(eng.h, C.c_int(self.max_features), C.c_double(1.0), C.c_double(1.0), C.c_double(0.0),
-                                      C.c_double(0.0), C.c_double(0.0), C.byref(self.p))
-            if rc != 0:
-                raise XkError(rc, "xk_trk_create", (self.L.xk_last_error(eng.h) or b"").decode())
+            self._create(eng, self.max_features)
         try:
             self.setup(width, height, win, max_level, max_iter, eps, min_eig_thr)
         except XkError:
@@ -135,21 +137,6 @@ class Klt:
         self._chk(self.L.xk_trk_klt_setup(self.p, C.c_int(width), C.c_int(height), C.c_int(win[0]), C.c_int(win[1]), C.c_int(max_level),
                                           C.c_int(max_iter), C.c_double(eps), C.c_double(min_eig_thr)), "xk_trk_klt_setup")
         self.width, self.height, self.win = int(width), int(height), (int(win[0]), int(win[1]))
-
-    def close(self):
-        if self.owner is None and self.p:
-            self.L.xk_trk_destroy(self.p)
-        self.p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise XkError(rc, what, (self.L.xk_last_error(self.eng.h) or b"").decode())
 
     def levels(self):
         """The highest pyramid level in use (rule 1 of DESIGN 3.11)."""
@@ -203,7 +190,7 @@ class Klt:
         rc = self.L.xk_trk_detect(self.p, C.c_int(which), old.ctypes.data_as(c_dp) if len(old) else None, C.c_int(len(old)),
                                   xy.ctypes.data_as(c_ip), score.ctypes.data_as(c_ip), C.byref(nf), C.byref(nc))
         if rc != 0:
-            err = XkError(rc, "xk_trk_detect", (self.L.xk_last_error(self.eng.h) or b"").decode())
+            err = self._error(rc, "xk_trk_detect")
             err.n_found, err.n_candidates = nf.value, nc.value
             raise err
         return dict(xy=xy[:nf.value].copy(), score=score[:nf.value].copy(), n_candidates=nc.value)
