@@ -1,6 +1,7 @@
 // x/place_recognition/database.h -- mirror of x::VLAD, x::Keyframe and x::Database
 // (include/x/place_recognition/{vlad,keyframe,database}.h, src/x/place_recognition/{vlad,keyframe,database}.cpp)
-// and of the matching front half of PlaceRecognition::findCorrespondences (place_recognition.cpp:137-390).
+// and of the matching front half of PlaceRecognition::findCorrespondences (place_recognition.cpp:137-390); and the
+// training of the vocabulary they take (DBoW3::Vocabulary::create).
 //
 // The reference keeps descriptors and VLADs in cv::Mat and the vocabulary in a DBoW3::Vocabulary; here a
 // descriptor set is a row-major byte matrix and the vocabulary is the plain tree DBoW3 stores (PRVocabulary).
@@ -84,6 +85,28 @@ class Database {                   // database.h / database.cpp
   xk_pr *pr_ = nullptr;
   double pr_score_thr_;
   int desc_bytes_;
+};
+
+// DBoW3::Vocabulary::create (third_party/DBow3/src/Vocabulary.cpp:157-186) for binary descriptors on the device
+// (xk_voc_*): hierarchical k-means with k-means++ seeding and bit-majority means.  The reference seeds with rand(); here
+// the tree is a function of (descriptors in the order added, k, L, seed, max_iter).
+class VocabularyTrainer {
+ public:
+  using Outcome = xk_voc_outcome;
+  VocabularyTrainer(xk_handle *xk, int k, int L, int desc_bytes = 32, int max_descriptors = 1 << 16);
+  ~VocabularyTrainer();
+  VocabularyTrainer(const VocabularyTrainer &) = delete;
+  VocabularyTrainer &operator=(const VocabularyTrainer &) = delete;
+
+  void add(const Descriptors &descriptors);                             // getFeatures (:220-228): appended in call order
+  int count() const;
+  void clear();
+  PRVocabulary train(unsigned long seed = 0, int max_iter = 100, Outcome *outcome = nullptr);   // kmax = k
+
+ private:
+  xk_handle *xk_;
+  xk_voc *voc_ = nullptr;
+  int k_, L_, desc_bytes_;
 };
 
 // The rest of findCorrespondences' non-GT branch on the 2-NN result: distance + ratio test (:252-263), optional

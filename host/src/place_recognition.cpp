@@ -73,6 +73,36 @@ std::vector<unsigned char> Database::essentialInliers(const std::vector<float> &
   return mask;
 }
 
+VocabularyTrainer::VocabularyTrainer(xk_handle *xk, int k, int L, int desc_bytes, int max_descriptors)
+    : xk_(xk), k_(k), L_(L), desc_bytes_(desc_bytes) {
+  check(xk_, xk_voc_create(xk_, k, L, desc_bytes, max_descriptors, &voc_), "xk_voc_create");
+}
+
+VocabularyTrainer::~VocabularyTrainer() { xk_voc_destroy(voc_); }
+
+int VocabularyTrainer::count() const { return xk_voc_count(voc_); }
+
+void VocabularyTrainer::clear() { check(xk_, xk_voc_clear(voc_), "xk_voc_clear"); }
+
+void VocabularyTrainer::add(const Descriptors &d) {
+  if (d.cols != desc_bytes_) throw std::runtime_error("VocabularyTrainer::add: descriptors of the wrong size");
+  check(xk_, xk_voc_add(voc_, d.ptr(), d.rows), "xk_voc_add");
+}
+
+PRVocabulary VocabularyTrainer::train(unsigned long seed, int max_iter, Outcome *outcome) {
+  Outcome oc;
+  check(xk_, xk_voc_train(voc_, seed, max_iter, &oc), "xk_voc_train");
+  PRVocabulary v;
+  v.k = k_; v.L = L_; v.kmax = k_; v.desc_bytes = desc_bytes_;
+  v.node_desc.resize((size_t)oc.n_nodes * desc_bytes_);
+  v.children.resize((size_t)oc.n_nodes * k_);
+  v.word_of_node.resize((size_t)oc.n_nodes);
+  v.node_of_word.resize((size_t)oc.n_words);
+  check(xk_, xk_voc_get(voc_, v.node_desc.data(), v.children.data(), v.word_of_node.data(), v.node_of_word.data()), "xk_voc_get");
+  if (outcome) *outcome = oc;
+  return v;
+}
+
 std::vector<GoodMatch> x::ratioTestMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
                                            double pr_ratio_thr) {
   std::vector<GoodMatch> good;

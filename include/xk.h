@@ -372,6 +372,46 @@ int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, i
 int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n_cand, double *E /* [count][10][9] */,
                                int *inliers /* [count][10] */);
 
+/* ---- training a vocabulary (DBoW3::Vocabulary::create, third_party/DBow3/src/Vocabulary.cpp:157-186) -------------
+ * Hierarchical k-means of binary descriptors on the device: HKmeansStep (Vocabulary.cpp:233-394) with k-means++ seeding
+ * (initiateClustersKMpp, :409-491), Hamming distances, bit-majority means (DescManip::meanValue, DescManip.cpp:26-75) and
+ * createWords (:496-515).  The result is bit-defined: the reference's unseeded rand() is replaced by a
+ * counter-based sampler on (seed, the node's path in the tree, the seeding step), and the unbounded Lloyd loop by at most
+ * max_iter association passes per node.  setNodeWeights is not computed: neither VLAD nor xk_pr_create reads weights.
+ * The tree is built level by level on the handle's stream; the host waits once per association pass of a level and once
+ * per level, never once per node. */
+typedef struct xk_voc xk_voc;
+
+#define XK_VOC_MAX_LEVELS 8
+typedef struct {
+  int n_nodes, n_words;                 /* sizes of what xk_voc_get returns (n_nodes counts the root) */
+  int levels;                           /* levels that had a node to split (<= L) */
+  int level_nodes[XK_VOC_MAX_LEVELS];   /* nodes split at each level, trivial ones (n <= k) included */
+  int level_passes[XK_VOC_MAX_LEVELS];  /* association passes run at each level = the most any of its nodes needed */
+  int capped_nodes;                     /* nodes whose Lloyd loop ended at max_iter, not by convergence */
+  int launches, host_waits;             /* kernels queued / stream synchronisations taken by the training */
+} xk_voc_outcome;
+
+/* 2 <= k <= 16, 1 <= L <= 8, desc_bytes a multiple of 4 up to 64, k^L * desc_bytes <= 64 MB (as xk_pr_create has it),
+ * max_desc >= 1: the most training descriptors.  Otherwise XK_EINVAL (XK_ECAPACITY for the 64 MB bound). */
+int xk_voc_create(xk_handle *h, int k, int L, int desc_bytes, int max_desc, xk_voc **out);
+void xk_voc_destroy(xk_voc *v);
+/* Vocabulary::getFeatures (Vocabulary.cpp:220-228): desc HOST [n][desc_bytes] rows are appended on the device, in call
+ * order.  XK_ECAPACITY (nothing appended) beyond max_desc; XK_EINVAL for n < 0 or null rows with n > 0. */
+int xk_voc_add(xk_voc *v, const unsigned char *desc, int n);
+int xk_voc_count(const xk_voc *v);
+int xk_voc_clear(xk_voc *v);            /* forgets the descriptors and the trained tree */
+/* HKmeansStep from the root (Vocabulary.cpp:178, :233-394) and createWords (:496-515) on the descriptors added so far.
+ * max_iter >= 1.  outcome may be NULL.  No descriptors: XK_OK with only the root (HKmeansStep's early return, :237) --
+ * a tree xk_pr_create refuses (n_nodes < 2).  A node with n <= k descriptors gets one child per descriptor (:248-258). */
+int xk_voc_train(xk_voc *v, unsigned long seed, int max_iter, xk_voc_outcome *outcome);
+/* The trained tree in DBoW3's node order (a node's children are one block of ids, then depth first, :361-393), as
+ * xk_pr_create takes it with kmax = k: node_desc HOST [n_nodes][desc_bytes] (root: zeros), children HOST [n_nodes][k]
+ * (-1 padded: seeding that stops early and trivial nodes give fewer than k), word_of_node HOST [n_nodes] (-1 for inner
+ * nodes and the root), node_of_word HOST [n_words] (the leaves in id order, :505-513).  Any output may be NULL.
+ * XK_EINVAL before a training. */
+int xk_voc_get(const xk_voc *v, unsigned char *node_desc, int *children, int *word_of_node, int *node_of_word);
+
 /* ---- outlier removal of the tracker's matches (Tracker::track, tracker.cpp:233-293) -----------------------------
  * Every frame the reference undistorts the previous and the current feature list through the FOV model
  * (camera.cpp:62-87,163-168), runs cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) on their float casts
@@ -534,6 +574,7 @@ int xk_trk_detect_stage(xk_trk *t, unsigned char *scores, unsigned int *keys, in
  * (25...4096; OpenCV's edgeThreshold 31).  pattern HOST [256][4] int8, x1 y1 x2 y2 per test, every coordinate within -15
  * ... 15: OpenCV's ORB is the first 256 rows of bit_pattern_31_ in its orb.cpp, which a binding that links OpenCV passes
  * here; NULL selects this project's default, whose descriptors match no vocabulary trained on OpenCV's.
+ * (A vocabulary for the default pattern, or for any other descriptor, is trained with xk_voc_* above.)
  * max_desc (1...32768): the most keypoints one call may pass, independent of max_matches.  Called after xk_trk_klt_setup,
  * whose image size it takes; allocates the two blurred images, the result block and its pinned staging.
  * XK_EINVAL: before xk_trk_klt_setup, orientation not 0 or 1, angle_deg not finite, edge or max_desc out of range, a

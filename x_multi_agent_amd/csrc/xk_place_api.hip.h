@@ -1,10 +1,12 @@
 // xk_place_api.hip.h -- host side of the place-recognition entries (xk_pr_*): the request filter and keyframe store
+// and the training of the vocabulary they consume (xk_voc_*, at the end)
 // (the component either side of the CI exchange on the communication axis; mirrors VLAD / Database /
 // Keyframe of src/x/place_recognition) and the essential-matrix RANSAC filter of findCorrespondences.  Part of xk_api.hip's
 // translation unit, included at its end.
 #pragma once
 #include "xk_place.hip.h"
 #include "xk_essential.hip.h"
+#include "xk_vocab.hip.h"
 
 #define XK_PR_MAX_KEYFRAMES 15   // database.h:70
 
@@ -322,4 +324,291 @@ extern "C" int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n
   if (!p) return XK_EINVAL;
   return ransac_hypotheses(p->h, "xk_pr_essential_hypotheses", "xk_pr_essential_ransac", p->d_ess ? p->ess_n_hyp : -1,
                            p->d_ess ? ess_args(p).s : XkRansacScratch{}, XK_ESS_MAXC, first, count, n_cand, E, inliers);
+}
+
+// ---------------------------------------------------------------------------
+// Vocabulary training (DBoW3::Vocabulary::create, third_party/DBow3/src/Vocabulary.cpp:157-186), xk_vocab.hip.h
+// ---------------------------------------------------------------------------
+struct XkVocHostNode { int first_child, nchild; };   // a node's children are one block of the host list
+
+struct xk_voc {
+  xk_handle *h;
+  int k, L, W, max_desc, count;
+  unsigned int *d_desc;                 // [max_desc][W]
+  int *d_perm[2], *d_nop[2];            // this level's and the next level's permutation / node of every position
+  int *d_assoc, *d_min, *d_hist;
+  unsigned long long *d_prefix, *d_bsum, *d_rec;
+  // sized by the nodes of a level, grown between levels
+  size_t a_cap;
+  XkVocNode *d_nodes;
+  unsigned int *d_cen;
+  int *d_cnt, *d_gsize, *d_csize, *d_dstoff, *d_childnext;
+  unsigned char *h_pin;                 // pinned: nodes | centres | csize | dst_off | child_next, each for a_cap nodes
+  unsigned long long *h_rec;            // pinned record: nodes that went on, capped nodes, changed associations (cumulative)
+  // the trained tree, DBoW3 order
+  bool trained;
+  std::vector<unsigned int> r_desc;
+  std::vector<int> r_children, r_won, r_now;
+  xk_voc_outcome outcome;
+};
+
+static void voc_free_level(xk_voc *v) {
+  hipFree(v->d_nodes); hipFree(v->d_cen); hipFree(v->d_cnt); hipFree(v->d_gsize); hipFree(v->d_csize); hipFree(v->d_dstoff);
+  hipFree(v->d_childnext);
+  if (v->h_pin) hipHostFree(v->h_pin);
+  v->d_nodes = nullptr; v->d_cen = nullptr; v->d_cnt = v->d_gsize = v->d_csize = v->d_dstoff = v->d_childnext = nullptr;
+  v->h_pin = nullptr; v->a_cap = 0;
+}
+
+extern "C" void xk_voc_destroy(xk_voc *v) {
+  if (!v) return;
+  hipFree(v->d_desc); hipFree(v->d_perm[0]); hipFree(v->d_perm[1]); hipFree(v->d_nop[0]); hipFree(v->d_nop[1]);
+  hipFree(v->d_assoc); hipFree(v->d_min); hipFree(v->d_hist); hipFree(v->d_prefix); hipFree(v->d_bsum); hipFree(v->d_rec);
+  voc_free_level(v);
+  if (v->h_rec) hipHostFree(v->h_rec);
+  delete v;
+}
+
+extern "C" int xk_voc_create(xk_handle *h, int k, int L, int desc_bytes, int max_desc, xk_voc **out) {
+  if (!h || !out) return XK_EINVAL;
+  if (k < 2 || k > XK_VOC_KMAX || L < 1 || L > XK_VOC_LMAX || max_desc < 1) return fail(h, XK_EINVAL, "xk_voc_create: k outside 2...16, L outside 1...8 or max_desc < 1");
+  if (desc_bytes < 4 || desc_bytes % 4 || desc_bytes > 4 * XK_PR_MAXW)
+    return fail(h, XK_EINVAL, "xk_voc_create: descriptor size must be a multiple of 4 bytes, at most 64");
+  double cl = 1.0;
+  for (int i = 0; i < L; ++i) cl *= k;
+  if (cl * desc_bytes > (double)(64 << 20)) return fail(h, XK_ECAPACITY, "xk_voc_create: k^L descriptors larger than 64 MB");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_voc *v = new (std::nothrow) xk_voc();
+  if (!v) return XK_ENOMEM;
+  v->h = h; v->k = k; v->L = L; v->W = desc_bytes / 4; v->max_desc = max_desc;
+  const size_t nb = ((size_t)max_desc + XK_VOC_T - 1) / XK_VOC_T;
+  const bool ok = dalloc(&v->d_desc, (size_t)max_desc * v->W) == hipSuccess && dalloc(&v->d_perm[0], (size_t)max_desc) == hipSuccess &&
+                  dalloc(&v->d_perm[1], (size_t)max_desc) == hipSuccess && dalloc(&v->d_nop[0], (size_t)max_desc) == hipSuccess &&
+                  dalloc(&v->d_nop[1], (size_t)max_desc) == hipSuccess && dalloc(&v->d_assoc, (size_t)max_desc) == hipSuccess &&
+                  dalloc(&v->d_min, (size_t)max_desc) == hipSuccess && dalloc(&v->d_prefix, (size_t)max_desc) == hipSuccess &&
+                  dalloc(&v->d_bsum, nb) == hipSuccess && dalloc(&v->d_hist, nb * k) == hipSuccess && dalloc(&v->d_rec, (size_t)4) == hipSuccess &&
+                  hipHostMalloc((void **)&v->h_rec, 4 * sizeof(unsigned long long)) == hipSuccess;
+  if (!ok) { xk_voc_destroy(v); return fail(h, XK_ENOMEM, "xk_voc_create: allocation failed"); }
+  *out = v;
+  return XK_OK;
+}
+
+extern "C" int xk_voc_count(const xk_voc *v) { return v ? v->count : 0; }
+
+extern "C" int xk_voc_clear(xk_voc *v) {
+  if (!v) return XK_EINVAL;
+  v->count = 0;
+  v->trained = false;
+  return XK_OK;
+}
+
+extern "C" int xk_voc_add(xk_voc *v, const unsigned char *desc, int n) {
+  if (!v) return XK_EINVAL;
+  xk_handle *h = v->h;
+  if (n < 0 || (n > 0 && !desc)) return fail(h, XK_EINVAL, "xk_voc_add: n < 0 or null descriptors");
+  if (n > v->max_desc - v->count) return fail(h, XK_ECAPACITY, "xk_voc_add: more descriptors than max_desc");
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  // (the caller's rows are pageable: the copy is staged by the runtime, and the wait makes the rows the caller's again)
+  HIPCHK(h, hipMemcpyAsync(v->d_desc + (size_t)v->count * v->W, desc, (size_t)n * v->W * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  v->count += n;
+  return XK_OK;
+}
+
+// the pinned block (the nodes first, then the regions below) and the device buffers for levels of up to `a` nodes; the
+// stream is idle when voc_reserve is called
+static size_t voc_pin_cen(size_t cap) { return sizeof(XkVocNode) * cap; }
+static size_t voc_pin_csize(const xk_voc *v, size_t cap) { return voc_pin_cen(cap) + sizeof(int) * cap * v->k * v->W; }
+static size_t voc_pin_dstoff(const xk_voc *v, size_t cap) { return voc_pin_csize(v, cap) + sizeof(int) * cap * v->k; }
+static size_t voc_pin_childnext(const xk_voc *v, size_t cap) { return voc_pin_dstoff(v, cap) + sizeof(int) * cap * v->k; }
+static size_t voc_pin_bytes(const xk_voc *v, size_t cap) { return voc_pin_childnext(v, cap) + sizeof(int) * cap * v->k; }
+
+static int voc_reserve(xk_voc *v, size_t a) {
+  if (a <= v->a_cap) return XK_OK;
+  xk_handle *h = v->h;
+  voc_free_level(v);
+  const size_t cap = std::max(a, (size_t)64), g = cap * v->k;
+  const bool ok = dalloc(&v->d_nodes, cap) == hipSuccess && dalloc(&v->d_cen, g * v->W) == hipSuccess &&
+                  dalloc(&v->d_cnt, g * v->W * 32) == hipSuccess && dalloc(&v->d_gsize, g) == hipSuccess &&
+                  dalloc(&v->d_csize, g) == hipSuccess && dalloc(&v->d_dstoff, g) == hipSuccess && dalloc(&v->d_childnext, g) == hipSuccess &&
+                  hipHostMalloc((void **)&v->h_pin, voc_pin_bytes(v, cap)) == hipSuccess;
+  if (!ok) { voc_free_level(v); return fail(h, XK_ENOMEM, "xk_voc_train: buffers of a level"); }
+  v->a_cap = cap;
+  HIPCHK(h, hipMemsetAsync(v->d_cnt, 0, sizeof(int) * g * v->W * 32, h->stream));   // (the majority kernels leave it zero)
+  return XK_OK;
+}
+
+extern "C" int xk_voc_train(xk_voc *v, unsigned long seed, int max_iter, xk_voc_outcome *outcome) {
+  if (!v) return XK_EINVAL;
+  xk_handle *h = v->h;
+  if (max_iter < 1) return fail(h, XK_EINVAL, "xk_voc_train: max_iter < 1");
+  HIPCHK(h, hipSetDevice(h->device));
+  v->trained = false;
+  const int k = v->k, W = v->W, N = v->count;
+  xk_voc_outcome oc{};
+  struct Lv { int start, cnt, hid; unsigned long long path; };
+  std::vector<Lv> cur, nxt;
+  std::vector<XkVocHostNode> hn(1, XkVocHostNode{0, 0});   // host list, level order; [0] is the root
+  std::vector<unsigned int> hdesc((size_t)W, 0u);          // [host node][W]
+  const dim3 T(XK_VOC_T);
+  auto blocks = [](size_t n) { return dim3((unsigned int)((n + XK_VOC_T - 1) / XK_VOC_T)); };
+  int which = 0, M = N;
+  unsigned long long went_on = 0;
+  if (N > 0) {
+    int rc = voc_reserve(v, 1);
+    if (rc != XK_OK) return rc;
+    HIPCHK(h, hipMemsetAsync(v->d_rec, 0, 4 * sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(xk_voc_iota, blocks(N), T, 0, h->stream, v->d_perm[0], v->d_nop[0], N);
+    ++oc.launches;
+    cur.push_back(Lv{0, N, 0, 0ull});
+  }
+  for (int level = 1; level <= v->L && !cur.empty(); ++level) {
+    const int A = (int)cur.size();
+    const size_t cap = v->a_cap;
+    XkVocNode *pn = (XkVocNode *)v->h_pin;
+    bool nontrivial = false;
+    for (int a = 0; a < A; ++a) {
+      pn[a] = XkVocNode{cur[a].start, cur[a].cnt, 0, cur[a].cnt > k ? 1 : 0, 0, 0,
+                        xk_ransac_mix((unsigned long long)seed ^ xk_ransac_mix(cur[a].path))};
+      nontrivial |= cur[a].cnt > k;
+    }
+    HIPCHK(h, hipMemcpyAsync(v->d_nodes, pn, sizeof(XkVocNode) * A, hipMemcpyHostToDevice, h->stream));
+    XkVocLevel lv{v->d_desc, W, k, M, A, v->d_perm[which], v->d_nop[which], v->d_nodes, v->d_cen, v->d_assoc, v->d_min,
+                  v->d_prefix, v->d_bsum, v->d_cnt, v->d_gsize, v->d_csize, v->d_hist, v->d_rec};
+    const dim3 GM = blocks(M), GA = blocks(A);
+    hipLaunchKernelGGL(xk_voc_seed_first, GA, T, 0, h->stream, lv);
+    ++oc.launches;
+    int passes = 0;
+    if (nontrivial) {
+      for (int j = 1; j < k; ++j) {                          // the cut is formed on the device: no wait while seeding
+        hipLaunchKernelGGL(xk_voc_seed_dist, GM, T, 0, h->stream, lv, j);
+        hipLaunchKernelGGL(xk_voc_scan_u64, dim3(1), T, 0, h->stream, v->d_bsum, (int)GM.x);
+        hipLaunchKernelGGL(xk_voc_prefix, GM, T, 0, h->stream, lv);
+        hipLaunchKernelGGL(xk_voc_seed_pick, GM, T, 0, h->stream, lv, j);
+        oc.launches += 4;
+      }
+      for (int pass = 1;; ++pass) {
+        hipLaunchKernelGGL(xk_voc_assoc, GM, T, 0, h->stream, lv, pass);
+        hipLaunchKernelGGL(xk_voc_status, GA, T, 0, h->stream, lv, pass, max_iter);
+        oc.launches += 2;
+        HIPCHK(h, hipMemcpyAsync(v->h_rec, v->d_rec, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        if (pass < max_iter) {                               // queued before the wait: nothing to do where no node goes on
+          hipLaunchKernelGGL(xk_voc_majority_count, GM, T, 0, h->stream, lv);
+          hipLaunchKernelGGL(xk_voc_majority_set, blocks((size_t)A * k * W), T, 0, h->stream, lv);
+          oc.launches += 2;
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        ++oc.host_waits;
+        passes = pass;
+        const bool more = v->h_rec[0] != went_on;
+        went_on = v->h_rec[0];
+        oc.capped_nodes = (int)v->h_rec[1];
+        if (!more) break;
+      }
+    }
+    // the level's result: children and centres of every node, and (above the last level) the sizes of the groups
+    int *pcs = (int *)(v->h_pin + voc_pin_csize(v, cap));
+    unsigned int *pcen = (unsigned int *)(v->h_pin + voc_pin_cen(cap));
+    const bool split = level < v->L;
+    if (split) {
+      HIPCHK(h, hipMemsetAsync(v->d_csize, 0, sizeof(int) * (size_t)A * k, h->stream));
+      hipLaunchKernelGGL(xk_voc_hist, GM, T, 0, h->stream, lv);
+      hipLaunchKernelGGL(xk_voc_scan_hist, dim3(1), T, 0, h->stream, v->d_hist, (int)GM.x, k);
+      oc.launches += 2;
+      HIPCHK(h, hipMemcpyAsync(pcs, v->d_csize, sizeof(int) * (size_t)A * k, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(pn, v->d_nodes, sizeof(XkVocNode) * A, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pcen, v->d_cen, sizeof(int) * (size_t)A * k * W, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ++oc.host_waits;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, XK_EDEVICE, "xk_voc_train launch", e);
+    oc.level_nodes[level - 1] = A;
+    oc.level_passes[level - 1] = passes;
+    oc.levels = level;
+    // host walk: one host node per centre; a child with more than one descriptor is a node of the next level (:371-392)
+    nxt.clear();
+    std::vector<int> dst_off((size_t)A * k, 0), child_next((size_t)A * k, -1);
+    int cum[XK_VOC_KMAX] = {0};
+    int M_next = 0;
+    for (int a = 0; a < A; ++a) {
+      const int nc = pn[a].ncent;
+      if (nc < 1 || nc > k) return fail(h, XK_EDEVICE, "xk_voc_train: a node without centres");
+      hn[cur[a].hid] = XkVocHostNode{(int)hn.size(), nc};
+      for (int c = 0; c < nc; ++c) {
+        const int id = (int)hn.size();
+        hn.push_back(XkVocHostNode{0, 0});
+        hdesc.insert(hdesc.end(), pcen + ((size_t)a * k + c) * W, pcen + ((size_t)a * k + c + 1) * W);
+        if (split) {
+          const int sz = pcs[(size_t)a * k + c];
+          if (sz > 1) {
+            child_next[(size_t)a * k + c] = (int)nxt.size();
+            dst_off[(size_t)a * k + c] = M_next - cum[c];
+            nxt.push_back(Lv{M_next, sz, id, cur[a].path * (unsigned long long)(k + 1) + (unsigned long long)c + 1ull});
+            M_next += sz;
+          }
+          cum[c] += sz;
+        }
+      }
+    }
+    if (!nxt.empty()) {
+      int rc = voc_reserve(v, std::max(nxt.size(), (size_t)A));   // (may move the pinned block: pn, pcs, pcen end here)
+      if (rc != XK_OK) return rc;
+      int *pdo = (int *)(v->h_pin + voc_pin_dstoff(v, v->a_cap)), *pch = (int *)(v->h_pin + voc_pin_childnext(v, v->a_cap));
+      memcpy(pdo, dst_off.data(), sizeof(int) * (size_t)A * k);
+      memcpy(pch, child_next.data(), sizeof(int) * (size_t)A * k);
+      HIPCHK(h, hipMemcpyAsync(v->d_dstoff, pdo, sizeof(int) * (size_t)A * k, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(v->d_childnext, pch, sizeof(int) * (size_t)A * k, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemsetAsync(v->d_nop[which ^ 1], 0xff, sizeof(int) * (size_t)M_next, h->stream));   // (-1: no node)
+      hipLaunchKernelGGL(xk_voc_scatter, GM, T, 0, h->stream, lv, (const int *)v->d_dstoff, (const int *)v->d_childnext,
+                         v->d_perm[which ^ 1], v->d_nop[which ^ 1], M_next);
+      ++oc.launches;
+      which ^= 1;
+      M = M_next;
+    }
+    cur.swap(nxt);
+  }
+  // DBoW3's ids: a node's children are appended as one block, then the recursion descends into them in order (:361-393)
+  const int n_nodes = (int)hn.size();
+  std::vector<int> newid((size_t)n_nodes, 0);
+  int next_id = 1;
+  std::function<void(int)> walk = [&](int id) {
+    for (int c = 0; c < hn[id].nchild; ++c) newid[hn[id].first_child + c] = next_id++;
+    for (int c = 0; c < hn[id].nchild; ++c)
+      if (hn[hn[id].first_child + c].nchild) walk(hn[id].first_child + c);
+  };
+  walk(0);
+  v->r_desc.assign((size_t)n_nodes * W, 0u);
+  v->r_children.assign((size_t)n_nodes * k, -1);
+  v->r_won.assign((size_t)n_nodes, -1);
+  std::vector<int> old_of_new((size_t)n_nodes, 0);
+  for (int id = 0; id < n_nodes; ++id) {
+    const int ni = newid[id];
+    old_of_new[ni] = id;
+    memcpy(&v->r_desc[(size_t)ni * W], &hdesc[(size_t)id * W], sizeof(unsigned int) * W);
+    for (int c = 0; c < hn[id].nchild; ++c) v->r_children[(size_t)ni * k + c] = newid[hn[id].first_child + c];
+  }
+  v->r_now.clear();
+  for (int ni = 1; ni < n_nodes; ++ni)                       // createWords (:496-515): the leaves in id order, root excluded
+    if (hn[old_of_new[ni]].nchild == 0) {
+      v->r_won[ni] = (int)v->r_now.size();
+      v->r_now.push_back(ni);
+    }
+  oc.n_nodes = n_nodes;
+  oc.n_words = (int)v->r_now.size();
+  v->outcome = oc;
+  v->trained = true;
+  if (outcome) *outcome = oc;
+  return XK_OK;
+}
+
+extern "C" int xk_voc_get(const xk_voc *v, unsigned char *node_desc, int *children, int *word_of_node, int *node_of_word) {
+  if (!v) return XK_EINVAL;
+  if (!v->trained) return fail(v->h, XK_EINVAL, "xk_voc_get: no trained tree");
+  if (node_desc) memcpy(node_desc, v->r_desc.data(), sizeof(unsigned int) * v->r_desc.size());
+  if (children) memcpy(children, v->r_children.data(), sizeof(int) * v->r_children.size());
+  if (word_of_node) memcpy(word_of_node, v->r_won.data(), sizeof(int) * v->r_won.size());
+  if (node_of_word && !v->r_now.empty()) memcpy(node_of_word, v->r_now.data(), sizeof(int) * v->r_now.size());
+  return XK_OK;
 }

@@ -1,5 +1,5 @@
 """Place-recognition request filter and keyframe store on the device -- ctypes binding of the xk_pr_* entry
-points (include/xk.h).  Mirrors the reference's `Database` / `VLAD` / `Keyframe`
+points (include/xk.h), and the training of the vocabulary they consume (xk_voc_*: DBoW3's Vocabulary::create).  Mirrors the reference's `Database` / `VLAD` / `Keyframe`
 (src/x/place_recognition/{database,vlad,keyframe}.cpp) and the matching front half of
 `PlaceRecognition::findCorrespondences` (place_recognition.cpp:137-390).
 
@@ -22,6 +22,19 @@ def load_vocabulary(name="visual", path=None):
     default: the package's own copy of the reference's vocabulary `name` (Vocabulary/<name>_voc_3_4_dbow3.yaml),
     x_multi_agent_amd/data/vocab_<name>.npz."""
     return dict(np.load(path if path else os.path.join(DATA, f"vocab_{name}.npz")))
+
+
+XK_VOC_MAX_LEVELS = 8
+# Host waits a training may take beyond one per association pass and k per level (it takes one per level there: the
+# level's result): none today; the allowance covers an entry and an exit wait.
+VOC_WAIT_SLACK = 2
+
+
+class XkVocOutcome(C.Structure):
+    """xk_voc_outcome of include/xk.h."""
+    _fields_ = [("n_nodes", C.c_int), ("n_words", C.c_int), ("levels", C.c_int), ("level_nodes", C.c_int * XK_VOC_MAX_LEVELS),
+                ("level_passes", C.c_int * XK_VOC_MAX_LEVELS), ("capped_nodes", C.c_int), ("launches", C.c_int),
+                ("host_waits", C.c_int)]
 
 
 def _u8(a):
@@ -198,3 +211,73 @@ def classify(good, n_cur_msckf, n_cur_slam, n_rec_msckf, n_rec_slam):
         if q >= max_rec_slam and t >= max_cur_slam:
             out.append(("opp_opp", t - max_cur_slam, q - max_rec_slam))
     return out
+
+
+class VocabularyTrainer:
+    """DBoW3's Vocabulary::create on one agent's GPU (xk_voc_*): add descriptor rows in any number of pieces, then train.
+    The tree is bit-defined by (descriptors in the order added, k, L, seed, max_iter): DESIGN 3.15."""
+
+    def __init__(self, eng, k, L, desc_bytes=32, max_desc=1 << 16):
+        self.eng, self.L = eng, eng.L
+        self.k, self.Lv, self.desc_bytes, self.max_desc = int(k), int(L), int(desc_bytes), int(max_desc)
+        self.p = C.c_void_p()
+        rc = self.L.xk_voc_create(eng.h, C.c_int(self.k), C.c_int(self.Lv), C.c_int(self.desc_bytes), C.c_int(self.max_desc),
+                                  C.byref(self.p))
+        if rc != 0:
+            raise XkError(rc, "xk_voc_create", (self.L.xk_last_error(eng.h) or b"").decode())
+
+    def close(self):
+        if self.p:
+            self.L.xk_voc_destroy(self.p)
+            self.p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise XkError(rc, what, (self.L.xk_last_error(self.eng.h) or b"").decode())
+
+    def __len__(self):
+        return int(self.L.xk_voc_count(self.p))
+
+    def add(self, descriptors):
+        d, dp = _u8(np.asarray(descriptors, np.uint8).reshape(-1, self.desc_bytes))
+        self._chk(self.L.xk_voc_add(self.p, dp, C.c_int(d.shape[0])), "xk_voc_add")
+
+    def clear(self):
+        self._chk(self.L.xk_voc_clear(self.p), "xk_voc_clear")
+
+    def train(self, seed=0, max_iter=100):
+        """-> the dict load_vocabulary returns (k, L, desc, children, word_of_node, node_of_word) plus `outcome`: n_nodes,
+        n_words, levels, level_nodes, level_passes, capped_nodes, launches, host_waits."""
+        oc = XkVocOutcome()
+        self._chk(self.L.xk_voc_train(self.p, C.c_ulong(seed), C.c_int(max_iter), C.byref(oc)), "xk_voc_train")
+        desc = np.zeros((oc.n_nodes, self.desc_bytes), np.uint8)
+        ch = np.full((oc.n_nodes, self.k), -1, np.int32)
+        won = np.full(oc.n_nodes, -1, np.int32)
+        now = np.zeros(oc.n_words, np.int32)
+        self._chk(self.L.xk_voc_get(self.p, desc.ctypes.data_as(c_ub), ch.ctypes.data_as(c_ip), won.ctypes.data_as(c_ip),
+                                    now.ctypes.data_as(c_ip)), "xk_voc_get")
+        outcome = dict(n_nodes=oc.n_nodes, n_words=oc.n_words, levels=oc.levels, level_nodes=list(oc.level_nodes)[:self.Lv],
+                       level_passes=list(oc.level_passes)[:self.Lv], capped_nodes=oc.capped_nodes, launches=oc.launches,
+                       host_waits=oc.host_waits)
+        return dict(k=np.int32(self.k), L=np.int32(self.Lv), desc=desc, children=ch, word_of_node=won, node_of_word=now,
+                    outcome=outcome)
+
+
+def train_vocabulary(eng, descriptors, k, L, seed=0, max_iter=100, max_desc=None):
+    """Vocabulary::create(training_features, k, L) on the device -> the dict of VocabularyTrainer.train.  It goes straight
+    into Database(eng, voc, ...) and, without `outcome`, into np.savez."""
+    d = np.ascontiguousarray(descriptors, np.uint8)
+    if d.ndim != 2:
+        raise ValueError("descriptors must be [n, desc_bytes]")
+    tr = VocabularyTrainer(eng, k, L, d.shape[1], max_desc if max_desc else max(len(d), 1))
+    try:
+        tr.add(d)
+        return tr.train(seed, max_iter)
+    finally:
+        tr.close()
