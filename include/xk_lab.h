@@ -16,7 +16,9 @@
  * "caqr_tall26", "pipe_kalman", "pipe_split" (0: 184 tiles always, 1: the adaptive default, 2: 152 tiles when the nominal rows fit,
  * 3: always), "caqr_hlite" (0: the per-feature kernel writes 64-row tiles of H0 as before round 5; 1, default: factor records for the
  * narrow single launch and the multi-launch schedule, csrc/xk_feature.hip.h XkFeatArgs::Hc; 2: for the wide single launch too -- measured
- * slower, config 2: 1546 -> 1524 updates/s).
+ * slower, config 2: 1546 -> 1524 updates/s), "feat_gate_form" (1, default: the gate statistic of tracks of at most 32 observations by
+ * generalised least squares on M = J P J^T + sigma^2 I itself, csrc/xk_feature.hip.h xk_chol_gate_gls; 0: the projected form
+ * S = A^T M A everywhere, as before -- the A/B switch, and what tests/test_gpu_gate_form.py compares the default against).
  */
 #ifndef XK_LAB_H_
 #define XK_LAB_H_

@@ -21,7 +21,9 @@ out = (C.c_longlong * n)()
 for rep in range(3):
     eng.L.xk_debug_feature_phases(eng.h, C.c_double(sc["sigma_img"]), out, C.c_int(n))
 w = np.array(list(out), dtype=np.int64).reshape(K, 12)
-names = ["tri(DLT+GN)", "jacobians", "hf_qr", "M build", "2-sided", "cholesky", "up/flag", "tile write"]
+# projected form: hf_qr beside M, nothing, 2-sided, cholesky beside the rows;  GLS form (tracks <= 32): M on four waves, the gate on wave 0
+# beside hf_qr + rows on wave 1, and the two projected-form stages only for a track the gate hands back (rank-deficient Hf)
+names = ["tri(DLT+GN)", "jacobians", "hf_qr||M / M", "gls gate||hf_qr", "2-sided", "cholesky", "up/flag", "tile write"]
 inl = np.asarray(res["inlier"]).astype(bool)
 ph = np.diff(w[:, :8], axis=1) / 2.4e3
 ph[~inl, 6] = 0   # rejected tracks return before the tile write

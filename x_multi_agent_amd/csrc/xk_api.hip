@@ -118,6 +118,7 @@ static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, x
   HIPCHK(h, hipMemset(h->d_A + (size_t)h->ntiles_max * h->DB * h->C1P, 0, sizeof(double) * 256 * h->C1P));
   h->hc_stride = xk_hc_stride(h->DB, h->C1P);
   h->opt_hlite = env_int("XK_HLITE", 1);
+  h->opt_gate_form = 1;
   h->rows_compact = false;
   HIPCHK(h, dalloc(&h->d_Hc, (size_t)std::max(k_max, 1) * h->hc_stride));
   HIPCHK(h, dalloc(&h->d_tile_rows, (size_t)h->ntiles_max));
@@ -747,7 +748,7 @@ static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
                       (h->DB == 128 || (h->opt_resident && h->persist_ok && (h->C1 <= XkPipeNarrow::COLS || h->opt_hlite >= 2)));   // (lab: 2 = the wide geometry too)
     a.Hc = h->rows_compact ? h->d_Hc : nullptr; a.hs = h->hc_stride; a.hcvr = xk_hc_vr(h->DB);
     a.tile_rows = h->d_tile_rows; a.inlier = h->d_inl; a.gamma = h->d_gam; a.gpf = h->d_gpf; a.gn_iters = h->d_gn;
-    a.gpf_in = nullptr; a.up_out = nullptr; a.batch = nullptr; a.dbg = h->feat_dbg;
+    a.gpf_in = nullptr; a.up_out = nullptr; a.batch = nullptr; a.dbg = h->feat_dbg; a.gate_form = h->opt_gate_form;
     a.inlier_h = h->h_flag_i; a.gamma_h = h->h_flag_d;     // gate results also straight into the pinned flag cache
     const bool packed = xk_feature_packed(h->n_poses);      // windows of more than 33 poses: gate matrix as a packed triangle
     feat_lds = xk_feature_lds_bytes(h->n_poses, packed);
@@ -1578,6 +1579,7 @@ extern "C" int xk_set_option(xk_handle *h, const char *name, int value) {
   else if (!strcmp(name, "pipe_kalman")) h->opt_kalman = value;
   else if (!strcmp(name, "pipe_split")) { if (h->opt_split >= 0) h->opt_split = value; }
   else if (!strcmp(name, "caqr_hlite")) h->opt_hlite = value;
+  else if (!strcmp(name, "feat_gate_form")) h->opt_gate_form = value ? 1 : 0;   // A/B switch, and the tests' handle on the fallback
 #endif
   else return fail(h, XK_EINVAL, "xk_set_option: unknown option");
   return XK_OK;

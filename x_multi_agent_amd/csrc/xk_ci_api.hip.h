@@ -377,6 +377,7 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
     a.A = nullptr; a.DB = 0; a.C1P = 0; a.na = n_i - XK_CORE;
     a.tile_rows = dint + 2; a.inlier = dint + 1; a.gamma = dscal + 2; a.gpf = dgpf + 4; a.gn_iters = dint + 3;
     a.gpf_in = dgpf; a.up_out = up + i * upsz; a.batch = nullptr; a.dbg = nullptr; a.inlier_h = nullptr; a.gamma_h = nullptr;
+    a.gate_form = h->opt_gate_form;
     hipLaunchKernelGGL(xk_msckf_feature, dim3(1), dim3(XK_FEAT_THREADS), xk_feature_lds_bytes(np_i), h->stream, a);
     if (self) {
       int inl = 0;
@@ -745,7 +746,7 @@ static void ci_round_prepare(xk_handle *h, CiRound &r, int j, CiStage (&stage)[8
   memset(&a, 0, sizeof(a));
   a.K = k1; a.var_img = r.var_img; a.chi95 = h->d_chi95; a.n = n; a.na = n - XK_CORE; a.n_poses = npmax; a.n_poses_max = N;
   a.tile_rows = dint + 8; a.inlier = dint; a.gamma = dscal + 2; a.gpf = (double *)(dint + 192); a.gn_iters = dint + 24;
-  a.gpf_in = dgpf; a.batch = db;
+  a.gpf_in = dgpf; a.batch = db; a.gate_form = h->opt_gate_form;
   stage[3].push_back([=]() { hipLaunchKernelGGL(xk_msckf_feature, dim3(k1), dim3(XK_FEAT_THREADS), xk_feature_lds_bytes(npmax), sj, a); return hipSuccess; });
   // null-space projection of the landmark and split into per-agent Jacobians (:207-223)
   XkCiProjArgs pa;

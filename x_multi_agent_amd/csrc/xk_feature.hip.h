@@ -12,7 +12,8 @@
 // What is exploited that the reference does not: J is block-sparse (one 2x3
 // position block and one 2x3 attitude block per observation), so
 //   J P J^T      is built from 6x6 blocks of P (never the dense d x n product),
-//   A^T(.)A      is applied as three Householder reflectors on both sides,
+//   A^T(.)A      is applied as three Householder reflectors on both sides -- or not at all: for tracks of <= 32 observations the
+//                gate statistic is the minimum of a generalised least-squares problem on M itself (xk_chol_gate_gls),
 //   A^T J        is formed column by column from the reflectors (WY form).
 // All arithmetic is IEEE double; the results differ from the reference only
 // by summation order (basis choice of A is immaterial).
@@ -69,6 +70,9 @@ struct XkFeatArgs {
   double *up_out;
   // batch mode (CI round): block b works on its OWN window / prior / track, described by batch[b]
   const struct XkFeatBatch *batch;
+  // gate statistic of tracks of <= 32 observations in the unpacked kernel: 1 = generalised least squares on M itself (xk_chol_gate_gls),
+  // 0 = the projected form S = A^T M A everywhere (what longer tracks, the packed kernel and rank-deficient Hf take anyway)
+  int gate_form;
   long long *dbg;   // probe builds only: phase stamps of block 0
 };
 
@@ -390,6 +394,144 @@ __device__ __forceinline__ void xk_chol_gate_blocked(const double *Mm, int ldm, 
 #undef XK_S
 }
 
+// The gate WITHOUT the projection, for 2L <= 64 rows: A spans the complement of range(Hf), so
+//     gamma = min_x (res - Hf x)^T M^-1 (res - Hf x) = |y - Y z|^2,   [y | Y] = L_M^-1 [res | Hf],   z = (Y^T Y)^-1 Y^T y,
+// one blocked Cholesky of M itself (same tiles, same pivot chain as xk_chol_gate_blocked) whose right-hand-side tile carries res in
+// column 0 and Hf in columns 1..3, then a 3 x 3 solve.  Neither the two-sided application nor the reflectors are on this chain.
+// Three pieces, so that the caller can put work between them: the right-hand-side tiles (from res and V BEFORE the reflectors
+// overwrite them), the tiles of M, the factorisation.
+//
+// XK_GLS_PIVOT_MIN: smallest pivot of C = Y^T Y scaled to unit diagonal below which the track takes the projected form instead
+// (Hf numerically rank-deficient: C is singular and z undefined, the projected form still has its implementation-defined answer).
+// Measured by tests/test_gate_form_np.py: the smallest pivot over every family of tests/feature_cases.py that triangulates is 1.7e-4
+// (forward_ragged_n30); on `forward` with every attitude the first one (Hf exactly rank 2) the largest is 1.3e-10 -- rounding noise
+// of the last pivot, eps divided by the one before it, not the 1e-33 of exact arithmetic.  The threshold sits between the two.
+#define XK_GLS_PIVOT_MIN 1e-7
+__device__ __forceinline__ double xk_readlane_f64(double x, int l) {
+  const long long q = __builtin_bit_cast(long long, x);
+  const int lo = __builtin_amdgcn_readlane((int)(q & 0xffffffffLL), l), hi = __builtin_amdgcn_readlane((int)(q >> 32), l);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+__device__ __forceinline__ void xk_gls_load_rhs(const double *res, const double *V, int m2, int lane, xk_d4 (&R)[4]) {
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = 16 * i + lk + 4 * q;
+      double v = 0.0;
+      if (r < m2 && li < 4) v = (li == 0) ? res[r] : V[(li - 1) * m2 + r];
+      R[i][q] = v;
+    }
+}
+__device__ __forceinline__ void xk_gls_load_tiles(const double *Mm, int ldm, int m2, int lane, xk_d4 (&T)[4][4]) {
+  const int nb = (m2 + 15) >> 4, li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int k = i; k < 4; ++k)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int r = 16 * i + lk + 4 * q, c = 16 * k + li;  // element (r, c), r <= c off the diagonal tile
+        double v = (r == c) ? 1.0 : 0.0;                      // identity padding past 2L
+        if (i < nb && k < nb && r < m2 && c < m2) v = (r >= c) ? Mm[(size_t)r * ldm + c] : Mm[(size_t)c * ldm + r];
+        T[i][k][q] = v;
+      }
+}
+// -> scal[12] = gamma, scal[10] on a non-positive pivot of M, scal[14] = 1 where the track has to take the projected form
+__device__ __forceinline__ void xk_chol_gate_gls(xk_d4 (&T)[4][4], xk_d4 (&R)[4], int m2, int lane, double *scal, double *work) {
+  constexpr int NB = 4;
+  const int nb = (m2 + 15) >> 4, li = lane & 15, lk = lane >> 4;
+  double *dbuf = work, *Ls = work + 256;
+  xk_d4 G = {0, 0, 0, 0};                                     // Gram tile of [y | Y]: its 4 x 4 corner is register 0 of lanes 16 m + n
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    if (j < nb) {                                             // uniform
+#pragma unroll
+      for (int q = 0; q < 4; ++q) dbuf[64 * q + lane] = T[j][j][q];   // C/D layout == row-major 16 x 16
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      __builtin_amdgcn_wave_barrier();
+      if (xk_chol16_bcast(dbuf, Ls, lane)) bad = true;
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      __builtin_amdgcn_wave_barrier();
+      double lv[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) lv[q] = Ls[li * 17 + 4 * q + lk];
+      // row j
+#pragma unroll
+      for (int k = j + 1; k < NB; ++k) {
+        if (k < nb) {
+          xk_d4 x = {0, 0, 0, 0};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[q], T[j][k][q], x, 0, 0, 0);
+          T[j][k] = x;
+        }
+      }
+      {
+        xk_d4 x = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[q], R[j][q], x, 0, 0, 0);
+        R[j] = x;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) G = __builtin_amdgcn_mfma_f64_16x16x4f64(x[q], x[q], G, 0, 0, 0);
+      }
+      // trailing tiles
+#pragma unroll
+      for (int i = j + 1; i < NB; ++i) {
+        if (i < nb) {
+#pragma unroll
+          for (int k = i; k < NB; ++k) {
+            if (k < nb) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) T[i][k] = __builtin_amdgcn_mfma_f64_16x16x4f64(-T[j][i][q], T[j][k][q], T[i][k], 0, 0, 0);
+            }
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) R[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(-T[j][i][q], R[j][q], R[i], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // C = Y^T Y and b = Y^T y, uniform over the lanes; C to unit diagonal, Cholesky, z
+  const double b1 = xk_readlane_f64(G[0], 1), b2 = xk_readlane_f64(G[0], 2), b3 = xk_readlane_f64(G[0], 3);
+  const double c11 = xk_readlane_f64(G[0], 17), c12 = xk_readlane_f64(G[0], 18), c13 = xk_readlane_f64(G[0], 19);
+  const double c22 = xk_readlane_f64(G[0], 34), c23 = xk_readlane_f64(G[0], 35), c33 = xk_readlane_f64(G[0], 51);
+  // (inverse square roots from the hardware seed + two Newton steps, as in xk_null4: gamma is a minimum over z, an error of z enters
+  //  it squared, and thirteen IEEE divisions and square roots in one dependent chain were ~1 us on this wave)
+  auto rsq = [](double v) { double y = __builtin_amdgcn_rsq(v); y = y * fma(-0.5 * v * y, y, 1.5); return y * fma(-0.5 * v * y, y, 1.5); };
+  const double s1 = rsq(c11), s2 = rsq(c22), s3 = rsq(c33);
+  const double l21 = c12 * s1 * s2, l31 = c13 * s1 * s3, h23 = c23 * s2 * s3;
+  const double p2 = 1.0 - l21 * l21;
+  const double r2 = rsq(p2);
+  const double l32 = (h23 - l31 * l21) * r2;
+  const double p3 = 1.0 - l31 * l31 - l32 * l32;
+  const double r3 = rsq(p3);
+  const bool proj = !(p2 >= XK_GLS_PIVOT_MIN && p3 >= XK_GLS_PIVOT_MIN);   // (NaN included)
+  // L w = D b, L^T u = w, z = D u
+  const double w1 = b1 * s1, w2 = (b2 * s2 - l21 * w1) * r2, w3 = (b3 * s3 - l31 * w1 - l32 * w2) * r3;
+  const double u3 = w3 * r3, u2 = (w2 - l32 * u3) * r2, u1 = w1 - l21 * u2 - l31 * u3;
+  const double z1 = u1 * s1, z2 = u2 * s2, z3 = u3 * s3;
+  // gamma = |y - Y z|^2 over the rows of the right-hand-side tiles: columns 0..3 are the lanes li = 0..3 of each row of lanes, one quad
+  const double cf = (li == 0) ? 1.0 : (li == 1) ? -z1 : (li == 2) ? -z2 : (li == 3) ? -z3 : 0.0;
+  double g = 0.0;
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double t = (li < 4) ? cf * R[j][q] : 0.0;
+      t += xk_dpp_f64<0xB1>(t);    // quad_perm [1,0,3,2]
+      t += xk_dpp_f64<0x4E>(t);    // quad_perm [2,3,0,1]
+      if (li == 0) g = fma(t, t, g);
+    }
+  g = xk_wave_sum(g);
+  if (lane == 0) {
+    scal[12] = g;
+    if (bad) scal[10] = 1.0;
+    scal[14] = (proj && !bad) ? 1.0 : 0.0;
+  }
+}
+
 // The blocked gate for 64 <= d <= 125 (windows of 34..64 poses) on the FOUR waves of the workgroup: 16 x 16 tiles as above,
 // tile column k -- tiles (i, k), i <= k -- in the registers of wave k % 4; the residual rides along as tile column nb.
 // Per block step j: the owner of column j factors and inverts the diagonal tile (xk_chol16_bcast), barrier, every wave turns
@@ -707,10 +849,8 @@ __device__ __forceinline__ void xk_msckf_feature_body(XkFeatArgs a_in) {
   __syncthreads();
 
   XK_STAMP(2);
-  // ---- wave 0: Householder QR of Hf (2L x 3) -> three reflectors (:423), then the residual r' = Q^T res;
-  //      waves 1-3 meanwhile: the gate matrix (independent of the reflectors)
-  if (tid < 64) {
-    const int lane = tid;
+  // ---- one wave: Householder QR of Hf (2L x 3) -> three reflectors (:423), then the residual r' = Q^T res
+  auto reflectors = [&](const int lane) {
     for (int kk = 0; kk < 3; ++kk) {
       double *col = V + kk * m2;
       double tail = 0.0;
@@ -777,8 +917,10 @@ __device__ __forceinline__ void xk_msckf_feature_body(XkFeatArgs a_in) {
       __builtin_amdgcn_s_waitcnt(0);
       __builtin_amdgcn_wave_barrier();
     }
-  } else {
-    // ---- gate matrix M = J P J^T + sigma^2 I from 6x6 blocks of P (:452-457)
+  };
+  // ---- gate matrix M = J P J^T + sigma^2 I from 6x6 blocks of P (:452-457), by the threads t0, t0 + 1, .. of a group of `nthr`
+  //      (independent of the reflectors)
+  auto build_M = [&](const int t0, const int nthr) {
     {
       const int n = a.n;
       const double *P = a.P;
@@ -787,7 +929,7 @@ __device__ __forceinline__ void xk_msckf_feature_body(XkFeatArgs a_in) {
       // scattered lines.  Column ib = c carries c + 1 pairs and column L-1-c carries L - c: together L + 1 slots,
       // one group of G lanes per such couple of columns.
       const int G = (L + 1 <= 32) ? 32 : (L + 1 <= 64) ? 64 : 128, ncouple = (L + 1) / 2;
-      for (int idx = tid - 64; idx < ncouple * G; idx += XK_FEAT_THREADS - 64) {
+      for (int idx = t0; idx < ncouple * G; idx += nthr) {
         const int cpl = idx / G, u = idx - cpl * G, ib2 = L - 1 - cpl;
         if (u > L || (u > cpl && ib2 == cpl)) continue;          // past the slots / the middle column of an odd L
         const int ia = (u <= cpl) ? u : u - cpl - 1, ib = (u <= cpl) ? cpl : ib2;
@@ -823,13 +965,110 @@ __device__ __forceinline__ void xk_msckf_feature_body(XkFeatArgs a_in) {
           }
       }
     }
+  };
+  double tau0 = 0.0, tau1 = 0.0, tau2 = 0.0, g01 = 0.0, g02 = 0.0, g12 = 0.0;   // of the reflectors, from scal[0..5] once they are there
+  // ---- tile write: rows 3.. of Q^T [J | res] over the active columns (:431-432,468-479), by the threads
+  //      t0, t0 + 1, .. of a group of `nthr`
+  auto tile_write = [&](int t0, int nthr) {
+    double *tile = a.A + (size_t)k * a.DB * a.C1P;
+    const int N3 = 3 * a.n_poses_max;
+    for (int c = t0; c < a.C1P; c += nthr) {
+      if (c == a.na) {
+        for (int r = 3; r < m2; ++r) tile[(size_t)(r - 3) * a.C1P + c] = res[r];
+        continue;
+      }
+      int i = -1, comp = 0;
+      const double *blk = nullptr;
+      if (c < N3) { i = c / 3 - p0; comp = c % 3; blk = Jp; }
+      else if (c < 2 * N3) { i = (c - N3) / 3 - p0; comp = (c - N3) % 3; blk = Ja; }
+      if (c >= a.na || i < 0 || i >= L) {
+        for (int r = 3; r < m2; ++r) tile[(size_t)(r - 3) * a.C1P + c] = 0.0;
+        continue;
+      }
+      const double x0 = blk[6 * i + comp], x1 = blk[6 * i + 3 + comp];
+      const int r0 = 2 * i;
+      const double a0 = V[r0] * x0 + V[r0 + 1] * x1;
+      const double a1 = V[m2 + r0] * x0 + V[m2 + r0 + 1] * x1;
+      const double a2 = V[2 * m2 + r0] * x0 + V[2 * m2 + r0 + 1] * x1;
+      const double w0 = tau0 * a0;
+      const double w1 = tau1 * (a1 - w0 * g01);
+      const double w2 = tau2 * (a2 - w0 * g02 - w1 * g12);
+      for (int r = 3; r < m2; ++r) tile[(size_t)(r - 3) * a.C1P + c] = xk_h0_entry(w0, w1, w2, x0, x1, r0, V[r], V[m2 + r], V[2 * m2 + r], 0.0, r);
+    }
+  };
+  // ---- or the factor record of the track (a.Hc): the same numbers, not multiplied out
+  auto record_write = [&](int t0, int nthr) {
+    double *rec = a.Hc + (size_t)k * a.hs;
+    for (int r = t0; r < m2; r += nthr) {
+      xk_d2 p0v = {V[r], V[m2 + r]}, p1v = {V[2 * m2 + r], res[r]};
+      reinterpret_cast<xk_d2 *>(rec + 4 * r)[0] = p0v;
+      reinterpret_cast<xk_d2 *>(rec + 4 * r)[1] = p1v;
+    }
+    const int N3 = 3 * a.n_poses_max;
+    for (int c = t0; c < a.C1P; c += nthr) {
+      double w0 = 0.0, w1 = 0.0, w2 = 0.0, x0 = 0.0, x1 = 0.0;
+      int r0 = -2;
+      if (c == a.na) r0 = -1;
+      else {
+        int i = -1, comp = 0;
+        const double *blk = nullptr;
+        if (c < N3) { i = c / 3 - p0; comp = c % 3; blk = Jp; }
+        else if (c < 2 * N3) { i = (c - N3) / 3 - p0; comp = (c - N3) % 3; blk = Ja; }
+        if (c < a.na && i >= 0 && i < L) {
+          x0 = blk[6 * i + comp]; x1 = blk[6 * i + 3 + comp];
+          r0 = 2 * i;
+          const double a0 = V[r0] * x0 + V[r0 + 1] * x1;
+          const double a1 = V[m2 + r0] * x0 + V[m2 + r0 + 1] * x1;
+          const double a2 = V[2 * m2 + r0] * x0 + V[2 * m2 + r0 + 1] * x1;
+          w0 = tau0 * a0;
+          w1 = tau1 * (a1 - w0 * g01);
+          w2 = tau2 * (a2 - w0 * g02 - w1 * g12);
+        }
+      }
+      xk_d2 *wc = reinterpret_cast<xk_d2 *>(rec + a.hcvr + XK_HC_WC * c);
+      xk_d2 q0 = {w0, w1}, q1 = {w2, x0}, q2 = {x1, (double)r0};
+      wc[0] = q0; wc[1] = q1; wc[2] = q2;
+    }
+  };
+  // (the gates' work area is read two doubles at a time: 16-byte aligned)
+  double *work = scal + 32 + 12 * Lmax + 64;
+  work += ((size_t)work >> 3) & 1;
+  // ---- stage plan.  gls (tracks of <= 32 observations, XkFeatArgs::gate_form): all four waves build M; wave 0 takes the tiles and
+  //      [res | Hf] into registers and factors (xk_chol_gate_gls) with no workgroup barrier inside; beside it wave 1 makes the
+  //      reflectors and then writes the factor record itself -- one wave does both, so no hand-off inside the workgroup orders
+  //      them.  A tile launch (a.A: 10 500 doubles, too much for one wave) has the reflectors beside the tile LOAD instead, one
+  //      barrier, and waves 1-3 write the tile beside the factorisation.  Otherwise: wave 0 the reflectors, waves 1-3 M.
+  const bool tiles = a.A && !a.Hc;
+  bool gls = !PACKED && a.gate_form != 0 && m2 <= 64, rows_done = false;
+  if (gls) {
+    xk_d4 T[4][4], R[4];
+    if (tid < 64) xk_gls_load_rhs(res, V, m2, tid, R);         // before the barrier behind which wave 1 overwrites res and V
+    build_M(tid, XK_FEAT_THREADS);
+    __syncthreads();
+    XK_STAMP(3);
+    if (tid < 64) xk_gls_load_tiles(Mm, ldm, m2, tid, T);
+    else if (tid < 128) reflectors(tid - 64);
+    if (tiles) __syncthreads();
+    if (tid < 64) xk_chol_gate_gls(T, R, m2, tid, scal, work);
+    else if (tiles || tid < 128) {
+      tau0 = scal[0]; tau1 = scal[1]; tau2 = scal[2]; g01 = scal[3]; g02 = scal[4]; g12 = scal[5];
+      if (tiles) tile_write(tid - 64, XK_FEAT_THREADS - 64);   // (a rejected track's tile is masked by tile_rows = 0)
+      else if (a.Hc) record_write(tid - 64, 64);
+    }
+    __syncthreads();
+    rows_done = true;
+    gls = scal[14] == 0.0;   // else: Hf numerically rank-deficient, the projected form below (M is intact: the gate only read it)
+  } else {
+    if (tid < 64) reflectors(tid);
+    else build_M(tid - 64, XK_FEAT_THREADS - 64);
+    __syncthreads();
+    XK_STAMP(3);
   }
-  __syncthreads();
-  const double tau0 = scal[0], tau1 = scal[1], tau2 = scal[2];
-  const double g01 = scal[3], g02 = scal[4], g12 = scal[5];
+  tau0 = scal[0]; tau1 = scal[1]; tau2 = scal[2];
+  g01 = scal[3]; g02 = scal[4]; g12 = scal[5];
 
-  XK_STAMP(3);
   XK_STAMP(4);
+  if (!gls) {
   // ---- M <- Q^T M Q with Q = H0 H1 H2 = I - V T V^T (compact WY):
   //        Q^T M Q = M - V Z^T - Z V^T,   Z = Y T - V B / 2,  Y = M V,  B = T^T (V^T Y) T
   // one matvec sweep + one rank-6 sweep over the lower triangle instead of six reflector sweeps.
@@ -910,69 +1149,6 @@ __device__ __forceinline__ void xk_msckf_feature_body(XkFeatArgs a_in) {
   }
   __syncthreads();
   XK_STAMP(5);
-  // ---- tile write: rows 3.. of Q^T [J | res] over the active columns (:431-432,468-479), by the threads
-  //      t0, t0 + 1, .. of a group of `nthr`
-  auto tile_write = [&](int t0, int nthr) {
-    double *tile = a.A + (size_t)k * a.DB * a.C1P;
-    const int N3 = 3 * a.n_poses_max;
-    for (int c = t0; c < a.C1P; c += nthr) {
-      if (c == a.na) {
-        for (int r = 3; r < m2; ++r) tile[(size_t)(r - 3) * a.C1P + c] = res[r];
-        continue;
-      }
-      int i = -1, comp = 0;
-      const double *blk = nullptr;
-      if (c < N3) { i = c / 3 - p0; comp = c % 3; blk = Jp; }
-      else if (c < 2 * N3) { i = (c - N3) / 3 - p0; comp = (c - N3) % 3; blk = Ja; }
-      if (c >= a.na || i < 0 || i >= L) {
-        for (int r = 3; r < m2; ++r) tile[(size_t)(r - 3) * a.C1P + c] = 0.0;
-        continue;
-      }
-      const double x0 = blk[6 * i + comp], x1 = blk[6 * i + 3 + comp];
-      const int r0 = 2 * i;
-      const double a0 = V[r0] * x0 + V[r0 + 1] * x1;
-      const double a1 = V[m2 + r0] * x0 + V[m2 + r0 + 1] * x1;
-      const double a2 = V[2 * m2 + r0] * x0 + V[2 * m2 + r0 + 1] * x1;
-      const double w0 = tau0 * a0;
-      const double w1 = tau1 * (a1 - w0 * g01);
-      const double w2 = tau2 * (a2 - w0 * g02 - w1 * g12);
-      for (int r = 3; r < m2; ++r) tile[(size_t)(r - 3) * a.C1P + c] = xk_h0_entry(w0, w1, w2, x0, x1, r0, V[r], V[m2 + r], V[2 * m2 + r], 0.0, r);
-    }
-  };
-  // ---- or the factor record of the track (a.Hc): the same numbers, not multiplied out
-  auto record_write = [&](int t0, int nthr) {
-    double *rec = a.Hc + (size_t)k * a.hs;
-    for (int r = t0; r < m2; r += nthr) {
-      xk_d2 p0v = {V[r], V[m2 + r]}, p1v = {V[2 * m2 + r], res[r]};
-      reinterpret_cast<xk_d2 *>(rec + 4 * r)[0] = p0v;
-      reinterpret_cast<xk_d2 *>(rec + 4 * r)[1] = p1v;
-    }
-    const int N3 = 3 * a.n_poses_max;
-    for (int c = t0; c < a.C1P; c += nthr) {
-      double w0 = 0.0, w1 = 0.0, w2 = 0.0, x0 = 0.0, x1 = 0.0;
-      int r0 = -2;
-      if (c == a.na) r0 = -1;
-      else {
-        int i = -1, comp = 0;
-        const double *blk = nullptr;
-        if (c < N3) { i = c / 3 - p0; comp = c % 3; blk = Jp; }
-        else if (c < 2 * N3) { i = (c - N3) / 3 - p0; comp = (c - N3) % 3; blk = Ja; }
-        if (c < a.na && i >= 0 && i < L) {
-          x0 = blk[6 * i + comp]; x1 = blk[6 * i + 3 + comp];
-          r0 = 2 * i;
-          const double a0 = V[r0] * x0 + V[r0 + 1] * x1;
-          const double a1 = V[m2 + r0] * x0 + V[m2 + r0 + 1] * x1;
-          const double a2 = V[2 * m2 + r0] * x0 + V[2 * m2 + r0 + 1] * x1;
-          w0 = tau0 * a0;
-          w1 = tau1 * (a1 - w0 * g01);
-          w2 = tau2 * (a2 - w0 * g02 - w1 * g12);
-        }
-      }
-      xk_d2 *wc = reinterpret_cast<xk_d2 *>(rec + a.hcvr + XK_HC_WC * c);
-      xk_d2 q0 = {w0, w1}, q1 = {w2, x0}, q2 = {x1, (double)r0};
-      wc[0] = q0; wc[1] = q1; wc[2] = q2;
-    }
-  };
   // ---- Cholesky of S = M[3:,3:] (d x d) with the residual as an extra row d (:457-458):
   //      y = L^-1 r0 falls out of the factorisation, gamma = |y|^2
   // Right-looking, un-normalised: S(i,j) -= S(i,k) S(j,k) / S(k,k) for i >= j > k touches only
@@ -982,22 +1158,21 @@ __device__ __forceinline__ void xk_msckf_feature_body(XkFeatArgs a_in) {
   for (int j = tid; j < d; j += XK_FEAT_THREADS) Mm[xk_gm<PACKED>(m2, 3 + j, ldm)] = res[3 + j];
   __syncthreads();
   if (d < 64) {
-    // (the work area is read two doubles at a time: 16-byte aligned)
-    double *work = scal + 32 + 12 * Lmax + 64;
-    work += ((size_t)work >> 3) & 1;
     if (tid < 64) xk_chol_gate_blocked<PACKED>(Mm, ldm, d, tid, scal, work);
+    else if (rows_done) {}                                       // (written beside xk_chol_gate_gls already)
     else if (a.Hc) record_write(tid - 64, XK_FEAT_THREADS - 64);
     else if (a.A) tile_write(tid - 64, XK_FEAT_THREADS - 64);   // the other three waves write the tile meanwhile: a
                                                                  // rejected track's tile is masked by tile_rows = 0
   } else if (PACKED) {
-    double *work = scal + 32 + 12 * Lmax + 64;
-    work += ((size_t)work >> 3) & 1;
     if (d <= 111) xk_chol_gate_blocked4<PACKED, 2>(Mm, ldm, d, tid, scal, work);
     else xk_chol_gate_blocked4<PACKED, 3>(Mm, ldm, d, tid, scal, work);   // (34 spilled VGPRs, in this branch only)
   } else {
     xk_chol_gate<8, PACKED>(Mm, ldm, d, tid, scal);
   }
   __syncthreads();
+  } else {   // (!gls)
+    XK_STAMP(5);
+  }
   if (tid == 0) {
     const double g = scal[12];
     const bool valid = scal[9] != 0.0 && gx == gx;
