@@ -20,7 +20,8 @@
 //     k has seen the eliminations of panels <= k and must enter panel k + 1's tree (keeping it longer at the top does not
 //     move that deadline -- the first version tried).
 //   * Hand-off counters are fire-and-forget (no returning atomics on a producer's chain), consumers poll the counter itself
-//     and fetch every phase that is already complete; strips travel in blocks of 4 columns x 16 rows (xk_blk).
+//     and fetch every phase that is already complete; strips travel in blocks of 4 columns x 16 rows (xk_blk).  The XCD-local
+//     counters are per first-level GROUP: with two groups per XCD a tile and a first-level workgroup wait for their own group only.
 // Hand-offs inside an XCD: plain stores + s_waitcnt vmcnt(0) + sc1 loads; across XCDs: write-through stores into per-panel
 // slabs that are never reused inside a launch (xk_xcd_sync.hip.h).  All spins are bounded and look at an abort word; a launch
 // that gives up is redone by the multi-launch schedule (xk_api.hip).  DESIGN 3.2.2 has the anatomy and the numbers.
@@ -151,15 +152,20 @@ __host__ __device__ constexpr int xk_pbn(int q) {
 enum {
   XP_CENSUS = 0,                    // [8] workgroups per XCD
   XP_ABORT = 9,
-  // per XCD, monotonic arrival counters (a panel is complete at NT (k + 1) resp. NM (k + 1))
-  XP_TQ_CNT = 16,                   // [4][8] tiles: rows of phase q of the pivot strips are out
-  XP_MB_CNT = 48,                   // [8] first level: the strips are back
+  // per XCD and first-level group, monotonic arrival counters (a panel is complete at nts (k + 1) resp. NMG (k + 1)): a group's
+  // tiles and its first-level workgroups hand over to each other only -- with two groups per XCD neither waits for a straggler
+  // of the other group (group 1's words stay zero when NG = 1)
+  XP_TQ_CNT = 16,                   // [4][8][2] tiles: rows of phase q of the pivot strips are out
+  XP_MB_CNT = 80,                   // [8][2] first level: the strips are back
   // per panel (XCDs run up to a panel apart)
-  XP_X1_CNT = 64,                   // [4][MAXP] first-level items whose root rows of phase q are out
-  XP_P_CNT = 64 + 4 * XK_CAQR_MAXP,   // [MAXP] last-level workgroups whose pending strips are out
-  XP_R_CNT = 64 + 5 * XK_CAQR_MAXP,   // [MAXP] last-level workgroups whose rows of R are out (Kalman role only)
-  XP_WORDS = 64 + 6 * XK_CAQR_MAXP
+  XP_X1_CNT = 96,                   // [4][MAXP] first-level items whose root rows of phase q are out
+  XP_P_CNT = 96 + 4 * XK_CAQR_MAXP,   // [MAXP] last-level workgroups whose pending strips are out
+  XP_R_CNT = 96 + 5 * XK_CAQR_MAXP,   // [MAXP] last-level workgroups whose rows of R are out (Kalman role only)
+  XP_WORDS = 96 + 6 * XK_CAQR_MAXP
 };
+#define XK_PIPE_TQ_STRIDE (8 * 2 * 16)   // unsigneds between the counters of two phases of XP_TQ_CNT
+// the counter of first-level group grp of XCD xcc inside XP_TQ_CNT (phase 0) / XP_MB_CNT
+__device__ __forceinline__ unsigned *xk_pipe_grp_cnt(unsigned *sync, int first, int xcc, int grp) { return sync + (size_t)(first + xcc * 2 + grp) * 16; }
 
 struct XkCaqrPipeArgs {
   const double *A;        // tiles [ntiles][64][C1P] row-major as the per-feature kernels wrote them (read once)
@@ -209,7 +215,7 @@ __device__ __forceinline__ XkCaqrPipeArgs xk_pipe_args(XkPipeArgsPtr ap) {
 // Hand-off counters: the producer's thread 0 adds one WITHOUT asking for the old value (a returning atomic is a round trip to
 // the L2 that its wave -- and, at the next barrier, its whole workgroup -- sits out: ~0.7 us per hand-off in the first
 // version, which kept an arrival counter + a flag the last arriver raised); the consumers poll the counter itself.  They are
-// few (8 first-level workgroups per tile counter, 23 tiles per first-level counter, one lane each, s_sleep between polls).
+// few (a group's <= 8 first-level workgroups per tile counter, its <= 23 tiles per first-level counter, one lane each, s_sleep between polls).
 __device__ __forceinline__ void xk_pipe_arrive(unsigned *cnt) {
   (void)__hip_atomic_fetch_add(cnt, 1u, XK_ARRIVE_ORDER, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -572,6 +578,7 @@ __device__ __noinline__ bool xk_pipe_tile(XkPipeArgsPtr ap, int xcc, int slot, l
   unsigned *sync = a.sync, *ab = sync + XP_ABORT * 16;
   const int tid = threadIdx.x;
   const int j = xcc * NT + slot;                           // my fat tile: valid rows [j TR, (j + 1) TR)
+  const int tgrp = G::NG > 1 ? slot / G::NTG : 0;          // the first-level group that merges my strip (xk_pipe_first: base)
   const int cabs = tid / LPC, part_ = tid % LPC;           // ABSOLUTE column of this thread, all panels
   const bool mine = cabs < a.C1;
   const int npanels = (a.C1 + 15) / 16;
@@ -729,7 +736,7 @@ __device__ __noinline__ bool xk_pipe_tile(XkPipeArgsPtr ap, int xcc, int slot, l
     // ARRD steps into the next phase (their stores drain behind those steps), the last phase after the panel
     auto phase = [&](auto qc) {
       constexpr int q = decltype(qc)::value;
-      auto hook = [&]() { xk_pipe_arrive(sync + (XP_TQ_CNT + (q - 1) * 8 + xcc) * 16); if (a.dbg && k == 0 && q == 1) a.dbg[47104 + j] = wall_clock64(); };
+      auto hook = [&]() { xk_pipe_arrive(xk_pipe_grp_cnt(sync, XP_TQ_CNT, xcc, tgrp) + (q - 1) * XK_PIPE_TQ_STRIDE); if (a.dbg && k == 0 && q == 1) a.dbg[47104 + j] = wall_clock64(); };
       xk_pipe_range<LPC, xk_pbn<NPH>(q), xk_pbn<NPH>(q + 1), (q > 0 ? xk_pbn<NPH>(q) + ARRD : -1), RPL>(b, nullptr, rel, mine, false, part, nsteps, ubuf, sc, full, hook);
       if (pub) {
         if (rel < 16) {
@@ -757,12 +764,13 @@ __device__ __noinline__ bool xk_pipe_tile(XkPipeArgsPtr ap, int xcc, int slot, l
     __syncthreads();
     if (tid == 0) {
       for (int q = full ? NPH - 1 : 0; q < NPH; ++q)
-        xk_pipe_arrive(sync + (XP_TQ_CNT + q * 8 + xcc) * 16);
+        xk_pipe_arrive(xk_pipe_grp_cnt(sync, XP_TQ_CNT, xcc, tgrp) + q * XK_PIPE_TQ_STRIDE);
     }
     if (stamp) a.dbg[16 * k + 5] = wall_clock64();
     if (k + 1 == npanels) break;
-    // my strip comes back from the first level (trailing columns of the NEXT panels only: everything up to c0 + 15 is finished)
-    if (!xk_pipe_wait(sync + (XP_MB_CNT + xcc) * 16, (unsigned)G::NM * epoch, ab, 2u, s_ok)) return false;
+    // my strip comes back from the first level (trailing columns of the NEXT panels only: everything up to c0 + 15 is finished);
+    // it is written by the workgroups of my group alone
+    if (!xk_pipe_wait(xk_pipe_grp_cnt(sync, XP_MB_CNT, xcc, tgrp), (unsigned)G::NMG * epoch, ab, 2u, s_ok)) return false;
     if (stamp) a.dbg[16 * k + 6] = wall_clock64();
     XK_INV_LOC();
     if (mine && rel >= 16 && part == 0) {
@@ -882,6 +890,7 @@ __device__ __noinline__ bool xk_pipe_first(XkPipeArgsPtr ap, int xcc, int item, 
     const unsigned pfw_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)pfw);   // (LDS offset = low half of the flat address)
     const double *pfsrc = (panel ? a.PB + (size_t)base * 256 + xk_blk(cid4, 0) : a.S + (size_t)base * SS + xk_blk(wcol, 0)) +
                           (size_t)(ln >> 3) * strip_step + (ln & 7) * 2;
+    unsigned *tq = xk_pipe_grp_cnt(sync, XP_TQ_CNT, xcc, grp);   // my group's tiles: nts arrivals per phase and panel
     auto phase = [&](auto qc) {
       constexpr int q = decltype(qc)::value;
       if (!ok) return;
@@ -889,17 +898,17 @@ __device__ __noinline__ bool xk_pipe_first(XkPipeArgsPtr ap, int xcc, int item, 
       // TIMING PROBE ONLY (wrong results): all rows were fetched with phase 0, but every phase still WAITS for the tiles' rows
       // of its own -- separates what the waits (the tiles' pace) cost from what the loads cost
       if (q > 0 && loaded > q) {
-        if (xk_pipe_wait_phases(sync + (XP_TQ_CNT + xcc) * 16, 8 * 16, q, NPH, (unsigned)NT * epoch, ab, 6u, s_ok) == 0) { ok = false; return; }
+        if (xk_pipe_wait_phases(tq, XK_PIPE_TQ_STRIDE, q, NPH, (unsigned)nts * epoch, ab, 6u, s_ok) == 0) { ok = false; return; }
       }
 #endif
       if (loaded <= q) {
 #ifdef XK_PIPE_PROBE_M1ALL
         // TIMING PROBE ONLY (wrong results): every phase's rows are fetched with phase 0's -- what the first level would cost if
         // the load latency of phases 1..3 were hidden
-        int av = xk_pipe_wait_phases(sync + (XP_TQ_CNT + xcc) * 16, 8 * 16, q, NPH, (unsigned)NT * epoch, ab, 6u, s_ok);
+        int av = xk_pipe_wait_phases(tq, XK_PIPE_TQ_STRIDE, q, NPH, (unsigned)nts * epoch, ab, 6u, s_ok);
         if (av != 0) av = NPH;
 #else
-        const int av = xk_pipe_wait_phases(sync + (XP_TQ_CNT + xcc) * 16, 8 * 16, q, NPH, (unsigned)NT * epoch, ab, 6u, s_ok);
+        const int av = xk_pipe_wait_phases(tq, XK_PIPE_TQ_STRIDE, q, NPH, (unsigned)nts * epoch, ab, 6u, s_ok);
 #endif
         if (av == 0) { ok = false; return; }
         if (stamp && q < 4) a.dbg[512 + 16 * k + 2 * q] = wall_clock64();
@@ -994,7 +1003,7 @@ __device__ __noinline__ bool xk_pipe_first(XkPipeArgsPtr ap, int xcc, int item, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
-      xk_pipe_arrive(sync + (XP_MB_CNT + xcc) * 16);
+      xk_pipe_arrive(xk_pipe_grp_cnt(sync, XP_MB_CNT, xcc, grp));
       if (!XK_DATA_POLL)
         for (int q = (full && active) ? NPH - 1 : 0; q < NPH; ++q) xk_pipe_arrive(sync + (XP_X1_CNT + q * XK_CAQR_MAXP + k) * 16);
     }
