@@ -59,7 +59,9 @@ struct Quaternion {
   double &x() { return x_; } double &y() { return y_; } double &z() { return z_; } double &w() { return w_; }
   double x() const { return x_; } double y() const { return y_; } double z() const { return z_; } double w() const { return w_; }
   double norm() const { return std::sqrt(x_ * x_ + y_ * y_ + z_ * z_ + w_ * w_); }
-  Quaternion normalized() const { double n = norm(); return Quaternion(w_ / n, x_ / n, y_ / n, z_ / n); }
+  // a zero quaternion stays as it is, as Eigen's normalized() leaves it (its `if (z > 0)`): State::correct normalises every slot of
+  // the window, the ones no pose has entered yet included, and must not turn them into NaN
+  Quaternion normalized() const { double n = norm(); return n > 0.0 ? Quaternion(w_ / n, x_ / n, y_ / n, z_ / n) : *this; }
   void normalize() { *this = normalized(); }
   Quaternion operator*(const Quaternion &b) const {
     return Quaternion(w_ * b.w_ - x_ * b.x_ - y_ * b.y_ - z_ * b.z_, w_ * b.x_ + x_ * b.w_ + y_ * b.z_ - z_ * b.y_,

@@ -1,6 +1,7 @@
 // x/vio/vio_updater.h -- mirror of the concrete updater x::VioUpdater (include/x/vio/vio_updater.h:35,
 // src/x/vio/vio_updater.cpp) restricted to the hot path: measurements arrive as ready-made track lists and match
-// lists (the tracker / track manager / place-recognition front end is out of scope); preUpdate runs
+// lists (x::TrackManager, x/vio/track_manager.h, makes them from a frame's matches and fills them in with fill(); the tracker and the
+// place-recognition front end are classes of their own); preUpdate runs
 // StateManager::manage, constructUpdate runs the MSCKF + MSCKF-SLAM + SLAM builders, the MSCKF-MSCKF CI block and the
 // QR compression on the GPU, postUpdate initialises the new persistent features.
 #pragma once
@@ -35,8 +36,8 @@ struct VioMeasurement {
   SlamMatches slam_matches;        // persistent features matched to other agents' (processed in collaborativeUpdate)
   RangeMeasurement range;          // vio_updater.cpp:358-382
   SunAngleMeasurement sun_angle;   // :386-405
-  std::vector<int> range_facet;    // the three SLAM feature ids around the LRF point: TrackManager::featureTriangleAtPoint (:368-369)
-                                   // runs in the caller's front end; empty = no facet found
+  std::vector<int> range_facet;    // the three SLAM feature ids around the LRF point: x::TrackManager::featureTriangleAtPoint (:368-369),
+                                   // called by whoever owns the manager; empty = no facet found
 };
 
 class VioUpdater : public Updater {

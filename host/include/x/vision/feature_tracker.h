@@ -33,6 +33,8 @@ class TileGrid {
   unsigned int getMaxFeatPerTile() const { return max_feat_per_tile_; }
   double getTileHeight() const { return tile_height_; }
   double getTileWidth() const { return tile_width_; }
+  unsigned int getNTilesH() const { return n_tiles_h_; }
+  unsigned int getNTilesW() const { return n_tiles_w_; }
 
  private:
   unsigned int rows_, n_tiles_h_, n_tiles_w_, max_feat_per_tile_;

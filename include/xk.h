@@ -692,6 +692,37 @@ int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const double *prev_i
                            int *keep_idx, double *intensity, int *sum, int *count, int *n_kept, double *a_rel, double *b_rel,
                            int *support, double *frame_ab, int *estimated);
 
+/* ---- the track manager's candidate tracks: normalisation and baseline check ----------------------------------------
+ * TrackManager::manageTracks (src/x/vio/track_manager.cpp:115-436) sorts a frame's matches into persistent (SLAM) and
+ * opportunistic tracks; its numerical part is Camera::normalize(track, max_size) and checkBaseline (:576-636) of every
+ * track that may become a measurement.  Neither depends on the state of the list walk, so the same xk_trk does both for
+ * all of a frame's candidates in one call (the walk itself is host/src/track_manager.cpp). */
+
+/* Capacities of one xk_trk_baseline call: at most max_tracks tracks with max_obs observations in all.  Allocates the
+ * device block and its pinned mirror; a call that fails leaves an earlier setup as it was.  XK_EINVAL: max_tracks or
+ * max_obs < 1 (or beyond 2^20 / 2^26). */
+int xk_trk_baseline_setup(xk_trk *t, int max_tracks, int max_obs);
+
+/* K tracks in CSR form: trk_off HOST [K+1] (in observations, ascending), obs_xy HOST [trk_off[K]][2] fp64 UNDISTORTED
+ * PIXELS oldest first, drop_last HOST [K]; C_q_G HOST [n_quats][4] (x,y,z,w), the window's camera attitudes oldest
+ * first.  Track k is checked against the first n_quats - drop_last[k] attitudes (drop_last = 1: the reference's
+ * cam_rots_short, for tracks that ended at the previous frame) and cropped to its newest min(length, that list's size)
+ * observations.
+ * -> norm_off HOST [K+1], norm_xy HOST [norm_off[K]][2]: the kept observations as (u - cx) / fx, (v - cy) / fy with the
+ *    intrinsics of xk_trk_create, equal to x::Camera::normalize bit for bit;
+ *    delta_xy HOST [K][2]: per axis, max - min over the kept rays (x, y, 1) rotated into the list's last camera
+ *    (both quaternions normalised, Cn_q_Ci = conj(Ci_q_G) Cn_q_G, ray = conj(Cn_q_Ci) (0,x,y,1) Cn_q_Ci, divided by
+ *    its z) AND the unrotated last observation, where the reference starts.  A NaN coordinate takes no part, an
+ *    infinite one does; a NaN last observation gives NaN;
+ *    flag HOST [K]: delta_x > min_baseline_x_n || delta_y > min_baseline_y_n.
+ * One wavefront per track; one copy in, one launch, one copy out, one synchronisation.  K = 0 is XK_OK.
+ * XK_EINVAL: null pointers, K < 0, before xk_trk_baseline_setup, trk_off not ascending, a track of fewer than 2
+ * observations, drop_last beyond 1, n_quats outside 2...64, n_quats - drop_last < 2 (the cropped length would be), K
+ * or trk_off[K] beyond the capacities.  The object stays usable after every one of them. */
+int xk_trk_baseline(xk_trk *t, const int *trk_off, const double *obs_xy, const unsigned char *drop_last, int K,
+                    const double *C_q_G, int n_quats, double min_baseline_x_n, double min_baseline_y_n, int *norm_off,
+                    double *norm_xy, double *delta_xy, unsigned char *flag);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and
@@ -732,8 +763,8 @@ int xk_fetch_flags(xk_handle *h, int *inlier_msckf, double *gamma_msckf, int *in
  * if sigma_range were sigma_img, a reference quirk kept on purpose); uncompressed, each row keeps its own variance. */
 
 /* RangeUpdate::processRangedFacet (src/x/vio/range_update.cpp:61-270) as stacked at vio_updater.cpp:358-382: one row, the LRF range
- * against the plane of the facet of SLAM features facet[3] (indices into the staged features: TrackManager::featureTriangleAtPoint, which
- * stays with the caller, as does the camera model that gives the undistorted normalised image point (img_x_n, img_y_n) of the ray,
+ * against the plane of the facet of SLAM features facet[3] (indices into the staged features: TrackManager::featureTriangleAtPoint, host
+ * code of the mirror's x::TrackManager; the camera model that gives the undistorted normalised image point (img_x_n, img_y_n) of the ray,
  * vio.cpp:289-294), gated by chi2_1(0.9) against the prior: a rejected row stays as a zero row of variance 1.  Preconditions of the
  * reference (range.timestamp > 0.1, a SLAM track, a facet found) are the caller's.  XK_EINVAL: no SLAM features staged, an id outside
  * [0, M) or repeated, sigma_range <= 0. */

@@ -2,7 +2,8 @@
 // (tracker.cpp:233-293, camera.cpp:62-87; xk_fundamental.hip.h) and the pyramidal Lucas-Kanade tracking in front of it
 // (tracker.cpp:623-690; xk_klt.hip.h), the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h) and their
 // rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h), and the photometric calibration of the images in front of
-// all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).
+// all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).  Behind them, the normalisation and baseline check of the
+// track manager's candidate tracks (track_manager.cpp:576-636, camera.cpp; xk_tracks.hip.h).
 // Every stage keeps its buffers in one xk_block (a device block and its pinned mirror, carved once by the stage's setup, which stores
 // every pointer an entry needs) and reaches them through the same helpers: sub_of (the stage's setup or XK_EINVAL), img_slot (the
 // slot of the previous or the current image or XK_EINVAL), launched (the check behind a group of launches), kept_count_out, setup_install.
@@ -13,6 +14,7 @@
 #include "xk_klt.hip.h"
 #include "xk_orb.hip.h"
 #include "xk_photo.hip.h"
+#include "xk_tracks.hip.h"
 
 #define XKCHK(call)                          \
   do {                                       \
@@ -133,6 +135,14 @@ struct xk_klt {
   size_t slot_bytes;          // of one slot: its levels are one contiguous block
 };
 
+// The baseline setup (xk_trk_baseline_setup): capacities of one batch of tracks.  It belongs to the xk_trk, not to an image size.
+struct xk_bl {
+  int max_tracks, max_obs;
+  xk_block blk;                 // device and pinned, the SAME layout: in: attitudes | trk_off | norm_off | drop_last | observations;
+                                //   out: delta_xy | flag | norm_xy.  The variable-length pieces come last in each half
+  size_t o_quat, o_trk_off, o_norm_off, o_drop, o_obs, o_delta, o_flag, o_norm;
+};
+
 struct xk_trk {
   xk_handle *h;
   int max_matches;
@@ -144,6 +154,7 @@ struct xk_trk {
   unsigned char *h_res;       // pinned: points in (4 max_matches doubles), then the result block out, at h_res
   int n_hyp;                  // hypotheses of the last RANSAC (0: none yet)
   struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
+  struct xk_bl *bl;           // the baseline check of the track manager's candidates (xk_trk_baseline_setup); NULL before
 };
 
 // the result blocks for n pairs: F [9] | kept pairs | mask [n], and cur_xy [n][2] | min_eig [n] | kept pairs | status [n]
@@ -232,8 +243,9 @@ static const XkKltPyr &photo_raw_slot(const xk_klt *k, int s) { return k->photo 
 // ---------------------------------------------------------------------------
 extern "C" void xk_trk_destroy(xk_trk *t) {
   if (!t) return;
-  if (t->klt) hipStreamSynchronize(t->h->stream);
+  if (t->klt || t->bl) hipStreamSynchronize(t->h->stream);
   setup_free(t->klt);
+  setup_free(t->bl);
   blk_free(t->blk);
   free(t);
 }
@@ -1132,4 +1144,85 @@ extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const dou
   if (kept > 4) p->n_hyp[0] = n_hyp;
   if (!s->estimated) return photo_state_out(h, p, 0, nullptr, nullptr, nullptr, nullptr);
   return photo_state_out(h, p, 1, a_rel, b_rel, support, frame_ab);
+}
+
+// ---------------------------------------------------------------------------
+// Normalisation and baseline check of the track manager's candidate tracks (track_manager.cpp:576-636), xk_tracks.hip.h
+// ---------------------------------------------------------------------------
+/* The capacities of one xk_trk_baseline call and its device and pinned blocks */
+extern "C" int xk_trk_baseline_setup(xk_trk *t, int max_tracks, int max_obs) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (max_tracks < 1 || max_tracks > (1 << 20)) return fail(h, XK_EINVAL, "xk_trk_baseline_setup: max_tracks outside 1...2^20");
+  if (max_obs < 1 || max_obs > (1 << 26)) return fail(h, XK_EINVAL, "xk_trk_baseline_setup: max_obs outside 1...2^26");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_bl *b = (xk_bl *)calloc(1, sizeof(xk_bl));
+  if (!b) return XK_ENOMEM;
+  b->max_tracks = max_tracks; b->max_obs = max_obs;
+  size_t off = 0;
+  const auto piece = [&off](size_t bytes) { const size_t at = off; off += up16(bytes); return at; };
+  b->o_quat = piece(sizeof(double) * 4 * XK_TRACKS_MAX_QUATS);
+  b->o_trk_off = piece(sizeof(int) * ((size_t)max_tracks + 1));
+  b->o_norm_off = piece(sizeof(int) * ((size_t)max_tracks + 1));
+  b->o_drop = piece((size_t)max_tracks);
+  b->o_obs = piece(sizeof(double) * 2 * (size_t)max_obs);
+  b->o_delta = piece(sizeof(double) * 2 * (size_t)max_tracks);
+  b->o_flag = piece((size_t)max_tracks);
+  b->o_norm = piece(sizeof(double) * 2 * (size_t)max_obs);
+  const int rc = blk_alloc(h, b->blk, off, off, "xk_trk_baseline_setup");
+  return setup_install(h, rc, "xk_trk_baseline_setup", t->bl, b);
+}
+
+/* Camera::normalize(track, list size) and TrackManager::checkBaseline of K tracks against one attitude list */
+extern "C" int xk_trk_baseline(xk_trk *t, const int *trk_off, const double *obs_xy, const unsigned char *drop_last, int K, const double *C_q_G,
+                               int n_quats, double min_baseline_x_n, double min_baseline_y_n, int *norm_off, double *norm_xy,
+                               double *delta_xy, unsigned char *flag) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  const char *who = "xk_trk_baseline";
+  xk_bl *b = t->bl;
+  if (!b) return fail_at(h, XK_EINVAL, who, "before xk_trk_baseline_setup");
+  if (K < 0 || !trk_off || !norm_off || (K > 0 && (!obs_xy || !drop_last || !C_q_G || !norm_xy || !delta_xy || !flag)))
+    return fail_at(h, XK_EINVAL, who, "null argument or negative K");
+  if (K > b->max_tracks) return fail_at(h, XK_EINVAL, who, "more tracks than max_tracks");
+  if (n_quats < 2 || n_quats > XK_TRACKS_MAX_QUATS) return fail_at(h, XK_EINVAL, who, "n_quats outside 2...64");
+  if (trk_off[0] < 0) return fail_at(h, XK_EINVAL, who, "trk_off is not monotone");
+  int *h_norm_off = (int *)(b->blk.h + b->o_norm_off);          // built here, in the pinned block: it goes up with the rest
+  h_norm_off[0] = 0;
+  for (int k = 0; k < K; ++k) {
+    const long long len = (long long)trk_off[k + 1] - trk_off[k];
+    if (len < 0) return fail_at(h, XK_EINVAL, who, "trk_off is not monotone");
+    if (trk_off[k + 1] > b->max_obs) return fail_at(h, XK_EINVAL, who, "more observations than max_obs");
+    if (len < 2) return fail_at(h, XK_EINVAL, who, "a track of fewer than 2 observations");
+    if (drop_last[k] > 1) return fail_at(h, XK_EINVAL, who, "drop_last is 0 or 1");
+    const int nq = n_quats - (int)drop_last[k];
+    if (nq < 2) return fail_at(h, XK_EINVAL, who, "an attitude list of fewer than 2 entries");   // (so the cropped length is >= 2 too)
+    h_norm_off[k + 1] = h_norm_off[k] + (int)std::min<long long>(len, nq);
+  }
+  memcpy(norm_off, h_norm_off, sizeof(int) * ((size_t)K + 1));
+  if (K == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n_obs = (size_t)trk_off[K], n_norm = (size_t)h_norm_off[K];
+  memcpy(b->blk.h + b->o_quat, C_q_G, sizeof(double) * 4 * (size_t)n_quats);
+  memcpy(b->blk.h + b->o_trk_off, trk_off, sizeof(int) * ((size_t)K + 1));
+  memcpy(b->blk.h + b->o_drop, drop_last, (size_t)K);
+  memcpy(b->blk.h + b->o_obs, obs_xy, sizeof(double) * 2 * n_obs);
+  XkTracksArgs a{};
+  a.quat = (const double *)(b->blk.d + b->o_quat); a.trk_off = (const int *)(b->blk.d + b->o_trk_off);
+  a.norm_off = (const int *)(b->blk.d + b->o_norm_off); a.drop_last = b->blk.d + b->o_drop; a.obs_xy = (const double *)(b->blk.d + b->o_obs);
+  a.K = K; a.n_quats = n_quats;
+  a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy;
+  a.min_x = min_baseline_x_n; a.min_y = min_baseline_y_n;
+  a.norm_xy = (double *)(b->blk.d + b->o_norm); a.delta_xy = (double *)(b->blk.d + b->o_delta); a.flag = b->blk.d + b->o_flag;
+  // one copy in, one launch, one copy out, one wait
+  HIPCHK(h, hipMemcpyAsync(b->blk.d, b->blk.h, b->o_obs + sizeof(double) * 2 * n_obs, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_tracks_baseline, dim3((K + XK_TRACKS_WAVES - 1) / XK_TRACKS_WAVES), dim3(64 * XK_TRACKS_WAVES), 0, h->stream, a);
+  XKCHK(launched(h, "baseline launch"));
+  HIPCHK(h, hipMemcpyAsync(b->blk.h + b->o_delta, b->blk.d + b->o_delta, b->o_norm - b->o_delta + sizeof(double) * 2 * n_norm,
+                           hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  memcpy(norm_xy, b->blk.h + b->o_norm, sizeof(double) * 2 * n_norm);
+  memcpy(delta_xy, b->blk.h + b->o_delta, sizeof(double) * 2 * (size_t)K);
+  memcpy(flag, b->blk.h + b->o_flag, (size_t)K);
+  return XK_OK;
 }

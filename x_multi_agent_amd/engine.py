@@ -44,6 +44,7 @@ SYMBOLS = [
     "xk_trk_describe_setup", "xk_trk_describe", "xk_trk_describe_stage",
     "xk_trk_photo_setup", "xk_trk_photo_intensity", "xk_trk_photo_gains", "xk_trk_photo_hypotheses", "xk_trk_photo_params",
     "xk_trk_photo_reset", "xk_trk_photo_set_spatial", "xk_trk_photo_correct", "xk_trk_photo_raw", "xk_trk_photo_calibrate",
+    "xk_trk_baseline_setup", "xk_trk_baseline",
 ]
 
 

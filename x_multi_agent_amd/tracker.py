@@ -10,8 +10,11 @@ from two images and the previous features to the pairs that filter takes.  `Klt.
 place.Database takes.  `Klt.photo_*` is the photometric calibration a PHOTOMETRIC_CALI build runs in front of all of them
 (`Tracker::calibrateImage`, tracker.cpp:761-877, and IRPhotoCalib): photo_calibrate between push_image and track.
 
+`MatchFilter.baseline` is what the track manager behind them asks every frame (`TrackManager::checkBaseline`,
+track_manager.cpp:576-636, and `Camera::normalize`): the normalisation, crop and baseline check of all candidate tracks at once.
+
 No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h, csrc/xk_fast.hip.h,
-csrc/xk_orb.hip.h, csrc/xk_photo.hip.h)."""
+csrc/xk_orb.hip.h, csrc/xk_photo.hip.h, csrc/xk_tracks.hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -110,6 +113,32 @@ class MatchFilter(_Trk):
                                                C.byref(ninl)), "xk_trk_filter_matches")
         m = ninl.value
         return mask[:n], keep[:m], pxy[:m], cxy[:m]
+
+    def baseline_setup(self, max_tracks, max_obs):
+        """xk_trk_baseline_setup: the capacities of one baseline() call."""
+        self._chk(self.L.xk_trk_baseline_setup(self.p, C.c_int(max_tracks), C.c_int(max_obs)), "xk_trk_baseline_setup")
+
+    def baseline(self, tracks, drop_last, C_q_G, min_baseline_x_n, min_baseline_y_n):
+        """Camera::normalize(track, list size) and TrackManager::checkBaseline (track_manager.cpp:576-636) of a frame's
+        candidate tracks: tracks = a list of fp64 [L_k, 2] arrays of undistorted pixels (oldest first), drop_last uint8 [K],
+        C_q_G fp64 [n_quats, 4] (x, y, z, w) -> dict of norm_off int32 [K + 1], norm_xy fp64 [norm_off[K], 2], delta_xy fp64
+        [K, 2], flag uint8 [K]."""
+        trk = [np.ascontiguousarray(t, np.float64).reshape(-1, 2) for t in tracks]
+        K = len(trk)
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(t) for t in trk])
+        obs = np.concatenate(trk + [np.zeros((1, 2))])
+        drop = np.ascontiguousarray(drop_last, np.uint8).ravel()
+        if len(drop) != K:
+            raise ValueError("baseline: one drop_last per track")
+        q = np.ascontiguousarray(C_q_G, np.float64).reshape(-1, 4)
+        norm_off, norm = np.zeros(K + 1, np.int32), np.zeros((len(obs), 2))
+        delta, flag = np.zeros((max(K, 1), 2)), np.zeros(max(K, 1), np.uint8)
+        self._chk(self.L.xk_trk_baseline(self.p, off.ctypes.data_as(c_ip), obs.ctypes.data_as(c_dp), drop.ctypes.data_as(c_ub), C.c_int(K),
+                                         q.ctypes.data_as(c_dp), C.c_int(len(q)), C.c_double(min_baseline_x_n), C.c_double(min_baseline_y_n),
+                                         norm_off.ctypes.data_as(c_ip), norm.ctypes.data_as(c_dp), delta.ctypes.data_as(c_dp),
+                                         flag.ctypes.data_as(c_ub)), "xk_trk_baseline")
+        return dict(norm_off=norm_off, norm_xy=norm[:norm_off[K]].copy(), delta_xy=delta[:K], flag=flag[:K])
 
 
 class Klt(_Trk):
