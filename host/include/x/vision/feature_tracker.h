@@ -99,6 +99,21 @@ class FeatureTracker {
   // Tracker::calibrateImage (tracker.cpp:761-858) on the features of the previous image (getXDist / getYDist, getIntensity):
   // call it between pushImage and track, as tracker.cpp:186-195 orders them.  The current image is corrected on the device.
   Calibration calibrate(const FeatureList &previous, unsigned long seed = 0);
+  // The spatial map of IRPhotoCalib (xk_trk_photo_spatial_setup), after setPhotometric: div is the reference's
+  // temporal_params_div, thr its spatial_params_thr (spatial_params switches it on: calling this is that switch); the cap per cell,
+  // the row capacity and the GP's hyperparameters are IRPhotoCalib's own (500; 5, 0.01, 0.01).  From then on calibrate() also
+  // accumulates the frame's rows on the device, reads the status after its call, and once the coverage passes thr runs the
+  // estimate and installs the map.  That is synchronous, on the caller's thread; the reference starts a std::thread
+  // (irPhotoCalib.cpp:204).  An estimate that does not converge installs nothing and the accumulation goes on (:372-385).
+  void setSpatialCalibration(int div = 16, double thr = 0.9, int max_rows = 1 << 18);
+  bool spatialCalibrated() const { return spatial_done_; }   // IRPhotoCalib::isReady
+  struct SpatialStatus {
+    int rows = 0, covered = 0, cells = 0, dropped = 0, state = 0;   // state: 0 accumulating, 1 estimated, 2 failed and accumulating
+    bool ready = false;
+  };
+  SpatialStatus spatialStatus();
+  const xk_photo_spatial_outcome &spatialOutcome() const { return spatial_outcome_; }   // of the last estimate calibrate() ran
+  std::vector<float> spatialMap();   // the last estimate's map, height rows of width floats
   // level 0 of the current (or previous) image as the device holds it, height rows of width bytes: the working image, which the
   // tracking, the detection and the description read, or with raw = true (after setPhotometric) the image as pushed
   std::vector<uint8_t> image(bool current_image = true, bool raw = false);
@@ -125,5 +140,7 @@ class FeatureTracker {
   int photo_hyp_ = 0;                         // 0: no photometric calibration set up
   std::vector<double> photo_val_, photo_in_;
   std::vector<int> photo_xy_, photo_sum_, photo_cnt_;
+  bool spatial_set_ = false, spatial_done_ = false;
+  xk_photo_spatial_outcome spatial_outcome_ = {};
 };
 }  // namespace x

@@ -60,6 +60,7 @@ std::pair<FeatureList, FeatureList> FeatureTracker::track(const FeatureList &pre
 void FeatureTracker::setPhotometric(int kernel_size, double epsilon_gap, double epsilon_base, int n_hyp) {
   check(xk_, xk_trk_photo_setup(trk_, kernel_size, epsilon_gap, epsilon_base, n_hyp), "xk_trk_photo_setup");
   photo_hyp_ = n_hyp;
+  spatial_set_ = spatial_done_ = false;                          // (a new photo setup drops the spatial one)
   const size_t m = (size_t)max_features_;
   photo_val_.resize(m); photo_in_.resize(m); photo_xy_.resize(2 * m); photo_sum_.resize(m); photo_cnt_.resize(m);
 }
@@ -90,7 +91,32 @@ FeatureTracker::Calibration FeatureTracker::calibrate(const FeatureList &previou
                                     photo_sum_.data(), photo_cnt_.data(), &c.kept, &c.a_rel, &c.b_rel, &c.support, c.frame_ab, &estimated),
         "xk_trk_photo_calibrate");
   c.estimated = estimated != 0;
+  if (spatial_set_ && !spatial_done_ && c.estimated && spatialStatus().ready) {   // irPhotoCalib.cpp:199-209, without the thread
+    check(xk_, xk_trk_photo_spatial_estimate(trk_, 1, &spatial_outcome_), "xk_trk_photo_spatial_estimate");
+    spatial_done_ = spatial_outcome_.converged != 0;
+  }
   return c;
+}
+
+void FeatureTracker::setSpatialCalibration(int div, double thr, int max_rows) {
+  if (photo_hyp_ == 0) throw std::runtime_error("FeatureTracker::setSpatialCalibration: before setPhotometric");
+  check(xk_, xk_trk_photo_spatial_setup(trk_, div, thr, 500, max_rows, 5.0, 0.01, 0.01), "xk_trk_photo_spatial_setup");
+  spatial_set_ = true; spatial_done_ = false;
+  spatial_outcome_ = xk_photo_spatial_outcome{};
+}
+
+FeatureTracker::SpatialStatus FeatureTracker::spatialStatus() {
+  SpatialStatus s;
+  int ready = 0;
+  check(xk_, xk_trk_photo_spatial_status(trk_, &s.rows, &s.covered, &s.cells, &ready, &s.dropped, &s.state), "xk_trk_photo_spatial_status");
+  s.ready = ready != 0;
+  return s;
+}
+
+std::vector<float> FeatureTracker::spatialMap() {
+  std::vector<float> out((size_t)width_ * height_);
+  check(xk_, xk_trk_photo_spatial_stage(trk_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out.data()), "xk_trk_photo_spatial_stage");
+  return out;
 }
 
 std::vector<uint8_t> FeatureTracker::image(bool current_image, bool raw) {

@@ -620,8 +620,9 @@ int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed c
  *   correction in float32, every operation rounded once: f = v * (1.f/255.f); c = ((f * (float)(a - b) + (float)b) -
  *              PS[y][x]) * 255.f; x = c truncated toward zero (0 where c is not finite or |c| >= 2^31); m = x % 256 with
  *              C's sign rule; u = max(m, 0); out = u < 128 ? 2u : (u == 128 ? 255 : 512 - 2u) (the table of :42-51)
- * Out of scope: the estimation of the spatial parameters (:162-210, :314-420; the correction takes the caller's map), the
- * second Lucas-Kanade parameter set and FAST threshold (tracker.cpp:641-645, :848; the caller re-runs the setups),
+ * The spatial map PS is estimated on the device too, through the xk_trk_photo_spatial_* entries below; until
+ * one is installed the correction takes the caller's map (zeros by default).
+ * Out of scope: the second Lucas-Kanade parameter set and FAST threshold (tracker.cpp:641-645, :848; the caller re-runs the setups),
  * keyframe mode, the detached thread of refinePhotometricParams, pyramid levels above 0. */
 
 /* intensities_kernel_size_ (2...64; tracker.h:366: 30), epsilon_gap and epsilon_base of IRPhotoCalib (finite, in [0, 1]),
@@ -691,6 +692,96 @@ int xk_trk_photo_raw(xk_trk *t, int which, unsigned char *img);
 int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const double *prev_intensity, int n, int n_hyp, unsigned long seed,
                            int *keep_idx, double *intensity, int *sum, int *count, int *n_kept, double *a_rel, double *b_rel,
                            int *support, double *frame_ab, int *estimated);
+
+/* ---- the spatial photometric map (IRPhotoCalib, irPhotoCalib.cpp:162-210 and :314-420) ------------------------------
+ * PS, the per-pixel map the correction subtracts, comes from IRPhotoCalib itself: every frame it collects correspondences
+ * between grid cells, and once enough cells are covered it solves a sparse least-squares problem for one value per cell
+ * and smooths the result with a Gaussian-process regression.  Opt-in through xk_trk_photo_spatial_setup: without it no
+ * entry above queues a launch more or changes an output.  The algorithm is this project's statement of those lines
+ * (DESIGN 3.17), restated in NumPy by tests/photo_spatial_np.py:
+ *   grid        cw = width / div, ch = height / div (integer division), cells = cw ch; the cell of pixel (x, y) is
+ *               (y / div) cw + x / div.  A point is SKIPPED if one of its pixels lies outside the image, or x / div >= cw,
+ *               or y / div >= ch (the remainder column and row of an image that is no multiple of div): the reference
+ *               aliases such a pixel into another cell's id or indexes out of bounds there
+ *   rows        sequential in point order, group by group (:164-198).  sh = the cell of the history pixel, sc = of the
+ *               current one.  Skip if sh == sc or count[sh] > max_count (the reference tests sid_history twice and never
+ *               sid_current; restated as written).  Otherwise coverage[sh] = coverage[sc] = 1, the row (sh, sc, b) is
+ *               appended, b = o_cur (a_hc - b_hc) - o_hist + b_hc in fp64, every operation rounded once, with (a_hc, b_hc)
+ *               = getRelativeGains(ring[last - frame_back], ring[last]) operation by operation (:68-74); then count[sc]
+ *               and count[sh] grow by one.  Beyond max_rows a row is dropped and counted in `dropped`; counts and
+ *               coverage still advance for it
+ *   ready       (double)covered / (double)cells > (double)(float)coverage_thr, strict (:202)
+ *   unknowns    the covered cells in ASCENDING CELL ID (the reference numbers them by first appearance: a permutation of
+ *               the same unknowns), n of them.  A row reads x[sc] - x[sh] = b.  L = A^T A is the multigraph Laplacian, its
+ *               entries exact integers; c = A^T b, each entry summed in ASCENDING ROW ORDER
+ *   solve       Jacobi-preconditioned conjugate gradients on L x = c from x = 0, M = diag(L) (a variable of degree 0, all
+ *               of whose rows were dropped, keeps x = 0); it stops when |r|^2 < tol^2 |c|^2, tol = 1e-13, or after 2 n
+ *               iterations.  In exact arithmetic this is Eigen's preconditioned least-squares CG from zero (:369-379); it
+ *               selects the solution with sum deg_i x_i = 0 on every connected component.  Not converging within 2 n
+ *               iterations is an outcome, not an error: no map is installed and the accumulation goes on (:372-385)
+ *   GP          inputs the cell coordinates (sid % cw, sid / cw), outputs x; K_ij = sf^2 exp(-d^2 / (2 l^2)) + sn^2 [i = j]
+ *               in fp64 from the FLOAT values of the hyperparameters (defaults 5, 0.01, 0.01, :53-55); K alpha = x by the
+ *               same iteration, tolerance and cap.  The reference factors K in float (LDLT): agreement with its last bits
+ *               is NOT claimed
+ *   prediction  coarse[r][c] = (float) sum_i K((c, r), X_i) alpha_i over every cell; PS[y][x] = coarse[min(y / div, ch - 1)]
+ *               [min(x / div, cw - 1)] (the clamp replaces the reference's out-of-bounds read on an image that is no
+ *               multiple of div)
+ * The estimate runs on the caller's thread (the reference starts a std::thread, :204).  Out of scope: keyframe mode, the
+ * reference's first-appearance variable order, the float LDLT's rounding. */
+
+/* What an estimate did: n unknowns, the iterations and final relative residual |r| / |rhs| of both solves, converged
+ * (both of them). */
+typedef struct {
+  int n, converged;
+  int ls_iterations, gp_iterations;
+  double ls_residual, gp_residual;
+} xk_photo_spatial_outcome;
+
+/* div (2...256: temporal_params_div), coverage_thr (spatial_params_thr, kept as a float), max_count (SP_max_correscount_:
+ * 500), max_rows (the row list's capacity) and the GP's length scale, sigma_f, sigma_n (kept as floats, each > 0).  Called
+ * after xk_trk_photo_setup.  Allocates counts, coverage, the row list, two dense n_max x n_max fp64 matrices with n_max =
+ * min(cells, 2048), vectors and a pinned status block.  XK_EINVAL: no photo setup, div out of range, fewer than 2 cells,
+ * a parameter that is not finite, max_count < 1, max_rows < 1, a hyperparameter <= 0.  A call that fails leaves an earlier
+ * spatial setup as it was.  A later xk_trk_klt_setup or xk_trk_photo_setup DROPS it. */
+int xk_trk_photo_spatial_setup(xk_trk *t, int div, double coverage_thr, int max_count, int max_rows, double gp_length,
+                               double gp_sigma_f, double gp_sigma_n);
+
+/* One ProcessCurrentFrame worth of rows against the ring as it stands (call it after xk_trk_photo_gains): G groups as in
+ * xk_trk_photo_gains, pix_hist, pix_cur HOST [off[G]][2] int32 (x, y), o_hist, o_cur HOST [off[G]] fp64.  One copy in, one
+ * launch of one wavefront, the status through pinned memory.  After an installed estimate it does nothing (XK_OK).
+ * XK_EINVAL: null pointers, G or off out of range, no spatial setup, frame_back[g] outside 1 ... ring size - 1.
+ * XK_ECAPACITY: a group of more than max_matches points.
+ * xk_trk_photo_calibrate, with a spatial setup that is still accumulating and on a frame that estimated gains, queues the
+ * same kernel behind its chain on lists it already holds on the device (the truncated prev_xy of the kept points, their
+ * truncated current pixels, previous and new intensities; one group, frame_back 1): no extra copy, no extra
+ * synchronisation, and every output of that call stays as it is. */
+int xk_trk_photo_spatial_add(xk_trk *t, int G, const int *off, const int *pix_hist, const int *pix_cur, const double *o_hist,
+                             const double *o_cur, const int *frame_back);
+
+/* Where the accumulation stands: rows kept, cells covered, cells, ready (above), rows dropped, state (0 accumulating,
+ * 1 estimated: a map is installed and accumulation has stopped, 2 the last estimate did not converge and accumulation
+ * goes on).  Any pointer may be NULL.  One small copy and a wait. */
+int xk_trk_photo_spatial_status(xk_trk *t, int *rows, int *covered, int *cells, int *ready, int *dropped, int *state);
+
+/* Rows first ... first+count-1: sid_hist, sid_cur HOST [count] int32, b HOST [count] fp64; counts HOST [cells] int32,
+ * coverage HOST [cells] uint8.  Straight copies, any pointer may be NULL.  XK_EINVAL: a range outside the kept rows. */
+int xk_trk_photo_spatial_rows(xk_trk *t, int first, int count, int *sid_hist, int *sid_cur, double *b, int *counts,
+                              unsigned char *coverage);
+
+/* EstimateSpatialParameters on the rows accumulated so far: numbering, L and c, the least squares, the GP, the prediction
+ * and the upsample, all on the device; the host reads a done flag through pinned memory after every batch of 32
+ * iterations, and every such wait has a bound (XK_EDEVICE beyond it).  install = 1 and convergence: the map is copied into
+ * the PS plane, device to device, and accumulation stops.  No convergence: XK_OK, outcome->converged = 0, nothing is
+ * installed, state 2.  XK_EINVAL: no spatial setup, null outcome, no row accumulated.  XK_ECAPACITY: n > n_max. */
+int xk_trk_photo_spatial_estimate(xk_trk *t, int install, xk_photo_spatial_outcome *outcome);
+
+/* The last estimate's intermediates, for tests: var_of_cell HOST [cells] int32 (-1: not covered), L HOST [n][n], c, x,
+ * alpha HOST [n] fp64, coarse HOST [cells] float32, ps HOST [height][width] float32 (coarse and ps only after an estimate
+ * that converged).  Straight copies, any pointer may be NULL.  XK_EINVAL: no estimate since the setup or the last reset. */
+int xk_trk_photo_spatial_stage(xk_trk *t, int *var_of_cell, double *L, double *c, double *x, double *alpha, float *coarse, float *ps);
+
+/* Counts, coverage and rows back to empty, the state back to accumulating.  The PS plane keeps what it holds. */
+int xk_trk_photo_spatial_reset(xk_trk *t);
 
 /* ---- the track manager's candidate tracks: normalisation and baseline check ----------------------------------------
  * TrackManager::manageTracks (src/x/vio/track_manager.cpp:115-436) sorts a frame's matches into persistent (SLAM) and

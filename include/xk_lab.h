@@ -18,7 +18,9 @@
  * narrow single launch and the multi-launch schedule, csrc/xk_feature.hip.h XkFeatArgs::Hc; 2: for the wide single launch too -- measured
  * slower, config 2: 1546 -> 1524 updates/s), "feat_gate_form" (1, default: the gate statistic of tracks of at most 32 observations by
  * generalised least squares on M = J P J^T + sigma^2 I itself, csrc/xk_feature.hip.h xk_chol_gate_gls; 0: the projected form
- * S = A^T M A everywhere, as before -- the A/B switch, and what tests/test_gpu_gate_form.py compares the default against).
+ * S = A^T M A everywhere, as before -- the A/B switch, and what tests/test_gpu_gate_form.py compares the default against),
+ * "photo_spatial_cap" (> 0: the iteration cap of both solves of xk_trk_photo_spatial_estimate in place of 2 n; 0, default: 2 n --
+ * the tests' handle on an estimate that does not converge).
  */
 #ifndef XK_LAB_H_
 #define XK_LAB_H_

@@ -1580,6 +1580,7 @@ extern "C" int xk_set_option(xk_handle *h, const char *name, int value) {
   else if (!strcmp(name, "pipe_split")) { if (h->opt_split >= 0) h->opt_split = value; }
   else if (!strcmp(name, "caqr_hlite")) h->opt_hlite = value;
   else if (!strcmp(name, "feat_gate_form")) h->opt_gate_form = value ? 1 : 0;   // A/B switch, and the tests' handle on the fallback
+  else if (!strcmp(name, "photo_spatial_cap")) h->opt_psp_cap = value > 0 ? value : 0;   // the tests' handle on a solve that does not converge
 #endif
   else return fail(h, XK_EINVAL, "xk_set_option: unknown option");
   return XK_OK;

@@ -60,6 +60,7 @@ struct xk_handle {
   double *d_Hc;            // factor records of the MSCKF tracks (xk_feature.hip.h: XkFeatArgs::Hc), hc_stride doubles each, 64-row slots only
   int hc_stride;
   int opt_hlite;           // 1 (default): the per-feature kernel leaves factor records when the single launch is expected to run
+  int opt_psp_cap;         // lab: > 0 caps the iterations of both solves of xk_trk_photo_spatial_estimate (0: 2 n, the statement's cap)
   int opt_gate_form;       // 1 (default): gate of tracks of <= 32 observations by generalised least squares (XkFeatArgs::gate_form); lab: 0 = the projected form everywhere
   bool rows_compact;       // the last build left records, not tiles, for slots [0, K)
   int *d_tile_rows;

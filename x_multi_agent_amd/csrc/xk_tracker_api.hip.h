@@ -9,11 +9,15 @@
 // slot of the previous or the current image or XK_EINVAL), launched (the check behind a group of launches), kept_count_out, setup_install.
 // Part of xk_api.hip's translation unit, included at its end.
 #pragma once
+#include <sched.h>
+#include <time.h>
+
 #include "xk_fast.hip.h"
 #include "xk_fundamental.hip.h"
 #include "xk_klt.hip.h"
 #include "xk_orb.hip.h"
 #include "xk_photo.hip.h"
+#include "xk_photo_spatial.hip.h"
 #include "xk_tracks.hip.h"
 
 #define XKCHK(call)                          \
@@ -116,6 +120,25 @@ struct xk_photo {
   XkRansacScratch sc[XK_PHOTO_MAX_GROUPS];
   int ring_n, done;           // host mirrors of the state
   int n_hyp[XK_PHOTO_MAX_GROUPS];   // hypotheses per group of the last call (0: none, or a group of <= 4)
+  struct xk_psp *sp;          // xk_trk_photo_spatial_setup; NULL before.  It goes with this setup
+};
+
+// The spatial-map setup (xk_trk_photo_spatial_setup): it belongs to the xk_photo whose PS plane it estimates.
+struct xk_psp {
+  XkPspGrid g;
+  int max_count, max_rows, n_max, ld;
+  float thr, gp_l, gp_sf, gp_sn;
+  xk_block blk;                 // device: counts | coverage | rows | numbering | L | K (and the int32 multiplicities before it) | vectors |
+                                //   coarse | the estimated map | state | the staging of one xk_trk_photo_spatial_add.  Pinned: state | staging
+  int *count, *sid_hist, *sid_cur, *var_of_cell, *cell_of_var, *deg;
+  unsigned char *coverage, *d_in;
+  double *b, *L, *K, *c, *x, *alpha, *r, *p, *q, *partial, *diag_l, *diag_k;
+  float *coarse, *ps;         // ps: [height][pitch of level 0], as xk_photo::PS
+  XkPspState *st;
+  size_t in_bytes, cov_bytes;
+  hipEvent_t batch;           // behind every batch of launches the host waits for, with a bound
+  int state;                  // XK_PSP_ACCUMULATING, _ESTIMATED, _FAILED
+  int staged_n;               // n of the last estimate whose intermediates xk_trk_photo_spatial_stage hands out (-1: none)
 };
 
 struct xk_klt {
@@ -184,6 +207,20 @@ static int kept_pairs_out(xk_handle *h, const char *who, const XkKeptPairs &k, c
 template <class T>
 static void setup_free(T *p) {
   if (!p) return;
+  blk_free(p->blk);
+  free(p);
+}
+
+static void setup_free(xk_psp *s) {
+  if (!s) return;
+  if (s->batch) hipEventDestroy(s->batch);
+  blk_free(s->blk);
+  free(s);
+}
+
+static void setup_free(xk_photo *p) {
+  if (!p) return;
+  setup_free(p->sp);
   blk_free(p->blk);
   free(p);
 }
@@ -1084,6 +1121,15 @@ extern "C" int xk_trk_photo_raw(xk_trk *t, int which, unsigned char *img) {
   return XK_OK;
 }
 
+// What every launch of xk_photo_sp_accumulate shares: the grid, the caps, the lists it appends to.  The caller adds the points.
+static XkPspAccArgs psp_acc_args(const xk_photo *p, const xk_psp *s, int G) {
+  XkPspAccArgs a{};
+  a.g = s->g; a.max_count = s->max_count; a.max_rows = s->max_rows; a.thr = (double)s->thr;
+  a.G = G; a.ring = p->st;
+  a.count = s->count; a.coverage = s->coverage; a.sid_hist = s->sid_hist; a.sid_cur = s->sid_cur; a.b = s->b; a.st = s->st;
+  return a;
+}
+
 /* Tracker::calibrateImage (tracker.cpp:761-858): track the previous features between the RAW images, their intensities in the
  * current one, the gain estimate against the previous intensities, the correction of the current image */
 extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const double *prev_intensity, int n, int n_hyp, unsigned long seed,
@@ -1127,6 +1173,12 @@ extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const dou
   XKCHK(launched(h, "calibration launch"));
   XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp, seed, 1);
   XKCHK(photo_queue_gains(h, p, g));
+  if (p->sp && p->sp->state != XK_PSP_ESTIMATED) {               // the spatial rows of this frame, from the lists already on the device
+    XkPspAccArgs sa = psp_acc_args(p, p->sp, 1);
+    sa.prev_f = p->pts; sa.keep_idx = a.kept.keep_idx; sa.pix_cur = p->ixy; sa.o_hist = p->o_hist; sa.o_cur = p->value;
+    sa.off = p->off; sa.frame_back = p->frame_back; sa.per_frame = 1;
+    hipLaunchKernelGGL(xk_photo_sp_accumulate, dim3(1), dim3(64), 0, h->stream, sa);
+  }
   XKCHK(photo_queue_correct(h, k, k->cur, 1));
   // one copy out: state | value | sum | count | the tracking's result block
   const size_t out_bytes = (size_t)(p->klt_res - p->d_io) + klt_res_bytes(n);
@@ -1144,6 +1196,299 @@ extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const dou
   if (kept > 4) p->n_hyp[0] = n_hyp;
   if (!s->estimated) return photo_state_out(h, p, 0, nullptr, nullptr, nullptr, nullptr);
   return photo_state_out(h, p, 1, a_rel, b_rel, support, frame_ab);
+}
+
+// ---------------------------------------------------------------------------
+// The spatial photometric map estimated on the device (irPhotoCalib.cpp:162-210, :314-420), xk_photo_spatial.hip.h
+// ---------------------------------------------------------------------------
+#define XK_PSP_BATCH 32            // iterations queued between two looks at the done flag
+#define XK_PSP_WAIT_S 20.0         // the bound of every host wait of the estimate
+
+static double psp_now() {
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+// The state block into its pinned mirror and a bounded wait for it: a batch that does not come back is XK_EDEVICE, never a spin.
+static int psp_fetch(xk_handle *h, xk_psp *s, const char *who) {
+  HIPCHK(h, hipMemcpyAsync(s->blk.h, s->st, sizeof(XkPspState), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipEventRecord(s->batch, h->stream));
+  const double until = psp_now() + XK_PSP_WAIT_S;
+  for (;;) {
+    const hipError_t e = hipEventQuery(s->batch);
+    if (e == hipSuccess) return XK_OK;
+    if (e != hipErrorNotReady) return fail(h, XK_EDEVICE, who, e);
+    if (psp_now() > until) return fail_at(h, XK_EDEVICE, who, "a batch of launches did not come back");
+    sched_yield();
+  }
+}
+
+static const XkPspState *psp_host(const xk_psp *s) { return (const XkPspState *)s->blk.h; }
+
+// counts, coverage, rows and the state back to empty: queued, the caller waits
+static int psp_queue_reset(xk_handle *h, xk_psp *s) {
+  HIPCHK(h, hipMemsetAsync(s->count, 0, sizeof(int) * (size_t)s->g.cells, h->stream));
+  HIPCHK(h, hipMemsetAsync(s->coverage, 0, s->cov_bytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(s->st, 0, sizeof(XkPspState), h->stream));
+  s->state = XK_PSP_ACCUMULATING;
+  s->staged_n = -1;
+  return XK_OK;
+}
+
+/* temporal_params_div, spatial_params_thr, SP_max_correscount_ and the GP's hyperparameters (irPhotoCalib.cpp:15-55) */
+extern "C" int xk_trk_photo_spatial_setup(xk_trk *t, int div, double coverage_thr, int max_count, int max_rows, double gp_length,
+                                          double gp_sigma_f, double gp_sigma_n) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_spatial_setup", "xk_trk_photo_setup");
+  if (!p) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (div < 2 || div > 256) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_setup: div outside 2...256");
+  const int cw = k->width / div, ch = k->height / div;
+  if ((long)cw * ch < 2) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_setup: fewer than 2 cells");
+  if (!std::isfinite(coverage_thr) || !std::isfinite(gp_length) || !std::isfinite(gp_sigma_f) || !std::isfinite(gp_sigma_n))
+    return fail(h, XK_EINVAL, "xk_trk_photo_spatial_setup: a parameter is not finite");
+  if (max_count < 1 || max_rows < 1) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_setup: max_count or max_rows < 1");
+  if (!((float)gp_length > 0.f) || !((float)gp_sigma_f > 0.f) || !((float)gp_sigma_n > 0.f))
+    return fail(h, XK_EINVAL, "xk_trk_photo_spatial_setup: a hyperparameter <= 0");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_psp *s = (xk_psp *)calloc(1, sizeof(xk_psp));
+  if (!s) return XK_ENOMEM;
+  s->g = XkPspGrid{k->width, k->height, div, cw, ch, cw * ch};
+  s->max_count = max_count; s->max_rows = max_rows;
+  s->n_max = std::min(s->g.cells, XK_PSP_NMAX); s->ld = round_up(s->n_max, 2);
+  s->thr = (float)coverage_thr; s->gp_l = (float)gp_length; s->gp_sf = (float)gp_sigma_f; s->gp_sn = (float)gp_sigma_n;
+  const size_t cells = (size_t)s->g.cells, nm = (size_t)s->n_max, mat = sizeof(double) * nm * (size_t)s->ld;
+  const size_t gm = XK_PHOTO_MAX_GROUPS * (size_t)round_up(t->max_matches, 4);
+  const size_t ps_bytes = sizeof(float) * (size_t)k->slot[0].lv[0].pitch * k->height;
+  s->cov_bytes = up16(cells);
+  s->in_bytes = 4 * 8 * gm + 128;
+  const size_t st_bytes = up16(sizeof(XkPspState));
+  const size_t slots = (nm + XK_PSP_MV_ROWS - 1) / XK_PSP_MV_ROWS;
+  const size_t d_bytes = up16(4 * cells) + s->cov_bytes + 2 * up16(4 * (size_t)max_rows) + up16(8 * (size_t)max_rows) + up16(4 * cells) +
+                         2 * up16(4 * nm) + 2 * up16(mat) + 8 * up16(8 * nm) + up16(8 * slots) + up16(4 * cells) + up16(ps_bytes) + st_bytes +
+                         s->in_bytes;
+  int rc = blk_alloc(h, s->blk, d_bytes, st_bytes + s->in_bytes, "xk_trk_photo_spatial_setup");
+  if (rc == XK_OK) {
+    size_t off = 0;
+    unsigned char *d = s->blk.d;
+    s->count = carve<int>(d, off, 4 * cells); s->coverage = carve<unsigned char>(d, off, s->cov_bytes);
+    s->sid_hist = carve<int>(d, off, 4 * (size_t)max_rows); s->sid_cur = carve<int>(d, off, 4 * (size_t)max_rows);
+    s->b = carve<double>(d, off, 8 * (size_t)max_rows);
+    s->var_of_cell = carve<int>(d, off, 4 * cells); s->cell_of_var = carve<int>(d, off, 4 * nm); s->deg = carve<int>(d, off, 4 * nm);
+    s->L = carve<double>(d, off, mat); s->K = carve<double>(d, off, mat);
+    s->c = carve<double>(d, off, 8 * nm); s->x = carve<double>(d, off, 8 * nm); s->alpha = carve<double>(d, off, 8 * nm);
+    s->r = carve<double>(d, off, 8 * nm); s->p = carve<double>(d, off, 8 * nm); s->q = carve<double>(d, off, 8 * nm);
+    s->diag_l = carve<double>(d, off, 8 * nm); s->diag_k = carve<double>(d, off, 8 * nm);
+    s->partial = carve<double>(d, off, 8 * slots);
+    s->coarse = carve<float>(d, off, 4 * cells); s->ps = carve<float>(d, off, ps_bytes);
+    s->st = carve<XkPspState>(d, off, sizeof(XkPspState));
+    s->d_in = carve<unsigned char>(d, off, s->in_bytes);
+    s->staged_n = -1;
+    if (hipEventCreateWithFlags(&s->batch, hipEventDisableTiming) != hipSuccess) rc = fail(h, XK_ENOMEM, "xk_trk_photo_spatial_setup: allocation failed");
+  }
+  return setup_install(h, rc, "xk_trk_photo_spatial_setup", p->sp, s);       // (blk_alloc zeroed the block: accumulating, no rows)
+}
+
+// the spatial setup of entry `who`, or nullptr after fail(XK_EINVAL)
+static xk_psp *psp_of(xk_trk *t, const char *who) {
+  xk_photo *p = sub_of(t, &xk_klt::photo, who, "xk_trk_photo_setup");
+  if (!p) return nullptr;
+  if (!p->sp) fail_at(t->h, XK_EINVAL, who, "before xk_trk_photo_spatial_setup");
+  return p->sp;
+}
+
+/* The spatial part of one IRPhotoCalib::ProcessCurrentFrame (irPhotoCalib.cpp:162-198) against the ring as it stands */
+extern "C" int xk_trk_photo_spatial_add(xk_trk *t, int G, const int *off, const int *pix_hist, const int *pix_cur, const double *o_hist,
+                                        const double *o_cur, const int *frame_back) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_psp *s = psp_of(t, "xk_trk_photo_spatial_add");
+  if (!s) return XK_EINVAL;
+  xk_photo *p = t->klt->photo;
+  if (G < 1 || G > XK_PHOTO_MAX_GROUPS) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_add: G outside 1...14");
+  if (!off || !frame_back) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_add: null argument");
+  if (off[0] != 0) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_add: off[0] is not 0");
+  for (int g = 0; g < G; ++g) {
+    if (off[g + 1] < off[g]) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_add: off is not ascending");
+    if (off[g + 1] - off[g] > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_photo_spatial_add: a group of more points than max_matches");
+    if (frame_back[g] < 1 || frame_back[g] > p->ring_n - 1)
+      return fail(h, XK_EINVAL, "xk_trk_photo_spatial_add: frame_back outside 1...the ring's size - 1");
+  }
+  const size_t total = (size_t)off[G];
+  if (total > 0 && (!pix_hist || !pix_cur || !o_hist || !o_cur)) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_add: null argument");
+  if (s->state == XK_PSP_ESTIMATED) return XK_OK;                            // the map is installed: accumulation has stopped
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));                                // (the pinned staging is free)
+  // one copy in: pixels | pixels | o_hist | o_cur | off | frame_back, packed for this call's total
+  unsigned char *in = s->blk.h + up16(sizeof(XkPspState));
+  size_t at = 0;
+  XkPspAccArgs a = psp_acc_args(p, s, G);
+  const auto put = [&](const void *src, size_t bytes) {
+    const unsigned char *dev = s->d_in + at;
+    if (bytes) memcpy(in + at, src, bytes);
+    at += up16(bytes);
+    return dev;
+  };
+  a.pix_hist = (const int *)put(pix_hist, 8 * total); a.pix_cur = (const int *)put(pix_cur, 8 * total);
+  a.o_hist = (const double *)put(o_hist, 8 * total); a.o_cur = (const double *)put(o_cur, 8 * total);
+  a.off = (const int *)put(off, sizeof(int) * (size_t)(G + 1)); a.frame_back = (const int *)put(frame_back, sizeof(int) * (size_t)G);
+  HIPCHK(h, hipMemcpyAsync(s->d_in, in, at, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_photo_sp_accumulate, dim3(1), dim3(64), 0, h->stream, a);
+  XKCHK(launched(h, "spatial accumulation launch"));
+  return psp_fetch(h, s, "xk_trk_photo_spatial_add");
+}
+
+/* Where the accumulation stands */
+extern "C" int xk_trk_photo_spatial_status(xk_trk *t, int *rows, int *covered, int *cells, int *ready, int *dropped, int *state) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_psp *s = psp_of(t, "xk_trk_photo_spatial_status");
+  if (!s) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  XKCHK(psp_fetch(h, s, "xk_trk_photo_spatial_status"));
+  const XkPspState *st = psp_host(s);
+  if (st->rows < 0 || st->rows > s->max_rows || st->covered < 0 || st->covered > s->g.cells)
+    return fail(h, XK_EDEVICE, "xk_trk_photo_spatial_status: state out of range");
+  if (rows) *rows = st->rows;
+  if (covered) *covered = st->covered;
+  if (cells) *cells = s->g.cells;
+  if (ready) *ready = st->ready;
+  if (dropped) *dropped = st->dropped;
+  if (state) *state = s->state;
+  return XK_OK;
+}
+
+/* Rows first ... first+count-1, and the counts and coverage of every cell.  Straight copies */
+extern "C" int xk_trk_photo_spatial_rows(xk_trk *t, int first, int count, int *sid_hist, int *sid_cur, double *b, int *counts,
+                                         unsigned char *coverage) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_psp *s = psp_of(t, "xk_trk_photo_spatial_rows");
+  if (!s) return XK_EINVAL;
+  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_rows: negative range");
+  HIPCHK(h, hipSetDevice(h->device));
+  XKCHK(psp_fetch(h, s, "xk_trk_photo_spatial_rows"));
+  if (first + (long)count > psp_host(s)->rows) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_rows: range outside the accumulated rows");
+  const size_t n = (size_t)count;
+  if (sid_hist && n) HIPCHK(h, hipMemcpyAsync(sid_hist, s->sid_hist + first, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+  if (sid_cur && n) HIPCHK(h, hipMemcpyAsync(sid_cur, s->sid_cur + first, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+  if (b && n) HIPCHK(h, hipMemcpyAsync(b, s->b + first, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  if (counts) HIPCHK(h, hipMemcpyAsync(counts, s->count, sizeof(int) * (size_t)s->g.cells, hipMemcpyDeviceToHost, h->stream));
+  if (coverage) HIPCHK(h, hipMemcpyAsync(coverage, s->coverage, (size_t)s->g.cells, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// One solve: the start, then batches of iterations with the done flag read through the pinned block after each.
+static int psp_solve(xk_handle *h, xk_psp *s, XkPspPcgArgs a, int n, const XkPspSolve *rec_host) {
+  hipLaunchKernelGGL(xk_photo_sp_pcg_init, dim3(1), dim3(XK_PSP_T), 0, h->stream, a);
+  const int cap = a.cap > 0 ? a.cap : 2 * n, grid = (n + XK_PSP_MV_ROWS - 1) / XK_PSP_MV_ROWS;
+  for (int queued = 0;;) {
+    for (int i = 0; i < XK_PSP_BATCH && queued < cap; ++i, ++queued) {
+      hipLaunchKernelGGL(xk_photo_sp_matvec, dim3(grid), dim3(64 * XK_PSP_MV_ROWS), 0, h->stream, a);
+      hipLaunchKernelGGL(xk_photo_sp_step, dim3(1), dim3(XK_PSP_T), 0, h->stream, a);
+    }
+    XKCHK(launched(h, "spatial solve launch"));
+    XKCHK(psp_fetch(h, s, "xk_trk_photo_spatial_estimate"));
+    if (rec_host->done) return XK_OK;
+    if (queued >= cap) return fail(h, XK_EDEVICE, "xk_trk_photo_spatial_estimate: the solve passed its cap without a done flag");
+  }
+}
+
+/* IRPhotoCalib::EstimateSpatialParameters (irPhotoCalib.cpp:314-420) on the accumulated rows */
+extern "C" int xk_trk_photo_spatial_estimate(xk_trk *t, int install, xk_photo_spatial_outcome *outcome) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_psp *s = psp_of(t, "xk_trk_photo_spatial_estimate");
+  if (!s) return XK_EINVAL;
+  xk_photo *p = t->klt->photo;
+  if (!outcome) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_estimate: null argument");
+  memset(outcome, 0, sizeof *outcome);
+  HIPCHK(h, hipSetDevice(h->device));
+  const XkPspState *st = psp_host(s);
+  XKCHK(psp_fetch(h, s, "xk_trk_photo_spatial_estimate"));
+  if (st->rows < 1) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_estimate: no row accumulated");
+  s->staged_n = -1;
+  // numbering, L and c, K
+  XkPspNumArgs na{s->coverage, s->g.cells, s->n_max, s->var_of_cell, s->cell_of_var, s->st};
+  hipLaunchKernelGGL(xk_photo_sp_number, dim3(1), dim3(XK_PSP_T), 0, h->stream, na);
+  XkPspNormArgs ma{};
+  ma.sid_hist = s->sid_hist; ma.sid_cur = s->sid_cur; ma.b = s->b; ma.var_of_cell = s->var_of_cell;
+  ma.mult = (int *)s->K; ma.deg = s->deg; ma.L = s->L; ma.c = s->c; ma.diag = s->diag_l;
+  ma.ld = s->ld; ma.n_max = s->n_max; ma.max_rows = s->max_rows; ma.st = s->st;
+  hipLaunchKernelGGL(xk_photo_sp_clear, dim3(s->n_max), dim3(XK_PSP_T), 0, h->stream, ma);
+  hipLaunchKernelGGL(xk_photo_sp_count, dim3((st->rows + XK_PSP_T - 1) / XK_PSP_T), dim3(XK_PSP_T), 0, h->stream, ma);
+  hipLaunchKernelGGL(xk_photo_sp_normal, dim3((s->n_max + XK_PSP_T / 64 - 1) / (XK_PSP_T / 64)), dim3(XK_PSP_T), 0, h->stream, ma);
+  XkPspGpArgs ga{};
+  ga.cell_of_var = s->cell_of_var; ga.K = s->K; ga.diag = s->diag_k; ga.ld = s->ld; ga.n_max = s->n_max; ga.g = s->g;
+  ga.sf2 = (double)s->gp_sf * (double)s->gp_sf; ga.sn2 = (double)s->gp_sn * (double)s->gp_sn;
+  ga.inv2l2 = 1.0 / (2.0 * (double)s->gp_l * (double)s->gp_l);
+  ga.alpha = s->alpha; ga.coarse = s->coarse; ga.ps = s->ps; ga.pitch = t->klt->slot[0].lv[0].pitch; ga.st = s->st;
+  hipLaunchKernelGGL(xk_photo_sp_kernel, dim3(s->n_max), dim3(XK_PSP_T), 0, h->stream, ga);
+  XKCHK(launched(h, "spatial normal-equation launch"));
+  XKCHK(psp_fetch(h, s, "xk_trk_photo_spatial_estimate"));
+  const int n = st->n;
+  outcome->n = n;
+  if (n > s->n_max) return fail(h, XK_ECAPACITY, "xk_trk_photo_spatial_estimate: more covered cells than n_max");
+  if (n < 2) return fail(h, XK_EDEVICE, "xk_trk_photo_spatial_estimate: fewer than 2 unknowns");
+  // the least squares, then the GP's weights on its solution
+  XkPspPcgArgs pa{};
+  pa.A = s->L; pa.rhs = s->c; pa.diag = s->diag_l; pa.x = s->x; pa.r = s->r; pa.p = s->p; pa.q = s->q; pa.partial = s->partial;
+  pa.ld = s->ld; pa.n_max = s->n_max; pa.cap = h->opt_psp_cap; pa.s = &s->st->ls; pa.st = s->st;
+  XKCHK(psp_solve(h, s, pa, n, &st->ls));
+  pa.A = s->K; pa.rhs = s->x; pa.diag = s->diag_k; pa.x = s->alpha; pa.s = &s->st->gp; pa.after = &s->st->ls;
+  XKCHK(psp_solve(h, s, pa, n, &st->gp));
+  const bool ok = st->ls.converged && st->gp.converged;
+  if (ok) {
+    hipLaunchKernelGGL(xk_photo_sp_predict, dim3(s->g.cells), dim3(64), 0, h->stream, ga);
+    XKCHK(launched(h, "spatial prediction launch"));
+    if (install) HIPCHK(h, hipMemcpyAsync(p->PS, s->ps, sizeof(float) * (size_t)ga.pitch * s->g.h, hipMemcpyDeviceToDevice, h->stream));
+    XKCHK(psp_fetch(h, s, "xk_trk_photo_spatial_estimate"));
+  }
+  outcome->converged = ok ? 1 : 0;
+  outcome->ls_iterations = st->ls.it; outcome->gp_iterations = st->gp.it;
+  outcome->ls_residual = st->ls.bb > 0.0 ? sqrt(st->ls.rr / st->ls.bb) : 0.0;
+  outcome->gp_residual = st->gp.bb > 0.0 ? sqrt(st->gp.rr / st->gp.bb) : 0.0;
+  s->staged_n = n;
+  // not converging is an outcome, not an error: no map, and the accumulation goes on (irPhotoCalib.cpp:372-385)
+  if (!ok) s->state = XK_PSP_FAILED;
+  else if (install) s->state = XK_PSP_ESTIMATED;
+  return XK_OK;
+}
+
+/* The last estimate's intermediates, for tests.  Straight copies; any pointer may be NULL */
+extern "C" int xk_trk_photo_spatial_stage(xk_trk *t, int *var_of_cell, double *L, double *c, double *x, double *alpha, float *coarse, float *ps) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_psp *s = psp_of(t, "xk_trk_photo_spatial_stage");
+  if (!s) return XK_EINVAL;
+  if (s->staged_n < 0) return fail(h, XK_EINVAL, "xk_trk_photo_spatial_stage: no estimate since the setup or the last reset");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = (size_t)s->staged_n, cells = (size_t)s->g.cells, pitch = (size_t)t->klt->slot[0].lv[0].pitch;
+  if (var_of_cell) HIPCHK(h, hipMemcpyAsync(var_of_cell, s->var_of_cell, sizeof(int) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (L) HIPCHK(h, hipMemcpy2DAsync(L, 8 * n, s->L, 8 * (size_t)s->ld, 8 * n, n, hipMemcpyDeviceToHost, h->stream));
+  if (c) HIPCHK(h, hipMemcpyAsync(c, s->c, 8 * n, hipMemcpyDeviceToHost, h->stream));
+  if (x) HIPCHK(h, hipMemcpyAsync(x, s->x, 8 * n, hipMemcpyDeviceToHost, h->stream));
+  if (alpha) HIPCHK(h, hipMemcpyAsync(alpha, s->alpha, 8 * n, hipMemcpyDeviceToHost, h->stream));
+  if (coarse) HIPCHK(h, hipMemcpyAsync(coarse, s->coarse, sizeof(float) * cells, hipMemcpyDeviceToHost, h->stream));
+  if (ps) HIPCHK(h, hipMemcpy2DAsync(ps, sizeof(float) * (size_t)s->g.w, s->ps, sizeof(float) * pitch, sizeof(float) * (size_t)s->g.w, (size_t)s->g.h,
+                                    hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+/* Counts, coverage and rows back to empty, the state back to accumulating.  The PS plane keeps what it holds */
+extern "C" int xk_trk_photo_spatial_reset(xk_trk *t) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_psp *s = psp_of(t, "xk_trk_photo_spatial_reset");
+  if (!s) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  XKCHK(psp_queue_reset(h, s));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -44,6 +44,8 @@ SYMBOLS = [
     "xk_trk_describe_setup", "xk_trk_describe", "xk_trk_describe_stage",
     "xk_trk_photo_setup", "xk_trk_photo_intensity", "xk_trk_photo_gains", "xk_trk_photo_hypotheses", "xk_trk_photo_params",
     "xk_trk_photo_reset", "xk_trk_photo_set_spatial", "xk_trk_photo_correct", "xk_trk_photo_raw", "xk_trk_photo_calibrate",
+    "xk_trk_photo_spatial_setup", "xk_trk_photo_spatial_add", "xk_trk_photo_spatial_status", "xk_trk_photo_spatial_rows",
+    "xk_trk_photo_spatial_estimate", "xk_trk_photo_spatial_stage", "xk_trk_photo_spatial_reset",
     "xk_trk_baseline_setup", "xk_trk_baseline",
 ]
 
@@ -489,7 +491,7 @@ class Engine:
 
     def set_option(self, name, value):
         """xk_set_option: "caqr_resident", "caqr_rearm", "ci_weight_search" (release library); the lab build (Engine(..., lab=True)) adds the test hooks and
-        A/B switches "caqr_poison", "caqr_test_stall", "caqr_tall26", "pipe_kalman" (include/xk_lab.h)."""
+        A/B switches "caqr_poison", "caqr_test_stall", "caqr_tall26", "pipe_kalman", "photo_spatial_cap" (include/xk_lab.h)."""
         self._chk(self.L.xk_set_option(self.h, name.encode(), C.c_int(int(value))), "xk_set_option")
 
     def probe_fp64_peak(self, use_mfma=True):

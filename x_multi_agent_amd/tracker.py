@@ -369,3 +369,88 @@ class Klt(_Trk):
         k = nk.value
         return dict(keep_idx=keep[:k].copy(), intensity=val[:k].copy(), sum=s[:k].copy(), count=c[:k].copy(), a_rel=a.value, b_rel=b.value,
                     support=sup.value, frame_ab=fab, estimated=bool(est.value))
+
+    # ---- the spatial photometric map (irPhotoCalib.cpp:162-210, :314-420), csrc/xk_photo_spatial.hip.h ----
+    SPATIAL_STATES = ("accumulating", "estimated", "failed-and-accumulating")
+    spatial_n = 0                    # unknowns of the last estimate: what photo_spatial_stage sizes its arrays by
+
+    def photo_spatial_setup(self, div=16, coverage_thr=0.9, max_count=500, max_rows=65536, gp_length=5.0, gp_sigma_f=0.01, gp_sigma_n=0.01):
+        """xk_trk_photo_spatial_setup, after photo_setup: the grid of div x div cells, the coverage threshold, the per-cell cap
+        (SP_max_correscount_), the row list's capacity and the GP's hyperparameters.  A later setup() or photo_setup() drops it."""
+        self._chk(self.L.xk_trk_photo_spatial_setup(self.p, C.c_int(div), C.c_double(coverage_thr), C.c_int(max_count), C.c_int(max_rows),
+                                                    C.c_double(gp_length), C.c_double(gp_sigma_f), C.c_double(gp_sigma_n)),
+                  "xk_trk_photo_spatial_setup")
+        self.spatial_grid = (self.width // div, self.height // div)
+
+    def photo_spatial_add(self, pix_hist, pix_cur, o_hist, o_cur, frame_back=(1,)):
+        """One ProcessCurrentFrame worth of rows (irPhotoCalib.cpp:162-198), after photo_gains: lists of G arrays (or one array each:
+        one group) of int32 pixels [n, 2] and fp64 intensities [n], frame_back one int per group."""
+        if not isinstance(pix_hist, (list, tuple)):
+            pix_hist, pix_cur, o_hist, o_cur = [pix_hist], [pix_cur], [o_hist], [o_cur]
+        ph = [np.ascontiguousarray(v, np.int32).reshape(-1, 2) for v in pix_hist]
+        pc = [np.ascontiguousarray(v, np.int32).reshape(-1, 2) for v in pix_cur]
+        oh = [np.ascontiguousarray(v, np.float64).ravel() for v in o_hist]
+        oc = [np.ascontiguousarray(v, np.float64).ravel() for v in o_cur]
+        G = len(ph)
+        if not (len(pc) == len(oh) == len(oc) == len(frame_back) == G) or any(not (len(a) == len(b) == len(c) == len(d))
+                                                                               for a, b, c, d in zip(ph, pc, oh, oc)):
+            raise ValueError("photo_spatial_add: the lists differ in length")
+        off = np.zeros(G + 1, np.int32)
+        off[1:] = np.cumsum([len(v) for v in ph])
+        PH, PC = np.concatenate(ph + [np.zeros((1, 2), np.int32)]), np.concatenate(pc + [np.zeros((1, 2), np.int32)])
+        OH, OC = np.concatenate(oh + [np.zeros(1)]), np.concatenate(oc + [np.zeros(1)])
+        fb = np.ascontiguousarray(frame_back, np.int32)
+        self._chk(self.L.xk_trk_photo_spatial_add(self.p, C.c_int(G), off.ctypes.data_as(c_ip), PH.ctypes.data_as(c_ip), PC.ctypes.data_as(c_ip),
+                                                  OH.ctypes.data_as(c_dp), OC.ctypes.data_as(c_dp), fb.ctypes.data_as(c_ip)),
+                  "xk_trk_photo_spatial_add")
+
+    def photo_spatial_status(self):
+        """-> dict of rows, covered, cells, ready (bool), dropped, state (one of SPATIAL_STATES)."""
+        v = [C.c_int(0) for _ in range(6)]
+        self._chk(self.L.xk_trk_photo_spatial_status(self.p, *[C.byref(x) for x in v]), "xk_trk_photo_spatial_status")
+        return dict(rows=v[0].value, covered=v[1].value, cells=v[2].value, ready=bool(v[3].value), dropped=v[4].value,
+                    state=self.SPATIAL_STATES[v[5].value])
+
+    def photo_spatial_rows(self, first=0, count=None):
+        """Rows first ... first+count-1 (count None: to the last one) -> dict of sid_hist, sid_cur int32 [count], b fp64 [count],
+        counts int32 [cells], coverage uint8 [cells]."""
+        if count is None:
+            count = self.photo_spatial_status()["rows"] - first
+        m, cells = max(count, 1), self.spatial_grid[0] * self.spatial_grid[1]
+        sh, sc, b = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m)
+        cnt, cov = np.zeros(cells, np.int32), np.zeros(cells, np.uint8)
+        self._chk(self.L.xk_trk_photo_spatial_rows(self.p, C.c_int(first), C.c_int(count), sh.ctypes.data_as(c_ip), sc.ctypes.data_as(c_ip),
+                                                   b.ctypes.data_as(c_dp), cnt.ctypes.data_as(c_ip), cov.ctypes.data_as(c_ub)),
+                  "xk_trk_photo_spatial_rows")
+        return dict(sid_hist=sh[:count], sid_cur=sc[:count], b=b[:count], counts=cnt, coverage=cov)
+
+    def photo_spatial_estimate(self, install=True):
+        """EstimateSpatialParameters (irPhotoCalib.cpp:314-420) on the accumulated rows -> dict of n, converged (bool), ls_iterations,
+        gp_iterations, ls_residual, gp_residual.  install: a converged map goes into the PS plane and accumulation stops."""
+        o = SpatialOutcome()
+        self._chk(self.L.xk_trk_photo_spatial_estimate(self.p, C.c_int(int(bool(install))), C.byref(o)), "xk_trk_photo_spatial_estimate")
+        self.spatial_n = o.n
+        return dict(n=o.n, converged=bool(o.converged), ls_iterations=o.ls_iterations, gp_iterations=o.gp_iterations,
+                    ls_residual=o.ls_residual, gp_residual=o.gp_residual)
+
+    def photo_spatial_stage(self):
+        """The last estimate's intermediates -> dict of var_of_cell int32 [cells], L fp64 [n, n], c, x, alpha fp64 [n], coarse float32
+        [ch, cw], ps float32 [height, width]."""
+        n, (cw, ch) = max(self.spatial_n, 1), self.spatial_grid
+        voc, L = np.zeros(cw * ch, np.int32), np.zeros((n, n))
+        c, x, al = np.zeros(n), np.zeros(n), np.zeros(n)
+        coarse, ps = np.zeros((ch, cw), np.float32), np.zeros((self.height, self.width), np.float32)
+        self._chk(self.L.xk_trk_photo_spatial_stage(self.p, voc.ctypes.data_as(c_ip), L.ctypes.data_as(c_dp), c.ctypes.data_as(c_dp),
+                                                    x.ctypes.data_as(c_dp), al.ctypes.data_as(c_dp), coarse.ctypes.data_as(c_fp),
+                                                    ps.ctypes.data_as(c_fp)), "xk_trk_photo_spatial_stage")
+        return dict(var_of_cell=voc, L=L, c=c, x=x, alpha=al, coarse=coarse, ps=ps)
+
+    def photo_spatial_reset(self):
+        """Counts, coverage and rows back to empty, the state back to accumulating; the PS plane keeps what it holds."""
+        self._chk(self.L.xk_trk_photo_spatial_reset(self.p), "xk_trk_photo_spatial_reset")
+
+
+class SpatialOutcome(C.Structure):
+    """xk_photo_spatial_outcome (include/xk.h)"""
+    _fields_ = [("n", C.c_int), ("converged", C.c_int), ("ls_iterations", C.c_int), ("gp_iterations", C.c_int),
+                ("ls_residual", C.c_double), ("gp_residual", C.c_double)]
