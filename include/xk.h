@@ -597,6 +597,74 @@ int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsigned char *d
  * An inspection path, not part of a frame: straight copies.  XK_EINVAL as for xk_trk_describe. */
 int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed char *pattern);
 
+/* ---- Tracker::track in one call (tracker.cpp:134-306) on a feature list that stays on the device ---------------------
+ * The stage entries above are the five stages of a frame; xk_trk_frame is the frame: an image goes in, the frame's match
+ * list comes out, and previous_features_ (tracker.cpp:299) never leaves the device.  It is Tracker::track of a build WITHOUT
+ * PHOTOMETRIC_CALI, on pyramid level 0 as the stage entries are.  Every stage is queued on the handle's
+ * stream with its count in device memory; the re-detection is queued on every frame and its kernels return at once
+ * where the flag the overflow pass left is clear.  Per frame: one copy of the image in, one copy of the result block out
+ * (sized by the host's bound: the resident count plus the detection's packing bound, at most max_matches), and one wait
+ * besides the wait for the previous push's staging buffer.
+ *
+ * The PHOTOMETRIC frame (calibrateImage between the push and the tracking, tracker.cpp:186-190) is NOT built: xk_trk_frame
+ * returns XK_EINVAL while a photometric setup is in place on this xk_trk.
+ *
+ * xk_trk_frame_setup: n_feat_min (tracker.cpp:204), the tile grid of TiledImage (n_tiles_h x n_tiles_w, at most 4096
+ * tiles) and max_feat_per_tile (tracker.cpp:614), threshold_px and n_hyp of the outlier removal as in
+ * xk_trk_filter_matches.  Called after xk_trk_klt_setup and xk_trk_detect_setup; where an xk_trk_describe_setup is in
+ * place every feature carries its descriptor, and the detection's margin must then be at least the description's edge
+ * (a detected feature is always described).  XK_EINVAL: before those setups, a parameter out of range, margin < edge.
+ * A later xk_trk_klt_setup, xk_trk_detect_setup or xk_trk_describe_setup that succeeds DROPS the frame setup. */
+int xk_trk_frame_setup(xk_trk *t, int n_feat_min, int n_tiles_h, int n_tiles_w, int max_feat_per_tile, double threshold_px, int n_hyp);
+
+/* What a frame returns.  The arrays are the caller's, HOST, max_matches rows each; the first n_matches rows are written.
+ * prev_xy, cur_xy: undistorted pixels of the match's previous and current feature; prev_dist_xy, cur_dist_xy: their
+ * distorted pixels; score: the FAST score the feature was detected with; tiles [.][4]: previous row, previous column,
+ * current row, current column as the overflow pass set them (tracker.cpp:598-600) -- for a pair the frame's re-detection
+ * added, the previous feature's tile as the detection set it (tracker.cpp:578) and -1, -1, a new Feature's, for the current;
+ * origin: the position of the match's feature in the previous frame's match list (in the first frame's detections after
+ * a first frame), or -(k + 1) for the k-th feature this frame's re-detection accepted; desc [.][32]: the descriptor
+ * (required with a description setup, ignored without). */
+typedef struct {
+  int n_tracked;       /* pairs the tracking's post-filter kept (tracker.cpp:658-686) */
+  int n_left;          /* pairs left by removeOverflowFeatures */
+  int redetected;      /* 1: n_left < n_feat_min, the frame re-detected */
+  int n_candidates;    /* of the re-detection (of the detection, on a first frame) */
+  int n_accepted;      /* features it accepted */
+  int n_new_tracked;   /* of those, tracked into the current image */
+  int n_matches;       /* pairs the outlier removal kept: the rows written, and the next frame's feature count */
+  int winner;          /* its winning hypothesis, -1: none (fewer than 7 pairs, or no candidate) */
+  double *prev_xy, *cur_xy, *prev_dist_xy, *cur_dist_xy;
+  int *score, *origin, *tiles;
+  unsigned char *desc;
+} xk_trk_frame_out;
+
+/* One image of Tracker::track: img HOST, height rows of stride bytes.
+ * First frame (after the setup, xk_trk_frame_reset, a direct xk_trk_push_image or an XK_ECAPACITY): the image is pushed,
+ * featureDetection runs on it with no old features, the accepted features are described and become the resident list in
+ * ascending key order; n_candidates and n_accepted are set, n_matches = 0.
+ * Every later frame: 1. the push; 2. featureTracking of the resident list (its float cast, tracker.cpp:629-633) and the
+ * post-filter; 3. removeOverflowFeatures with its quirks (the last pair is never examined, the counts are those of the
+ * current features' tiles and stay as counted); 4. where fewer than n_feat_min pairs are left, featureDetection on the
+ * PREVIOUS image outside the neighbourhoods of the previous list, the description, the tracking and post-filter of the
+ * new features, appended behind the old pairs -- no second overflow pass; 5. Camera::undistort of both lists and the
+ * seven-point RANSAC with n_hyp hypotheses and `seed`, fewer than 7 pairs keep nothing; 6. the kept current features
+ * become the resident list.  The result is bit for bit what the stage entries return when chained through the host.
+ * XK_EINVAL: null arguments, stride below the width, no frame setup, a photometric setup in place.
+ * XK_ECAPACITY, decided on the device and reported at the frame's wait: more candidates than max_candidates, more
+ * features accepted than max_matches, more keypoints than max_desc, old plus new pairs beyond max_matches; the counts
+ * reached are returned, n_matches = 0, and the next frame is a first frame.  The stage entries and their inspection
+ * entries keep result blocks of their own and work between frames (xk_trk_detect_stage and
+ * xk_trk_fundamental_hypotheses then ask for a stage call first: a frame overwrites the scratch they read). */
+int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, xk_trk_frame_out *out);
+
+/* The resident list: dist_xy HOST [max_matches][2], score HOST [max_matches], desc HOST [max_matches][32], each may be
+ * NULL; *n features (0 before a first frame).  An inspection path: straight copies, one synchronisation. */
+int xk_trk_frame_features(xk_trk *t, double *dist_xy, int *score, unsigned char *desc, int *n);
+
+/* The next xk_trk_frame is a first frame; the pushed images stay.  XK_EINVAL without a frame setup. */
+int xk_trk_frame_reset(xk_trk *t);
+
 /* ---- photometric calibration of the images (Tracker::calibrateImage, tracker.cpp:761-877; irPhotoCalib.cpp) ---------
  * A PHOTOMETRIC_CALI build passes every frame after the first through calibrateImage (tracker.cpp:186-190) before it is
  * tracked: a Lucas-Kanade pass between the UNCORRECTED images, a box-mean intensity per feature, a RANSAC estimate of the

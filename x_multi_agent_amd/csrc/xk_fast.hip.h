@@ -54,6 +54,8 @@ struct XkFastArgs {
   int n_old;
   int threshold, nms, b, margin, max_candidates, max_matches;
   int *res;                                  // n_found, n_candidates, 0, 0 | xy [max_matches][2] | score [max_matches]
+  const int *n_old_dev;                      // NULL: n_old old features.  Else n_old is their bound, *n_old_dev the count (xk_dev_count)
+  const int *pred;                           // NULL: run.  Else the three kernels return at once where *pred is 0 (the frame's re-detection)
 };
 
 // any nine contiguous bits set in the 16-bit ring m
@@ -84,6 +86,7 @@ __device__ __forceinline__ int xk_fast_arc_maxmin(const int (&d)[16]) {
 
 __global__ __launch_bounds__(256) void xk_fast_score(XkFastArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char s_in[XK_FAST_ROWS][XK_FAST_COLS];
+  if (a.pred && *a.pred == 0) return;                                               // (the same in every thread)
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.count = 0;       // (read by the next launch)
   const int w = a.w, h = a.h, pitch = a.pitch;
   const int tx0 = blockIdx.x * XK_FAST_TW, ty0 = blockIdx.y * XK_FAST_TH;
@@ -140,6 +143,7 @@ __global__ __launch_bounds__(256) void xk_fast_score(XkFastArgs a) {
 __global__ __launch_bounds__(256) void xk_fast_candidates(XkFastArgs a) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int w = a.w, h = a.h, pitch = a.pitch;
+  if (a.pred && *a.pred == 0) return;
   if (x < 3 || x >= w - 3 || y < 3 || y >= h - 3) return;         // (S is 0 on the 3-pixel frame; inside it every neighbour exists)
   if (x < a.margin || x > w - a.margin - 1 || y < a.margin || y > h - a.margin - 1) return;
   const unsigned char *p = a.S + (size_t)y * pitch + x;
@@ -172,6 +176,8 @@ __device__ __forceinline__ void xk_fast_paint(unsigned int *mask, int wpr, int x
 __global__ __launch_bounds__(XK_FAST_SEL_T) void xk_fast_select(XkFastArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned int xk_fast_sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (a.pred && *a.pred == 0) return;                               // (the same in every thread: before any barrier)
+  const int n_old = xk_dev_count(a.n_old_dev, a.n_old);
   const int n = *a.count;
   if (n > a.max_candidates) {                                       // reported, nothing selected
     if (tid == 0) { a.res[0] = 0; a.res[1] = n; }
@@ -187,7 +193,7 @@ __global__ __launch_bounds__(XK_FAST_SEL_T) void xk_fast_select(XkFastArgs a) {
   __syncthreads();
   // computeNeighborhoodMask: one old feature per wavefront and turn, its box clipped to the image.  The clipping is done in fp64
   // so that it also decides for coordinates no int holds.
-  for (int f = wave; f < a.n_old; f += XK_FAST_SEL_T / 64) {
+  for (int f = wave; f < n_old; f += XK_FAST_SEL_T / 64) {
     const double ox = a.old_xy[2 * f], oy = a.old_xy[2 * f + 1];
     if (!(isfinite(ox) && isfinite(oy))) continue;
     const double rx = round(ox), ry = round(oy);                    // half away from zero

@@ -169,11 +169,14 @@ struct XkFundArgs {
   double *F;                        // [9]
   XkKeptPairs kept;                 // res: n_inliers, winner hypothesis
   unsigned char *mask;              // [n]
+  const int *n_dev;                 // NULL: n pairs.  Else n is the bound every list is laid out by (the current list starts 2 n doubles behind
+                                    //   the previous one), *n_dev the count (xk_dev_count); xk_fund_undistort then takes n_pts = 2 n
 };
 
 __global__ __launch_bounds__(256) void xk_fund_undistort(XkFundArgs a) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n_pts) return;
+  if (a.n_dev && (i >= a.n ? i - a.n : i) >= xk_dev_count(a.n_dev, a.n)) return;   // (past the count of its list)
   double u, v;
   xk_fund_undistort1(a.dist[2 * i], a.dist[2 * i + 1], a.fx, a.fy, a.cx, a.cy, a.s, a.s_term, &u, &v);
   a.und[2 * i] = u; a.und[2 * i + 1] = v;
@@ -184,8 +187,13 @@ __global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {
   const int h = blockIdx.x * XK_FUND_SOLVE_T + threadIdx.x;
   if (h == 0) *a.sc.key = 0ull;
   if (h >= a.n_hyp) return;
+  const int n = xk_dev_count(a.n_dev, a.n);
+  if (n < 7) {                                  // (only with a device count: the stage entries return before the launch.  No candidate, so
+    a.sc.ncand[h] = 0;                          //  the key stays zero and xk_fund_mask keeps nothing)
+    return;
+  }
   int pick[7];
-  xk_ransac_sample<7>(a.seed, h, a.n, pick);
+  xk_ransac_sample<7>(a.seed, h, n, pick);
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
   double p1[7][2], p2[7][2];
 #pragma unroll
@@ -201,7 +209,7 @@ __global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {
 
 __global__ __launch_bounds__(256) void xk_fund_score(XkFundArgs a) {
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
-  xk_ransac_score<XK_FUND_MAXC>(a.sc, a.n, a.t2, [&](const double *F, int i) {
+  xk_ransac_score<XK_FUND_MAXC>(a.sc, xk_dev_count(a.n_dev, a.n), a.t2, [&](const double *F, int i) {
     return xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]);
   });
 }
@@ -214,7 +222,7 @@ __global__ __launch_bounds__(256) void xk_fund_mask(XkFundArgs a) {
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
   const double *U1 = a.und, *U2 = a.und + 2 * (size_t)a.n;
   const int kept = xk_ransac_compact(
-      a.n,
+      xk_dev_count(a.n_dev, a.n),
       [&](int i) {
         const bool keep = w.valid && xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]) <= a.t2;
         a.mask[i] = keep ? 1 : 0;

@@ -54,6 +54,7 @@ struct XkKltArgs {
   double *min_eig;                 // [n]
   unsigned char *status;           // [n]
   XkKeptPairs kept;                // res: n_kept
+  const int *n_dev;                // NULL: n features.  Else n is the bound the buffers are laid out by, *n_dev the count (xk_dev_count)
 };
 
 // reflect-101 (-1 -> 1, n -> n - 2), then clamped: a caller that needs the value stays within one reflection, a tile's unused
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(64 * XK_KLT_WAVES) void xk_klt_track(XkKltArgs a) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * XK_KLT_WAVES + (threadIdx.x >> 6);
-  if (f >= a.n) return;                                          // (a whole wavefront; the kernel has no barrier)
+  if (f >= xk_dev_count(a.n_dev, a.n)) return;                   // (a whole wavefront; the kernel has no barrier)
   const double px = (double)a.pts[2 * f], py = (double)a.pts[2 * f + 1];
   if (!(isfinite(px) && isfinite(py))) {
     if (lane == 0) { a.cur_xy[2 * f] = px; a.cur_xy[2 * f + 1] = py; a.status[f] = 0; a.min_eig[f] = 0.0; }
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(256) void xk_klt_compact(XkKltArgs a) {
   const double xmax = (double)a.cur.lv[0].w - 0.5, ymax = (double)a.cur.lv[0].h - 0.5;
   double x = 0.0, y = 0.0;                     // of this thread's index: loaded by the predicate, written by the writer
   const int kept = xk_ransac_compact(
-      a.n,
+      xk_dev_count(a.n_dev, a.n),
       [&](int i) {
         x = a.cur_xy[2 * i]; y = a.cur_xy[2 * i + 1];
         return a.status[i] != 0 && x >= -0.5 && y >= -0.5 && x <= xmax && y <= ymax;

@@ -48,6 +48,8 @@ struct XkOrbArgs {
   const signed char *pattern;                // [256][4]: x1 y1 x2 y2
   int *kept_xy;                              // [max_desc][2]: the kept keypoints, in input order
   int *res;                                  // n_kept, 0, 0, 0 | keep_idx [n] | dir [n][2] | moments [n][2] | desc [n][32]
+  const int *n_dev;                          // NULL: n keypoints.  Else n is the bound the block is laid out by, *n_dev the count (xk_dev_count)
+  const int *pred;                           // NULL: blur.  Else xk_orb_blur returns at once where *pred is 0 (the frame's re-detection)
 };
 // the result block for n keypoints; desc starts at a multiple of 8 (res itself is 16-byte aligned)
 inline __host__ __device__ size_t xk_orb_desc_off(size_t n) { return (sizeof(int) * (4 + 5 * n) + 7) / 8 * 8; }
@@ -64,6 +66,7 @@ __global__ __launch_bounds__(256) void xk_orb_blur(XkOrbArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char s_in[XK_ORB_ROWS][XK_ORB_COLS];
   __shared__ unsigned short s_h[XK_ORB_ROWS][XK_ORB_TW];
   const int w = a.w, h = a.h, pitch = a.pitch;
+  if (a.pred && *a.pred == 0) return;                            // (the same in every thread)
   const int tx0 = blockIdx.x * XK_ORB_TW, ty0 = blockIdx.y * XK_ORB_TH;
   const int cx0 = tx0 - 4, cy0 = ty0 - 3;
   for (int i = threadIdx.x; i < XK_ORB_ROWS * (XK_ORB_COLS / 4); i += 256) {
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(256) void xk_orb_filter(XkOrbArgs a) {
   const int w = a.w, h = a.h, edge = a.edge;
   int x = 0, y = 0;
   const int kept = xk_ransac_compact(
-      a.n,
+      xk_dev_count(a.n_dev, a.n),
       [&](int i) {
         x = a.xy[2 * i]; y = a.xy[2 * i + 1];
         return x >= edge && x < w - edge && y >= edge && y < h - edge;

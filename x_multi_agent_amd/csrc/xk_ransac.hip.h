@@ -18,6 +18,11 @@
 
 #define XK_RANSAC_HD __host__ __device__ inline
 
+// The count of a launch.  n_dev == NULL: n, by value, as the stage entries pass it.  Otherwise the host knows only the bound n (it sized
+// the grid and the buffers by it) and the count is what an earlier launch on the same stream left at n_dev: a plain load, held
+// within the bound.  The frame entry (xk_frame.hip.h) launches this way.
+__device__ __forceinline__ int xk_dev_count(const int *n_dev, int n) { return n_dev ? min(max(*n_dev, 0), n) : n; }
+
 XK_RANSAC_HD unsigned long long xk_ransac_mix(unsigned long long z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

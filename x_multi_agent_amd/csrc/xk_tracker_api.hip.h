@@ -13,6 +13,7 @@
 #include <time.h>
 
 #include "xk_fast.hip.h"
+#include "xk_frame.hip.h"
 #include "xk_fundamental.hip.h"
 #include "xk_klt.hip.h"
 #include "xk_orb.hip.h"
@@ -155,7 +156,24 @@ struct xk_klt {
   struct xk_det *det;         // xk_trk_detect_setup; NULL before.  It goes with this setup
   struct xk_orb *orb;         // xk_trk_describe_setup; likewise
   struct xk_photo *photo;     // xk_trk_photo_setup; likewise
+  struct xk_frm *frm;         // xk_trk_frame_setup; likewise
   size_t slot_bytes;          // of one slot: its levels are one contiguous block
+};
+
+// The frame setup (xk_trk_frame_setup): Tracker::track's parameters and the feature list that stays on the device between frames.
+// It belongs to the xk_klt whose images it tracks on, and uses the detection and description setups that existed when it was made.
+struct xk_frm {
+  int n_feat_min, tiles_h, tiles_w, max_per_tile, n_hyp;
+  double threshold_px;
+  const struct xk_det *det;   // the setups it was made over: a frame asks that they are still the ones in place
+  const struct xk_orb *orb;   // NULL: no description
+  int n_res;                  // the resident count: the previous frame's matches; -1: the next frame is a first frame
+  int cap_det, cap_new;       // the detection's packing bound; the bound of a re-detection's lists (max_desc with a description)
+  xk_block blk;                 // device: counts | resident list | pair lists | the stages' result blocks | the frame's result block.  Pinned: the latter
+  XkFrameArgs a;              // every device pointer, placed once
+  unsigned char *klt_res[2];  // result blocks of the two trackings (klt_res_bytes(max_matches) each)
+  unsigned char *fund_res;    // of the outlier removal (trk_res_bytes(max_matches))
+  int *orb_res;               // of the description (xk_orb_res_bytes(cap_new)); NULL without one
 };
 
 // The baseline setup (xk_trk_baseline_setup): capacities of one batch of tracks.  It belongs to the xk_trk, not to an image size.
@@ -230,6 +248,7 @@ static void setup_free(xk_klt *k) {
   setup_free(k->det);
   setup_free(k->orb);
   setup_free(k->photo);
+  setup_free(k->frm);
   blk_free(k->blk);
   if (k->h_img) hipHostFree(k->h_img);
   if (k->img_copied) hipEventDestroy(k->img_copied);
@@ -270,6 +289,13 @@ static int img_slot(xk_trk *t, const char *who, int which) {
   if (!what) return which == 1 ? k->cur : k->cur ^ 1;
   fail_at(t->h, XK_EINVAL, who, what);
   return -1;
+}
+
+// A frame setup was made over the detection and description setups in place: when one of them is replaced it goes (the stream is idle:
+// setup_install has waited).
+static void frame_drop(xk_klt *k) {
+  setup_free(k->frm);
+  k->frm = nullptr;
 }
 
 // The slot's plane that a push fills first: the raw one with a photo setup, the only one without.
@@ -509,14 +535,10 @@ static int klt_pyramid(xk_handle *h, const xk_klt *k, const XkKltPyr &P) {
   return launched(h, "pyramid launch");
 }
 
-/* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
-extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride) {
-  if (!t) return XK_EINVAL;
+// The push behind xk_trk_push_image and xk_trk_frame: the arguments are checked and the device is set.
+static int trk_push(xk_trk *t, const unsigned char *img, int stride) {
   xk_handle *h = t->h;
   xk_klt *k = t->klt;
-  if (!k) return fail(h, XK_EINVAL, "xk_trk_push_image: before xk_trk_klt_setup");
-  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_push_image: null image or stride below the width");
-  HIPCHK(h, hipSetDevice(h->device));
   const int s = k->cur ^ 1;
   const XkKltPyr &P = k->slot[s];
   const XkKltPyr &B = photo_raw_slot(k, s);                                  // where the pyramid is built: the raw plane with a photo setup
@@ -533,16 +555,33 @@ extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride
   return XK_OK;
 }
 
+/* previous_img_ = current_img.clone() (tracker.cpp:302) and the pyramid cv::calcOpticalFlowPyrLK builds of the new image */
+extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_push_image: before xk_trk_klt_setup");
+  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_push_image: null image or stride below the width");
+  HIPCHK(h, hipSetDevice(h->device));
+  XKCHK(trk_push(t, img, stride));
+  if (k->frm) k->frm->n_res = -1;                                          // (the resident list belongs to an image that is no longer the previous one)
+  return XK_OK;
+}
+
+// The kept pairs in a tracking's result block for n points: cur_xy [n][2] | min_eig [n] | kept pairs | status [n].
+static XkKeptPairs klt_kept_at(unsigned char *d_res, int n) { return xk_kept_pairs((double *)d_res + 3 * (size_t)n, n); }
+
 // The tracking of the n points at d_pts from pyramid `prev` to `cur`, queued: the result block (klt_res_bytes(n)) goes to d_res.
 static int klt_queue_track(xk_handle *h, const xk_klt *k, const XkKltPyr &prev, const XkKltPyr &cur, const float *d_pts, unsigned char *d_res,
-                           int n, XkKltArgs &a) {
+                           int n, XkKltArgs &a, const int *n_dev = nullptr) {
   a = XkKltArgs{};
+  a.n_dev = n_dev;                                                // (then n is the bound the grid and the block are sized by)
   a.prev = prev; a.cur = cur;
   a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
   a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
   a.pts = d_pts;
   a.cur_xy = (double *)d_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
-  a.kept = xk_kept_pairs(a.min_eig + n, n);
+  a.kept = klt_kept_at(d_res, n);
   a.status = xk_kept_pairs_end(a.kept, n);
   hipLaunchKernelGGL(xk_klt_track, dim3((n + XK_KLT_WAVES - 1) / XK_KLT_WAVES), dim3(64 * XK_KLT_WAVES), 0, h->stream, a);
   hipLaunchKernelGGL(xk_klt_compact, dim3(1), dim3(256), 0, h->stream, a);
@@ -639,7 +678,9 @@ extern "C" int xk_trk_detect_setup(xk_trk *t, int threshold, int non_max_supp, i
     d->mask_g = mask_in_lds ? nullptr : carve<unsigned int>(d->blk.d, off, mask_bytes);
     d->h_res = (int *)(d->blk.h + old_bytes);
   }
-  return setup_install(h, rc, "xk_trk_detect_setup", k->det, d);
+  XKCHK(setup_install(h, rc, "xk_trk_detect_setup", k->det, d));
+  frame_drop(k);
+  return XK_OK;
 }
 
 /* Tracker::featureDetection (tracker.cpp:390-590) on level 0 of the previous (which = 0) or the current (1) image */
@@ -768,7 +809,9 @@ extern "C" int xk_trk_describe_setup(xk_trk *t, int orientation, double angle_de
     if (hipMemcpyAsync(o->pattern, o->blk.h, sizeof o->h_pattern, hipMemcpyHostToDevice, h->stream) != hipSuccess)
       rc = fail(h, XK_ENOMEM, "xk_trk_describe_setup: allocation failed");
   }
-  return setup_install(h, rc, "xk_trk_describe_setup", k->orb, o);
+  XKCHK(setup_install(h, rc, "xk_trk_describe_setup", k->orb, o));
+  frame_drop(k);
+  return XK_OK;
 }
 
 // The slot s as XkOrbArgs, its blur queued if this is the slot's first description since its push.
@@ -1569,5 +1612,254 @@ extern "C" int xk_trk_baseline(xk_trk *t, const int *trk_off, const double *obs_
   memcpy(norm_xy, b->blk.h + b->o_norm, sizeof(double) * 2 * n_norm);
   memcpy(delta_xy, b->blk.h + b->o_delta, sizeof(double) * 2 * (size_t)K);
   memcpy(flag, b->blk.h + b->o_flag, (size_t)K);
+  return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One frame of Tracker::track (tracker.cpp:134-306) on a feature list that stays on the device, xk_frame.hip.h
+// ---------------------------------------------------------------------------
+/* The parameters of Tracker::track as Tracker and its TiledImage hold them (tracker.h:234-261, tiled_image.cpp:98-105) and the resident list */
+extern "C" int xk_trk_frame_setup(xk_trk *t, int n_feat_min, int n_tiles_h, int n_tiles_w, int max_feat_per_tile, double threshold_px,
+                                  int n_hyp) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_frame_setup: before xk_trk_klt_setup");
+  const xk_det *d = k->det;
+  const xk_orb *o = k->orb;
+  if (!d) return fail(h, XK_EINVAL, "xk_trk_frame_setup: before xk_trk_detect_setup");
+  if (n_feat_min < 0) return fail(h, XK_EINVAL, "xk_trk_frame_setup: n_feat_min < 0");
+  if (n_tiles_h < 1 || n_tiles_w < 1 || (long long)n_tiles_h * n_tiles_w > XK_FRAME_MAX_TILES)
+    return fail(h, XK_EINVAL, "xk_trk_frame_setup: tile counts outside 1...4096 tiles");
+  if (max_feat_per_tile < 0) return fail(h, XK_EINVAL, "xk_trk_frame_setup: max_feat_per_tile < 0");
+  if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) return fail(h, XK_EINVAL, "xk_trk_frame_setup: threshold_px < 0");
+  if (n_hyp < 1 || n_hyp > XK_FUND_MAX_HYP) return fail(h, XK_EINVAL, "xk_trk_frame_setup: n_hyp outside 1...4096");
+  if (o && d->margin < o->edge)   // (a feature the description's filter dropped would have no descriptor to carry: FeatureTracker::detect throws there)
+    return fail(h, XK_EINVAL, "xk_trk_frame_setup: the detection's margin is below the description's edge");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_frm *f = (xk_frm *)calloc(1, sizeof(xk_frm));
+  if (!f) return XK_ENOMEM;
+  f->n_feat_min = n_feat_min; f->tiles_h = n_tiles_h; f->tiles_w = n_tiles_w; f->max_per_tile = max_feat_per_tile;
+  f->threshold_px = threshold_px; f->n_hyp = n_hyp;
+  f->det = d; f->orb = o; f->n_res = -1;
+  const size_t M = (size_t)t->max_matches;
+  // accepted points are pairwise more than b apart (xk_trk_detect)
+  const long long bound = (long long)((k->width + d->b) / (d->b + 1)) * ((k->height + d->b) / (d->b + 1));
+  f->cap_det = (int)std::min<long long>(bound, t->max_matches);
+  f->cap_new = o ? std::min(f->cap_det, o->max_desc) : f->cap_det;
+  const size_t N = (size_t)f->cap_new;
+  const size_t klt_bytes = up16(klt_res_bytes(t->max_matches)), det_bytes = up16(det_res_bytes(t->max_matches));
+  const size_t orb_bytes = o ? up16(xk_orb_res_bytes(N)) : 0, fund_bytes = up16(trk_res_bytes(t->max_matches));
+  const size_t out_bytes = up16(xk_frame_out_bytes(M, o != nullptr)), desc_bytes = o ? up16(32 * M) : 0;
+  const size_t d_bytes = up16(sizeof(int) * XK_FC_N) + up16(16 * M) + up16(8 * M) + up16(4 * M) + desc_bytes       // counts, resident list
+                         + 2 * up16(4 * M) + 2 * up16(16 * M) + desc_bytes + up16(8 * N)                             // pair lists, new points
+                         + 2 * klt_bytes + det_bytes + orb_bytes + fund_bytes + out_bytes;
+  int rc = blk_alloc(h, f->blk, d_bytes, out_bytes, "xk_trk_frame_setup");
+  if (rc == XK_OK && hipFuncSetAttribute((const void *)xk_fast_select, hipFuncAttributeMaxDynamicSharedMemorySize, XK_FAST_LDS_MAX) != hipSuccess)
+    rc = fail(h, XK_ENOMEM, "xk_trk_frame_setup: allocation failed");
+  if (rc == XK_OK) {
+    XkFrameArgs &a = f->a;
+    unsigned char *b = f->blk.d;
+    size_t off = 0;
+    a.c = carve<int>(b, off, sizeof(int) * XK_FC_N);
+    a.res_dist = carve<double>(b, off, 16 * M);
+    a.res_pts = carve<float>(b, off, 8 * M);
+    a.res_score = carve<int>(b, off, 4 * M);
+    a.res_desc = o ? carve<unsigned char>(b, off, 32 * M) : nullptr;
+    a.l_score = carve<int>(b, off, 4 * M);
+    a.l_origin = carve<int>(b, off, 4 * M);
+    a.l_tiles = carve<int>(b, off, 16 * M);
+    a.tmp_tiles = carve<int>(b, off, 16 * M);
+    a.l_desc = o ? carve<unsigned char>(b, off, 32 * M) : nullptr;
+    a.pts_new = carve<float>(b, off, 8 * N);
+    f->klt_res[0] = carve<unsigned char>(b, off, klt_bytes);
+    f->klt_res[1] = carve<unsigned char>(b, off, klt_bytes);
+    a.det_res = carve<int>(b, off, det_bytes);
+    f->orb_res = o ? carve<int>(b, off, orb_bytes) : nullptr;
+    f->fund_res = carve<unsigned char>(b, off, fund_bytes);
+    a.out = carve<unsigned char>(b, off, out_bytes);
+    a.orb_res = f->orb_res;
+    a.und = t->und;                                                 // (the outlier removal's scratch is the stage entries': every call fills it anew)
+    a.n_feat_min = n_feat_min; a.tiles_h = n_tiles_h; a.tiles_w = n_tiles_w; a.max_per_tile = max_feat_per_tile;
+    a.height = (double)k->height;
+    a.tile_h = (double)k->height / n_tiles_h; a.tile_w = (double)k->width / n_tiles_w;        // tiled_image.cpp:104-105
+    a.cap_new = f->cap_new; a.max_candidates = d->max_candidates; a.max_matches = t->max_matches; a.max_desc = o ? o->max_desc : 0;
+  }
+  return setup_install(h, rc, "xk_trk_frame_setup", k->frm, f);
+}
+
+/* The next frame is a first frame; the images stay */
+extern "C" int xk_trk_frame_reset(xk_trk *t) {
+  if (!t) return XK_EINVAL;
+  xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame_reset", "xk_trk_frame_setup");
+  if (!f) return XK_EINVAL;
+  f->n_res = -1;
+  return XK_OK;
+}
+
+/* The resident list as the device holds it.  Straight copies */
+extern "C" int xk_trk_frame_features(xk_trk *t, double *dist_xy, int *score, unsigned char *desc, int *n) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame_features", "xk_trk_frame_setup");
+  if (!f) return XK_EINVAL;
+  if (!n) return fail(h, XK_EINVAL, "xk_trk_frame_features: null count");
+  const size_t r = (size_t)std::max(f->n_res, 0);
+  *n = (int)r;
+  if (r == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (dist_xy) HIPCHK(h, hipMemcpyAsync(dist_xy, f->a.res_dist, sizeof(double) * 2 * r, hipMemcpyDeviceToHost, h->stream));
+  if (score) HIPCHK(h, hipMemcpyAsync(score, f->a.res_score, sizeof(int) * r, hipMemcpyDeviceToHost, h->stream));
+  if (desc && f->a.res_desc) HIPCHK(h, hipMemcpyAsync(desc, f->a.res_desc, 32 * r, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// The detection of a frame on slot s, queued: no old features (n_old_bound = 0) or the device's list of at most n_old_bound; pred as XkFastArgs::pred.
+static int frame_queue_detect(xk_trk *t, const xk_frm *f, int s, const int *pred, const double *old_xy, int n_old_bound, const int *n_old_dev) {
+  xk_handle *h = t->h;
+  xk_det *d = t->klt->det;
+  const XkKltLevel &L = t->klt->slot[s].lv[0];
+  XkFastArgs a{};
+  a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
+  a.S = d->S; a.keys = d->keys; a.count = d->count; a.mask_g = d->mask_g; a.key_cap = d->key_cap; a.wpr = d->wpr;
+  a.old_xy = old_xy; a.n_old = n_old_bound; a.n_old_dev = n_old_dev; a.pred = pred;
+  a.threshold = d->threshold; a.nms = d->nms; a.b = d->b; a.margin = d->margin; a.max_candidates = d->max_candidates;
+  a.max_matches = t->max_matches;
+  a.res = f->a.det_res;
+  d->n_cand = -1;                                                   // (the score image and the keys are no longer those of the last xk_trk_detect)
+  hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fast_select, dim3(1), dim3(XK_FAST_SEL_T), d->lds_bytes, h->stream, a);
+  return launched(h, "frame detection launch");
+}
+
+// The description of the detected features (the detection's result block holds their pixels) on slot s, queued; the count is the gate's.
+static int frame_queue_describe(xk_trk *t, const xk_frm *f, int s, const int *pred) {
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_orb *o = k->orb;
+  const XkKltLevel &L = k->slot[s].lv[0];
+  XkOrbArgs a{};
+  a.img = L.img; a.G = o->G[s]; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
+  a.edge = o->edge; a.centroid = o->centroid; a.A = o->A; a.B = o->B;
+  a.pattern = o->pattern; a.xy = f->a.det_res + 4; a.kept_xy = o->kept_xy; a.res = f->orb_res;
+  a.n = f->cap_new; a.n_dev = f->a.c + XK_FC_NEW; a.pred = pred;
+  if (!o->blurred[s]) {
+    hipLaunchKernelGGL(xk_orb_blur, dim3((a.w + XK_ORB_TW - 1) / XK_ORB_TW, (a.h + XK_ORB_TH - 1) / XK_ORB_TH), dim3(256), 0, h->stream, a);
+    if (!pred) o->blurred[s] = 1;                                   // (a predicated blur may not have run: the host cannot count on it)
+  }
+  hipLaunchKernelGGL(xk_orb_filter, dim3(1), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_orb_describe, dim3(std::min((a.n + XK_ORB_WAVES - 1) / XK_ORB_WAVES, XK_ORB_MAX_GRID)), dim3(64 * XK_ORB_WAVES), 0,
+                     h->stream, a);
+  return launched(h, "frame description launch");
+}
+
+static const char *frame_status_text(int status) {
+  switch (status) {
+    case XK_FRAME_ECAND: return "more candidates than max_candidates";
+    case XK_FRAME_EACCEPTED: return "more features accepted than max_matches";
+    case XK_FRAME_EDESC: return "more keypoints than max_desc";
+    case XK_FRAME_ETOTAL: return "old plus new features exceed max_matches";
+  }
+  return "status out of range";
+}
+
+/* Tracker::track (tracker.cpp:134-306), a build without PHOTOMETRIC_CALI, pyramid level 0: everything queued on the handle's stream, one wait */
+extern "C" int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, xk_trk_frame_out *out) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame", "xk_trk_frame_setup");
+  if (!f) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (k->photo) return fail(h, XK_EINVAL, "xk_trk_frame: a photometric setup is in place (the photometric frame is not built)");
+  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_frame: null image or stride below the width");
+  if (!out || !out->prev_xy || !out->cur_xy || !out->prev_dist_xy || !out->cur_dist_xy || !out->score || !out->origin || !out->tiles ||
+      (f->orb && !out->desc))
+    return fail(h, XK_EINVAL, "xk_trk_frame: null output");
+  out->n_tracked = out->n_left = out->redetected = out->n_candidates = out->n_accepted = out->n_new_tracked = out->n_matches = 0;
+  out->winner = -1;
+  HIPCHK(h, hipSetDevice(h->device));
+  const bool first = f->n_res < 0;
+  const int M = t->max_matches, R = first ? 0 : f->n_res;
+  f->n_res = -1;                                                    // (whatever fails below: the next frame is a first frame)
+  XKCHK(trk_push(t, img, stride));
+  XkFrameArgs a = f->a;
+  a.first = first ? 1 : 0;
+  a.n_res = R;
+  a.B = first ? 1 : std::min(M, R + f->cap_det);
+  const size_t B = (size_t)a.B;
+  a.l_prev = t->dist; a.l_cur = t->dist + 2 * B;
+  int *c = a.c;
+  const int *head = (const int *)f->blk.h;
+  if (first) {
+    XKCHK(frame_queue_detect(t, f, k->cur, nullptr, nullptr, 0, nullptr));
+    hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
+    if (f->orb) XKCHK(frame_queue_describe(t, f, k->cur, nullptr));
+    hipLaunchKernelGGL(xk_frame_first, dim3((f->cap_new + 255) / 256), dim3(256), 0, h->stream, a);
+    XKCHK(launched(h, "first frame launch"));
+    HIPCHK(h, hipMemcpyAsync(f->blk.h, a.out, sizeof(int) * XK_FC_N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  } else {
+    const XkKltPyr &prev = k->slot[k->cur ^ 1], &cur = k->slot[k->cur];
+    XkKltArgs ka;
+    a.kept1 = klt_kept_at(f->klt_res[0], R);
+    a.kept2 = klt_kept_at(f->klt_res[1], f->cap_new);
+    XkFundArgs fa{};
+    fa.dist = t->dist; fa.und = t->und; fa.pts = t->pts; fa.sc = t->sc;
+    fa.F = (double *)f->fund_res;
+    fa.kept = xk_kept_pairs(fa.F + 9, B);
+    fa.mask = xk_kept_pairs_end(fa.kept, B);
+    fa.n = a.B; fa.n_pts = 2 * a.B; fa.n_dev = c + XK_FC_TOTAL;
+    fa.fx = t->fx; fa.fy = t->fy; fa.cx = t->cx; fa.cy = t->cy; fa.s = t->s; fa.s_term = t->s_term;
+    fa.n_hyp = f->n_hyp; fa.t2 = f->threshold_px * f->threshold_px; fa.seed = (unsigned long long)seed;
+    a.kept3 = fa.kept;
+    t->n_hyp = 0;                                                   // (the scratch no longer holds the last xk_trk_filter_matches)
+    // 2. the resident list from the previous image to the current one, its post-filter; 3. the overflow pass
+    if (R > 0) XKCHK(klt_queue_track(h, k, prev, cur, a.res_pts, f->klt_res[0], R, ka));
+    hipLaunchKernelGGL(xk_frame_overflow, dim3(1), dim3(256), sizeof(int) * (size_t)f->tiles_h * f->tiles_w, h->stream, a);
+    // 4. the re-detection on the PREVIOUS image, queued on every frame and predicated on the flag the overflow pass left.  (With
+    // n_feat_min = 0 the flag is never set: nothing is queued, and xk_frame_concat finds the zero count the overflow pass wrote.)
+    if (f->n_feat_min > 0) {
+      XKCHK(frame_queue_detect(t, f, k->cur ^ 1, c + XK_FC_REDETECT, a.l_prev, R, c + XK_FC_LEFT));
+      hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
+      if (f->orb) XKCHK(frame_queue_describe(t, f, k->cur ^ 1, c + XK_FC_REDETECT));
+      XKCHK(klt_queue_track(h, k, prev, cur, a.pts_new, f->klt_res[1], f->cap_new, ka, c + XK_FC_NEW));
+    }
+    hipLaunchKernelGGL(xk_frame_concat, dim3(1), dim3(256), 0, h->stream, a);
+    // 5. the outlier removal, as trk_run queues it
+    hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.B + 255) / 256), dim3(256), 0, h->stream, fa);
+    hipLaunchKernelGGL(xk_fund_solve, dim3((fa.n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, fa);
+    hipLaunchKernelGGL(xk_fund_score, dim3(fa.n_hyp), dim3(256), 0, h->stream, fa);
+    hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, fa);
+    // 6. the result block and the new resident list
+    hipLaunchKernelGGL(xk_frame_pack, dim3((a.B + 255) / 256), dim3(256), 0, h->stream, a);
+    XKCHK(launched(h, "frame launch"));
+    HIPCHK(h, hipMemcpyAsync(f->blk.h, a.out, xk_frame_out_bytes(B, f->orb != nullptr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                     // the frame's one wait
+  }
+  const int status = head[XK_FC_STATUS], m = head[XK_FC_MATCHES];
+  for (int j = 0; j <= XK_FC_TOTAL; ++j)
+    if (head[j] < 0 || (j != XK_FC_CAND && j != XK_FC_ACCEPTED && head[j] > M)) return fail(h, XK_EDEVICE, "xk_trk_frame: counts out of range");
+  if (m < 0 || m > a.B || status < 0 || status > XK_FRAME_ETOTAL) return fail(h, XK_EDEVICE, "xk_trk_frame: counts out of range");
+  out->n_tracked = head[XK_FC_TRACKED]; out->n_left = head[XK_FC_LEFT]; out->redetected = head[XK_FC_REDETECT];
+  out->n_candidates = head[XK_FC_CAND]; out->n_accepted = head[XK_FC_ACCEPTED]; out->n_new_tracked = head[XK_FC_NEW_TRACKED];
+  out->winner = head[XK_FC_WINNER];
+  if (status != 0) return fail_at(h, XK_ECAPACITY, "xk_trk_frame", frame_status_text(status));
+  if (first) {
+    f->n_res = head[XK_FC_NEW];
+    return XK_OK;
+  }
+  out->n_matches = m;
+  const unsigned char *r = f->blk.h;
+  memcpy(out->prev_xy, r + xk_frame_out_xy(B, 0), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->cur_xy, r + xk_frame_out_xy(B, 1), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->prev_dist_xy, r + xk_frame_out_xy(B, 2), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->cur_dist_xy, r + xk_frame_out_xy(B, 3), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->score, r + xk_frame_out_score(B), sizeof(int) * (size_t)m);
+  memcpy(out->origin, r + xk_frame_out_origin(B), sizeof(int) * (size_t)m);
+  memcpy(out->tiles, r + xk_frame_out_tiles(B), sizeof(int) * 4 * (size_t)m);
+  if (f->orb) memcpy(out->desc, r + xk_frame_out_desc(B), 32 * (size_t)m);
+  f->n_res = m;
   return XK_OK;
 }

@@ -9,6 +9,8 @@ from two images and the previous features to the pairs that filter takes.  `Klt.
 `Klt.describe` their rotated-BRIEF descriptors (`PlaceRecognition::compute`, place_recognition.cpp:72-94), which is what
 place.Database takes.  `Klt.photo_*` is the photometric calibration a PHOTOMETRIC_CALI build runs in front of all of them
 (`Tracker::calibrateImage`, tracker.cpp:761-877, and IRPhotoCalib): photo_calibrate between push_image and track.
+`Klt.frame` is `Tracker::track` itself (tracker.cpp:134-306, without the photometric step): one call per image on a feature list
+that stays on the device (csrc/xk_frame.hip.h).
 
 `MatchFilter.baseline` is what the track manager behind them asks every frame (`TrackManager::checkBaseline`,
 track_manager.cpp:576-636, and `Camera::normalize`): the normalisation, crop and baseline check of all candidate tracks at once.
@@ -267,6 +269,65 @@ class Klt(_Trk):
         self._chk(self.L.xk_trk_describe_stage(self.p, C.c_int(which), G.ctypes.data_as(c_ub), pat.ctypes.data_as(c_sb)), "xk_trk_describe_stage")
         return G, pat
 
+    # ---- Tracker::track in one call (tracker.cpp:134-306) on a feature list that stays on the device, csrc/xk_frame.hip.h ----
+    _frame_buf = None
+
+    def frame_setup(self, n_feat_min=40, n_tiles_h=1, n_tiles_w=1, max_feat_per_tile=10000, threshold_px=0.3, n_hyp=1024):
+        """xk_trk_frame_setup, after detect_setup (and describe_setup, if the features carry descriptors): n_feat_min of
+        tracker.cpp:204, the tile grid and cap of removeOverflowFeatures, threshold and hypotheses of the outlier removal.  A
+        later setup(), detect_setup() or describe_setup() drops it."""
+        self._chk(self.L.xk_trk_frame_setup(self.p, C.c_int(n_feat_min), C.c_int(n_tiles_h), C.c_int(n_tiles_w), C.c_int(max_feat_per_tile),
+                                            C.c_double(threshold_px), C.c_int(n_hyp)), "xk_trk_frame_setup")
+
+    def _frame_arrays(self):
+        """What xk_trk_frame_out points at: max_features rows each, allocated once."""
+        m = self.max_features
+        if self._frame_buf is None or len(self._frame_buf["score"]) != m:
+            self._frame_buf = dict(prev_xy=np.zeros((m, 2)), cur_xy=np.zeros((m, 2)), prev_dist_xy=np.zeros((m, 2)), cur_dist_xy=np.zeros((m, 2)),
+                                   score=np.zeros(m, np.int32), origin=np.zeros(m, np.int32), tiles=np.zeros((m, 4), np.int32),
+                                   desc=np.zeros((m, 32), np.uint8))
+        return self._frame_buf
+
+    def frame(self, img, seed=0):
+        """xk_trk_frame, Tracker::track of one image (uint8 [height, >= width]) -> dict of the counts n_tracked, n_left, redetected,
+        n_candidates, n_accepted, n_new_tracked, n_matches, winner, and per match prev_xy, cur_xy (undistorted fp64 pixels),
+        prev_dist_xy, cur_dist_xy, score, origin, tiles int32 [m, 4] (previous row, column, current row, column), desc uint8
+        [m, 32].  A first frame returns no matches.  On XK_ECAPACITY the XkError carries the counts reached as `counts`."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] != self.height or img.shape[1] < self.width:
+            raise ValueError("frame: a uint8 image of the set-up height and at least the set-up width")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        b, o = self._frame_arrays(), FrameOut()
+        for name in ("prev_xy", "cur_xy", "prev_dist_xy", "cur_dist_xy"):
+            setattr(o, name, b[name].ctypes.data_as(c_dp))
+        for name in ("score", "origin", "tiles"):
+            setattr(o, name, b[name].ctypes.data_as(c_ip))
+        o.desc = b["desc"].ctypes.data_as(c_ub)
+        rc = self.L.xk_trk_frame(self.p, img.ctypes.data_as(c_ub), C.c_int(img.strides[0]), C.c_ulong(seed), C.byref(o))
+        counts = {k: int(getattr(o, k)) for k in FrameOut.COUNTS}
+        if rc != 0:
+            err = self._error(rc, "xk_trk_frame")
+            err.counts = counts
+            raise err
+        m = counts["n_matches"]
+        out = dict(counts)
+        out.update({k: v[:m].copy() for k, v in b.items()})
+        return out
+
+    def frame_features(self):
+        """The resident list as the device holds it -> dict of dist_xy fp64 [n, 2], score int32 [n], desc uint8 [n, 32] (zeros
+        without a description)."""
+        m = self.max_features
+        xy, score, desc, n = np.zeros((m, 2)), np.zeros(m, np.int32), np.zeros((m, 32), np.uint8), C.c_int(0)
+        self._chk(self.L.xk_trk_frame_features(self.p, xy.ctypes.data_as(c_dp), score.ctypes.data_as(c_ip), desc.ctypes.data_as(c_ub),
+                                               C.byref(n)), "xk_trk_frame_features")
+        return dict(dist_xy=xy[:n.value].copy(), score=score[:n.value].copy(), desc=desc[:n.value].copy())
+
+    def frame_reset(self):
+        """The next frame is a first frame; the pushed images stay."""
+        self._chk(self.L.xk_trk_frame_reset(self.p), "xk_trk_frame_reset")
+
     # ---- photometric calibration (Tracker::calibrateImage, tracker.cpp:761-877; irPhotoCalib.cpp), csrc/xk_photo.hip.h ----
     def photo_setup(self, kernel_size=30, epsilon_gap=0.0, epsilon_base=0.0, max_hyp=512):
         """xk_trk_photo_setup: the raw plane of both image slots, the spatial map (zeros), the parameter ring (one entry (1, 0))
@@ -448,6 +509,13 @@ class Klt(_Trk):
     def photo_spatial_reset(self):
         """Counts, coverage and rows back to empty, the state back to accumulating; the PS plane keeps what it holds."""
         self._chk(self.L.xk_trk_photo_spatial_reset(self.p), "xk_trk_photo_spatial_reset")
+
+
+class FrameOut(C.Structure):
+    """xk_trk_frame_out (include/xk.h)"""
+    COUNTS = ("n_tracked", "n_left", "redetected", "n_candidates", "n_accepted", "n_new_tracked", "n_matches", "winner")
+    _fields_ = [(k, C.c_int) for k in COUNTS] + [(k, c_dp) for k in ("prev_xy", "cur_xy", "prev_dist_xy", "cur_dist_xy")] + \
+               [(k, c_ip) for k in ("score", "origin", "tiles")] + [("desc", c_ub)]
 
 
 class SpatialOutcome(C.Structure):
