@@ -1,7 +1,8 @@
 // x/vision/tracker.h -- Tracker::track (src/x/vision/tracker.cpp:134-306) on the mirror: an image goes in, the frame's MatchList comes
-// out.  A build without PHOTOMETRIC_CALI, pyramid level 0.  The whole frame -- pyramid, Lucas-Kanade tracking, removeOverflowFeatures,
-// the re-detection with its descriptors, the undistortion and the fundamental-matrix RANSAC -- runs on the GPU behind xk_trk_frame
-// (include/xk.h), and previous_features_ (tracker.cpp:299) stays on the device between frames.  There is no CPU fallback.
+// out.  Pyramid level 0.  The whole frame -- pyramid, Lucas-Kanade tracking, removeOverflowFeatures, the re-detection with its
+// descriptors, the undistortion and the fundamental-matrix RANSAC -- runs on the GPU behind xk_trk_frame (include/xk.h),
+// and previous_features_ (tracker.cpp:299) stays on the device between frames.  After setPhotometric it is the frame of a
+// PHOTOMETRIC_CALI build, calibrateImage included, behind xk_trk_photo_frame.  There is no CPU fallback.
 // x::FeatureTracker and x::MatchFilter remain the stage-by-stage mirrors.
 #pragma once
 #include <cstdint>
@@ -32,6 +33,28 @@ class Tracker {
   void setDescription(bool centroid_orientation = false, double angle_deg = -1.0, int edge = 31, const signed char *pattern = nullptr);
   // the seed of the next frame's RANSAC (each frame then takes the next one)
   void setSeed(unsigned long seed) { seed_ = seed; }
+  // PHOTOMETRIC_CALI: calibrateImage on every image after the first (tracker.cpp:186-190).  kernel_size is intensities_kernel_size_
+  // (tracker.h:366), epsilon_gap and epsilon_base the drift parameters of IRPhotoCalib, n_hyp_photo the most hypotheses of a frame's
+  // gain estimate, fast_detection_delta_photo the FAST threshold once gains were estimated (tracker.cpp:848; < 0: no switch).  From
+  // then on track() goes through xk_trk_photo_frame and every TrackedFeature of a match carries its getIntensity().  The frame tracks
+  // with the one Lucas-Kanade parameter set of the constructor (the reference's second set, tracker.cpp:641-645, is out of scope).
+  void setPhotometric(int kernel_size, double epsilon_gap, double epsilon_base, int n_hyp_photo, int fast_detection_delta_photo = -1);
+  // IRPhotoCalib's spatial map, as FeatureTracker::setSpatialCalibration, after setPhotometric: every frame accumulates its rows on the
+  // device; after a frame that estimated gains track() reads the status and, once the coverage passes thr, runs the estimate and
+  // installs the map (synchronous, on the caller's thread)
+  void setSpatialCalibration(int div = 16, double thr = 0.9, int max_rows = 1 << 18);
+  bool spatialCalibrated() const { return spatial_done_; }
+  const xk_photo_spatial_outcome &spatialOutcome() const { return spatial_outcome_; }
+  // the seed of the next frame's gain RANSAC (each frame then takes the next one)
+  void setPhotoSeed(unsigned long seed) { seed_photo_ = seed; }
+  struct Calibration {
+    bool estimated = false, done = false;   // gains were estimated by this frame; by a frame so far
+    int kept = 0, support = 0;              // features the raw tracking kept, inliers of the estimate
+    double a_rel = 1.0, b_rel = 0.0;        // the estimate against the previous frame
+    double frame_ab[4] = {0, 0, 0, 0};      // the pair after the drift adjustments, the frame's origin pair
+  };
+  // the outcome of the last frame's calibrateImage
+  const Calibration &calibration() const { return calibration_; }
   // the next tracked image is a first image
   void reset();
 
@@ -58,7 +81,14 @@ class Tracker {
   double angle_deg_ = -1.0;
   int edge_ = 31;
   signed char pattern_[1024];
-  unsigned long seed_ = 0;
+  unsigned long seed_ = 0, seed_photo_ = 0;
+  bool photo_ = false, spatial_ = false, spatial_done_ = false;
+  int photo_kernel_ = 30, photo_hyp_ = 0, photo_threshold_ = -1, spatial_div_ = 16, spatial_rows_ = 0;
+  double eps_gap_ = 0.0, eps_base_ = 0.0, spatial_thr_ = 0.9;
+  Calibration calibration_;
+  xk_photo_spatial_outcome spatial_outcome_ = {};
+  xk_trk_photo_frame_out pout_{};
+  std::vector<double> prev_int_, cur_int_;
   int img_id_ = 0;
   MatchList matches_;
   xk_trk_frame_out out_{};

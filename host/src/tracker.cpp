@@ -1,4 +1,5 @@
-// Mirror of Tracker::track, src/x/vision/tracker.cpp:134-306; the frame runs in libxk.so behind xk_trk_frame.
+// Mirror of Tracker::track, src/x/vision/tracker.cpp:134-306; the frame runs in libxk.so behind xk_trk_frame, and behind
+// xk_trk_photo_frame after setPhotometric.
 #include "x/vision/tracker.h"
 
 #include <algorithm>
@@ -46,6 +47,20 @@ void Tracker::setDescription(bool centroid_orientation, double angle_deg, int ed
   dirty_ = true;
 }
 
+void Tracker::setPhotometric(int kernel_size, double epsilon_gap, double epsilon_base, int n_hyp_photo, int fast_detection_delta_photo) {
+  photo_ = true; photo_kernel_ = kernel_size; eps_gap_ = epsilon_gap; eps_base_ = epsilon_base; photo_hyp_ = n_hyp_photo;
+  photo_threshold_ = fast_detection_delta_photo;
+  const size_t m = (size_t)max_features_;
+  prev_int_.resize(m); cur_int_.resize(m);
+  dirty_ = true;
+}
+
+void Tracker::setSpatialCalibration(int div, double thr, int max_rows) {
+  if (!photo_) throw std::runtime_error("Tracker::setSpatialCalibration: before setPhotometric");
+  spatial_ = true; spatial_div_ = div; spatial_thr_ = thr; spatial_rows_ = max_rows;
+  dirty_ = true;
+}
+
 void Tracker::reset() {
   img_id_ = 0;
   matches_.clear();
@@ -59,6 +74,15 @@ void Tracker::apply() {
     check(xk_, xk_trk_describe_setup(trk_, centroid_ ? 1 : 0, angle_deg_, edge_, own_pattern_ ? pattern_ : nullptr, max_features_),
           "xk_trk_describe_setup");
   check(xk_, xk_trk_frame_setup(trk_, n_feat_min_, (int)tiles_h_, (int)tiles_w_, (int)max_per_tile_, threshold_px_, n_hyp_), "xk_trk_frame_setup");
+  if (photo_) {                                               // a new photo setup: the ring starts over, as the tracker does
+    check(xk_, xk_trk_photo_setup(trk_, photo_kernel_, eps_gap_, eps_base_, photo_hyp_), "xk_trk_photo_setup");
+    if (spatial_)
+      check(xk_, xk_trk_photo_spatial_setup(trk_, spatial_div_, spatial_thr_, 500, spatial_rows_, 5.0, 0.01, 0.01), "xk_trk_photo_spatial_setup");
+    check(xk_, xk_trk_photo_frame_setup(trk_, photo_hyp_, photo_threshold_), "xk_trk_photo_frame_setup");
+    spatial_done_ = false;
+    spatial_outcome_ = xk_photo_spatial_outcome{};
+  }
+  calibration_ = Calibration{};
   dirty_ = false;
   img_id_ = 0;
 }
@@ -67,9 +91,31 @@ const MatchList &Tracker::track(const uint8_t *img, int stride, double /*timesta
   if (dirty_) apply();
   matches_.clear();
   origin_v_.clear();
-  const int rc = xk_trk_frame(trk_, img, stride, seed_++, &out_);
+  int rc;
+  if (photo_) {
+    pout_.prev_xy = out_.prev_xy; pout_.cur_xy = out_.cur_xy; pout_.prev_dist_xy = out_.prev_dist_xy; pout_.cur_dist_xy = out_.cur_dist_xy;
+    pout_.score = out_.score; pout_.origin = out_.origin; pout_.tiles = out_.tiles; pout_.desc = out_.desc;
+    pout_.prev_intensity = prev_int_.data(); pout_.cur_intensity = cur_int_.data();
+    rc = xk_trk_photo_frame(trk_, img, stride, seed_++, seed_photo_++, &pout_);
+    out_.n_tracked = pout_.n_tracked; out_.n_left = pout_.n_left; out_.redetected = pout_.redetected; out_.n_candidates = pout_.n_candidates;
+    out_.n_accepted = pout_.n_accepted; out_.n_new_tracked = pout_.n_new_tracked; out_.n_matches = pout_.n_matches; out_.winner = pout_.winner;
+    Calibration &c = calibration_;
+    c.estimated = pout_.estimated != 0; c.done = pout_.done != 0; c.kept = pout_.n_cal_kept; c.support = pout_.support;
+    c.a_rel = pout_.a_rel; c.b_rel = pout_.b_rel;
+    std::memcpy(c.frame_ab, pout_.frame_ab, sizeof c.frame_ab);
+  } else {
+    rc = xk_trk_frame(trk_, img, stride, seed_++, &out_);
+  }
   if (rc != XK_OK) img_id_ = 0;                               // (the device starts over too)
-  check(xk_, rc, "xk_trk_frame");
+  check(xk_, rc, photo_ ? "xk_trk_photo_frame" : "xk_trk_frame");
+  if (spatial_ && !spatial_done_ && calibration_.estimated) {  // irPhotoCalib.cpp:199-209, without the thread: as FeatureTracker::calibrate
+    int rows, covered, cells, ready = 0, dropped, state;
+    check(xk_, xk_trk_photo_spatial_status(trk_, &rows, &covered, &cells, &ready, &dropped, &state), "xk_trk_photo_spatial_status");
+    if (ready) {
+      check(xk_, xk_trk_photo_spatial_estimate(trk_, 1, &spatial_outcome_), "xk_trk_photo_spatial_estimate");
+      spatial_done_ = spatial_outcome_.converged != 0;
+    }
+  }
   img_id_++;                                                  // tracker.cpp:137
   const size_t n = (size_t)out_.n_matches;
   matches_.resize(n);
@@ -85,6 +131,7 @@ const MatchList &Tracker::track(const uint8_t *img, int stride, double /*timesta
       f->setPyramidLevel(0);
       if (described_) f->setDescriptor(desc_.data() + 32 * i);
     }
+    if (photo_) { m.previous.setIntensity(prev_int_[i]); m.current.setIntensity(cur_int_[i]); }   // tracker.cpp:461, :666
   }
   return matches_;
 }

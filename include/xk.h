@@ -606,8 +606,8 @@ int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurred, signed c
  * (sized by the host's bound: the resident count plus the detection's packing bound, at most max_matches), and one wait
  * besides the wait for the previous push's staging buffer.
  *
- * The PHOTOMETRIC frame (calibrateImage between the push and the tracking, tracker.cpp:186-190) is NOT built: xk_trk_frame
- * returns XK_EINVAL while a photometric setup is in place on this xk_trk.
+ * The PHOTOMETRIC frame (calibrateImage between the push and the tracking, tracker.cpp:186-190) is an entry of its own,
+ * xk_trk_photo_frame below: xk_trk_frame returns XK_EINVAL while a photometric setup is in place on this xk_trk.
  *
  * xk_trk_frame_setup: n_feat_min (tracker.cpp:204), the tile grid of TiledImage (n_tiles_h x n_tiles_w, at most 4096
  * tiles) and max_feat_per_tile (tracker.cpp:614), threshold_px and n_hyp of the outlier removal as in
@@ -650,7 +650,8 @@ typedef struct {
  * new features, appended behind the old pairs -- no second overflow pass; 5. Camera::undistort of both lists and the
  * seven-point RANSAC with n_hyp hypotheses and `seed`, fewer than 7 pairs keep nothing; 6. the kept current features
  * become the resident list.  The result is bit for bit what the stage entries return when chained through the host.
- * XK_EINVAL: null arguments, stride below the width, no frame setup, a photometric setup in place.
+ * XK_EINVAL: null arguments, stride below the width, no frame setup, a photometric setup in place (xk_trk_photo_frame is
+ * the frame of that build).
  * XK_ECAPACITY, decided on the device and reported at the frame's wait: more candidates than max_candidates, more
  * features accepted than max_matches, more keypoints than max_desc, old plus new pairs beyond max_matches; the counts
  * reached are returned, n_matches = 0, and the next frame is a first frame.  The stage entries and their inspection
@@ -662,8 +663,59 @@ int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long 
  * NULL; *n features (0 before a first frame).  An inspection path: straight copies, one synchronisation. */
 int xk_trk_frame_features(xk_trk *t, double *dist_xy, int *score, unsigned char *desc, int *n);
 
-/* The next xk_trk_frame is a first frame; the pushed images stay.  XK_EINVAL without a frame setup. */
+/* The next xk_trk_frame (or xk_trk_photo_frame) is a first frame; the pushed images stay.  XK_EINVAL without a frame setup. */
 int xk_trk_frame_reset(xk_trk *t);
+
+/* ---- Tracker::track in one call, a PHOTOMETRIC_CALI build (calibrateImage at tracker.cpp:186-190) -----------------------
+ * xk_trk_photo_frame is xk_trk_frame of a build that calibrates every image: the resident list also holds each feature's
+ * intensity (Feature::getIntensity), the calibration is fed from it with nothing uploaded, and the frame still has one
+ * image copied in, one result block out and one wait.  xk_trk_frame_reset and xk_trk_frame_features serve
+ * both frames.  It tracks with the one Lucas-Kanade parameter set of xk_trk_klt_setup (the reference's second set,
+ * tracker.cpp:641-645, is out of scope), and leaves refinePhotometricParams to the caller (xk_trk_photo_gains).
+ *
+ * xk_trk_photo_frame_setup, after xk_trk_frame_setup AND xk_trk_photo_setup: n_hyp_photo in 1 ... max_hyp of the photo
+ * setup caps the gain RANSAC -- a frame with R resident features evaluates max(1, min(R, n_hyp_photo)) hypotheses;
+ * threshold_photo is fast_detection_delta_photo_ (tracker.cpp:848), 1 ... 254: the FAST threshold of every detection
+ * once a frame has estimated gains (XkPhotoState's done flag, read on the device: the frame of the first estimate
+ * already re-detects with it); < 0: no switch.  It allocates the intensities and the larger result block.
+ * XK_EINVAL: before either setup, a parameter out of range.  A failed call leaves an earlier setup as it was.  Whatever
+ * drops the frame setup drops it, and so does a later xk_trk_photo_setup. */
+int xk_trk_photo_frame_setup(xk_trk *t, int n_hyp_photo, int threshold_photo);
+
+/* What a photometric frame returns: the fields of xk_trk_frame_out, the getIntensity() of both features of each match
+ * (HOST, max_matches rows each, n_matches written), and the outcome of the frame's calibration with the meaning of the
+ * outputs of xk_trk_photo_calibrate: n_cal_kept points its tracking between the raw images kept; estimated, and then
+ * a_rel, b_rel, support, frame_ab (otherwise 1, 0, 0 and zeros); done: a frame so far has estimated. */
+typedef struct {
+  int n_tracked, n_left, redetected, n_candidates, n_accepted, n_new_tracked, n_matches, winner;
+  double *prev_xy, *cur_xy, *prev_dist_xy, *cur_dist_xy;
+  int *score, *origin, *tiles;
+  unsigned char *desc;
+  double *prev_intensity, *cur_intensity;
+  int n_cal_kept, estimated, done, support;
+  double a_rel, b_rel, frame_ab[4];
+} xk_trk_photo_frame_out;
+
+/* One image of Tracker::track with PHOTOMETRIC_CALI.
+ * First frame: the push (the raw plane, the working plane as its copy), featureDetection on the working plane, the
+ * intensity of every accepted feature there at its integer pixel (tracker.cpp:461), the description; no calibration
+ * (tracker.cpp:160-168).
+ * Every later frame: 1. the push; 2. calibrateImage as xk_trk_photo_calibrate runs it, from the resident points and
+ * intensities, with seed_photo: with fewer than 4 resident features only the correction, which corrects iff an earlier
+ * frame estimated; the rows of a spatial setup that is still accumulating; 3. featureTracking of the resident list on
+ * the WORKING planes; 4. the intensity of the kept current features on the RAW current plane at the truncated pixel
+ * (tracker.cpp:666); 5. removeOverflowFeatures; 6. the re-detection on the previous working plane with the threshold
+ * selected on the device, the new features' intensities there, their description, tracking, and intensities in the raw
+ * current plane; 7. undistortion and the fundamental RANSAC with `seed`; 8. the kept current features and their
+ * intensities become the resident list.  Bit for bit what the stage entries return when chained through the host.
+ * Errors as xk_trk_frame, and XK_EINVAL without the photometric frame setup.  After XK_ECAPACITY the counts and the
+ * calibration's outcome are returned (the ring has advanced), and the next frame is a first frame. */
+int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, unsigned long seed_photo,
+                       xk_trk_photo_frame_out *out);
+
+/* The resident intensities beside xk_trk_frame_features: intensity HOST [max_matches] (may be NULL), *n features.
+ * An inspection path: a straight copy, one synchronisation. */
+int xk_trk_photo_frame_intensities(xk_trk *t, double *intensity, int *n);
 
 /* ---- photometric calibration of the images (Tracker::calibrateImage, tracker.cpp:761-877; irPhotoCalib.cpp) ---------
  * A PHOTOMETRIC_CALI build passes every frame after the first through calibrateImage (tracker.cpp:186-190) before it is

@@ -56,6 +56,8 @@ struct XkFastArgs {
   int *res;                                  // n_found, n_candidates, 0, 0 | xy [max_matches][2] | score [max_matches]
   const int *n_old_dev;                      // NULL: n_old old features.  Else n_old is their bound, *n_old_dev the count (xk_dev_count)
   const int *pred;                           // NULL: run.  Else the three kernels return at once where *pred is 0 (the frame's re-detection)
+  const int *alt_on;                         // NULL: `threshold`, by value.  Else alt_threshold where *alt_on is not 0 (the photometric frame:
+  int alt_threshold;                         //   fast_detection_delta_photo_ once the calibration is done, tracker.cpp:848)
 };
 
 // any nine contiguous bits set in the 16-bit ring m
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(256) void xk_fast_score(XkFastArgs a) {
   const int cdx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
   const int cdy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
   const int lx = threadIdx.x & 63, x = tx0 + lx;
-  const int t = a.threshold;
+  const int t = (a.alt_on && *a.alt_on != 0) ? a.alt_threshold : a.threshold;
 #pragma unroll
   for (int q = 0; q < XK_FAST_TH / 4; ++q) {
     const int ly = (threadIdx.x >> 6) + 4 * q, y = ty0 + ly;

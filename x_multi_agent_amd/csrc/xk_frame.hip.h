@@ -18,6 +18,11 @@
 //   xk_frame_pack       the kept pairs of the RANSAC into the result block, and the kept current features into the resident list
 //                       (tracker.cpp:299)
 //   xk_frame_first      the first frame: the detected features become the resident list
+//   xk_frame_trunc      (photometric frame) the kept current points of a tracking truncated to the integer pixels
+//                       Tracker::computeIntensity is asked at (tracker.cpp:666), for xk_photo_intensity behind it
+// The photometric frame (xk_trk_photo_frame, Tracker::track of a PHOTOMETRIC_CALI build) runs the same kernels with the optional
+// pointers of XkFrameArgs set: every pair then carries the intensity of its previous and of its current feature, the resident
+// list the intensity of each feature, and the head of the result block the outcome of the frame's calibration.
 // No kernel waits on another: every count and flag is a plain load of what an earlier launch on the same stream wrote.  Integer
 // atomics on LDS only; no inline assembly.
 #pragma once
@@ -25,6 +30,7 @@
 #include <math.h>
 
 #include "xk_orb.hip.h"
+#include "xk_photo.hip.h"
 #include "xk_ransac.hip.h"
 
 // the frame's counts in device memory, and the head of the result block in the same order
@@ -40,6 +46,12 @@ enum {
   XK_FC_WINNER,          // its winning hypothesis, -1: none
   XK_FC_STATUS,          // 0, or an XK_FRAME_E* below
   XK_FC_NEW,             // what the description and the second tracking run on: ACCEPTED, 0 after an error or without a re-detection
+  // the photometric frame only, head of the result block only (zero otherwise): the outcome of the frame's calibration
+  XK_FC_CAL_KEPT,        // points its tracking between the raw images kept
+  XK_FC_ESTIMATED,       // 1: it estimated gains and the ring advanced
+  XK_FC_DONE,            // XkPhotoState::done after it
+  XK_FC_SUPPORT,         // inliers of the refit
+  XK_FC_RING_N,          // the ring's size after it
   XK_FC_N = 16
 };
 #define XK_FRAME_ECAND 1       // more candidates than max_candidates
@@ -74,6 +86,14 @@ struct XkFrameArgs {
   const int *orb_res;            // the description's (XkOrbArgs::res), laid out by cap_new
   float *pts_new;                // [cap_new][2]
   unsigned char *out;            // the result block, xk_frame_out_*
+  // The photometric frame; res_int NULL: none of these is read.  fp64 box means as xk_photo_intensity leaves them.
+  double *res_int;               // [max_matches] of the resident list
+  double *l_iprev, *l_icur;      // [B] of the pair lists: the previous and the current feature's
+  const double *val1;            // [n_res] of the tracked current features, by kept1's position
+  const double *val_new;         // [cap_new] of the features the detection accepted, by its position
+  const double *val2;            // [cap_new] of the newly tracked current features, by kept2's position
+  const XkPhotoState *photo_st;  // the calibration's state
+  const int *cal_kept;           // the kept count of the calibration's tracking; NULL: the frame ran none (fewer than 4 resident features)
 };
 
 // The result block for bound B: head [XK_FC_N] ints | undistorted previous, current, distorted previous, current [B][2] fp64 each |
@@ -84,6 +104,21 @@ inline __host__ __device__ size_t xk_frame_out_origin(size_t B) { return xk_fram
 inline __host__ __device__ size_t xk_frame_out_tiles(size_t B) { return xk_frame_out_origin(B) + sizeof(int) * B; }
 inline __host__ __device__ size_t xk_frame_out_desc(size_t B) { return xk_frame_out_tiles(B) + sizeof(int) * 4 * B; }   // (a multiple of 8)
 inline __host__ __device__ size_t xk_frame_out_bytes(size_t B, bool desc) { return xk_frame_out_desc(B) + (desc ? 32 * B : 0); }
+// The photometric frame's block: the same, then previous intensities [B] | current intensities [B] | a_rel, b_rel, frame_ab [4], fp64.
+inline __host__ __device__ size_t xk_frame_out_int(size_t B, bool desc, int which) { return xk_frame_out_bytes(B, desc) + sizeof(double) * B * (size_t)which; }
+inline __host__ __device__ size_t xk_frame_out_cal(size_t B, bool desc) { return xk_frame_out_int(B, desc, 2); }
+inline __host__ __device__ size_t xk_frame_photo_out_bytes(size_t B, bool desc) { return xk_frame_out_cal(B, desc) + sizeof(double) * 6; }
+
+// The calibration's outcome into the head of the photometric frame's result block (thread 0 of the packing kernel, after the counts).
+__device__ __forceinline__ void xk_frame_cal_head(const XkFrameArgs &a, int *head) {
+  const XkPhotoState *st = a.photo_st;
+  const int est = a.cal_kept ? st->estimated : 0;                 // (without a calibration the flag is an earlier frame's)
+  head[XK_FC_CAL_KEPT] = a.cal_kept ? a.cal_kept[0] : 0;
+  head[XK_FC_ESTIMATED] = est;
+  head[XK_FC_DONE] = st->done;
+  head[XK_FC_SUPPORT] = est ? st->support[0] : 0;
+  head[XK_FC_RING_N] = st->ring_n;
+}
 
 // TiledImage::setTileForFeature (tiled_image.cpp:139-158): the loops as written, each bounded by its tile count (a feature inside the
 // image leaves them earlier).
@@ -138,6 +173,7 @@ __global__ __launch_bounds__(256) void xk_frame_overflow(XkFrameArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) a.l_tiles[4 * pos + j] = a.tmp_tiles[4 * i + j];
         if (a.l_desc) xk_frame_copy_desc(a.l_desc + 32 * (size_t)pos, a.res_desc + 32 * (size_t)k);
+        if (a.res_int) { a.l_iprev[pos] = a.res_int[k]; a.l_icur[pos] = a.val1[i]; }   // getIntensity of both features, tracker.cpp:666
       });
   if (threadIdx.x == 0) {
     for (int j = 0; j < XK_FC_N; ++j) a.c[j] = 0;
@@ -191,6 +227,7 @@ __global__ __launch_bounds__(256) void xk_frame_concat(XkFrameArgs a) {
       xk_frame_tile(a, x, y, &row, &col);                         // tracker.cpp:578; the tracked feature is a new Feature: no tile yet
       a.l_tiles[4 * pos] = row; a.l_tiles[4 * pos + 1] = col; a.l_tiles[4 * pos + 2] = -1; a.l_tiles[4 * pos + 3] = -1;
       if (a.l_desc) xk_frame_copy_desc(a.l_desc + 32 * (size_t)pos, orb_desc + 32 * (size_t)k);   // (every accepted feature is described: margin >= edge)
+      if (a.res_int) { a.l_iprev[pos] = a.val_new[k]; a.l_icur[pos] = a.val2[j]; }                // tracker.cpp:461, :666
     }
   }
   if (threadIdx.x == 0) { a.c[XK_FC_NEW_TRACKED] = n3; a.c[XK_FC_TOTAL] = total; a.c[XK_FC_STATUS] = status; }
@@ -206,6 +243,14 @@ __global__ __launch_bounds__(256) void xk_frame_pack(XkFrameArgs a) {
     for (int j = 0; j < XK_FC_N; ++j) head[j] = a.c[j];
     head[XK_FC_MATCHES] = m;
     head[XK_FC_WINNER] = status == 0 ? a.kept3.res[1] : -1;
+    if (a.res_int) {
+      xk_frame_cal_head(a, head);
+      double *cal = reinterpret_cast<double *>(a.out + xk_frame_out_cal(B, a.l_desc != nullptr));
+      const bool est = head[XK_FC_ESTIMATED] != 0;
+      cal[0] = est ? a.photo_st->a_rel[0] : 1.0; cal[1] = est ? a.photo_st->b_rel[0] : 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cal[2 + j] = est ? a.photo_st->frame_ab[j] : 0.0;
+    }
   }
   if (pos >= m) return;
   const int i = a.kept3.keep_idx[pos];
@@ -230,6 +275,12 @@ __global__ __launch_bounds__(256) void xk_frame_pack(XkFrameArgs a) {
     xk_frame_copy_desc(a.out + xk_frame_out_desc(B) + 32 * (size_t)pos, a.l_desc + 32 * (size_t)i);
     xk_frame_copy_desc(a.res_desc + 32 * (size_t)pos, a.l_desc + 32 * (size_t)i);
   }
+  if (a.res_int) {
+    const double ic = a.l_icur[i];
+    reinterpret_cast<double *>(a.out + xk_frame_out_int(B, a.l_desc != nullptr, 0))[pos] = a.l_iprev[i];
+    reinterpret_cast<double *>(a.out + xk_frame_out_int(B, a.l_desc != nullptr, 1))[pos] = ic;
+    a.res_int[pos] = ic;
+  }
 }
 
 __global__ __launch_bounds__(256) void xk_frame_first(XkFrameArgs a) {
@@ -238,6 +289,7 @@ __global__ __launch_bounds__(256) void xk_frame_first(XkFrameArgs a) {
   if (pos == 0) {
     int *head = reinterpret_cast<int *>(a.out);
     for (int j = 0; j < XK_FC_N; ++j) head[j] = a.c[j];
+    if (a.res_int) xk_frame_cal_head(a, head);
   }
   if (pos >= n) return;
   const int *det_xy = a.det_res + 4, *det_score = a.det_res + 4 + 2 * (size_t)a.max_matches;
@@ -248,4 +300,20 @@ __global__ __launch_bounds__(256) void xk_frame_first(XkFrameArgs a) {
   if (a.res_desc)
     xk_frame_copy_desc(a.res_desc + 32 * (size_t)pos,
                        reinterpret_cast<const unsigned char *>(a.orb_res) + xk_orb_desc_off((size_t)a.cap_new) + 32 * (size_t)pos);
+  if (a.res_int) a.res_int[pos] = a.val_new[pos];                 // tracker.cpp:461
+}
+
+// static_cast<int> of the kept current points of a tracking (tracker.cpp:666; they lie within [-0.5, W - 0.5] x [-0.5, H - 0.5])
+struct XkFrameTruncArgs {
+  const double *xy;              // [n][2]
+  const int *n_dev;              // where the device holds the count (xk_dev_count)
+  int n;                         // its bound
+  int *ixy;                      // [n][2]
+};
+
+__global__ __launch_bounds__(256) void xk_frame_trunc(XkFrameTruncArgs a) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= xk_dev_count(a.n_dev, a.n)) return;
+  const double x = a.xy[2 * j], y = a.xy[2 * j + 1];
+  a.ixy[2 * j] = (int)x; a.ixy[2 * j + 1] = (int)y;
 }

@@ -3,7 +3,8 @@
 // (tracker.cpp:623-690; xk_klt.hip.h), the FAST detection that produces the features (tracker.cpp:390-590; xk_fast.hip.h) and their
 // rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h), and the photometric calibration of the images in front of
 // all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).  Behind them, the normalisation and baseline check of the
-// track manager's candidate tracks (track_manager.cpp:576-636, camera.cpp; xk_tracks.hip.h).
+// track manager's candidate tracks (track_manager.cpp:576-636, camera.cpp; xk_tracks.hip.h).  At the end, Tracker::track itself in
+// one call on a resident feature list (tracker.cpp:134-306; xk_frame.hip.h): xk_trk_frame, and xk_trk_photo_frame with calibrateImage.
 // Every stage keeps its buffers in one xk_block (a device block and its pinned mirror, carved once by the stage's setup, which stores
 // every pointer an entry needs) and reaches them through the same helpers: sub_of (the stage's setup or XK_EINVAL), img_slot (the
 // slot of the previous or the current image or XK_EINVAL), launched (the check behind a group of launches), kept_count_out, setup_install.
@@ -174,6 +175,18 @@ struct xk_frm {
   unsigned char *klt_res[2];  // result blocks of the two trackings (klt_res_bytes(max_matches) each)
   unsigned char *fund_res;    // of the outlier removal (trk_res_bytes(max_matches))
   int *orb_res;               // of the description (xk_orb_res_bytes(cap_new)); NULL without one
+  struct xk_pfrm *pf;         // xk_trk_photo_frame_setup; NULL before.  It goes with this setup, and with the photo setup it was made over
+};
+
+// The photometric frame setup (xk_trk_photo_frame_setup): what Tracker::track of a PHOTOMETRIC_CALI build needs beyond xk_frm.
+struct xk_pfrm {
+  int n_hyp, threshold;       // the cap of the gain RANSAC; fast_detection_delta_photo_, < 0: no switch
+  const struct xk_photo *photo;   // the setup it was made over
+  xk_block blk;                 // device: resident and pair intensities | the three intensity lists | truncated pixels | sums, counts |
+                                //   the frame's result block.  Pinned: the latter
+  double *res_int, *l_iprev, *l_icur, *val1, *val_new, *val2;
+  int *ixy1, *ixy2, *sum, *count;
+  unsigned char *out;
 };
 
 // The baseline setup (xk_trk_baseline_setup): capacities of one batch of tracks.  It belongs to the xk_trk, not to an image size.
@@ -234,6 +247,13 @@ static void setup_free(xk_psp *s) {
   if (s->batch) hipEventDestroy(s->batch);
   blk_free(s->blk);
   free(s);
+}
+
+static void setup_free(xk_frm *f) {
+  if (!f) return;
+  setup_free(f->pf);
+  blk_free(f->blk);
+  free(f);
 }
 
 static void setup_free(xk_photo *p) {
@@ -944,7 +964,12 @@ extern "C" int xk_trk_photo_setup(xk_trk *t, int kernel_size, double epsilon_gap
     p->off = carve<int>(io, off, 64); p->frame_back = carve<int>(io, off, 64);
     if (!ok || photo_state_reset(h, p) != XK_OK) rc = fail(h, XK_ENOMEM, "xk_trk_photo_setup: allocation failed");
   }
-  return setup_install(h, rc, "xk_trk_photo_setup", k->photo, p);
+  XKCHK(setup_install(h, rc, "xk_trk_photo_setup", k->photo, p));
+  if (k->frm) {                                                    // (the photometric frame setup was made over the old photo setup)
+    setup_free(k->frm->pf);
+    k->frm->pf = nullptr;
+  }
+  return XK_OK;
 }
 
 // the pinned mirror of a device pointer into the i/o block
@@ -1716,7 +1741,9 @@ extern "C" int xk_trk_frame_features(xk_trk *t, double *dist_xy, int *score, uns
 }
 
 // The detection of a frame on slot s, queued: no old features (n_old_bound = 0) or the device's list of at most n_old_bound; pred as XkFastArgs::pred.
-static int frame_queue_detect(xk_trk *t, const xk_frm *f, int s, const int *pred, const double *old_xy, int n_old_bound, const int *n_old_dev) {
+// The photometric frame (f->pf in use) selects the threshold on the device: fast_detection_delta_photo_ once the calibration is done.
+static int frame_queue_detect(xk_trk *t, const xk_frm *f, int s, const int *pred, const double *old_xy, int n_old_bound, const int *n_old_dev,
+                              bool photo = false) {
   xk_handle *h = t->h;
   xk_det *d = t->klt->det;
   const XkKltLevel &L = t->klt->slot[s].lv[0];
@@ -1727,6 +1754,7 @@ static int frame_queue_detect(xk_trk *t, const xk_frm *f, int s, const int *pred
   a.threshold = d->threshold; a.nms = d->nms; a.b = d->b; a.margin = d->margin; a.max_candidates = d->max_candidates;
   a.max_matches = t->max_matches;
   a.res = f->a.det_res;
+  if (photo && f->pf->threshold >= 0) { a.alt_on = &t->klt->photo->st->done; a.alt_threshold = f->pf->threshold; }
   d->n_cand = -1;                                                   // (the score image and the keys are no longer those of the last xk_trk_detect)
   hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
@@ -1772,7 +1800,7 @@ extern "C" int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, uns
   xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame", "xk_trk_frame_setup");
   if (!f) return XK_EINVAL;
   xk_klt *k = t->klt;
-  if (k->photo) return fail(h, XK_EINVAL, "xk_trk_frame: a photometric setup is in place (the photometric frame is not built)");
+  if (k->photo) return fail(h, XK_EINVAL, "xk_trk_frame: a photometric setup is in place (the photometric frame is xk_trk_photo_frame)");
   if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_frame: null image or stride below the width");
   if (!out || !out->prev_xy || !out->cur_xy || !out->prev_dist_xy || !out->cur_dist_xy || !out->score || !out->origin || !out->tiles ||
       (f->orb && !out->desc))
@@ -1860,6 +1888,239 @@ extern "C" int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, uns
   memcpy(out->origin, r + xk_frame_out_origin(B), sizeof(int) * (size_t)m);
   memcpy(out->tiles, r + xk_frame_out_tiles(B), sizeof(int) * 4 * (size_t)m);
   if (f->orb) memcpy(out->desc, r + xk_frame_out_desc(B), 32 * (size_t)m);
+  f->n_res = m;
+  return XK_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One frame of Tracker::track of a PHOTOMETRIC_CALI build (calibrateImage between the push and the tracking, tracker.cpp:186-190),
+// xk_frame.hip.h with the intensities, xk_photo.hip.h fed from the resident list
+// ---------------------------------------------------------------------------
+/* n_hyp_photo caps the gain RANSAC of a frame; threshold_photo is fast_detection_delta_photo_ (tracker.cpp:848), < 0: no switch */
+extern "C" int xk_trk_photo_frame_setup(xk_trk *t, int n_hyp_photo, int threshold_photo) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_photo_frame_setup", "xk_trk_frame_setup");
+  if (!f) return XK_EINVAL;
+  xk_photo *p = sub_of(t, &xk_klt::photo, "xk_trk_photo_frame_setup", "xk_trk_photo_setup");
+  if (!p) return XK_EINVAL;
+  if (n_hyp_photo < 1 || n_hyp_photo > p->max_hyp) return fail(h, XK_EINVAL, "xk_trk_photo_frame_setup: n_hyp_photo outside 1...max_hyp");
+  if (threshold_photo == 0 || threshold_photo > 254) return fail(h, XK_EINVAL, "xk_trk_photo_frame_setup: threshold_photo outside 1...254 (< 0: no switch)");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_pfrm *pf = (xk_pfrm *)calloc(1, sizeof(xk_pfrm));
+  if (!pf) return XK_ENOMEM;
+  pf->n_hyp = n_hyp_photo; pf->threshold = threshold_photo < 0 ? -1 : threshold_photo; pf->photo = p;
+  const size_t M = (size_t)round_up(t->max_matches, 4), N = (size_t)round_up(f->cap_new, 4);
+  const size_t out_bytes = up16(xk_frame_photo_out_bytes((size_t)t->max_matches, f->orb != nullptr));
+  const size_t d_bytes = 4 * 8 * M + 2 * 8 * N + 8 * M + 8 * N + 2 * 4 * M + out_bytes;
+  const int rc = blk_alloc(h, pf->blk, d_bytes, out_bytes, "xk_trk_photo_frame_setup");
+  if (rc == XK_OK) {
+    unsigned char *b = pf->blk.d;
+    size_t off = 0;
+    pf->res_int = carve<double>(b, off, 8 * M); pf->l_iprev = carve<double>(b, off, 8 * M); pf->l_icur = carve<double>(b, off, 8 * M);
+    pf->val1 = carve<double>(b, off, 8 * M); pf->val_new = carve<double>(b, off, 8 * N); pf->val2 = carve<double>(b, off, 8 * N);
+    pf->ixy1 = carve<int>(b, off, 8 * M); pf->ixy2 = carve<int>(b, off, 8 * N);
+    pf->sum = carve<int>(b, off, 4 * M); pf->count = carve<int>(b, off, 4 * M);
+    pf->out = carve<unsigned char>(b, off, out_bytes);
+  }
+  return setup_install(h, rc, "xk_trk_photo_frame_setup", f->pf, pf);
+}
+
+// The frame setup with its photometric part, both made over the setups still in place; or nullptr after fail(XK_EINVAL).
+static xk_frm *photo_frame_of(xk_trk *t, const char *who) {
+  xk_frm *f = sub_of(t, &xk_klt::frm, who, "xk_trk_frame_setup");
+  if (!f) return nullptr;
+  if (!f->pf || !t->klt->photo || f->pf->photo != t->klt->photo) {
+    fail_at(t->h, XK_EINVAL, who, "before xk_trk_photo_frame_setup");
+    return nullptr;
+  }
+  return f;
+}
+
+/* The resident intensities as the device holds them.  A straight copy */
+extern "C" int xk_trk_photo_frame_intensities(xk_trk *t, double *intensity, int *n) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_frm *f = photo_frame_of(t, "xk_trk_photo_frame_intensities");
+  if (!f) return XK_EINVAL;
+  if (!n) return fail(h, XK_EINVAL, "xk_trk_photo_frame_intensities: null count");
+  const size_t r = (size_t)std::max(f->n_res, 0);
+  *n = (int)r;
+  if (r == 0 || !intensity) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(intensity, f->pf->res_int, sizeof(double) * r, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// Tracker::computeIntensity of the points at xy (their count on the device, at most n_bound) on level 0 of plane P, queued: values to `value`.
+static void photo_frame_queue_intensity(xk_handle *h, const xk_photo *p, const xk_pfrm *pf, const XkKltPyr &P, const int *xy, const int *n_dev,
+                                        int n_bound, double *value) {
+  XkPhotoIntArgs a = photo_int_args(p, P.lv[0], n_bound);
+  a.xy = xy; a.n_dev = n_dev; a.value = value; a.sum = pf->sum; a.count = pf->count;
+  hipLaunchKernelGGL(xk_photo_intensity, dim3((n_bound + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, a);
+}
+
+// The kept current points of a tracking truncated to pixels, and their intensities on level 0 of plane P, queued.
+static void photo_frame_queue_kept_intensity(xk_handle *h, const xk_photo *p, const xk_pfrm *pf, const XkKltPyr &P, const XkKeptPairs &kept,
+                                             int n_bound, int *ixy, double *value) {
+  XkFrameTruncArgs ta{};
+  ta.xy = kept.kept_cur; ta.n_dev = kept.res; ta.n = n_bound; ta.ixy = ixy;
+  hipLaunchKernelGGL(xk_frame_trunc, dim3((n_bound + 255) / 256), dim3(256), 0, h->stream, ta);
+  photo_frame_queue_intensity(h, p, pf, P, ixy, kept.res, n_bound, value);
+}
+
+/* Tracker::track (tracker.cpp:134-306), a build with PHOTOMETRIC_CALI, pyramid level 0: everything queued on the handle's stream, one wait */
+extern "C" int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, unsigned long seed_photo,
+                                  xk_trk_photo_frame_out *out) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  xk_frm *f = photo_frame_of(t, "xk_trk_photo_frame");
+  if (!f) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  xk_photo *p = k->photo;
+  xk_pfrm *pf = f->pf;
+  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_photo_frame: null image or stride below the width");
+  if (!out || !out->prev_xy || !out->cur_xy || !out->prev_dist_xy || !out->cur_dist_xy || !out->score || !out->origin || !out->tiles ||
+      !out->prev_intensity || !out->cur_intensity || (f->orb && !out->desc))
+    return fail(h, XK_EINVAL, "xk_trk_photo_frame: null output");
+  out->n_tracked = out->n_left = out->redetected = out->n_candidates = out->n_accepted = out->n_new_tracked = out->n_matches = 0;
+  out->winner = -1;
+  out->n_cal_kept = out->estimated = out->support = 0;
+  out->done = p->done;
+  out->a_rel = 1.0; out->b_rel = 0.0;
+  memset(out->frame_ab, 0, sizeof out->frame_ab);
+  HIPCHK(h, hipSetDevice(h->device));
+  const bool first = f->n_res < 0;
+  const int M = t->max_matches, R = first ? 0 : f->n_res;
+  const bool cal = R >= 4;                                          // tracker.cpp:763
+  const int n_hyp_photo = std::max(1, std::min(R, pf->n_hyp));
+  f->n_res = -1;                                                    // (whatever fails below: the next frame is a first frame)
+  XKCHK(trk_push(t, img, stride));
+  const int sc = k->cur, sp = k->cur ^ 1;
+  XkFrameArgs a = f->a;
+  a.first = first ? 1 : 0;
+  a.n_res = R;
+  a.B = first ? 1 : std::min(M, R + f->cap_det);
+  const size_t B = (size_t)a.B;
+  a.l_prev = t->dist; a.l_cur = t->dist + 2 * B;
+  a.out = pf->out;
+  a.res_int = pf->res_int; a.l_iprev = pf->l_iprev; a.l_icur = pf->l_icur;
+  a.val1 = pf->val1; a.val_new = pf->val_new; a.val2 = pf->val2;
+  a.photo_st = p->st;
+  int *c = a.c;
+  const int *head = (const int *)pf->blk.h;
+  const bool desc = f->orb != nullptr;
+  if (first) {
+    XKCHK(frame_queue_detect(t, f, sc, nullptr, nullptr, 0, nullptr, true));
+    hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
+    photo_frame_queue_intensity(h, p, pf, k->slot[sc], a.det_res + 4, c + XK_FC_NEW, f->cap_new, pf->val_new);   // the WORKING plane, tracker.cpp:461
+    if (f->orb) XKCHK(frame_queue_describe(t, f, sc, nullptr));
+    hipLaunchKernelGGL(xk_frame_first, dim3((f->cap_new + 255) / 256), dim3(256), 0, h->stream, a);
+    XKCHK(launched(h, "first photometric frame launch"));
+    HIPCHK(h, hipMemcpyAsync(pf->blk.h, a.out, sizeof(int) * XK_FC_N, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  } else {
+    XkKltArgs ka;
+    // 2. calibrateImage, as xk_trk_photo_calibrate queues it, from the resident points and intensities
+    memset(p->n_hyp, 0, sizeof p->n_hyp);
+    if (cal) {
+      XKCHK(klt_queue_track(h, k, p->raw[sp], p->raw[sc], a.res_pts, p->klt_res, R, ka));
+      a.cal_kept = ka.kept.res;
+      XkPhotoGatherArgs ga{};
+      ga.kept = ka.kept; ga.prev_intensity = pf->res_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
+      hipLaunchKernelGGL(xk_photo_gather, dim3((R + 255) / 256), dim3(256), 0, h->stream, ga);
+      XkPhotoIntArgs ia = photo_int_args(p, p->raw[sc].lv[0], R);
+      ia.n_dev = ka.kept.res;
+      hipLaunchKernelGGL(xk_photo_intensity, dim3((R + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, ia);
+      XKCHK(launched(h, "frame calibration launch"));
+      XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp_photo, seed_photo, 1);
+      XKCHK(photo_queue_gains(h, p, g));
+      if (p->sp && p->sp->state != XK_PSP_ESTIMATED) {
+        XkPspAccArgs sa = psp_acc_args(p, p->sp, 1);
+        sa.prev_f = a.res_pts; sa.keep_idx = ka.kept.keep_idx; sa.pix_cur = p->ixy; sa.o_hist = p->o_hist; sa.o_cur = p->value;
+        sa.off = p->off; sa.frame_back = p->frame_back; sa.per_frame = 1;
+        hipLaunchKernelGGL(xk_photo_sp_accumulate, dim3(1), dim3(64), 0, h->stream, sa);
+      }
+    }
+    XKCHK(photo_queue_correct(h, k, sc, 1));                        // (fewer than 4 features: corrected iff an earlier frame estimated)
+    const XkKltPyr &prev = k->slot[sp], &cur = k->slot[sc];
+    a.kept1 = klt_kept_at(f->klt_res[0], R);
+    a.kept2 = klt_kept_at(f->klt_res[1], f->cap_new);
+    XkFundArgs fa{};
+    fa.dist = t->dist; fa.und = t->und; fa.pts = t->pts; fa.sc = t->sc;
+    fa.F = (double *)f->fund_res;
+    fa.kept = xk_kept_pairs(fa.F + 9, B);
+    fa.mask = xk_kept_pairs_end(fa.kept, B);
+    fa.n = a.B; fa.n_pts = 2 * a.B; fa.n_dev = c + XK_FC_TOTAL;
+    fa.fx = t->fx; fa.fy = t->fy; fa.cx = t->cx; fa.cy = t->cy; fa.s = t->s; fa.s_term = t->s_term;
+    fa.n_hyp = f->n_hyp; fa.t2 = f->threshold_px * f->threshold_px; fa.seed = (unsigned long long)seed;
+    a.kept3 = fa.kept;
+    t->n_hyp = 0;
+    // 3. featureTracking of the resident list on the WORKING planes; 4. the kept current features' intensities on the RAW current plane
+    if (R > 0) {
+      XKCHK(klt_queue_track(h, k, prev, cur, a.res_pts, f->klt_res[0], R, ka));
+      photo_frame_queue_kept_intensity(h, p, pf, p->raw[sc], a.kept1, R, pf->ixy1, pf->val1);
+    }
+    // 5. the overflow pass: both intensities move with their pair
+    hipLaunchKernelGGL(xk_frame_overflow, dim3(1), dim3(256), sizeof(int) * (size_t)f->tiles_h * f->tiles_w, h->stream, a);
+    // 6. the re-detection on the PREVIOUS working plane, predicated, its threshold selected on the device
+    if (f->n_feat_min > 0) {
+      XKCHK(frame_queue_detect(t, f, sp, c + XK_FC_REDETECT, a.l_prev, R, c + XK_FC_LEFT, true));
+      hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
+      photo_frame_queue_intensity(h, p, pf, prev, a.det_res + 4, c + XK_FC_NEW, f->cap_new, pf->val_new);
+      if (f->orb) XKCHK(frame_queue_describe(t, f, sp, c + XK_FC_REDETECT));
+      XKCHK(klt_queue_track(h, k, prev, cur, a.pts_new, f->klt_res[1], f->cap_new, ka, c + XK_FC_NEW));
+      photo_frame_queue_kept_intensity(h, p, pf, p->raw[sc], a.kept2, f->cap_new, pf->ixy2, pf->val2);
+    }
+    hipLaunchKernelGGL(xk_frame_concat, dim3(1), dim3(256), 0, h->stream, a);
+    // 7. the outlier removal
+    hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.B + 255) / 256), dim3(256), 0, h->stream, fa);
+    hipLaunchKernelGGL(xk_fund_solve, dim3((fa.n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, fa);
+    hipLaunchKernelGGL(xk_fund_score, dim3(fa.n_hyp), dim3(256), 0, h->stream, fa);
+    hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, fa);
+    // 8. the result block with the calibration's outcome in its head, and the new resident list
+    hipLaunchKernelGGL(xk_frame_pack, dim3((a.B + 255) / 256), dim3(256), 0, h->stream, a);
+    XKCHK(launched(h, "photometric frame launch"));
+    HIPCHK(h, hipMemcpyAsync(pf->blk.h, a.out, xk_frame_photo_out_bytes(B, desc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                     // the frame's one wait
+  }
+  const int status = head[XK_FC_STATUS], m = head[XK_FC_MATCHES];
+  for (int j = 0; j <= XK_FC_TOTAL; ++j)
+    if (head[j] < 0 || (j != XK_FC_CAND && j != XK_FC_ACCEPTED && head[j] > M)) return fail(h, XK_EDEVICE, "xk_trk_photo_frame: counts out of range");
+  if (m < 0 || m > a.B || status < 0 || status > XK_FRAME_ETOTAL || head[XK_FC_RING_N] < 1 || head[XK_FC_RING_N] > XK_PHOTO_RING ||
+      head[XK_FC_CAL_KEPT] < 0 || head[XK_FC_CAL_KEPT] > R)
+    return fail(h, XK_EDEVICE, "xk_trk_photo_frame: counts out of range");
+  // the host's mirrors of the photometric state
+  p->ring_n = head[XK_FC_RING_N]; p->done = head[XK_FC_DONE];
+  if (head[XK_FC_CAL_KEPT] > 4) p->n_hyp[0] = n_hyp_photo;
+  out->n_tracked = head[XK_FC_TRACKED]; out->n_left = head[XK_FC_LEFT]; out->redetected = head[XK_FC_REDETECT];
+  out->n_candidates = head[XK_FC_CAND]; out->n_accepted = head[XK_FC_ACCEPTED]; out->n_new_tracked = head[XK_FC_NEW_TRACKED];
+  out->winner = head[XK_FC_WINNER];
+  out->n_cal_kept = head[XK_FC_CAL_KEPT]; out->estimated = head[XK_FC_ESTIMATED]; out->done = head[XK_FC_DONE];
+  out->support = head[XK_FC_SUPPORT];
+  const unsigned char *r = pf->blk.h;
+  if (!first) {
+    const double *calv = (const double *)(r + xk_frame_out_cal(B, desc));
+    out->a_rel = calv[0]; out->b_rel = calv[1];
+    memcpy(out->frame_ab, calv + 2, sizeof out->frame_ab);
+  }
+  if (status != 0) return fail_at(h, XK_ECAPACITY, "xk_trk_photo_frame", frame_status_text(status));
+  if (first) {
+    f->n_res = head[XK_FC_NEW];
+    return XK_OK;
+  }
+  out->n_matches = m;
+  memcpy(out->prev_xy, r + xk_frame_out_xy(B, 0), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->cur_xy, r + xk_frame_out_xy(B, 1), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->prev_dist_xy, r + xk_frame_out_xy(B, 2), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->cur_dist_xy, r + xk_frame_out_xy(B, 3), sizeof(double) * 2 * (size_t)m);
+  memcpy(out->score, r + xk_frame_out_score(B), sizeof(int) * (size_t)m);
+  memcpy(out->origin, r + xk_frame_out_origin(B), sizeof(int) * (size_t)m);
+  memcpy(out->tiles, r + xk_frame_out_tiles(B), sizeof(int) * 4 * (size_t)m);
+  if (f->orb) memcpy(out->desc, r + xk_frame_out_desc(B), 32 * (size_t)m);
+  memcpy(out->prev_intensity, r + xk_frame_out_int(B, desc, 0), sizeof(double) * (size_t)m);
+  memcpy(out->cur_intensity, r + xk_frame_out_int(B, desc, 1), sizeof(double) * (size_t)m);
   f->n_res = m;
   return XK_OK;
 }

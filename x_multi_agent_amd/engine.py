@@ -43,6 +43,7 @@ SYMBOLS = [
     "xk_trk_detect_setup", "xk_trk_detect", "xk_trk_detect_stage",
     "xk_trk_describe_setup", "xk_trk_describe", "xk_trk_describe_stage",
     "xk_trk_frame_setup", "xk_trk_frame", "xk_trk_frame_features", "xk_trk_frame_reset",
+    "xk_trk_photo_frame_setup", "xk_trk_photo_frame", "xk_trk_photo_frame_intensities",
     "xk_trk_photo_setup", "xk_trk_photo_intensity", "xk_trk_photo_gains", "xk_trk_photo_hypotheses", "xk_trk_photo_params",
     "xk_trk_photo_reset", "xk_trk_photo_set_spatial", "xk_trk_photo_correct", "xk_trk_photo_raw", "xk_trk_photo_calibrate",
     "xk_trk_photo_spatial_setup", "xk_trk_photo_spatial_add", "xk_trk_photo_spatial_status", "xk_trk_photo_spatial_rows",

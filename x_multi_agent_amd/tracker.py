@@ -10,7 +10,8 @@ from two images and the previous features to the pairs that filter takes.  `Klt.
 place.Database takes.  `Klt.photo_*` is the photometric calibration a PHOTOMETRIC_CALI build runs in front of all of them
 (`Tracker::calibrateImage`, tracker.cpp:761-877, and IRPhotoCalib): photo_calibrate between push_image and track.
 `Klt.frame` is `Tracker::track` itself (tracker.cpp:134-306, without the photometric step): one call per image on a feature list
-that stays on the device (csrc/xk_frame.hip.h).
+that stays on the device (csrc/xk_frame.hip.h); `Klt.photo_frame` is the same call of a PHOTOMETRIC_CALI build, with the
+calibration between the push and the tracking and the features' intensities resident beside them.
 
 `MatchFilter.baseline` is what the track manager behind them asks every frame (`TrackManager::checkBaseline`,
 track_manager.cpp:576-636, and `Camera::normalize`): the normalisation, crop and baseline check of all candidate tracks at once.
@@ -328,6 +329,56 @@ class Klt(_Trk):
         """The next frame is a first frame; the pushed images stay."""
         self._chk(self.L.xk_trk_frame_reset(self.p), "xk_trk_frame_reset")
 
+    # ---- Tracker::track in one call, a PHOTOMETRIC_CALI build (calibrateImage at tracker.cpp:186-190) ----
+    _photo_frame_buf = None
+
+    def photo_frame_setup(self, n_hyp_photo=None, threshold_photo=-1):
+        """xk_trk_photo_frame_setup, after frame_setup and photo_setup: the cap of a frame's gain RANSAC (None: max_hyp of the
+        photo setup) and fast_detection_delta_photo_, the FAST threshold once a frame has estimated gains (< 0: no switch).  Whatever
+        drops the frame setup drops it, and so does a later photo_setup()."""
+        self._chk(self.L.xk_trk_photo_frame_setup(self.p, C.c_int(self.photo_max_hyp if n_hyp_photo is None else n_hyp_photo),
+                                                  C.c_int(threshold_photo)), "xk_trk_photo_frame_setup")
+
+    def photo_frame(self, img, seed=0, seed_photo=0):
+        """xk_trk_photo_frame, Tracker::track of one image with the photometric calibration -> frame()'s dict, and prev_intensity,
+        cur_intensity fp64 [m] (getIntensity of both features of each match), n_cal_kept, estimated (bool), done (bool), support,
+        a_rel, b_rel, frame_ab fp64 [4] (the calibration's outcome, as photo_calibrate's).  On XK_ECAPACITY the XkError carries the
+        counts reached as `counts` and the calibration's outcome as `calibration`."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] != self.height or img.shape[1] < self.width:
+            raise ValueError("photo_frame: a uint8 image of the set-up height and at least the set-up width")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        b, m = self._frame_arrays(), self.max_features
+        if self._photo_frame_buf is None or len(self._photo_frame_buf["prev_intensity"]) != m:
+            self._photo_frame_buf = dict(prev_intensity=np.zeros(m), cur_intensity=np.zeros(m))
+        b = dict(b, **self._photo_frame_buf)
+        o = PhotoFrameOut()
+        for name in ("prev_xy", "cur_xy", "prev_dist_xy", "cur_dist_xy", "prev_intensity", "cur_intensity"):
+            setattr(o, name, b[name].ctypes.data_as(c_dp))
+        for name in ("score", "origin", "tiles"):
+            setattr(o, name, b[name].ctypes.data_as(c_ip))
+        o.desc = b["desc"].ctypes.data_as(c_ub)
+        rc = self.L.xk_trk_photo_frame(self.p, img.ctypes.data_as(c_ub), C.c_int(img.strides[0]), C.c_ulong(seed), C.c_ulong(seed_photo),
+                                       C.byref(o))
+        counts = {k: int(getattr(o, k)) for k in FrameOut.COUNTS}
+        cal = dict(n_cal_kept=int(o.n_cal_kept), estimated=bool(o.estimated), done=bool(o.done), support=int(o.support), a_rel=float(o.a_rel),
+                   b_rel=float(o.b_rel), frame_ab=np.array(o.frame_ab[:], np.float64))
+        if rc != 0:
+            err = self._error(rc, "xk_trk_photo_frame")
+            err.counts, err.calibration = counts, cal
+            raise err
+        n = counts["n_matches"]
+        out = dict(counts, **cal)
+        out.update({k: v[:n].copy() for k, v in b.items()})
+        return out
+
+    def photo_frame_intensities(self):
+        """The resident intensities beside frame_features() -> fp64 [n]."""
+        v, n = np.zeros(self.max_features), C.c_int(0)
+        self._chk(self.L.xk_trk_photo_frame_intensities(self.p, v.ctypes.data_as(c_dp), C.byref(n)), "xk_trk_photo_frame_intensities")
+        return v[:n.value].copy()
+
     # ---- photometric calibration (Tracker::calibrateImage, tracker.cpp:761-877; irPhotoCalib.cpp), csrc/xk_photo.hip.h ----
     def photo_setup(self, kernel_size=30, epsilon_gap=0.0, epsilon_base=0.0, max_hyp=512):
         """xk_trk_photo_setup: the raw plane of both image slots, the spatial map (zeros), the parameter ring (one entry (1, 0))
@@ -516,6 +567,13 @@ class FrameOut(C.Structure):
     COUNTS = ("n_tracked", "n_left", "redetected", "n_candidates", "n_accepted", "n_new_tracked", "n_matches", "winner")
     _fields_ = [(k, C.c_int) for k in COUNTS] + [(k, c_dp) for k in ("prev_xy", "cur_xy", "prev_dist_xy", "cur_dist_xy")] + \
                [(k, c_ip) for k in ("score", "origin", "tiles")] + [("desc", c_ub)]
+
+
+class PhotoFrameOut(C.Structure):
+    """xk_trk_photo_frame_out (include/xk.h)"""
+    _fields_ = FrameOut._fields_ + [(k, c_dp) for k in ("prev_intensity", "cur_intensity")] + \
+               [(k, C.c_int) for k in ("n_cal_kept", "estimated", "done", "support")] + \
+               [("a_rel", C.c_double), ("b_rel", C.c_double), ("frame_ab", C.c_double * 4)]
 
 
 class SpatialOutcome(C.Structure):
