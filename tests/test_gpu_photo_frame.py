@@ -183,7 +183,8 @@ def test_twice_and_after_a_reset(eng):
 
 def test_stage_entries_between_frames(eng):
     """photo_intensity, photo_hypotheses of the frame's estimate, track, detect and filter_matches between two frames return what
-    they return on a tracker without the frame, and the frames go on as if nothing had been called."""
+    they return on a tracker without the frame, and the frames go on as if nothing had been called.  describe of the PREVIOUS image
+    after a frame that did not re-detect likewise."""
     sc = pc.SCENES["gain_walk"]
     seq = sc["sequences"][0]
     first = frames_of(eng, "gain_walk")[0]
@@ -221,6 +222,24 @@ def test_stage_entries_between_frames(eng):
                 fb = plain.mf.filter_matches(r["prev_dist_xy"], r["cur_dist_xy"], sc["threshold_px"], sc["n_hyp"], 3)
                 assert all(x.tobytes() == y.tobytes() for x, y in zip(fa, fb)) and len(fa[1]) > 0
         same_frames([frames], [first], "with stage entries between the frames", state=False)
+    finally:
+        rig.close()
+        plain.close()
+    # describe(xy, 0) after a frame that did NOT re-detect: it queued the blur of the PREVIOUS slot under a predicate that was 0, and the
+    # host may not count on a blur it queued there.  gain_walk re-detects on every later frame; with n_feat_min = 1 no frame does.  From
+    # frame 2 on the previous slot holds no earlier blur (frame 0 blurred its image without a predicate; the correction clears the flag).
+    sc = dict(sc, n_feat_min=1)
+    rig, plain = PhotoRig(eng, sc), PhotoRig(eng, sc, frame=False)
+    try:
+        c, described_previous = PhotoChain(plain), 0
+        for i, img in enumerate(seq):
+            r = rig.k.photo_frame(img, seed=pc.SEED + i, seed_photo=pc.SEED_PHOTO + i)
+            c.frame(img, pc.SEED + i, pc.SEED_PHOTO + i)
+            if i > 1 and not r["redetected"]:
+                a, b = rig.k.describe(ipts, 0), plain.k.describe(ipts, 0)
+                assert all(a[key].tobytes() == b[key].tobytes() for key in ("desc", "keep_idx", "dir", "moments")) and len(a["desc"]) > 0, i
+                described_previous += 1
+        assert described_previous > 0
     finally:
         rig.close()
         plain.close()

@@ -143,7 +143,7 @@ def test_twice_and_after_a_reset(eng):
 
 def test_stage_calls_between_frames(eng):
     """xk_trk_track and xk_trk_detect between two frames return what they return without a frame setup, and the frames go on as
-    if nothing had been called."""
+    if nothing had been called.  xk_trk_describe of the PREVIOUS image after a frame that did not re-detect likewise."""
     sc = tc.SCENES["walk"]
     seq = sc["sequences"][0]
     first = frames_of(eng, "walk")[0]
@@ -169,6 +169,24 @@ def test_stage_calls_between_frames(eng):
                 a, b = rig.k.describe(a["xy"], 1), plain.k.describe(b["xy"], 1)
                 assert a["desc"].tobytes() == b["desc"].tobytes() and len(a["desc"]) > 0
         same_bytes([frames], [first], "with stage calls between the frames")
+    finally:
+        rig.close()
+        plain.close()
+    # describe(xy, 0) after a frame that did NOT re-detect: it queued the blur of the PREVIOUS slot under a predicate that was 0, and the
+    # host may not count on a blur it queued there.  Above, the one such frame (4) finds that slot blurred by the describe(xy, 1) after
+    # frame 3 and queues none; with n_feat_min = 1 no frame re-detects, and from frame 2 on the previous slot holds no earlier blur.
+    sc = dict(sc, n_feat_min=1)
+    rig, plain = Rig(eng, sc), Rig(eng, sc, frame=False)
+    try:
+        described_previous = 0
+        for i, img in enumerate(seq):
+            r = rig.k.frame(img, seed=tc.SEED + i)
+            plain.k.push_image(img)
+            if i > 1 and not r["redetected"]:
+                a, b = rig.k.describe(pts.astype(np.int32), 0), plain.k.describe(pts.astype(np.int32), 0)
+                assert all(a[key].tobytes() == b[key].tobytes() for key in ("desc", "keep_idx", "dir", "moments")) and len(a["desc"]) > 0, i
+                described_previous += 1
+        assert described_previous > 0
     finally:
         rig.close()
         plain.close()

@@ -11,6 +11,8 @@ bench_fundamental.py); about 200 and about 400 features (block_half_length 26 an
     re-detecting               n_feat_min = 100000: every frame detects on the previous image and tracks what it accepts
 
     python tools/bench_tracker_frame.py [--frames 300]
+The frame entry of another build of the library (the parent commit's, as the yardstick of a change to the host code):
+    python tools/bench_tracker_frame.py --only-frame --lib /path/to/the/parent's/libxk.so
 One profiler run of its own lists the HIP calls of a frame (the single hipStreamSynchronize, the two hipMemcpyAsync):
     rocprofv3 --hip-trace --stats --output-format csv -d DIR -o f -- python tools/bench_tracker_frame.py --frames 50 --only-frame"""
 import argparse, os, sys, time
@@ -22,6 +24,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=300)
 ap.add_argument("--only-frame", action="store_true", help="the frame entry alone, steady and queued (profiler runs)")
+ap.add_argument("--lib", default=None, help="the libxk.so to load instead of this tree's")
 args = ap.parse_args()
 
 import torch
@@ -49,7 +52,7 @@ def blobs_image(seed, shift):
 
 
 pair = (blobs_image(7, (0.0, 0.0)), blobs_image(7, (3.3, -2.1)))
-eng = engine.Engine(4, 0, 4)
+eng = engine.Engine(4, 0, 4, lib_path=args.lib)
 
 
 def make(b, n_feat_min, frame):

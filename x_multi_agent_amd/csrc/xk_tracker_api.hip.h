@@ -4,7 +4,9 @@
 // rotated-BRIEF descriptors (place_recognition.cpp:72-94; xk_orb.hip.h), and the photometric calibration of the images in front of
 // all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).  Behind them, the normalisation and baseline check of the
 // track manager's candidate tracks (track_manager.cpp:576-636, camera.cpp; xk_tracks.hip.h).  At the end, Tracker::track itself in
-// one call on a resident feature list (tracker.cpp:134-306; xk_frame.hip.h): xk_trk_frame, and xk_trk_photo_frame with calibrateImage.
+// one call on a resident feature list (tracker.cpp:134-306; xk_frame.hip.h): xk_trk_frame, and xk_trk_photo_frame with calibrateImage,
+// which are one body (frame_run).  A stage's launches are queued in one place, by the function its stage entry and the frame both call
+// (klt_queue_track, det_queue, orb_queue, trk_queue_ransac, photo_queue_calibrate): it takes what differs as parameters.
 // Every stage keeps its buffers in one xk_block (a device block and its pinned mirror, carved once by the stage's setup, which stores
 // every pointer an entry needs) and reaches them through the same helpers: sub_of (the stage's setup or XK_EINVAL), img_slot (the
 // slot of the previous or the current image or XK_EINVAL), launched (the check behind a group of launches), kept_count_out, setup_install.
@@ -360,15 +362,29 @@ extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy
   return XK_OK;
 }
 
-static XkFundArgs trk_args(xk_trk *t, int n) {
+// The outlier removal of n pairs whose result block (trk_res_bytes(n)) starts at d_res: the stage entries' t->d_res or a frame's.  With
+// n_dev the count is the device's and n the bound the block is laid out by.
+static XkFundArgs trk_args(xk_trk *t, unsigned char *d_res, int n, const int *n_dev = nullptr) {
   XkFundArgs a{};
   a.dist = t->dist; a.und = t->und; a.pts = t->pts; a.sc = t->sc;
-  a.F = (double *)t->d_res;
+  a.F = (double *)d_res;
   a.kept = xk_kept_pairs(a.F + 9, n);
   a.mask = xk_kept_pairs_end(a.kept, n);
-  a.n = n; a.n_pts = 2 * n;
+  a.n = n; a.n_pts = 2 * n; a.n_dev = n_dev;
   a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.s = t->s; a.s_term = t->s_term;
   return a;
+}
+
+// The RANSAC of a's pairs, queued: Camera::undistort of both lists first (undistort = true), then solve, score and mask.
+static int trk_queue_ransac(xk_handle *h, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
+  a.n_hyp = n_hyp;
+  a.t2 = threshold_px * threshold_px;
+  a.seed = (unsigned long long)seed;
+  if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
+  return launched(h, "fundamental RANSAC launch");
 }
 
 /* Camera::undistort (camera.cpp:62-87) */
@@ -379,7 +395,7 @@ extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double 
   if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_undistort: more points than max_matches");
   if (n == 0) return XK_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  XkFundArgs a = trk_args(t, 0);
+  XkFundArgs a = trk_args(t, t->d_res, 0);
   a.n_pts = n;
   memcpy(t->blk.h, dist_xy, sizeof(double) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->blk.h, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
@@ -396,17 +412,10 @@ extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double 
 static int trk_run(xk_trk *t, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
   xk_handle *h = t->h;
   const int n = a.n;
-  a.n_hyp = n_hyp;
-  a.t2 = threshold_px * threshold_px;
-  a.seed = (unsigned long long)seed;
   if (!undistort) a.und = a.pts;
   t->n_hyp = 0;
   HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->blk.h, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * n + 255) / 256), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
-  XKCHK(launched(h, "fundamental RANSAC launch"));
+  XKCHK(trk_queue_ransac(h, a, undistort, threshold_px, n_hyp, seed));
   HIPCHK(h, hipMemcpyAsync(t->h_res, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   t->n_hyp = n_hyp;
@@ -434,7 +443,7 @@ extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const 
   if (F) memset(F, 0, 9 * sizeof(double));
   if (n < 7) { t->n_hyp = 0; return XK_OK; }                 // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
   HIPCHK(h, hipSetDevice(h->device));
-  XkFundArgs a = trk_args(t, n);
+  XkFundArgs a = trk_args(t, t->d_res, n);
   double *h_pts = (double *)t->blk.h;
   for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
   XKCHK(trk_run(t, a, false, threshold_px, n_hyp, seed));
@@ -448,7 +457,7 @@ extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const 
 /* What the last RANSAC of the tracker's matches (tracker.cpp:259-260) left for hypotheses first ... first+count-1 */
 extern "C" int xk_trk_fundamental_hypotheses(xk_trk *t, int first, int count, int *n_cand, double *F, int *inliers) {
   if (!t) return XK_EINVAL;
-  return ransac_hypotheses(t->h, "xk_trk_fundamental_hypotheses", "RANSAC", t->n_hyp, trk_args(t, 0).sc, XK_FUND_MAXC, first, count,
+  return ransac_hypotheses(t->h, "xk_trk_fundamental_hypotheses", "RANSAC", t->n_hyp, t->sc, XK_FUND_MAXC, first, count,
                            n_cand, F, inliers);
 }
 
@@ -464,7 +473,7 @@ extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, cons
   memset(mask, 0, (size_t)n);
   if (n < 7) { t->n_hyp = 0; return XK_OK; }
   HIPCHK(h, hipSetDevice(h->device));
-  XkFundArgs a = trk_args(t, n);
+  XkFundArgs a = trk_args(t, t->d_res, n);
   memcpy(t->blk.h, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
   memcpy(t->blk.h + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
   XKCHK(trk_run(t, a, true, threshold_px, n_hyp, seed));
@@ -703,6 +712,34 @@ extern "C" int xk_trk_detect_setup(xk_trk *t, int threshold, int non_max_supp, i
   return XK_OK;
 }
 
+// Accepted points are pairwise more than b apart: at most ceil(W / (b + 1)) ceil(H / (b + 1)) of them come back, and at most max_matches.
+static int det_cap(const xk_trk *t, const xk_det *d) {
+  const long long bound = (long long)((t->klt->width + d->b) / (d->b + 1)) * ((t->klt->height + d->b) / (d->b + 1));
+  return (int)std::min<long long>(bound, t->max_matches);
+}
+
+// The detection on level 0 of slot s, queued: the result block goes to res.  The old features are the n_old at old_xy or, with n_old_dev,
+// the device's count of at most n_old; pred as XkFastArgs::pred; alt_threshold >= 0: the photometric frame's, which the device selects
+// (fast_detection_delta_photo_ once the calibration is done).
+static int det_queue(xk_trk *t, int s, int *res, const double *old_xy, int n_old, const int *n_old_dev, const int *pred, int alt_threshold) {
+  xk_handle *h = t->h;
+  xk_det *d = t->klt->det;
+  const XkKltLevel &L = t->klt->slot[s].lv[0];
+  XkFastArgs a{};
+  a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
+  a.S = d->S; a.keys = d->keys; a.count = d->count; a.mask_g = d->mask_g; a.key_cap = d->key_cap; a.wpr = d->wpr;
+  a.old_xy = old_xy; a.n_old = n_old; a.n_old_dev = n_old_dev; a.pred = pred;
+  a.threshold = d->threshold; a.nms = d->nms; a.b = d->b; a.margin = d->margin; a.max_candidates = d->max_candidates;
+  a.max_matches = t->max_matches;
+  a.res = res;
+  if (alt_threshold >= 0) { a.alt_on = &t->klt->photo->st->done; a.alt_threshold = alt_threshold; }
+  d->n_cand = -1;                                                   // (the score image and the keys are no longer those xk_trk_detect_stage hands out)
+  hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fast_select, dim3(1), dim3(XK_FAST_SEL_T), d->lds_bytes, h->stream, a);
+  return launched(h, "detection launch");
+}
+
 /* Tracker::featureDetection (tracker.cpp:390-590) on level 0 of the previous (which = 0) or the current (1) image */
 extern "C" int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_old, int *xy, int *score, int *n_found, int *n_candidates) {
   if (!t) return XK_EINVAL;
@@ -716,26 +753,12 @@ extern "C" int xk_trk_detect(xk_trk *t, int which, const double *old_xy, int n_o
   *n_found = 0; *n_candidates = 0;
   if (n_old > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_detect: more old features than max_matches");
   HIPCHK(h, hipSetDevice(h->device));
-  const XkKltLevel &L = t->klt->slot[s].lv[0];
-  XkFastArgs a{};
-  a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
-  a.S = d->S; a.keys = d->keys; a.count = d->count; a.mask_g = d->mask_g; a.key_cap = d->key_cap; a.wpr = d->wpr;
-  a.old_xy = d->old_xy; a.n_old = n_old;
-  a.threshold = d->threshold; a.nms = d->nms; a.b = d->b; a.margin = d->margin; a.max_candidates = d->max_candidates;
-  a.max_matches = t->max_matches;
-  a.res = d->res;
-  d->n_cand = -1;
   if (n_old > 0) {
     memcpy(d->blk.h, old_xy, sizeof(double) * 2 * (size_t)n_old);
     HIPCHK(h, hipMemcpyAsync(d->old_xy, d->blk.h, sizeof(double) * 2 * (size_t)n_old, hipMemcpyHostToDevice, h->stream));
   }
-  hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fast_select, dim3(1), dim3(XK_FAST_SEL_T), d->lds_bytes, h->stream, a);
-  XKCHK(launched(h, "detection launch"));
-  // accepted points are pairwise more than b apart: at most ceil(W / (b + 1)) ceil(H / (b + 1)) of them come back
-  const long long bound = (long long)((a.w + d->b) / (d->b + 1)) * ((a.h + d->b) / (d->b + 1));
-  const int cap = (int)std::min<long long>(bound, t->max_matches);
+  XKCHK(det_queue(t, s, d->res, d->old_xy, n_old, nullptr, nullptr, -1));
+  const int cap = det_cap(t, d);
   const int *r = d->h_res;
   HIPCHK(h, hipMemcpyAsync(d->h_res, d->res, det_res_bytes(t->max_matches), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -834,21 +857,34 @@ extern "C" int xk_trk_describe_setup(xk_trk *t, int orientation, double angle_de
   return XK_OK;
 }
 
-// The slot s as XkOrbArgs, its blur queued if this is the slot's first description since its push.
-static int orb_slot(xk_trk *t, int s, XkOrbArgs &a) {
-  xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  xk_orb *o = k->orb;
-  const XkKltLevel &L = k->slot[s].lv[0];
-  a.img = L.img; a.G = o->G[s]; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
-  a.edge = o->edge; a.centroid = o->centroid; a.A = o->A; a.B = o->B;
-  a.pattern = o->pattern; a.xy = o->xy; a.kept_xy = o->kept_xy; a.res = o->res;
-  if (!o->blurred[s]) {
-    hipLaunchKernelGGL(xk_orb_blur, dim3((a.w + XK_ORB_TW - 1) / XK_ORB_TW, (a.h + XK_ORB_TH - 1) / XK_ORB_TH), dim3(256), 0, h->stream, a);
-    XKCHK(launched(h, "blur launch"));
-    o->blurred[s] = 1;
-  }
+// The blur of slot s into G[s], queued unless G[s] holds it, under pred (as XkOrbArgs::pred) if given.  The rule of blurred[s]: an
+// unpredicated blur sets the flag; a predicated one may not have run, the host cannot count on it, and the flag stays clear.
+static int orb_queue_blur(xk_trk *t, int s, const int *pred, XkOrbArgs &a) {
+  xk_orb *o = t->klt->orb;
+  const XkKltLevel &L = t->klt->slot[s].lv[0];
+  a = XkOrbArgs{};
+  a.img = L.img; a.G = o->G[s]; a.w = L.w; a.h = L.h; a.pitch = L.pitch; a.pred = pred;
+  if (o->blurred[s]) return XK_OK;
+  hipLaunchKernelGGL(xk_orb_blur, dim3((a.w + XK_ORB_TW - 1) / XK_ORB_TW, (a.h + XK_ORB_TH - 1) / XK_ORB_TH), dim3(256), 0, t->h->stream, a);
+  XKCHK(launched(t->h, "blur launch"));
+  if (!pred) o->blurred[s] = 1;
   return XK_OK;
+}
+
+// The description on slot s of the n keypoints at xy (with n_dev, the device's count of at most n), queued: the blur if it is the slot's
+// first since its push, the filter, the descriptors.  The result block (xk_orb_res_bytes(n)) goes to res.
+static int orb_queue(xk_trk *t, int s, const int *xy, int *res, int n, const int *n_dev, const int *pred) {
+  xk_handle *h = t->h;
+  const xk_orb *o = t->klt->orb;
+  XkOrbArgs a;
+  XKCHK(orb_queue_blur(t, s, pred, a));
+  a.edge = o->edge; a.centroid = o->centroid; a.A = o->A; a.B = o->B;
+  a.pattern = o->pattern; a.xy = xy; a.kept_xy = o->kept_xy; a.res = res;
+  a.n = n; a.n_dev = n_dev;
+  hipLaunchKernelGGL(xk_orb_filter, dim3(1), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_orb_describe, dim3(std::min((n + XK_ORB_WAVES - 1) / XK_ORB_WAVES, XK_ORB_MAX_GRID)), dim3(64 * XK_ORB_WAVES), 0,
+                     h->stream, a);
+  return launched(h, "description launch");
 }
 
 /* cv::ORB::compute(img, keypoints, descriptors) (place_recognition.cpp:72-94) on the previous (which = 0) or the current (1) image */
@@ -865,15 +901,9 @@ extern "C" int xk_trk_describe(xk_trk *t, int which, const int *xy, int n, unsig
   *n_kept = 0;
   if (n == 0) return XK_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  XkOrbArgs a{};
-  a.n = n;
   memcpy(o->blk.h, xy, sizeof(int) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync(o->xy, o->blk.h, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  XKCHK(orb_slot(t, s, a));
-  hipLaunchKernelGGL(xk_orb_filter, dim3(1), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_orb_describe, dim3(std::min((n + XK_ORB_WAVES - 1) / XK_ORB_WAVES, XK_ORB_MAX_GRID)), dim3(64 * XK_ORB_WAVES), 0,
-                     h->stream, a);
-  XKCHK(launched(h, "description launch"));
+  XKCHK(orb_queue(t, s, o->xy, o->res, n, nullptr, nullptr));
   const unsigned char *r = o->h_res;
   HIPCHK(h, hipMemcpyAsync(o->h_res, o->res, xk_orb_res_bytes((size_t)n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -898,8 +928,8 @@ extern "C" int xk_trk_describe_stage(xk_trk *t, int which, unsigned char *blurre
   HIPCHK(h, hipSetDevice(h->device));
   if (pattern) HIPCHK(h, hipMemcpyAsync(pattern, o->pattern, sizeof o->h_pattern, hipMemcpyDeviceToHost, h->stream));   // (the kernels' copy)
   if (blurred) {
-    XkOrbArgs a{};
-    XKCHK(orb_slot(t, s, a));
+    XkOrbArgs a;
+    XKCHK(orb_queue_blur(t, s, nullptr, a));
     HIPCHK(h, hipMemcpy2DAsync(blurred, (size_t)a.w, a.G, (size_t)a.pitch, (size_t)a.w, (size_t)a.h, hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1198,6 +1228,34 @@ static XkPspAccArgs psp_acc_args(const xk_photo *p, const xk_psp *s, int G) {
   return a;
 }
 
+// calibrateImage of n >= 4 features up to the correction, queued: the tracking of the device's points d_pts between the RAW planes (its
+// result block is p->klt_res, its kept pairs come back in `kept`), the kept features' previous intensities out of prev_int and their
+// pixels gathered, their intensities in the raw current plane, the gains, and the rows of a spatial setup that is still accumulating.
+static int photo_queue_calibrate(xk_trk *t, const float *d_pts, const double *prev_int, int n, int n_hyp, unsigned long seed, XkKeptPairs &kept) {
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_photo *p = k->photo;
+  XkKltArgs a;
+  XKCHK(klt_queue_track(h, k, p->raw[k->cur ^ 1], p->raw[k->cur], d_pts, p->klt_res, n, a));
+  kept = a.kept;
+  XkPhotoGatherArgs ga{};
+  ga.kept = kept; ga.prev_intensity = prev_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
+  hipLaunchKernelGGL(xk_photo_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, ga);
+  XkPhotoIntArgs ia = photo_int_args(p, p->raw[k->cur].lv[0], n);
+  ia.n_dev = kept.res;
+  hipLaunchKernelGGL(xk_photo_intensity, dim3((n + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, ia);
+  XKCHK(launched(h, "calibration launch"));
+  XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp, seed, 1);
+  XKCHK(photo_queue_gains(h, p, g));
+  if (p->sp && p->sp->state != XK_PSP_ESTIMATED) {               // the spatial rows of this frame, from the lists already on the device
+    XkPspAccArgs sa = psp_acc_args(p, p->sp, 1);
+    sa.prev_f = d_pts; sa.keep_idx = kept.keep_idx; sa.pix_cur = p->ixy; sa.o_hist = p->o_hist; sa.o_cur = p->value;
+    sa.off = p->off; sa.frame_back = p->frame_back; sa.per_frame = 1;
+    hipLaunchKernelGGL(xk_photo_sp_accumulate, dim3(1), dim3(64), 0, h->stream, sa);
+  }
+  return XK_OK;
+}
+
 /* Tracker::calibrateImage (tracker.cpp:761-858): track the previous features between the RAW images, their intensities in the
  * current one, the gain estimate against the previous intensities, the correction of the current image */
 extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const double *prev_intensity, int n, int n_hyp, unsigned long seed,
@@ -1230,32 +1288,17 @@ extern "C" int xk_trk_photo_calibrate(xk_trk *t, const float *prev_xy, const dou
   memcpy(photo_host(p, p->pts), prev_xy, sizeof(float) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync(p->prev_int, photo_host(p, p->prev_int), (size_t)((unsigned char *)p->ixy - (unsigned char *)p->prev_int),
                            hipMemcpyHostToDevice, h->stream));
-  XkKltArgs a;
-  XKCHK(klt_queue_track(h, k, p->raw[k->cur ^ 1], p->raw[k->cur], p->pts, p->klt_res, n, a));
-  XkPhotoGatherArgs ga{};
-  ga.kept = a.kept; ga.prev_intensity = p->prev_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
-  hipLaunchKernelGGL(xk_photo_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, ga);
-  XkPhotoIntArgs ia = photo_int_args(p, p->raw[k->cur].lv[0], n);
-  ia.n_dev = a.kept.res;
-  hipLaunchKernelGGL(xk_photo_intensity, dim3((n + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, ia);
-  XKCHK(launched(h, "calibration launch"));
-  XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp, seed, 1);
-  XKCHK(photo_queue_gains(h, p, g));
-  if (p->sp && p->sp->state != XK_PSP_ESTIMATED) {               // the spatial rows of this frame, from the lists already on the device
-    XkPspAccArgs sa = psp_acc_args(p, p->sp, 1);
-    sa.prev_f = p->pts; sa.keep_idx = a.kept.keep_idx; sa.pix_cur = p->ixy; sa.o_hist = p->o_hist; sa.o_cur = p->value;
-    sa.off = p->off; sa.frame_back = p->frame_back; sa.per_frame = 1;
-    hipLaunchKernelGGL(xk_photo_sp_accumulate, dim3(1), dim3(64), 0, h->stream, sa);
-  }
+  XkKeptPairs kp;
+  XKCHK(photo_queue_calibrate(t, p->pts, p->prev_int, n, n_hyp, seed, kp));
   XKCHK(photo_queue_correct(h, k, k->cur, 1));
   // one copy out: state | value | sum | count | the tracking's result block
   const size_t out_bytes = (size_t)(p->klt_res - p->d_io) + klt_res_bytes(n);
   HIPCHK(h, hipMemcpyAsync(p->blk.h, p->d_io, out_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const unsigned char *r = photo_host(p, p->klt_res);
-  XKCHK(kept_count_out(h, "xk_trk_photo_calibrate", r + ((unsigned char *)a.kept.res - p->klt_res), n, n_kept));
+  XKCHK(kept_count_out(h, "xk_trk_photo_calibrate", r + ((unsigned char *)kp.res - p->klt_res), n, n_kept));
   const int kept = *n_kept;
-  memcpy(keep_idx, r + ((unsigned char *)a.kept.keep_idx - p->klt_res), sizeof(int) * (size_t)kept);
+  memcpy(keep_idx, r + ((unsigned char *)kp.keep_idx - p->klt_res), sizeof(int) * (size_t)kept);
   memcpy(intensity, photo_host(p, p->value), sizeof(double) * (size_t)kept);
   memcpy(sum, photo_host(p, p->sum), sizeof(int) * (size_t)kept);
   memcpy(count, photo_host(p, p->count), sizeof(int) * (size_t)kept);
@@ -1668,9 +1711,7 @@ extern "C" int xk_trk_frame_setup(xk_trk *t, int n_feat_min, int n_tiles_h, int 
   f->threshold_px = threshold_px; f->n_hyp = n_hyp;
   f->det = d; f->orb = o; f->n_res = -1;
   const size_t M = (size_t)t->max_matches;
-  // accepted points are pairwise more than b apart (xk_trk_detect)
-  const long long bound = (long long)((k->width + d->b) / (d->b + 1)) * ((k->height + d->b) / (d->b + 1));
-  f->cap_det = (int)std::min<long long>(bound, t->max_matches);
+  f->cap_det = det_cap(t, d);
   f->cap_new = o ? std::min(f->cap_det, o->max_desc) : f->cap_det;
   const size_t N = (size_t)f->cap_new;
   const size_t klt_bytes = up16(klt_res_bytes(t->max_matches)), det_bytes = up16(det_res_bytes(t->max_matches));
@@ -1740,49 +1781,6 @@ extern "C" int xk_trk_frame_features(xk_trk *t, double *dist_xy, int *score, uns
   return XK_OK;
 }
 
-// The detection of a frame on slot s, queued: no old features (n_old_bound = 0) or the device's list of at most n_old_bound; pred as XkFastArgs::pred.
-// The photometric frame (f->pf in use) selects the threshold on the device: fast_detection_delta_photo_ once the calibration is done.
-static int frame_queue_detect(xk_trk *t, const xk_frm *f, int s, const int *pred, const double *old_xy, int n_old_bound, const int *n_old_dev,
-                              bool photo = false) {
-  xk_handle *h = t->h;
-  xk_det *d = t->klt->det;
-  const XkKltLevel &L = t->klt->slot[s].lv[0];
-  XkFastArgs a{};
-  a.img = L.img; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
-  a.S = d->S; a.keys = d->keys; a.count = d->count; a.mask_g = d->mask_g; a.key_cap = d->key_cap; a.wpr = d->wpr;
-  a.old_xy = old_xy; a.n_old = n_old_bound; a.n_old_dev = n_old_dev; a.pred = pred;
-  a.threshold = d->threshold; a.nms = d->nms; a.b = d->b; a.margin = d->margin; a.max_candidates = d->max_candidates;
-  a.max_matches = t->max_matches;
-  a.res = f->a.det_res;
-  if (photo && f->pf->threshold >= 0) { a.alt_on = &t->klt->photo->st->done; a.alt_threshold = f->pf->threshold; }
-  d->n_cand = -1;                                                   // (the score image and the keys are no longer those of the last xk_trk_detect)
-  hipLaunchKernelGGL(xk_fast_score, dim3((a.w + XK_FAST_TW - 1) / XK_FAST_TW, (a.h + XK_FAST_TH - 1) / XK_FAST_TH), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fast_candidates, dim3((a.w + 63) / 64, (a.h + 3) / 4), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fast_select, dim3(1), dim3(XK_FAST_SEL_T), d->lds_bytes, h->stream, a);
-  return launched(h, "frame detection launch");
-}
-
-// The description of the detected features (the detection's result block holds their pixels) on slot s, queued; the count is the gate's.
-static int frame_queue_describe(xk_trk *t, const xk_frm *f, int s, const int *pred) {
-  xk_handle *h = t->h;
-  xk_klt *k = t->klt;
-  xk_orb *o = k->orb;
-  const XkKltLevel &L = k->slot[s].lv[0];
-  XkOrbArgs a{};
-  a.img = L.img; a.G = o->G[s]; a.w = L.w; a.h = L.h; a.pitch = L.pitch;
-  a.edge = o->edge; a.centroid = o->centroid; a.A = o->A; a.B = o->B;
-  a.pattern = o->pattern; a.xy = f->a.det_res + 4; a.kept_xy = o->kept_xy; a.res = f->orb_res;
-  a.n = f->cap_new; a.n_dev = f->a.c + XK_FC_NEW; a.pred = pred;
-  if (!o->blurred[s]) {
-    hipLaunchKernelGGL(xk_orb_blur, dim3((a.w + XK_ORB_TW - 1) / XK_ORB_TW, (a.h + XK_ORB_TH - 1) / XK_ORB_TH), dim3(256), 0, h->stream, a);
-    if (!pred) o->blurred[s] = 1;                                   // (a predicated blur may not have run: the host cannot count on it)
-  }
-  hipLaunchKernelGGL(xk_orb_filter, dim3(1), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_orb_describe, dim3(std::min((a.n + XK_ORB_WAVES - 1) / XK_ORB_WAVES, XK_ORB_MAX_GRID)), dim3(64 * XK_ORB_WAVES), 0,
-                     h->stream, a);
-  return launched(h, "frame description launch");
-}
-
 static const char *frame_status_text(int status) {
   switch (status) {
     case XK_FRAME_ECAND: return "more candidates than max_candidates";
@@ -1791,105 +1789,6 @@ static const char *frame_status_text(int status) {
     case XK_FRAME_ETOTAL: return "old plus new features exceed max_matches";
   }
   return "status out of range";
-}
-
-/* Tracker::track (tracker.cpp:134-306), a build without PHOTOMETRIC_CALI, pyramid level 0: everything queued on the handle's stream, one wait */
-extern "C" int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, xk_trk_frame_out *out) {
-  if (!t) return XK_EINVAL;
-  xk_handle *h = t->h;
-  xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame", "xk_trk_frame_setup");
-  if (!f) return XK_EINVAL;
-  xk_klt *k = t->klt;
-  if (k->photo) return fail(h, XK_EINVAL, "xk_trk_frame: a photometric setup is in place (the photometric frame is xk_trk_photo_frame)");
-  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_frame: null image or stride below the width");
-  if (!out || !out->prev_xy || !out->cur_xy || !out->prev_dist_xy || !out->cur_dist_xy || !out->score || !out->origin || !out->tiles ||
-      (f->orb && !out->desc))
-    return fail(h, XK_EINVAL, "xk_trk_frame: null output");
-  out->n_tracked = out->n_left = out->redetected = out->n_candidates = out->n_accepted = out->n_new_tracked = out->n_matches = 0;
-  out->winner = -1;
-  HIPCHK(h, hipSetDevice(h->device));
-  const bool first = f->n_res < 0;
-  const int M = t->max_matches, R = first ? 0 : f->n_res;
-  f->n_res = -1;                                                    // (whatever fails below: the next frame is a first frame)
-  XKCHK(trk_push(t, img, stride));
-  XkFrameArgs a = f->a;
-  a.first = first ? 1 : 0;
-  a.n_res = R;
-  a.B = first ? 1 : std::min(M, R + f->cap_det);
-  const size_t B = (size_t)a.B;
-  a.l_prev = t->dist; a.l_cur = t->dist + 2 * B;
-  int *c = a.c;
-  const int *head = (const int *)f->blk.h;
-  if (first) {
-    XKCHK(frame_queue_detect(t, f, k->cur, nullptr, nullptr, 0, nullptr));
-    hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
-    if (f->orb) XKCHK(frame_queue_describe(t, f, k->cur, nullptr));
-    hipLaunchKernelGGL(xk_frame_first, dim3((f->cap_new + 255) / 256), dim3(256), 0, h->stream, a);
-    XKCHK(launched(h, "first frame launch"));
-    HIPCHK(h, hipMemcpyAsync(f->blk.h, a.out, sizeof(int) * XK_FC_N, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  } else {
-    const XkKltPyr &prev = k->slot[k->cur ^ 1], &cur = k->slot[k->cur];
-    XkKltArgs ka;
-    a.kept1 = klt_kept_at(f->klt_res[0], R);
-    a.kept2 = klt_kept_at(f->klt_res[1], f->cap_new);
-    XkFundArgs fa{};
-    fa.dist = t->dist; fa.und = t->und; fa.pts = t->pts; fa.sc = t->sc;
-    fa.F = (double *)f->fund_res;
-    fa.kept = xk_kept_pairs(fa.F + 9, B);
-    fa.mask = xk_kept_pairs_end(fa.kept, B);
-    fa.n = a.B; fa.n_pts = 2 * a.B; fa.n_dev = c + XK_FC_TOTAL;
-    fa.fx = t->fx; fa.fy = t->fy; fa.cx = t->cx; fa.cy = t->cy; fa.s = t->s; fa.s_term = t->s_term;
-    fa.n_hyp = f->n_hyp; fa.t2 = f->threshold_px * f->threshold_px; fa.seed = (unsigned long long)seed;
-    a.kept3 = fa.kept;
-    t->n_hyp = 0;                                                   // (the scratch no longer holds the last xk_trk_filter_matches)
-    // 2. the resident list from the previous image to the current one, its post-filter; 3. the overflow pass
-    if (R > 0) XKCHK(klt_queue_track(h, k, prev, cur, a.res_pts, f->klt_res[0], R, ka));
-    hipLaunchKernelGGL(xk_frame_overflow, dim3(1), dim3(256), sizeof(int) * (size_t)f->tiles_h * f->tiles_w, h->stream, a);
-    // 4. the re-detection on the PREVIOUS image, queued on every frame and predicated on the flag the overflow pass left.  (With
-    // n_feat_min = 0 the flag is never set: nothing is queued, and xk_frame_concat finds the zero count the overflow pass wrote.)
-    if (f->n_feat_min > 0) {
-      XKCHK(frame_queue_detect(t, f, k->cur ^ 1, c + XK_FC_REDETECT, a.l_prev, R, c + XK_FC_LEFT));
-      hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
-      if (f->orb) XKCHK(frame_queue_describe(t, f, k->cur ^ 1, c + XK_FC_REDETECT));
-      XKCHK(klt_queue_track(h, k, prev, cur, a.pts_new, f->klt_res[1], f->cap_new, ka, c + XK_FC_NEW));
-    }
-    hipLaunchKernelGGL(xk_frame_concat, dim3(1), dim3(256), 0, h->stream, a);
-    // 5. the outlier removal, as trk_run queues it
-    hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.B + 255) / 256), dim3(256), 0, h->stream, fa);
-    hipLaunchKernelGGL(xk_fund_solve, dim3((fa.n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, fa);
-    hipLaunchKernelGGL(xk_fund_score, dim3(fa.n_hyp), dim3(256), 0, h->stream, fa);
-    hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, fa);
-    // 6. the result block and the new resident list
-    hipLaunchKernelGGL(xk_frame_pack, dim3((a.B + 255) / 256), dim3(256), 0, h->stream, a);
-    XKCHK(launched(h, "frame launch"));
-    HIPCHK(h, hipMemcpyAsync(f->blk.h, a.out, xk_frame_out_bytes(B, f->orb != nullptr), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                     // the frame's one wait
-  }
-  const int status = head[XK_FC_STATUS], m = head[XK_FC_MATCHES];
-  for (int j = 0; j <= XK_FC_TOTAL; ++j)
-    if (head[j] < 0 || (j != XK_FC_CAND && j != XK_FC_ACCEPTED && head[j] > M)) return fail(h, XK_EDEVICE, "xk_trk_frame: counts out of range");
-  if (m < 0 || m > a.B || status < 0 || status > XK_FRAME_ETOTAL) return fail(h, XK_EDEVICE, "xk_trk_frame: counts out of range");
-  out->n_tracked = head[XK_FC_TRACKED]; out->n_left = head[XK_FC_LEFT]; out->redetected = head[XK_FC_REDETECT];
-  out->n_candidates = head[XK_FC_CAND]; out->n_accepted = head[XK_FC_ACCEPTED]; out->n_new_tracked = head[XK_FC_NEW_TRACKED];
-  out->winner = head[XK_FC_WINNER];
-  if (status != 0) return fail_at(h, XK_ECAPACITY, "xk_trk_frame", frame_status_text(status));
-  if (first) {
-    f->n_res = head[XK_FC_NEW];
-    return XK_OK;
-  }
-  out->n_matches = m;
-  const unsigned char *r = f->blk.h;
-  memcpy(out->prev_xy, r + xk_frame_out_xy(B, 0), sizeof(double) * 2 * (size_t)m);
-  memcpy(out->cur_xy, r + xk_frame_out_xy(B, 1), sizeof(double) * 2 * (size_t)m);
-  memcpy(out->prev_dist_xy, r + xk_frame_out_xy(B, 2), sizeof(double) * 2 * (size_t)m);
-  memcpy(out->cur_dist_xy, r + xk_frame_out_xy(B, 3), sizeof(double) * 2 * (size_t)m);
-  memcpy(out->score, r + xk_frame_out_score(B), sizeof(int) * (size_t)m);
-  memcpy(out->origin, r + xk_frame_out_origin(B), sizeof(int) * (size_t)m);
-  memcpy(out->tiles, r + xk_frame_out_tiles(B), sizeof(int) * 4 * (size_t)m);
-  if (f->orb) memcpy(out->desc, r + xk_frame_out_desc(B), 32 * (size_t)m);
-  f->n_res = m;
-  return XK_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1970,142 +1869,139 @@ static void photo_frame_queue_kept_intensity(xk_handle *h, const xk_photo *p, co
   photo_frame_queue_intensity(h, p, pf, P, ixy, kept.res, n_bound, value);
 }
 
-/* Tracker::track (tracker.cpp:134-306), a build with PHOTOMETRIC_CALI, pyramid level 0: everything queued on the handle's stream, one wait */
-extern "C" int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, unsigned long seed_photo,
-                                  xk_trk_photo_frame_out *out) {
-  if (!t) return XK_EINVAL;
+// ---------------------------------------------------------------------------
+// The body of both frames.  The kernels of xk_frame.hip.h treat the plain frame as the photometric one with res_int == NULL; so does the host
+// ---------------------------------------------------------------------------
+// What xk_trk_photo_frame has beyond xk_trk_frame: the seed of the gain RANSAC and its own outputs.  Its setups are k->photo and f->pf.
+struct frame_photo {
+  unsigned long seed;
+  xk_trk_photo_frame_out *out;
+};
+
+// featureDetection of a frame on the working plane of slot s and its gate, queued; then, of the accepted features, the intensities on that
+// plane (pf: the photometric frame, tracker.cpp:461) and the description.  Old features and pred as det_queue's.
+static int frame_queue_detect(xk_trk *t, const xk_frm *f, const XkFrameArgs &a, const xk_pfrm *pf, int s, const double *old_xy, int n_old,
+                              const int *n_old_dev, const int *pred) {
   xk_handle *h = t->h;
-  xk_frm *f = photo_frame_of(t, "xk_trk_photo_frame");
-  if (!f) return XK_EINVAL;
+  XKCHK(det_queue(t, s, a.det_res, old_xy, n_old, n_old_dev, pred, pf ? pf->threshold : -1));
+  hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
+  if (pf) photo_frame_queue_intensity(h, t->klt->photo, pf, t->klt->slot[s], a.det_res + 4, a.c + XK_FC_NEW, f->cap_new, pf->val_new);
+  return f->orb ? orb_queue(t, s, a.det_res + 4, f->orb_res, f->cap_new, a.c + XK_FC_NEW, pred) : XK_OK;
+}
+
+// featureTracking on the WORKING planes of the n points at pts (with n_dev, the device's count of at most n), queued: the resident list
+// (which = 0) or the re-detection's features (1), the result block goes to f->klt_res[which].  The photometric frame adds the kept current
+// features' intensities on the RAW current plane at the truncated pixel (tracker.cpp:666).
+static int frame_queue_track(xk_trk *t, const xk_frm *f, const xk_pfrm *pf, int which, const float *pts, int n, const int *n_dev) {
   xk_klt *k = t->klt;
-  xk_photo *p = k->photo;
-  xk_pfrm *pf = f->pf;
-  if (!img || stride < k->width) return fail(h, XK_EINVAL, "xk_trk_photo_frame: null image or stride below the width");
+  XkKltArgs ka;
+  XKCHK(klt_queue_track(t->h, k, k->slot[k->cur ^ 1], k->slot[k->cur], pts, f->klt_res[which], n, ka, n_dev));
+  if (pf) photo_frame_queue_kept_intensity(t->h, k->photo, pf, k->photo->raw[k->cur], ka.kept, n, which ? pf->ixy2 : pf->ixy1,
+                                           which ? pf->val2 : pf->val1);
+  return XK_OK;
+}
+
+// Tracker::track (tracker.cpp:134-306), pyramid level 0, for entry `who`: everything queued on the handle's stream, one copy out, one wait.
+// ph: the photometric frame, whose result block and pinned mirror are the xk_pfrm's; without it they are the frame setup's.
+static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char *img, int stride, unsigned long seed, xk_trk_frame_out *out,
+                     const frame_photo *ph) {
+  xk_handle *h = t->h;
+  xk_klt *k = t->klt;
+  xk_photo *p = ph ? k->photo : nullptr;
+  xk_pfrm *pf = ph ? f->pf : nullptr;
+  xk_trk_photo_frame_out *pout = ph ? ph->out : nullptr;
+  if (!img || stride < k->width) return fail_at(h, XK_EINVAL, who, "null image or stride below the width");
   if (!out || !out->prev_xy || !out->cur_xy || !out->prev_dist_xy || !out->cur_dist_xy || !out->score || !out->origin || !out->tiles ||
-      !out->prev_intensity || !out->cur_intensity || (f->orb && !out->desc))
-    return fail(h, XK_EINVAL, "xk_trk_photo_frame: null output");
+      (f->orb && !out->desc) || (ph && (!pout->prev_intensity || !pout->cur_intensity)))
+    return fail_at(h, XK_EINVAL, who, "null output");
   out->n_tracked = out->n_left = out->redetected = out->n_candidates = out->n_accepted = out->n_new_tracked = out->n_matches = 0;
   out->winner = -1;
-  out->n_cal_kept = out->estimated = out->support = 0;
-  out->done = p->done;
-  out->a_rel = 1.0; out->b_rel = 0.0;
-  memset(out->frame_ab, 0, sizeof out->frame_ab);
+  if (ph) {
+    pout->n_cal_kept = pout->estimated = pout->support = 0;
+    pout->done = p->done;
+    pout->a_rel = 1.0; pout->b_rel = 0.0;
+    memset(pout->frame_ab, 0, sizeof pout->frame_ab);
+  }
   HIPCHK(h, hipSetDevice(h->device));
-  const bool first = f->n_res < 0;
+  const bool first = f->n_res < 0, desc = f->orb != nullptr;
   const int M = t->max_matches, R = first ? 0 : f->n_res;
-  const bool cal = R >= 4;                                          // tracker.cpp:763
-  const int n_hyp_photo = std::max(1, std::min(R, pf->n_hyp));
+  const int n_hyp_photo = ph ? std::max(1, std::min(R, pf->n_hyp)) : 0;
   f->n_res = -1;                                                    // (whatever fails below: the next frame is a first frame)
   XKCHK(trk_push(t, img, stride));
-  const int sc = k->cur, sp = k->cur ^ 1;
   XkFrameArgs a = f->a;
   a.first = first ? 1 : 0;
   a.n_res = R;
   a.B = first ? 1 : std::min(M, R + f->cap_det);
   const size_t B = (size_t)a.B;
   a.l_prev = t->dist; a.l_cur = t->dist + 2 * B;
-  a.out = pf->out;
-  a.res_int = pf->res_int; a.l_iprev = pf->l_iprev; a.l_icur = pf->l_icur;
-  a.val1 = pf->val1; a.val_new = pf->val_new; a.val2 = pf->val2;
-  a.photo_st = p->st;
+  if (ph) {
+    a.out = pf->out;
+    a.res_int = pf->res_int; a.l_iprev = pf->l_iprev; a.l_icur = pf->l_icur;
+    a.val1 = pf->val1; a.val_new = pf->val_new; a.val2 = pf->val2;
+    a.photo_st = p->st;
+  }
   int *c = a.c;
-  const int *head = (const int *)pf->blk.h;
-  const bool desc = f->orb != nullptr;
+  unsigned char *r = ph ? pf->blk.h : f->blk.h;
+  const int *head = (const int *)r;
+  size_t out_bytes = sizeof(int) * XK_FC_N;
   if (first) {
-    XKCHK(frame_queue_detect(t, f, sc, nullptr, nullptr, 0, nullptr, true));
-    hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
-    photo_frame_queue_intensity(h, p, pf, k->slot[sc], a.det_res + 4, c + XK_FC_NEW, f->cap_new, pf->val_new);   // the WORKING plane, tracker.cpp:461
-    if (f->orb) XKCHK(frame_queue_describe(t, f, sc, nullptr));
+    XKCHK(frame_queue_detect(t, f, a, pf, k->cur, nullptr, 0, nullptr, nullptr));
     hipLaunchKernelGGL(xk_frame_first, dim3((f->cap_new + 255) / 256), dim3(256), 0, h->stream, a);
-    XKCHK(launched(h, "first photometric frame launch"));
-    HIPCHK(h, hipMemcpyAsync(pf->blk.h, a.out, sizeof(int) * XK_FC_N, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
   } else {
-    XkKltArgs ka;
-    // 2. calibrateImage, as xk_trk_photo_calibrate queues it, from the resident points and intensities
-    memset(p->n_hyp, 0, sizeof p->n_hyp);
-    if (cal) {
-      XKCHK(klt_queue_track(h, k, p->raw[sp], p->raw[sc], a.res_pts, p->klt_res, R, ka));
-      a.cal_kept = ka.kept.res;
-      XkPhotoGatherArgs ga{};
-      ga.kept = ka.kept; ga.prev_intensity = pf->res_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
-      hipLaunchKernelGGL(xk_photo_gather, dim3((R + 255) / 256), dim3(256), 0, h->stream, ga);
-      XkPhotoIntArgs ia = photo_int_args(p, p->raw[sc].lv[0], R);
-      ia.n_dev = ka.kept.res;
-      hipLaunchKernelGGL(xk_photo_intensity, dim3((R + XK_PHOTO_WAVES - 1) / XK_PHOTO_WAVES), dim3(64 * XK_PHOTO_WAVES), 0, h->stream, ia);
-      XKCHK(launched(h, "frame calibration launch"));
-      XkPhotoGainArgs g = photo_gain_args(p, 1, n_hyp_photo, seed_photo, 1);
-      XKCHK(photo_queue_gains(h, p, g));
-      if (p->sp && p->sp->state != XK_PSP_ESTIMATED) {
-        XkPspAccArgs sa = psp_acc_args(p, p->sp, 1);
-        sa.prev_f = a.res_pts; sa.keep_idx = ka.kept.keep_idx; sa.pix_cur = p->ixy; sa.o_hist = p->o_hist; sa.o_cur = p->value;
-        sa.off = p->off; sa.frame_back = p->frame_back; sa.per_frame = 1;
-        hipLaunchKernelGGL(xk_photo_sp_accumulate, dim3(1), dim3(64), 0, h->stream, sa);
+    // 2. calibrateImage as xk_trk_photo_calibrate queues it, from the resident points and intensities; with fewer than 4 features
+    // (tracker.cpp:763) only the correction, which corrects iff an earlier frame estimated
+    if (ph) {
+      memset(p->n_hyp, 0, sizeof p->n_hyp);
+      XkKeptPairs cal;
+      if (R >= 4) {
+        XKCHK(photo_queue_calibrate(t, a.res_pts, pf->res_int, R, n_hyp_photo, ph->seed, cal));
+        a.cal_kept = cal.res;
       }
+      XKCHK(photo_queue_correct(h, k, k->cur, 1));
     }
-    XKCHK(photo_queue_correct(h, k, sc, 1));                        // (fewer than 4 features: corrected iff an earlier frame estimated)
-    const XkKltPyr &prev = k->slot[sp], &cur = k->slot[sc];
     a.kept1 = klt_kept_at(f->klt_res[0], R);
     a.kept2 = klt_kept_at(f->klt_res[1], f->cap_new);
-    XkFundArgs fa{};
-    fa.dist = t->dist; fa.und = t->und; fa.pts = t->pts; fa.sc = t->sc;
-    fa.F = (double *)f->fund_res;
-    fa.kept = xk_kept_pairs(fa.F + 9, B);
-    fa.mask = xk_kept_pairs_end(fa.kept, B);
-    fa.n = a.B; fa.n_pts = 2 * a.B; fa.n_dev = c + XK_FC_TOTAL;
-    fa.fx = t->fx; fa.fy = t->fy; fa.cx = t->cx; fa.cy = t->cy; fa.s = t->s; fa.s_term = t->s_term;
-    fa.n_hyp = f->n_hyp; fa.t2 = f->threshold_px * f->threshold_px; fa.seed = (unsigned long long)seed;
+    XkFundArgs fa = trk_args(t, f->fund_res, a.B, c + XK_FC_TOTAL);
     a.kept3 = fa.kept;
-    t->n_hyp = 0;
-    // 3. featureTracking of the resident list on the WORKING planes; 4. the kept current features' intensities on the RAW current plane
-    if (R > 0) {
-      XKCHK(klt_queue_track(h, k, prev, cur, a.res_pts, f->klt_res[0], R, ka));
-      photo_frame_queue_kept_intensity(h, p, pf, p->raw[sc], a.kept1, R, pf->ixy1, pf->val1);
-    }
-    // 5. the overflow pass: both intensities move with their pair
+    t->n_hyp = 0;                                                   // (the scratch no longer holds the last xk_trk_filter_matches)
+    // 3. the resident list from the previous image to the current one, its post-filter; 4. the overflow pass (both intensities move with their pair)
+    if (R > 0) XKCHK(frame_queue_track(t, f, pf, 0, a.res_pts, R, nullptr));
     hipLaunchKernelGGL(xk_frame_overflow, dim3(1), dim3(256), sizeof(int) * (size_t)f->tiles_h * f->tiles_w, h->stream, a);
-    // 6. the re-detection on the PREVIOUS working plane, predicated, its threshold selected on the device
+    // 5. the re-detection on the PREVIOUS image, queued on every frame and predicated on the flag the overflow pass left.  (With
+    // n_feat_min = 0 the flag is never set: nothing is queued, and xk_frame_concat finds the zero count the overflow pass wrote.)
     if (f->n_feat_min > 0) {
-      XKCHK(frame_queue_detect(t, f, sp, c + XK_FC_REDETECT, a.l_prev, R, c + XK_FC_LEFT, true));
-      hipLaunchKernelGGL(xk_frame_gate, dim3(1), dim3(256), 0, h->stream, a);
-      photo_frame_queue_intensity(h, p, pf, prev, a.det_res + 4, c + XK_FC_NEW, f->cap_new, pf->val_new);
-      if (f->orb) XKCHK(frame_queue_describe(t, f, sp, c + XK_FC_REDETECT));
-      XKCHK(klt_queue_track(h, k, prev, cur, a.pts_new, f->klt_res[1], f->cap_new, ka, c + XK_FC_NEW));
-      photo_frame_queue_kept_intensity(h, p, pf, p->raw[sc], a.kept2, f->cap_new, pf->ixy2, pf->val2);
+      XKCHK(frame_queue_detect(t, f, a, pf, k->cur ^ 1, a.l_prev, R, c + XK_FC_LEFT, c + XK_FC_REDETECT));
+      XKCHK(frame_queue_track(t, f, pf, 1, a.pts_new, f->cap_new, c + XK_FC_NEW));
     }
     hipLaunchKernelGGL(xk_frame_concat, dim3(1), dim3(256), 0, h->stream, a);
-    // 7. the outlier removal
-    hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.B + 255) / 256), dim3(256), 0, h->stream, fa);
-    hipLaunchKernelGGL(xk_fund_solve, dim3((fa.n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, fa);
-    hipLaunchKernelGGL(xk_fund_score, dim3(fa.n_hyp), dim3(256), 0, h->stream, fa);
-    hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, fa);
-    // 8. the result block with the calibration's outcome in its head, and the new resident list
+    // 6. the outlier removal; 7. the result block (the calibration's outcome in its head) and the new resident list
+    XKCHK(trk_queue_ransac(h, fa, true, f->threshold_px, f->n_hyp, seed));
     hipLaunchKernelGGL(xk_frame_pack, dim3((a.B + 255) / 256), dim3(256), 0, h->stream, a);
-    XKCHK(launched(h, "photometric frame launch"));
-    HIPCHK(h, hipMemcpyAsync(pf->blk.h, a.out, xk_frame_photo_out_bytes(B, desc), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                     // the frame's one wait
+    out_bytes = ph ? xk_frame_photo_out_bytes(B, desc) : xk_frame_out_bytes(B, desc);
   }
+  XKCHK(launched(h, first ? "first frame launch" : "frame launch"));
+  HIPCHK(h, hipMemcpyAsync(r, a.out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));                       // the frame's one wait
   const int status = head[XK_FC_STATUS], m = head[XK_FC_MATCHES];
-  for (int j = 0; j <= XK_FC_TOTAL; ++j)
-    if (head[j] < 0 || (j != XK_FC_CAND && j != XK_FC_ACCEPTED && head[j] > M)) return fail(h, XK_EDEVICE, "xk_trk_photo_frame: counts out of range");
-  if (m < 0 || m > a.B || status < 0 || status > XK_FRAME_ETOTAL || head[XK_FC_RING_N] < 1 || head[XK_FC_RING_N] > XK_PHOTO_RING ||
-      head[XK_FC_CAL_KEPT] < 0 || head[XK_FC_CAL_KEPT] > R)
-    return fail(h, XK_EDEVICE, "xk_trk_photo_frame: counts out of range");
-  // the host's mirrors of the photometric state
-  p->ring_n = head[XK_FC_RING_N]; p->done = head[XK_FC_DONE];
-  if (head[XK_FC_CAL_KEPT] > 4) p->n_hyp[0] = n_hyp_photo;
+  bool ok = m >= 0 && m <= a.B && status >= 0 && status <= XK_FRAME_ETOTAL;
+  for (int j = 0; j <= XK_FC_TOTAL; ++j) ok = ok && head[j] >= 0 && (j == XK_FC_CAND || j == XK_FC_ACCEPTED || head[j] <= M);
+  if (ph) ok = ok && head[XK_FC_RING_N] >= 1 && head[XK_FC_RING_N] <= XK_PHOTO_RING && head[XK_FC_CAL_KEPT] >= 0 && head[XK_FC_CAL_KEPT] <= R;
+  if (!ok) return fail_at(h, XK_EDEVICE, who, "counts out of range");
   out->n_tracked = head[XK_FC_TRACKED]; out->n_left = head[XK_FC_LEFT]; out->redetected = head[XK_FC_REDETECT];
   out->n_candidates = head[XK_FC_CAND]; out->n_accepted = head[XK_FC_ACCEPTED]; out->n_new_tracked = head[XK_FC_NEW_TRACKED];
   out->winner = head[XK_FC_WINNER];
-  out->n_cal_kept = head[XK_FC_CAL_KEPT]; out->estimated = head[XK_FC_ESTIMATED]; out->done = head[XK_FC_DONE];
-  out->support = head[XK_FC_SUPPORT];
-  const unsigned char *r = pf->blk.h;
-  if (!first) {
-    const double *calv = (const double *)(r + xk_frame_out_cal(B, desc));
-    out->a_rel = calv[0]; out->b_rel = calv[1];
-    memcpy(out->frame_ab, calv + 2, sizeof out->frame_ab);
+  if (ph) {                                                         // the calibration's outcome, and the host's mirrors of the photometric state
+    p->ring_n = head[XK_FC_RING_N]; p->done = head[XK_FC_DONE];
+    if (head[XK_FC_CAL_KEPT] > 4) p->n_hyp[0] = n_hyp_photo;
+    pout->n_cal_kept = head[XK_FC_CAL_KEPT]; pout->estimated = head[XK_FC_ESTIMATED]; pout->done = head[XK_FC_DONE];
+    pout->support = head[XK_FC_SUPPORT];
+    if (!first) {
+      const double *calv = (const double *)(r + xk_frame_out_cal(B, desc));
+      pout->a_rel = calv[0]; pout->b_rel = calv[1];
+      memcpy(pout->frame_ab, calv + 2, sizeof pout->frame_ab);
+    }
   }
-  if (status != 0) return fail_at(h, XK_ECAPACITY, "xk_trk_photo_frame", frame_status_text(status));
+  if (status != 0) return fail_at(h, XK_ECAPACITY, who, frame_status_text(status));
   if (first) {
     f->n_res = head[XK_FC_NEW];
     return XK_OK;
@@ -2118,9 +2014,36 @@ extern "C" int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int strid
   memcpy(out->score, r + xk_frame_out_score(B), sizeof(int) * (size_t)m);
   memcpy(out->origin, r + xk_frame_out_origin(B), sizeof(int) * (size_t)m);
   memcpy(out->tiles, r + xk_frame_out_tiles(B), sizeof(int) * 4 * (size_t)m);
-  if (f->orb) memcpy(out->desc, r + xk_frame_out_desc(B), 32 * (size_t)m);
-  memcpy(out->prev_intensity, r + xk_frame_out_int(B, desc, 0), sizeof(double) * (size_t)m);
-  memcpy(out->cur_intensity, r + xk_frame_out_int(B, desc, 1), sizeof(double) * (size_t)m);
+  if (desc) memcpy(out->desc, r + xk_frame_out_desc(B), 32 * (size_t)m);
+  if (ph) {
+    memcpy(pout->prev_intensity, r + xk_frame_out_int(B, desc, 0), sizeof(double) * (size_t)m);
+    memcpy(pout->cur_intensity, r + xk_frame_out_int(B, desc, 1), sizeof(double) * (size_t)m);
+  }
   f->n_res = m;
   return XK_OK;
+}
+
+/* Tracker::track of a build without PHOTOMETRIC_CALI */
+extern "C" int xk_trk_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, xk_trk_frame_out *out) {
+  if (!t) return XK_EINVAL;
+  xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame", "xk_trk_frame_setup");
+  if (!f) return XK_EINVAL;
+  if (t->klt->photo) return fail(t->h, XK_EINVAL, "xk_trk_frame: a photometric setup is in place (the photometric frame is xk_trk_photo_frame)");
+  return frame_run(t, f, "xk_trk_frame", img, stride, seed, out, nullptr);
+}
+
+/* Tracker::track of a build with PHOTOMETRIC_CALI.  xk_trk_photo_frame_out begins with the fields of xk_trk_frame_out: the body fills those
+ * through a copy of that part, and the outputs this frame adds in place */
+extern "C" int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, unsigned long seed_photo,
+                                  xk_trk_photo_frame_out *out) {
+  static_assert(offsetof(xk_trk_photo_frame_out, prev_intensity) == sizeof(xk_trk_frame_out), "xk_trk_photo_frame_out begins with xk_trk_frame_out");
+  if (!t) return XK_EINVAL;
+  xk_frm *f = photo_frame_of(t, "xk_trk_photo_frame");
+  if (!f) return XK_EINVAL;
+  const frame_photo ph{seed_photo, out};
+  xk_trk_frame_out o;
+  if (out) memcpy(&o, out, sizeof o);
+  const int rc = frame_run(t, f, "xk_trk_photo_frame", img, stride, seed, out ? &o : nullptr, &ph);
+  if (out) memcpy(out, &o, sizeof o);
+  return rc;
 }

@@ -289,32 +289,38 @@ class Klt(_Trk):
                                    desc=np.zeros((m, 32), np.uint8))
         return self._frame_buf
 
+    def _frame_call(self, entry, img, o, arrays, seeds, calibration=None):
+        """What frame() and photo_frame() share: the image check, `arrays` wired into the struct o by field name, the call of `entry`
+        with `seeds`, the counts, and on a failure the XkError with `counts` (and with `calibration`, a function of o, its result as
+        `calibration`) -> the counts, the calibration's outcome and the first n_matches rows of every array."""
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] != self.height or img.shape[1] < self.width:
+            raise ValueError(entry[len("xk_trk_"):] + ": a uint8 image of the set-up height and at least the set-up width")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        types = dict(o._fields_)
+        for name, v in arrays.items():
+            setattr(o, name, v.ctypes.data_as(types[name]))
+        rc = getattr(self.L, entry)(self.p, img.ctypes.data_as(c_ub), C.c_int(img.strides[0]), *(C.c_ulong(s) for s in seeds), C.byref(o))
+        counts = {k: int(getattr(o, k)) for k in FrameOut.COUNTS}
+        cal = calibration(o) if calibration else {}
+        if rc != 0:
+            err = self._error(rc, entry)
+            err.counts = counts
+            if calibration:
+                err.calibration = cal
+            raise err
+        m = counts["n_matches"]
+        out = dict(counts, **cal)
+        out.update({k: v[:m].copy() for k, v in arrays.items()})
+        return out
+
     def frame(self, img, seed=0):
         """xk_trk_frame, Tracker::track of one image (uint8 [height, >= width]) -> dict of the counts n_tracked, n_left, redetected,
         n_candidates, n_accepted, n_new_tracked, n_matches, winner, and per match prev_xy, cur_xy (undistorted fp64 pixels),
         prev_dist_xy, cur_dist_xy, score, origin, tiles int32 [m, 4] (previous row, column, current row, column), desc uint8
         [m, 32].  A first frame returns no matches.  On XK_ECAPACITY the XkError carries the counts reached as `counts`."""
-        img = np.asarray(img)
-        if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] != self.height or img.shape[1] < self.width:
-            raise ValueError("frame: a uint8 image of the set-up height and at least the set-up width")
-        if img.strides[1] != 1:
-            img = np.ascontiguousarray(img)
-        b, o = self._frame_arrays(), FrameOut()
-        for name in ("prev_xy", "cur_xy", "prev_dist_xy", "cur_dist_xy"):
-            setattr(o, name, b[name].ctypes.data_as(c_dp))
-        for name in ("score", "origin", "tiles"):
-            setattr(o, name, b[name].ctypes.data_as(c_ip))
-        o.desc = b["desc"].ctypes.data_as(c_ub)
-        rc = self.L.xk_trk_frame(self.p, img.ctypes.data_as(c_ub), C.c_int(img.strides[0]), C.c_ulong(seed), C.byref(o))
-        counts = {k: int(getattr(o, k)) for k in FrameOut.COUNTS}
-        if rc != 0:
-            err = self._error(rc, "xk_trk_frame")
-            err.counts = counts
-            raise err
-        m = counts["n_matches"]
-        out = dict(counts)
-        out.update({k: v[:m].copy() for k, v in b.items()})
-        return out
+        return self._frame_call("xk_trk_frame", img, FrameOut(), self._frame_arrays(), (seed,))
 
     def frame_features(self):
         """The resident list as the device holds it -> dict of dist_xy fp64 [n, 2], score int32 [n], desc uint8 [n, 32] (zeros
@@ -344,34 +350,15 @@ class Klt(_Trk):
         cur_intensity fp64 [m] (getIntensity of both features of each match), n_cal_kept, estimated (bool), done (bool), support,
         a_rel, b_rel, frame_ab fp64 [4] (the calibration's outcome, as photo_calibrate's).  On XK_ECAPACITY the XkError carries the
         counts reached as `counts` and the calibration's outcome as `calibration`."""
-        img = np.asarray(img)
-        if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] != self.height or img.shape[1] < self.width:
-            raise ValueError("photo_frame: a uint8 image of the set-up height and at least the set-up width")
-        if img.strides[1] != 1:
-            img = np.ascontiguousarray(img)
-        b, m = self._frame_arrays(), self.max_features
+        m = self.max_features
         if self._photo_frame_buf is None or len(self._photo_frame_buf["prev_intensity"]) != m:
             self._photo_frame_buf = dict(prev_intensity=np.zeros(m), cur_intensity=np.zeros(m))
-        b = dict(b, **self._photo_frame_buf)
-        o = PhotoFrameOut()
-        for name in ("prev_xy", "cur_xy", "prev_dist_xy", "cur_dist_xy", "prev_intensity", "cur_intensity"):
-            setattr(o, name, b[name].ctypes.data_as(c_dp))
-        for name in ("score", "origin", "tiles"):
-            setattr(o, name, b[name].ctypes.data_as(c_ip))
-        o.desc = b["desc"].ctypes.data_as(c_ub)
-        rc = self.L.xk_trk_photo_frame(self.p, img.ctypes.data_as(c_ub), C.c_int(img.strides[0]), C.c_ulong(seed), C.c_ulong(seed_photo),
-                                       C.byref(o))
-        counts = {k: int(getattr(o, k)) for k in FrameOut.COUNTS}
-        cal = dict(n_cal_kept=int(o.n_cal_kept), estimated=bool(o.estimated), done=bool(o.done), support=int(o.support), a_rel=float(o.a_rel),
-                   b_rel=float(o.b_rel), frame_ab=np.array(o.frame_ab[:], np.float64))
-        if rc != 0:
-            err = self._error(rc, "xk_trk_photo_frame")
-            err.counts, err.calibration = counts, cal
-            raise err
-        n = counts["n_matches"]
-        out = dict(counts, **cal)
-        out.update({k: v[:n].copy() for k, v in b.items()})
-        return out
+
+        def calibration(o):
+            return dict(n_cal_kept=int(o.n_cal_kept), estimated=bool(o.estimated), done=bool(o.done), support=int(o.support),
+                        a_rel=float(o.a_rel), b_rel=float(o.b_rel), frame_ab=np.array(o.frame_ab[:], np.float64))
+        return self._frame_call("xk_trk_photo_frame", img, PhotoFrameOut(), dict(self._frame_arrays(), **self._photo_frame_buf),
+                                (seed, seed_photo), calibration)
 
     def photo_frame_intensities(self):
         """The resident intensities beside frame_features() -> fp64 [n]."""
