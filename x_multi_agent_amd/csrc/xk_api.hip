@@ -98,6 +98,8 @@ static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, x
   HIPCHK(h, hipMemset(h->d_done_cnt, 0, sizeof(unsigned)));
   h->h_win = (double *)calloc(7 * (size_t)n_poses_max, sizeof(double));
   if (!h->h_win) return fail(h, XK_EDEVICE, "host allocation");
+  h->upd.ct = (double *)calloc((size_t)h->n, sizeof(double));   // correction_total of a queued pass (XkPending)
+  if (!h->upd.ct) return fail(h, XK_ENOMEM, "host allocation");
   h->d_p = h->d_q + 4 * (size_t)n_poses_max;
   HIPCHK(h, dalloc(&h->d_obs, 2 * h->obs_cap + ((size_t)k_max + 2) / 2 + 1));
   h->d_trk_off = (int *)(h->d_obs + 2 * h->obs_cap);
@@ -281,7 +283,7 @@ extern "C" int xk_destroy(xk_handle *h) {
   if (h->d_R2) hipFree(h->d_R2);
   if (h->d_aux) hipFree(h->d_aux);
   if (h->d_Taug) hipFree(h->d_Taug);
-  delete h->fused_ct;
+  free(h->upd.ct);
   if (h->d_Psnap) hipFree(h->d_Psnap);
   if (h->d_Psnap2) hipFree(h->d_Psnap2);
   if (h->d_fq) hipFree(h->d_fq);
@@ -347,6 +349,7 @@ static char *stage_slot(xk_handle *h, size_t bytes) {
 // The completion markers kernels write into pinned host memory behind their results (xk_apply_update has the whole story).
 // XK_SPIN_DONE=0 (lab build): no marker is asked for, the stream's completion signal is waited for instead.
 static int spin_done() { static const int on = env_int("XK_SPIN_DONE", 1); return on; }
+static unsigned long long *done_marker(xk_handle *h) { return reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2); }   // (behind the correction and the status words)
 // Polls *word (acquire) until it holds seq: true when it was seen.  False after ~1 s, or as soon as a kernel has left a status
 // word (a launch that gave up writes no marker): the caller then waits for the stream.
 static bool wait_marker(xk_handle *h, const unsigned long long *word, unsigned long long seq) {
@@ -387,7 +390,7 @@ extern "C" int xk_stage_window(xk_handle *h, const double *C_q_G, const double *
     h->win_valid = true;
     h->n_poses = n_poses;
   }
-  h->have_rows = h->have_R = false;
+  pending_drop(h);
   h->ms_built = false;
   return XK_OK;
 }
@@ -430,7 +433,7 @@ extern "C" int xk_stage_tracks_end(xk_handle *h) {
     memcpy(h->h_trk_off, trk_off, sizeof(int) * (K + 1));
   }
   h->K = K;
-  h->have_rows = h->have_R = false;
+  pending_drop(h);
   h->h_pin_i[0] = lmax;                                                 // the longest track, validated against n_poses at build time
   return XK_OK;
 }
@@ -478,7 +481,7 @@ extern "C" int xk_stage_slam(xk_handle *h, const double *feat, const int *anchor
     HIPCHK(h, hipMemcpyAsync(h->d_tsz, si + M, sizeof(int) * M, hipMemcpyHostToDevice, h->stream));
   }
   h->M = M;
-  h->have_rows = h->have_R = false;
+  pending_drop(h);
   return XK_OK;
 }
 
@@ -504,7 +507,7 @@ extern "C" int xk_stage_msckf_slam(xk_handle *h, const int *trk_off, const doubl
   h->K2 = K2;
   h->ms_built = false;
   h->h_pin_i[1] = lmax;
-  h->have_rows = h->have_R = false;
+  pending_drop(h);
   return XK_OK;
 }
 
@@ -552,6 +555,108 @@ extern "C" int xk_stage_sun_angle(xk_handle *h, const double q_xyzw[4], double x
   return XK_OK;
 }
 
+// ---------------------------------------------------------------------------
+// StateManager::manage on the resident covariance (SURVEY 8(f) rank 1)
+// ---------------------------------------------------------------------------
+static int congruence(xk_handle *h, const int *row_ptr, const int *col_idx, const double *val, int nnz, const double *q,
+                      int qdim, int qoff) {
+  const int n = h->n;
+  HIPCHK(h, hipSetDevice(h->device));
+  // the operand goes through the pinned ring: nothing here waits for the device (a frame applies two or three of these
+  // back to back -- IMU steps, manage() -- before the update's one synchronisation)
+  // (+ the window lists staged since the last launch that needed them: they ride in this copy and the kernel leaves them in d_q)
+  const int wn = h->win_pending ? 7 * h->n_poses : 0;
+  const size_t vb = sizeof(double) * ((size_t)nnz + (q ? (size_t)qdim * qdim : 0) + wn), ib = sizeof(int) * ((size_t)n + 1 + nnz);
+  char *st = stage_slot(h, vb + ib);
+  if (!st) return fail(h, XK_ECAPACITY, "sparse operand exceeds the staging slot");
+  double *sv = (double *)st;
+  int *si = (int *)(st + vb);
+  if (nnz) memcpy(sv, val, sizeof(double) * nnz);
+  if (q) memcpy(sv + nnz, q, sizeof(double) * (size_t)qdim * qdim);
+  const size_t woff = (size_t)nnz + (q ? (size_t)qdim * qdim : 0);
+  if (wn) memcpy(sv + woff, h->h_win, sizeof(double) * wn);
+  memcpy(si, row_ptr, sizeof(int) * (n + 1));
+  if (nnz) memcpy(si + n + 1, col_idx, sizeof(int) * nnz);
+  // [values | additive block | row pointers | column indices] in one copy
+  HIPCHK(h, hipMemcpyAsync(h->d_csr_v, st, vb + ib, hipMemcpyHostToDevice, h->stream));
+  double *dq = q ? h->d_csr_v + nnz : nullptr;
+  const int *d_rp = (const int *)((const char *)h->d_csr_v + vb);
+  XkCongArgs a{h->d_P, h->d_Pout, n, d_rp, d_rp + n + 1, h->d_csr_v, dq, qdim, qoff, wn ? h->d_csr_v + woff : nullptr, h->d_q, wn};
+  h->win_pending = false;
+  hipLaunchKernelGGL(xk_congruence, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "congruence launch", e);
+  std::swap(h->d_P, h->d_Pout);
+  pending_drop(h);
+  return XK_OK;
+}
+
+extern "C" int xk_cov_congruence(xk_handle *h, const int *row_ptr, const int *col_idx, const double *val, int nnz) {
+  if (!h || !row_ptr || nnz < 0 || (nnz > 0 && (!col_idx || !val))) return XK_EINVAL;
+  const int n = h->n;
+  if (row_ptr[0] != 0 || row_ptr[n] != nnz) return fail(h, XK_EINVAL, "CSR row pointers inconsistent with nnz");
+  if ((size_t)nnz > h->csr_cap) return fail(h, XK_ECAPACITY, "sparse operand has more than 24 n non-zeros");
+  for (int i = 0; i < n; ++i)
+    if (row_ptr[i + 1] < row_ptr[i]) return fail(h, XK_EINVAL, "CSR row pointers not monotone");
+  for (int k = 0; k < nnz; ++k)
+    if (col_idx[k] < 0 || col_idx[k] >= n) return fail(h, XK_EINVAL, "CSR column index outside the state");
+  return congruence(h, row_ptr, col_idx, val, nnz, nullptr, 0, 0);
+}
+
+// Propagator::propagateCovarianceMatrices (propagator.cpp:166-205) on the resident covariance:
+//   P_ii <- F P_ii F^T + Q,  P_iv <- F P_iv,  P_vi <- P_vi F^T (computed on its own, as the reference insists),  P_vv kept
+extern "C" int xk_cov_propagate(xk_handle *h, const double *f_d, int ldf, const double *q_d, int ldq) {
+  if (!h || !f_d || !q_d || ldf < XK_CORE || ldq < XK_CORE) return XK_EINVAL;
+  const int n = h->n;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkPropArgs a;
+  a.P = h->d_P; a.n = n;
+  for (int c = 0; c < XK_CORE; ++c)
+    for (int r = 0; r < XK_CORE; ++r) {
+      a.FQ[r + XK_CORE * c] = f_d[r + (size_t)c * ldf];
+      a.FQ[225 + r + XK_CORE * c] = q_d[r + (size_t)c * ldq];
+    }
+  hipLaunchKernelGGL(xk_cov_propagate_k, dim3(1 + (2 * (n - XK_CORE) + 255) / 256), dim3(256), 0, h->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "propagate launch", e);
+  pending_drop(h);
+  return XK_OK;
+}
+
+extern "C" int xk_upload_P(xk_handle *h, const double *P, int ldp, int n) {
+  if (!h || !P || n != h->n || ldp < n) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpy2DAsync(h->d_P, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
+                             hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+extern "C" int xk_download_P(xk_handle *h, double *P, int ldp, int n) {
+  if (!h || !P || n != h->n || ldp < n) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpy2DAsync(P, sizeof(double) * ldp, h->d_P, sizeof(double) * n, sizeof(double) * n, n,
+                             hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// Keeps / brings back a copy of the resident covariance on the device (restore = 0: save, 1: restore).  Benchmarks
+// use it to replay a frame from the same prior without a PCIe upload.
+extern "C" int xk_snapshot_P(xk_handle *h, int restore) {
+  if (!h || restore < 0 || restore > 3) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t bytes = sizeof(double) * (size_t)h->n * h->n;
+  double *&slot = (restore >= 2) ? h->d_Psnap2 : h->d_Psnap;     // 0 / 1: the caller's slot; 2 / 3: the filter loop's own (x::Ekf)
+  const bool back = restore & 1;
+  if (!slot) {
+    if (back) return fail(h, XK_EINVAL, "xk_snapshot_P: nothing saved");
+    HIPCHK(h, dalloc(&slot, (size_t)h->n * h->n));
+  }
+  HIPCHK(h, hipMemcpyAsync(back ? h->d_P : slot, back ? slot : h->d_P, bytes, hipMemcpyDeviceToDevice, h->stream));
+  return XK_OK;
+}
+
 extern "C" int xk_msckf_slam_results(xk_handle *h, int *inlier, double *gamma, double *H1, int ldh1, double *H2, int ldh2,
                                      double *r1, double *features) {
   if (!h) return XK_EINVAL;
@@ -592,9 +697,6 @@ static bool inv3(const double *a /*col-major*/, double *o) {
   o[6] = (a[3] * a[7] - a[6] * a[4]) * id; o[7] = (a[6] * a[1] - a[0] * a[7]) * id; o[8] = (a[0] * a[4] - a[3] * a[1]) * id;
   return true;
 }
-
-static int congruence(xk_handle *h, const int *row_ptr, const int *col_idx, const double *val, int nnz, const double *q,
-                      int qdim, int qoff);
 
 // StateManager::initMsckfSlamFeatures + addFeatureStates (state_manager.cpp:151-174,199-226) on the resident
 // covariance: with G = H2^-1 H1 the new feature states are  f - G corr + H2^-1 r1,  their covariance blocks
@@ -667,845 +769,15 @@ extern "C" int xk_init_standard_slam_features(xk_handle *h, int n_features, int 
   return congruence(h, rp.data(), ci.data(), v.data(), (int)ci.size(), Q.data(), 3 * k, ns);
 }
 
-extern "C" int xk_upload_P(xk_handle *h, const double *P, int ldp, int n) {
-  if (!h || !P || n != h->n || ldp < n) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_P, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return XK_OK;
-}
-
-extern "C" int xk_download_P(xk_handle *h, double *P, int ldp, int n) {
-  if (!h || !P || n != h->n || ldp < n) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpy2DAsync(P, sizeof(double) * ldp, h->d_P, sizeof(double) * n, sizeof(double) * n, n,
-                             hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return XK_OK;
-}
-
 // ---------------------------------------------------------------------------
-// launch helpers (all asynchronous on h->stream)
+// the update path: rows, compression, Kalman update, the staged and queued entries, xk_apply_update, measurement
 // ---------------------------------------------------------------------------
-
-static int split_plan(const xk_handle *h);
-static long split_rows_nominal(const xk_handle *h);
-
-// The range / sun rows of this update (xk_aux.hip.h), queued behind the per-feature kernels: one workgroup, no host synchronisation.
-// Their variances follow the REFERENCE's stack, not this engine's schedule: the reference compresses when its rows -- every MSCKF and
-// MSCKF-SLAM track's 2 L - 3, the SLAM features' 2 M, 1 range row, 2 sun rows, accepted or not -- exceed n + 1
-// (vio_updater.cpp:487-490), and then gives EVERY row sigma_img^2 (:507-509): a compressed range row weighs as if sigma_range were
-// sigma_img.  Uncompressed, each row keeps its own: sigma_range^2 (1 for a gated-out row), var_sun.
-static int launch_aux(xk_handle *h, double sigma_img) {
-  XkAuxIn in = h->aux_in;
-  in.has_range = (h->aux_mask & 1) ? 1 : 0;
-  in.has_sun = (h->aux_mask & 2) ? 1 : 0;
-  if (in.has_range) {
-    if (h->M < 3) return fail(h, XK_EINVAL, "range row: fewer than 3 SLAM features staged");
-    for (int j = 0; j < 3; ++j)
-      if (in.facet[j] >= h->M) return fail(h, XK_EINVAL, "range row: facet feature id outside the staged SLAM features");
-  }
-  const long nominal = split_rows_nominal(h) + 2L * h->M + h->naux;
-  in.compressed = nominal > (long)h->n + 1 ? 1 : 0;
-  in.var_comp = sigma_img * sigma_img;
-  in.chi1 = XK_CHI2_090[1];
-  XkAuxArgs a;
-  a.q = h->d_q; a.p = h->d_p; a.n_poses = h->n_poses; a.N = h->N;
-  a.feat = h->d_feat; a.anchor = h->d_anchor; a.P = h->d_P; a.n = h->n;
-  a.in = in;                                      // (by value: no host-to-device copy, no staging slot, replays included)
-  a.rows = h->d_aux;
-  a.rdiag = a.rows + 3 * ((size_t)h->n + 1);
-  a.flags = a.rdiag + 3;
-  hipLaunchKernelGGL(xk_aux_rows, dim3(1), dim3(XK_AUX_THREADS), 0, h->stream, a);
-  return XK_OK;
-}
-
-// replay: the build of an update that is being redone (a retry) or repeated (xk_run_steps / xk_bench_staged past the first step) -- the
-// range / sun rows of that update are built again; any other build takes what has been staged since the last one (possibly nothing).
-static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
-  if (h->n_poses < 2) return fail(h, XK_EINVAL, "window not staged");
-  if (h->K > 0 && h->h_pin_i[0] > h->n_poses) return fail(h, XK_EINVAL, "track longer than the staged window");
-  const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
-  XkFeatArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  size_t feat_lds = 0;
-  { int rcw = flush_window(h); if (rcw != XK_OK) return rcw; }   // (normally carried by the frame's congruence launch already)
-  h->plan = split_plan(h);
-  outcome_release_R2(h->last);                    // (d_R2 holds nothing of THIS update until launch_compress writes it)
-  if (h->K > 0) {
-    XkFeatArgs &a = fa;
-    a.q = h->d_q; a.p = h->d_p; a.n_poses = h->n_poses; a.n_poses_max = h->N;
-    a.trk_off = h->d_trk_off; a.obs = h->d_obs; a.K = h->K;
-    a.P = h->d_P; a.n = h->n; a.var_img = sigma_img * sigma_img; a.chi95 = h->d_chi95;
-    a.A = h->d_A; a.DB = h->DB; a.C1P = h->C1P; a.na = h->na;
-    // factor records instead of tiles: H0 never visits HBM.  Whoever compresses forms its rows from them -- the tile workgroups
-    // of the single launch (narrow systems; next to the wide geometry's 80-row tiles and 2 lanes per column forming the entries
-    // costs more than the tiles' trip through HBM -- config 2: 1546 -> 1521 updates/s -- so those keep their tiles), or the
-    // first pass of the multi-launch schedule (128-row slots: always; 64-row slots: when the single launch was armed and then
-    // not taken or gave up).
-    h->rows_compact = h->opt_hlite && h->d_Hc && !h->feat_dbg && h->plan != 3 &&      // (an uncompressed small stack is copied from tiles)
-                      (h->DB == 128 || (h->opt_resident && h->persist_ok && (h->C1 <= XkPipeNarrow::COLS || h->opt_hlite >= 2)));   // (lab: 2 = the wide geometry too)
-    a.Hc = h->rows_compact ? h->d_Hc : nullptr; a.hs = h->hc_stride; a.hcvr = xk_hc_vr(h->DB);
-    a.tile_rows = h->d_tile_rows; a.inlier = h->d_inl; a.gamma = h->d_gam; a.gpf = h->d_gpf; a.gn_iters = h->d_gn;
-    a.gpf_in = nullptr; a.up_out = nullptr; a.batch = nullptr; a.dbg = h->feat_dbg; a.gate_form = h->opt_gate_form;
-    a.inlier_h = h->h_flag_i; a.gamma_h = h->h_flag_d;     // gate results also straight into the pinned flag cache
-    const bool packed = xk_feature_packed(h->n_poses);      // windows of more than 33 poses: gate matrix as a packed triangle
-    feat_lds = xk_feature_lds_bytes(h->n_poses, packed);
-    // (with SLAM features the tracks and the features share one launch, below)
-    if (packed) hipLaunchKernelGGL(xk_msckf_feature_packed, dim3(h->K), dim3(XK_FEAT_THREADS), feat_lds, h->stream, a);
-    else if (h->M == 0 || h->feat_dbg) hipLaunchKernelGGL(xk_msckf_feature, dim3(h->K), dim3(XK_FEAT_THREADS), feat_lds, h->stream, a);
-  }
-  if (h->K2 > 0) {   // tracks that become persistent features this frame: tiles K .. K + K2 - 1
-    if (h->h_pin_i[1] > h->n_poses) return fail(h, XK_EINVAL, "MSCKF-SLAM track longer than the staged window");
-    XkTriMultiArgs ta{h->d_q, h->d_p, h->d_obs2, 0, h->d_gpf2, h->d_gn2, h->d_trk2_off, h->n_poses};
-    hipLaunchKernelGGL(xk_triangulate_multi, dim3(h->K2), dim3(64), 0, h->stream, ta);
-    XkSlamInitArgs a;
-    a.q = h->d_q; a.p = h->d_p; a.n_poses = h->n_poses; a.n_poses_max = h->N;
-    a.trk_off = h->d_trk2_off; a.obs = h->d_obs2; a.gpf = h->d_gpf2;
-    a.P = h->d_P; a.n = h->n; a.na = h->na; a.var_img = sigma_img * sigma_img; a.chi95 = h->d_chi95;
-    a.A = h->d_A + (size_t)h->K * h->DB * h->C1P; a.DB = h->DB; a.C1P = h->C1P; a.W = h->d_W2;
-    a.tile_rows = h->d_tile_rows + h->K; a.inlier = h->d_inl2; a.gamma = h->d_gam2;
-    a.H1 = h->d_H1; a.H2 = h->d_H2; a.r1 = h->d_r1; a.features = h->d_feat2;
-    const size_t lds = xk_slaminit_lds_bytes(h->n_poses);
-    if (!h->attr_slaminit) {   // per handle = per device: a process may hold handles on several GPUs
-      hipFuncSetAttribute((const void *)xk_msckf_slam_init, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-      h->attr_slaminit = true;
-    }
-    hipLaunchKernelGGL(xk_msckf_slam_init, dim3(h->K2), dim3(XK_FEAT_THREADS), lds, h->stream, a);
-    h->ms_built = true;
-  }
-  if (h->M > 0) {
-    if (h->anchor_max >= h->n_poses) return fail(h, XK_EINVAL, "SLAM anchor outside the staged window");
-    XkSlamArgs s;
-    s.q = h->d_q; s.p = h->d_p; s.n_poses = h->n_poses; s.n_poses_max = h->N;
-    s.feat = h->d_feat; s.anchor_idxs = h->d_anchor; s.track_sizes = h->d_tsz; s.z_last = h->d_zlast; s.M = h->M;
-    s.P = h->d_P; s.n = h->n; s.var_img = sigma_img * sigma_img; s.chi90 = h->d_chi90; s.chi_len = XK_CHI2_LEN;
-    s.A = h->d_A + (size_t)(h->K + h->K2) * h->DB * h->C1P; s.DB = h->DB; s.C1P = h->C1P; s.na = h->na;
-    s.inlier = h->d_inl_s; s.gamma = h->d_gam_s;
-    if (h->K > 0 && !h->feat_dbg && !xk_feature_packed(h->n_poses)) hipLaunchKernelGGL(xk_build_rows, dim3(h->K + h->M), dim3(XK_FEAT_THREADS), feat_lds, h->stream, fa, s);
-    else hipLaunchKernelGGL(xk_slam_rows, dim3(h->M), dim3(64), 0, h->stream, s);
-    // rows per SLAM tile (gated-out features leave zero rows, as in the reference)
-    std::vector<int> tr(slam_tiles);
-    for (int t = 0; t < slam_tiles; ++t) tr[t] = std::min(h->DB, 2 * h->M - t * h->DB);
-    for (int t = 0; t < slam_tiles; ++t) h->h_pin_i[8 + t] = tr[t];
-    if (hipMemcpyAsync(h->d_tile_rows + h->K + h->K2, h->h_pin_i + 8, sizeof(int) * slam_tiles, hipMemcpyHostToDevice,
-                       h->stream) != hipSuccess)
-      return fail(h, XK_EDEVICE, "tile_rows upload");
-  }
-  if (h->aux_staged || !replay) {                  // (a replay keeps the rows of the update it repeats)
-    h->aux_mask = h->aux_staged;
-    h->aux_staged = 0;
-  }
-  h->naux = ((h->aux_mask & 1) ? 1 : 0) + ((h->aux_mask & 2) ? 2 : 0);
-  if (h->naux) { int rca = launch_aux(h, sigma_img); if (rca != XK_OK) return rca; }
-  h->sigma_img = sigma_img;
-  h->have_rows = true;
-  h->have_R = false;
-  h->compress_deferred = false;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "build launch", e);
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// compression of the staged rows: schedules, the system they leave for the update, status words
-// ---------------------------------------------------------------------------
-#include "xk_compress.hip.h"
-
-static void gemm(xk_handle *h, const XkGemmArgs &g) {
-  const int tiles = xk_gemm_grid(g);
-  if (tiles <= 0) return;
-  hipLaunchKernelGGL(xk_gemm_f64, dim3(tiles), dim3(64 * XK_GEMM_WAVES), 0, h->stream, g);
-}
-
-
-// Kalman algebra on the device (updater.cpp:117-141 / :144-161).  ev (optional)
-// = {before, after-gemm-part...} is not used here; stage split is timed by the caller.
-static int launch_update(xk_handle *h, const UpdateSpec &u_in) {
-  UpdateSpec u = u_in;
-  if (u.naux > 0) {
-    // the range / sun rows join the system as built (they never go through the QR): [T ; H_aux]^T [T ; H_aux] is the Gram matrix of the
-    // whole stack, and the same for the residual -- the argument of the split form for the SLAM rows.  The sun rows touch core columns
-    // 6..8, so the system is widened to all n columns, with one variance per row (xk_aux.hip.h chose the rows' own).
-    if (u.c + u.naux > h->CM) return fail(h, XK_ECAPACITY, "measurement rows exceed workspace");
-    XkAuxStackArgs s;
-    s.T = u.T; s.str = u.str; s.stc = u.stc; s.c = u.c; s.kdim = u.kdim; s.col0 = u.col0;
-    s.z = u.z; s.sz = u.sz; s.rdiag = u.rdiag; s.rscalar = u.rscalar;
-    s.aux = h->d_aux; s.aux_rdiag = s.aux + 3 * ((size_t)h->n + 1); s.naux = u.naux;
-    s.n = h->n; s.out = h->d_Taug; s.out_rdiag = h->d_Taug + (size_t)h->CM * (h->n + 1);
-    hipLaunchKernelGGL(xk_aux_stack, dim3(u.c + u.naux), dim3(256), 0, h->stream, s);
-    u.T = s.out; u.str = h->n + 1; u.stc = 1; u.c += u.naux; u.kdim = h->n; u.col0 = 0;
-    u.z = s.out + h->n; u.sz = h->n + 1; u.rdiag = s.out_rdiag; u.tri = 0; u.naux = 0;
-  }
-  const int c = u.c, n = h->n, LDA = h->LDA;
-  if (c <= 0 || c > h->CM) return fail(h, XK_ECAPACITY, "measurement rows exceed workspace");
-  XkGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  // W = T * Pin[col0:col0+kdim, :]                      (H P)
-  g.A = u.T; g.sar = u.str; g.sac = u.stc;
-  g.B = u.Pin + u.col0; g.sbr = 1; g.sbc = n;
-  g.C = h->d_Maug + c; g.scr = LDA; g.scc = 1;
-  g.D = g.C; g.sdr = LDA; g.sdc = 1;
-  g.M = c; g.N = n + 1; g.K = u.kdim; g.alpha = 1.0; g.beta = 0.0; g.mode = 0;
-  static const int struct_env = env_int("XK_GEMM_STRUCT", 1);   // 0: every product as a general one (A/B switch)
-  g.tri_a = struct_env && u.tri;
-  // extra column: z' = res + H corr_tot  (updater.cpp:126) lands next to W in the augmented matrix
-  g.xcol = 1; g.bx = u.ct ? u.ct + u.col0 : nullptr; g.sbx = 1; g.dx = u.z; g.sdx = u.sz;
-  g.cx = h->d_Maug + c + n; g.scx = LDA;
-  gemm(h, g);
-  if (u.S) {
-    XkCopyArgs cp{u.S, h->d_Maug, c, c, u.ssr, u.ssc, (long)LDA, 1};
-    hipLaunchKernelGGL(xk_copy2d, dim3((c * c + 255) / 256), dim3(256), 0, h->stream, cp);
-  } else {
-    // S = W[:, col0:col0+kdim] * T^T + R               (H P H^T + R)
-    memset(&g, 0, sizeof(g));
-    g.A = h->d_Maug + c + u.col0; g.sar = LDA; g.sac = 1;
-    g.B = u.T; g.sbr = u.stc; g.sbc = u.str;
-    g.C = h->d_Maug; g.scr = LDA; g.scc = 1;
-    g.D = g.C; g.sdr = LDA; g.sdc = 1;
-    g.M = c; g.N = c; g.K = u.kdim; g.alpha = 1.0; g.beta = 0.0; g.mode = 1;
-    g.tri_b = struct_env && u.tri;
-    g.sym_cols = struct_env ? c : 0;   // only the upper triangle of S is read (xk_chol_whole / xk_chol_step)
-    g.diag = u.rdiag; g.diag_scalar = u.rscalar;
-    gemm(h, g);
-  }
-  // blocked Cholesky with the right-hand sides carried along: one launch per 32-column block step
-  const int ncols = c + n + 1;
-  static const int whole_env = env_int("XK_CHOL_WHOLE", 1);
-  static const int split_env = env_int("XK_CHOL_SPLIT", 1);
-  if (whole_env && (c <= 16 * XK_CHOLW_MAXB || split_env)) {
-    // Every block step inside one launch (xk_chol_whole), one workgroup per 16 right-hand-side columns.  Systems with
-    // more than 192 rows (BASELINE configs 2 and 3: c = 331 / 301) are cut into 192-row slabs:
-    //   X[0:b, b:]  = L_11^-1 [S_12 | W_1 | z_1]        xk_chol_whole on the slab, the rest of ITS ROWS as right-hand sides
-    //   M[b:, b:]  -= X[0:b, b:c]^T X[0:b, b:]           one fp64-MFMA GEMM (Schur complement of S and of the right-hand sides)
-    // and the remainder is the same problem again: 2 slabs = 3 launches instead of 11 block-step launches.
-    const int B = 16 * XK_CHOLW_MAXB;
-    for (int off = 0; off < c;) {
-      const int cb = std::min(B, c - off);
-      XkCholWholeArgs d;
-      d.Maug = h->d_Maug + (size_t)off * LDA + off; d.ld = LDA; d.c = cb; d.ncols = ncols - off;
-      d.X = h->d_X + (size_t)off * LDA + off; d.status = h->d_status;
-      xk_cholw_table((cb + 15) / 16, d.tab);
-      hipLaunchKernelGGL(xk_chol_whole, dim3((ncols - off - cb + 15) / 16), dim3(64 * XK_CHOLW_WAVES), 0, h->stream, d);
-      off += cb;
-      if (off < c) {
-        XkGemmArgs s;
-        memset(&s, 0, sizeof(s));
-        const double *Xs = h->d_X + (size_t)(off - cb) * LDA + off;       // X[slab rows, off:]
-        s.A = Xs; s.sar = 1; s.sac = LDA;                                   // A[i][k] = X[k][off + i]
-        s.B = Xs; s.sbr = LDA; s.sbc = 1;                                   // B[k][j] = X[k][off + j]
-        s.C = h->d_Maug + (size_t)off * LDA + off; s.scr = LDA; s.scc = 1;
-        s.D = s.C; s.sdr = LDA; s.sdc = 1;
-        s.M = c - off; s.N = ncols - off; s.K = cb; s.alpha = -1.0; s.beta = 1.0; s.mode = 0;
-        s.sym_cols = struct_env ? c - off : 0;   // (the Schur complement of S: upper triangle only)
-        gemm(h, s);
-      }
-    }
-  } else
-  for (int kb = 0; kb < c; kb += XK_CHOL_NB) {
-    const int nb = std::min(XK_CHOL_NB, c - kb);
-    const int rest = ncols - (kb + nb), mrem = c - kb - nb;
-    XkCholStepArgs d{h->d_Maug, LDA, kb, nb, c, ncols, h->d_X, (rest + 15) / 16, h->d_status};
-    hipLaunchKernelGGL(xk_chol_step, dim3(d.ncb * (1 + (mrem + 15) / 16)), dim3(64), 0, h->stream, d);
-  }
-  // P+ = sym(P - X^T X),  X = L^-1 W                   (I-KH)P, (P+P^T)/2
-  if (u.cov_update) {
-    memset(&g, 0, sizeof(g));
-    g.A = h->d_X + c; g.sar = 1; g.sac = LDA;
-    g.B = h->d_X + c; g.sbr = LDA; g.sbc = 1;
-    g.D = u.Pin; g.sdr = 1; g.sdc = n;
-    g.C = u.Pout; g.scr = 1; g.scc = n;
-    g.M = n; g.N = n + 1; g.K = c; g.alpha = -1.0; g.beta = 1.0; g.mode = 2;
-    g.sym_cols = struct_env ? n : 0;       // tiles below the diagonal: mirror images of the ones above
-    // extra column: corr = X^T (L^-1 z') - corr_tot   (K z' - corr_tot, updater.cpp:126)
-    g.xcol = 1; g.bx = h->d_X + c + n; g.sbx = LDA; g.ex = u.ct; g.cx = u.corr ? u.corr : h->d_corr; g.scx = 1;
-    if (u.done_flag) { g.done_cnt = h->d_done_cnt; g.done_flag = u.done_flag; g.done_seq = u.done_seq; }
-    gemm(h, g);
-  } else {
-    if (u.Pout != u.Pin) hipMemcpyAsync(u.Pout, u.Pin, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, h->stream);
-    XkCorrArgs cr{h->d_X, LDA, c, n, c, c + n, u.ct, u.corr ? u.corr : h->d_corr};
-    hipLaunchKernelGGL(xk_corr, dim3((n + 63) / 64), dim3(64), 0, h->stream, cr);
-    if (u.done_flag) hipLaunchKernelGGL(xk_mark_done, dim3(1), dim3(1), 0, h->stream, u.done_flag, u.done_seq);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "update launch", e);
-  return XK_OK;
-}
-
-static int fetch_flags(xk_handle *h, int *inl, double *gam, int *inls, double *gams) {
-  if (h->K > 0 && inl) HIPCHK(h, hipMemcpyAsync(inl, h->d_inl, sizeof(int) * h->K, hipMemcpyDeviceToHost, h->stream));
-  if (h->K > 0 && gam) HIPCHK(h, hipMemcpyAsync(gam, h->d_gam, sizeof(double) * h->K, hipMemcpyDeviceToHost, h->stream));
-  if (h->M > 0 && inls) HIPCHK(h, hipMemcpyAsync(inls, h->d_inl_s, sizeof(int) * h->M, hipMemcpyDeviceToHost, h->stream));
-  if (h->M > 0 && gams) HIPCHK(h, hipMemcpyAsync(gams, h->d_gam_s, sizeof(double) * h->M, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// public staged API
-// ---------------------------------------------------------------------------
-extern "C" int xk_msckf_build(xk_handle *h, double sigma_img, int *inlier_msckf, double *gamma_msckf,
-                              int *inlier_slam, double *gamma_slam) {
-  if (!h || !(sigma_img > 0.0)) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = launch_build(h, sigma_img);
-  if (rc != XK_OK) return rc;
-  return fetch_flags(h, inlier_msckf, gamma_msckf, inlier_slam, gamma_slam);
-}
-
-extern "C" int xk_qr_compress(xk_handle *h, double *T_H, int ldt, double *z) {
-  if (!h) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  h->want_full_T = true;                         // (this call hands out the reference's upper-triangular T_H: no split compression)
-  int rc = launch_compress(h);
-  if (rc == XK_OK) rc = read_status(h, true);
-  if (rc == XK_RETRY_CLASSIC) {                  // rebuild the rows (the tiles were worked on in place) and compress the slow way
-    if ((rc = launch_build(h, h->sigma_img, true)) == XK_OK && (rc = launch_compress(h)) == XK_OK) rc = read_status(h);
-  }
-  h->want_full_T = false;
-  if (rc != XK_OK) return rc;
-  if (T_H || z) {
-    if (T_H && ldt < h->n) return XK_EINVAL;
-    std::vector<double> R((size_t)h->C1 * h->C1P);
-    HIPCHK(h, hipMemcpy(R.data(), h->d_R, sizeof(double) * R.size(), hipMemcpyDeviceToHost));
-    if (T_H) {
-      for (int j = 0; j < h->n; ++j)
-        for (int i = 0; i < h->n; ++i) T_H[i + (size_t)j * ldt] = 0.0;
-      // rows 0..na-1 of the triangle, placed at rows 0.. with the core columns zero
-      for (int i = 0; i < h->na; ++i)
-        for (int j = i; j < h->na; ++j) T_H[i + (size_t)(XK_CORE + j) * ldt] = R[(size_t)i * h->C1P + j];
-    }
-    if (z) {
-      for (int i = 0; i < h->n; ++i) z[i] = 0.0;
-      for (int i = 0; i < h->na; ++i) z[i] = R[(size_t)i * h->C1P + h->na];
-    }
-  }
-  return XK_OK;
-}
-
-// gate results of the last build -> the handle's pinned cache (asynchronous; valid after the next synchronisation)
-static int cache_flags(xk_handle *h) {
-  // MSCKF gate results: the per-feature kernel writes them into the pinned cache itself (XkFeatArgs::inlier_h / gamma_h);
-  // without SLAM rows there is nothing to copy and nothing to wait for but the stream (five runtime calls less per frame)
-  h->flags_direct = h->M == 0;
-  if (!h->flags_direct) {
-    HIPCHK(h, hipEventRecord(h->ev_flags, h->stream));               // the per-feature kernels have been queued
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_flags, 0));
-    HIPCHK(h, hipMemcpyAsync(h->h_flag_i + h->Kmax, h->d_inl_s, sizeof(int) * h->M, hipMemcpyDeviceToHost, h->copy_stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_flag_d + h->Kmax, h->d_gam_s, sizeof(double) * h->M, hipMemcpyDeviceToHost, h->copy_stream));
-    HIPCHK(h, hipEventRecord(h->ev_flags_done, h->copy_stream));
-  }
-  h->flags_cached = true;
-  h->flags_after_seq = h->done_seq;
-  return XK_OK;
-}
-
-// xk_msckf_build + xk_qr_compress without a host synchronisation and without host outputs: the launches are queued behind
-// whatever is already on the handle's stream (staging copies, covariance propagation, manage()) and xk_apply_update's
-// one synchronisation covers them all.  The gate results come back with that synchronisation (xk_fetch_flags).
-extern "C" int xk_build_compress_async(xk_handle *h, double sigma_img) {
-  if (!h || !(sigma_img > 0.0)) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  int rc = launch_build(h, sigma_img);
-  if (rc != XK_OK) return rc;
-  if ((rc = cache_flags(h)) != XK_OK) return rc;
-  // Who calls this instead of xk_build_compress_update[_pass]_async has something between constructUpdate and applyUpdate that
-  // rewrites the covariance (the applyCI entries of the MULTI_UAV order, updater.cpp:84-97).  [T_H | z] does not depend on the
-  // covariance -- the gates have read the prior in the per-feature kernel above -- so where the single launch can take the Kalman
-  // update along (narrow geometry, n <= 206) the compression is not queued now but by xk_apply_update, behind those entries, with
-  // the Kalman role on the covariance they left: one launch there instead of one here and five there.
-  h->compress_deferred = h->opt_resident && h->persist_ok && kalman_rides(h) &&
-                         h->K + h->K2 + h->M > 0 && h->plan < 2 &&   // (stacks that are not compressed at all: nothing to defer)
-                         h->naux == 0;   // (range / sun rows: the update is not taken along by the launch anyway)
-  if (h->compress_deferred) h->have_R = true;     // (as far as xk_apply_update's precondition goes: it runs the compression itself)
-  else if ((rc = launch_compress(h)) != XK_OK) return rc;
-  h->async_pending = true;
-  return XK_OK;
-}
-
-// The same with the Kalman update of Updater::applyUpdate(correction_total = 0, cov_update = true) queued as well -- inside the
-// compression launch where the geometry allows it (xk_pipe_kalman), behind it otherwise.  xk_apply_update(h, NULL or zeros, 1, ..)
-// then only waits for the result.  For callers that know at construction time that nothing comes between constructUpdate and
-// applyUpdate (single agent, iekf_iter = 1: updater.cpp:99-110 with one pass) -- not the MULTI_UAV order, whose applyCI entries
-// replace the covariance in between (updater.cpp:84-97).
-static int build_compress_update_pass(xk_handle *h, double sigma_img, const double *corr_total, int cov_update) {
-  if (!h || !(sigma_img > 0.0)) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  bool ct_zero = true;
-  if (corr_total)
-    for (int i = 0; i < h->n && ct_zero; ++i) ct_zero = corr_total[i] == 0.0;
-  const double *dct = nullptr;
-  if (!ct_zero) {
-    double *st = (double *)stage_slot(h, sizeof(double) * h->n);
-    if (!st) return fail(h, XK_ECAPACITY, "staging slot too small");
-    memcpy(st, corr_total, sizeof(double) * h->n);
-    HIPCHK(h, hipMemcpyAsync(h->d_ct, st, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    dct = h->d_ct;
-  }
-  int rc = launch_build(h, sigma_img);
-  if (rc != XK_OK) return rc;
-  if ((rc = cache_flags(h)) != XK_OK) return rc;
-  UpdateSpec u = compressed_spec(h, dct, cov_update ? 1 : 0);
-  u.corr = h->h_out;
-  const int spin_env = spin_done();
-  if (spin_env) { u.done_flag = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2); u.done_seq = ++h->done_seq; }
-  if ((rc = launch_compress(h, nullptr, &u)) != XK_OK) return rc;
-  if (!h->last.fused && (rc = launch_update(h, u)) != XK_OK) return rc;
-  h->async_pending = true;
-  h->fused_pending = true;
-  h->fused_seq = spin_env ? u.done_seq : 0;
-  h->fused_cov_update = cov_update ? 1 : 0;
-  h->fused_ct_zero = ct_zero;
-  if (!h->fused_ct) h->fused_ct = new std::vector<double>();
-  if (ct_zero) h->fused_ct->clear(); else h->fused_ct->assign(corr_total, corr_total + h->n);
-  return XK_OK;
-}
-extern "C" int xk_build_compress_update_async(xk_handle *h, double sigma_img) { return build_compress_update_pass(h, sigma_img, nullptr, 1); }
-extern "C" int xk_build_compress_update_pass_async(xk_handle *h, double sigma_img, const double *corr_total, int cov_update) {
-  return build_compress_update_pass(h, sigma_img, corr_total, cov_update);
-}
-
-extern "C" int xk_fetch_flags(xk_handle *h, int *inlier_msckf, double *gamma_msckf, int *inlier_slam, double *gamma_slam) {
-  if (!h) return XK_EINVAL;
-  if (!h->flags_cached) return fail(h, XK_EINVAL, "xk_fetch_flags: no build since the inputs were staged");
-  if (!h->flags_direct && hipEventQuery(h->ev_flags_done) != hipSuccess) {   // (normally long done: the copies ran beside the QR kernels)
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipEventSynchronize(h->ev_flags_done));
-  }
-  // the MSCKF results were written by the per-feature kernel: valid once the stream has passed it (after xk_apply_update
-  // it has; otherwise this waits)
-  // (a completion marker seen after the build was queued says the same without asking the runtime)
-  if (h->K > 0 && !(h->done_seen > h->flags_after_seq) && hipStreamQuery(h->stream) != hipSuccess) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  if (inlier_msckf && h->K > 0) memcpy(inlier_msckf, h->h_flag_i, sizeof(int) * h->K);
-  if (gamma_msckf && h->K > 0) memcpy(gamma_msckf, h->h_flag_d, sizeof(double) * h->K);
-  if (inlier_slam && h->M > 0) memcpy(inlier_slam, h->h_flag_i + h->Kmax, sizeof(int) * h->M);
-  if (gamma_slam && h->M > 0) memcpy(gamma_slam, h->h_flag_d + h->Kmax, sizeof(double) * h->M);
-  return XK_OK;
-}
-
-// Gate result of the range row of the last build (range_update.cpp:246-262): *range_inlier 1 / 0, -1 if that build had no range row.
-// Synchronises the stream.
-extern "C" int xk_fetch_aux_flags(xk_handle *h, int *range_inlier, double *range_gamma) {
-  if (!h) return XK_EINVAL;
-  double f[2] = {0.0, 0.0};
-  if (h->aux_mask & 1) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(f, h->d_aux + 3 * ((size_t)h->n + 1) + 3, sizeof(f), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  if (range_inlier) *range_inlier = (h->aux_mask & 1) ? (f[1] != 0.0 ? 1 : 0) : -1;
-  if (range_gamma) *range_gamma = f[0];
-  return XK_OK;
-}
-
-// The range / sun rows of the last build as built (h_lrf, h_sns, their residuals and r_diag entries, vio_updater.cpp:407-421), for a host
-// that applies the dense system itself (xk_apply_update_dense).  H: rows x n, column-major, ldh >= 3 (any pointer may be NULL).
-extern "C" int xk_aux_rows(xk_handle *h, double *H, int ldh, double *res, double *r_diag, int *rows) {
-  if (!h) return XK_EINVAL;
-  const int na = h->naux, n = h->n;
-  if (H && ldh < 3) return XK_EINVAL;
-  if (rows) *rows = na;
-  if (na == 0) return XK_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  std::vector<double> b((size_t)3 * (n + 1) + 3);
-  HIPCHK(h, hipMemcpyAsync(b.data(), h->d_aux, sizeof(double) * b.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (int r = 0; r < na; ++r) {
-    if (H)
-      for (int c = 0; c < n; ++c) H[r + (size_t)c * ldh] = b[(size_t)r * (n + 1) + c];
-    if (res) res[r] = b[(size_t)r * (n + 1) + n];
-    if (r_diag) r_diag[r] = b[(size_t)3 * (n + 1) + r];
-  }
-  return XK_OK;
-}
-
-extern "C" int xk_apply_update(xk_handle *h, const double *corr_total, int cov_update, double *correction) {
-  if (!h || !correction) return XK_EINVAL;
-  if (!h->have_R) return fail(h, XK_EINVAL, "xk_qr_compress has not run on the staged inputs");
-  HIPCHK(h, hipSetDevice(h->device));
-  const double *dct = nullptr;
-  bool ct_zero = true;                                 // Updater::update starts every update from a zero correction_total
-  if (corr_total)
-    for (int i = 0; i < h->n && ct_zero; ++i) ct_zero = corr_total[i] == 0.0;
-  // arguments first, before any state of the handle is touched: a mismatch with what xk_build_compress_update_async queued leaves the
-  // queued update (posterior in d_Pout, marker, retry bookkeeping) exactly as it was -- the matching call can still collect it
-  if (h->fused_pending) {
-    bool same = (cov_update ? 1 : 0) == h->fused_cov_update && ct_zero == h->fused_ct_zero;
-    if (same && !ct_zero) same = memcmp(corr_total, h->fused_ct->data(), sizeof(double) * h->n) == 0;
-    if (!same) return fail(h, XK_EINVAL, "xk_apply_update: not the correction_total / cov_update the queued pass was built with");
-  }
-  if (corr_total && !ct_zero) {
-    double *st = (double *)stage_slot(h, sizeof(double) * h->n);
-    if (!st) return fail(h, XK_ECAPACITY, "staging slot too small");
-    memcpy(st, corr_total, sizeof(double) * h->n);
-    HIPCHK(h, hipMemcpyAsync(h->d_ct, st, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    dct = h->d_ct;
-  }
-  const bool deferred = h->compress_deferred;
-  const bool async = h->async_pending || deferred, queued = h->fused_pending;
-  h->async_pending = false;
-  h->fused_pending = false;
-  h->compress_deferred = false;
-  int rc = XK_OK;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (attempt == 1) {   // the single-launch CAQR of xk_build_compress_async gave up: rows, compression and update again
-      if (deferred) {
-        // ... NOT the rows: they were linearised and gated at the prior, which the applyCI entries have replaced since -- and they
-        // are still there (the single launch only reads the tiles / factor records; it is the multi-launch schedule that works
-        // on the tiles in place, and it has not run)
-        h->have_rows = true;
-      } else {
-        if ((rc = launch_build(h, h->sigma_img, true)) != XK_OK) return rc;
-        if ((rc = cache_flags(h)) != XK_OK) return rc;
-      }
-      if ((rc = launch_compress(h)) != XK_OK) return rc;
-    }
-    UpdateSpec u = compressed_spec(h, dct, cov_update);
-    u.corr = h->h_out;
-    const bool waiting_only = queued && attempt == 0;      // the update is already on the stream (xk_build_compress_update_async)
-    // The kernels write the correction and (on failure) the status words into pinned host memory; the last workgroup of the
-    // last launch then writes a sequence number next to them, which the host polls: the results are there ~5 us before the
-    // runtime's completion signal says so (XK_SPIN_DONE=0: wait for that signal instead).  One wait per update, no copy.
-    const int spin_env = spin_done();
-    unsigned long long *done = reinterpret_cast<unsigned long long *>(h->h_out + h->n + 2);
-    if (waiting_only) u.done_seq = h->fused_seq;
-    else {
-      if (spin_env) { u.done_flag = done; u.done_seq = ++h->done_seq; }
-      if (deferred && attempt == 0) {                      // the compression xk_build_compress_async left for now, Kalman role inside
-        if ((rc = launch_compress(h, nullptr, &u)) != XK_OK) return rc;
-        rc = h->last.fused ? XK_OK : launch_update(h, u);
-      } else rc = launch_update(h, u);
-      if (rc != XK_OK) return rc;
-    }
-    bool seen = false;
-    if (spin_env && u.done_seq) {
-      // Acquire load: the correction and the status words read below are ordered after the marker.  The marker is the LAST
-      // host-visible store of the update.  Separate Kalman launches: a system-scope RELEASE by the last workgroup of the last
-      // kernel, after every workgroup of that kernel has been counted in (done_cnt).  Kalman role inside the single launch: the
-      // correction and the status word are relaxed system-scope stores whose acknowledgement the writing wave waits for
-      // (s_waitcnt vmcnt(0)) before it stores the marker, relaxed as well -- gfx950 behaviour, not a memory-model guarantee; the
-      // -DXK_SYNC_STRICT=1 build stores that marker with a system-scope release (XK_MARKER_ORDER, xk_xcd_sync.hip.h).  In both forms
-      // the marker covers ONLY the words in h_out: the posterior (d_Pout) may still be on its way out of the other waves when
-      // the marker lands and is valid to later work through STREAM ORDER -- everything that reads it is queued on h->stream
-      // behind this launch (the pointer swap below is host bookkeeping).  The kernels before it on the stream (whose failure
-      // paths write the status words into the same pinned allocation) had completed, their stores released to system scope at
-      // their kernel boundaries, before that kernel started: whatever they wrote is visible by the time the marker is.
-      // (a single launch that gave up before its Kalman role got going -- placement census -- writes no marker: the status word
-      //  ends the wait)
-      seen = wait_marker(h, done, u.done_seq);
-      if (seen) h->done_seen = u.done_seq;
-    }
-    if (!seen) HIPCHK(h, hipStreamSynchronize(h->stream));
-    stage_stream_idle(h);
-    rc = eval_status(h, h->d_status[0], h->d_status[1], async && attempt == 0);
-    if (rc != XK_RETRY_CLASSIC) break;
-  }
-  if (rc != XK_OK) return rc;
-  memcpy(correction, h->h_out, sizeof(double) * h->n);
-  std::swap(h->d_P, h->d_Pout);  // posterior becomes the resident covariance
-  h->have_rows = h->have_R = false;
-  return XK_OK;
-}
-
-extern "C" int xk_visual_update_staged(xk_handle *h, double sigma_img, double *correction, int *inlier_msckf,
-                                       double *gamma_msckf, int *inlier_slam, double *gamma_slam) {
-  if (!h || !correction || !(sigma_img > 0.0)) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->K == 0 && h->K2 == 0 && h->M == 0 && !h->aux_staged) {  // h.size() == 0 -> no update (updater.cpp:106); MSCKF-SLAM rows count (vio_updater.cpp:413-419)
-    for (int i = 0; i < h->n; ++i) correction[i] = 0.0;
-    h->last.schedule = XK_SCHED_EMPTY;            // (xk_caqr_status: 4; staging cleared have_R, or the compression it stands for was of this same empty stack: nothing else reads the record before the next one)
-    return XK_OK;
-  }
-  int rc = XK_OK;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    rc = launch_build(h, sigma_img, attempt > 0);
-    if (rc != XK_OK) return rc;
-    UpdateSpec u = compressed_spec(h, nullptr, 1);
-    rc = launch_compress(h, nullptr, &u);            // (the single launch takes the Kalman update along where it can)
-    if (rc != XK_OK) return rc;
-    if (!h->last.fused) rc = launch_update(h, u);
-    if (rc != XK_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(correction, h->d_corr, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream));
-    rc = fetch_flags(h, inlier_msckf, gamma_msckf, inlier_slam, gamma_slam);
-    if (rc != XK_OK) return rc;
-    rc = read_status(h, attempt == 0);
-    if (rc != XK_RETRY_CLASSIC) break;           // (the prior is untouched in d_P: the whole update is simply redone)
-  }
-  if (rc != XK_OK) return rc;
-  std::swap(h->d_P, h->d_Pout);
-  h->have_rows = h->have_R = false;
-  return XK_OK;
-}
-
-extern "C" int xk_visual_update(xk_handle *h, const double *C_q_G, const double *G_p_C, int n_poses,
-                                const int *trk_off, const double *obs_xy, int K, const double *feat,
-                                const int *anchor_idxs, const int *track_sizes, const double *z_last, int M,
-                                double *P, int ldp, int n, double sigma_img, double *correction,
-                                int *inlier_msckf, double *gamma_msckf, int *inlier_slam, double *gamma_slam) {
-  int rc;
-  if ((rc = xk_stage_window(h, C_q_G, G_p_C, n_poses)) != XK_OK) return rc;
-  if ((rc = xk_stage_tracks(h, trk_off, obs_xy, K)) != XK_OK) return rc;
-  if ((rc = xk_stage_slam(h, feat, anchor_idxs, track_sizes, z_last, M)) != XK_OK) return rc;
-  if ((rc = xk_stage_msckf_slam(h, nullptr, nullptr, 0)) != XK_OK) return rc;   // this entry point has no MSCKF-SLAM tracks
-  if ((rc = xk_upload_P(h, P, ldp, n)) != XK_OK) return rc;
-  if ((rc = xk_visual_update_staged(h, sigma_img, correction, inlier_msckf, gamma_msckf, inlier_slam,
-                                    gamma_slam)) != XK_OK)
-    return rc;
-  return xk_download_P(h, P, ldp, n);
-}
-
-// ---------------------------------------------------------------------------
-// dense (unfused) Kalman algebra
-// ---------------------------------------------------------------------------
-extern "C" int xk_apply_update_dense(xk_handle *h, double *P, int ldp, int n, const double *H, int ldh, int m,
-                                     const double *res, const double *r_diag, double *correction_total,
-                                     int cov_update, double *correction) {
-  if (!h || !P || !H || !res || !r_diag || !correction || n != h->n || ldp < n || ldh < m || m <= 0) return XK_EINVAL;
-  if (m > h->CM) return fail(h, XK_ECAPACITY, "m exceeds the dense workspace (n+1 rows); compress first");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpP, sizeof(double) * n, P, sizeof(double) * ldp, sizeof(double) * n, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(h->d_tmpH, sizeof(double) * m, H, sizeof(double) * ldh, sizeof(double) * m, n,
-                             hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_tmpz, res, sizeof(double) * m, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_rdiag, r_diag, sizeof(double) * m, hipMemcpyHostToDevice, h->stream));
-  const double *dct = nullptr;
-  if (correction_total) {
-    HIPCHK(h, hipMemcpyAsync(h->d_ct, correction_total, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    dct = h->d_ct;
-  }
-  UpdateSpec u;
-  memset(&u, 0, sizeof(u));
-  u.T = h->d_tmpH; u.str = 1; u.stc = m;  // column-major m x n
-  u.c = m; u.kdim = n; u.col0 = 0;
-  u.z = h->d_tmpz; u.sz = 1; u.rdiag = h->d_rdiag;
-  u.Pin = h->d_tmpP; u.Pout = h->d_Pout; u.ct = dct; u.cov_update = cov_update;
-  int rc = launch_update(h, u);
-  if (rc != XK_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(correction, h->d_corr, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpy2DAsync(P, sizeof(double) * ldp, h->d_Pout, sizeof(double) * n, sizeof(double) * n, n,
-                             hipMemcpyDeviceToHost, h->stream));
-  rc = read_status(h);
-  if (rc != XK_OK) return rc;
-  if (correction_total)
-    for (int i = 0; i < n; ++i) correction_total[i] += correction[i];  // updater.cpp:140
-  return XK_OK;
-}
-
-// A build + compression queued by xk_build_compress_async whose single-launch CAQR gave up must be redone (multi-launch
-// schedule) while the covariance it was linearised at is still the resident one: BEFORE a CI entry replaces it.  After this
-// the compressed [T_H | z] is known to be good and xk_apply_update has nothing to retry.
-static int settle_async(xk_handle *h) {
-  if (!h->async_pending) return XK_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  stage_stream_idle(h);
-  int rc = eval_status(h, h->d_status[0], h->d_status[1], true);
-  if (rc == XK_RETRY_CLASSIC) {
-    if ((rc = launch_build(h, h->sigma_img, true)) != XK_OK) return rc;
-    if ((rc = cache_flags(h)) != XK_OK) return rc;
-    if ((rc = launch_compress(h)) != XK_OK) return rc;
-  }
-  if (rc == XK_OK) h->async_pending = false;
-  return rc;
-}
-
-// Keeps / brings back a copy of the resident covariance on the device (restore = 0: save, 1: restore).  Benchmarks
-// use it to replay a frame from the same prior without a PCIe upload.
-extern "C" int xk_snapshot_P(xk_handle *h, int restore) {
-  if (!h || restore < 0 || restore > 3) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t bytes = sizeof(double) * (size_t)h->n * h->n;
-  double *&slot = (restore >= 2) ? h->d_Psnap2 : h->d_Psnap;     // 0 / 1: the caller's slot; 2 / 3: the filter loop's own (x::Ekf)
-  const bool back = restore & 1;
-  if (!slot) {
-    if (back) return fail(h, XK_EINVAL, "xk_snapshot_P: nothing saved");
-    HIPCHK(h, dalloc(&slot, (size_t)h->n * h->n));
-  }
-  HIPCHK(h, hipMemcpyAsync(back ? h->d_P : slot, back ? slot : h->d_P, bytes, hipMemcpyDeviceToDevice, h->stream));
-  return XK_OK;
-}
-
-// ---------------------------------------------------------------------------
-// measurement
-// ---------------------------------------------------------------------------
-extern "C" int xk_bench_staged(xk_handle *h, double sigma_img, int warmup, int steps, xk_timing *out) {
-  if (!h || !out || steps <= 0 || warmup < 0) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-  memset(out, 0, sizeof(*out));
-  const char *names[XK_NSTAGE] = {"xk_msckf_feature", "xk_slam_rows", "xk_caqr_panel0",
-                                  "xk_caqr_rest",
-                                  "xk_kalman_update", "(unused)"};
-  for (int s = 0; s < XK_NSTAGE; ++s) snprintf(out->stage_name[s], sizeof(out->stage_name[s]), "%s", names[s]);
-  double acc[XK_NSTAGE] = {0, 0, 0, 0, 0, 0}, tot = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-  for (int s = 0; s < XK_NSTAGE; ++s) acc[s] = 0;
-  tot = 0;
-  for (int it = 0; it < warmup + steps; ++it) {
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    int rc = launch_build(h, sigma_img, attempt > 0 || it > 0);   // (staged range / sun rows: in every step)
-    if (rc != XK_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    UpdateSpec u = compressed_spec(h, nullptr, 1);
-    rc = launch_compress(h, h->ev[2], &u);
-    if (rc != XK_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    if (!h->last.fused) rc = launch_update(h, u);     // (fused: the Kalman update is inside stage 2's launch, stage 4 reads 0)
-    if (rc != XK_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (it >= warmup) {
-      float ms;
-      hipEventElapsedTime(&ms, h->ev[0], h->ev[1]); acc[0] += ms;
-      hipEventElapsedTime(&ms, h->ev[1], h->ev[2]); acc[2] += ms;
-      hipEventElapsedTime(&ms, h->ev[2], h->ev[3]); acc[3] += ms;
-      hipEventElapsedTime(&ms, h->ev[3], h->ev[4]); acc[4] += ms;
-      hipEventElapsedTime(&ms, h->ev[0], h->ev[4]); tot += ms;
-    }
-  }
-  const int rc = read_status(h, attempt == 0);
-  if (rc == XK_RETRY_CLASSIC) continue;            // the single-launch CAQR gave up somewhere: measure the multi-launch schedule
-  if (rc != XK_OK) return rc;
-  break;
-  }
-  for (int s = 0; s < XK_NSTAGE; ++s) out->stage_ms[s] = (float)(acc[s] / steps);
-  out->total_ms = (float)(tot / steps);
-  out->stage_launches[0] = (h->K > 0) + (h->M > 0);
-  out->stage_launches[2] = 1;
-  out->stage_launches[3] = outcome_single(h->last) ? 0 : h->last.launches;   // (the single launch IS stage 2's one launch)
-  const int nblk = (h->na + XK_CHOL_NB - 1) / XK_CHOL_NB;
-  out->stage_launches[4] = h->last.fused ? 0 : 4 + 3 * nblk;
-  out->n = h->n; out->c1 = h->C1; out->k_tracks = h->K; out->n_leaf = h->last.leaves; out->n_levels = h->last.launches;
-  // stacked rows actually folded (inlier rows)
-  {
-    const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
-    std::vector<int> tr(h->K + h->K2 + slam_tiles);
-    HIPCHK(h, hipMemcpy(tr.data(), h->d_tile_rows, sizeof(int) * tr.size(), hipMemcpyDeviceToHost));
-    int rows = 0;
-    for (int v : tr) rows += v;
-    out->rows_stacked = rows;
-  }
-  // leave the posterior of the last step in d_Pout; the staged prior stays in d_P
-  return XK_OK;
-}
+#include "xk_update_api.hip.h"
 
 // ---------------------------------------------------------------------------
 // covariance intersection: the fuse / match / track entries, applyCI, the device-resident round, the inter-agent payload
 // ---------------------------------------------------------------------------
 #include "xk_ci_api.hip.h"
-
-// ---------------------------------------------------------------------------
-// StateManager::manage on the resident covariance (SURVEY 8(f) rank 1)
-// ---------------------------------------------------------------------------
-static int congruence(xk_handle *h, const int *row_ptr, const int *col_idx, const double *val, int nnz, const double *q,
-                      int qdim, int qoff) {
-  const int n = h->n;
-  HIPCHK(h, hipSetDevice(h->device));
-  // the operand goes through the pinned ring: nothing here waits for the device (a frame applies two or three of these
-  // back to back -- IMU steps, manage() -- before the update's one synchronisation)
-  // (+ the window lists staged since the last launch that needed them: they ride in this copy and the kernel leaves them in d_q)
-  const int wn = h->win_pending ? 7 * h->n_poses : 0;
-  const size_t vb = sizeof(double) * ((size_t)nnz + (q ? (size_t)qdim * qdim : 0) + wn), ib = sizeof(int) * ((size_t)n + 1 + nnz);
-  char *st = stage_slot(h, vb + ib);
-  if (!st) return fail(h, XK_ECAPACITY, "sparse operand exceeds the staging slot");
-  double *sv = (double *)st;
-  int *si = (int *)(st + vb);
-  if (nnz) memcpy(sv, val, sizeof(double) * nnz);
-  if (q) memcpy(sv + nnz, q, sizeof(double) * (size_t)qdim * qdim);
-  const size_t woff = (size_t)nnz + (q ? (size_t)qdim * qdim : 0);
-  if (wn) memcpy(sv + woff, h->h_win, sizeof(double) * wn);
-  memcpy(si, row_ptr, sizeof(int) * (n + 1));
-  if (nnz) memcpy(si + n + 1, col_idx, sizeof(int) * nnz);
-  // [values | additive block | row pointers | column indices] in one copy
-  HIPCHK(h, hipMemcpyAsync(h->d_csr_v, st, vb + ib, hipMemcpyHostToDevice, h->stream));
-  double *dq = q ? h->d_csr_v + nnz : nullptr;
-  const int *d_rp = (const int *)((const char *)h->d_csr_v + vb);
-  XkCongArgs a{h->d_P, h->d_Pout, n, d_rp, d_rp + n + 1, h->d_csr_v, dq, qdim, qoff, wn ? h->d_csr_v + woff : nullptr, h->d_q, wn};
-  h->win_pending = false;
-  hipLaunchKernelGGL(xk_congruence, dim3(((size_t)n * n + 255) / 256), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "congruence launch", e);
-  std::swap(h->d_P, h->d_Pout);
-  h->have_rows = h->have_R = false;
-  return XK_OK;
-}
-
-extern "C" int xk_cov_congruence(xk_handle *h, const int *row_ptr, const int *col_idx, const double *val, int nnz) {
-  if (!h || !row_ptr || nnz < 0 || (nnz > 0 && (!col_idx || !val))) return XK_EINVAL;
-  const int n = h->n;
-  if (row_ptr[0] != 0 || row_ptr[n] != nnz) return fail(h, XK_EINVAL, "CSR row pointers inconsistent with nnz");
-  if ((size_t)nnz > h->csr_cap) return fail(h, XK_ECAPACITY, "sparse operand has more than 24 n non-zeros");
-  for (int i = 0; i < n; ++i)
-    if (row_ptr[i + 1] < row_ptr[i]) return fail(h, XK_EINVAL, "CSR row pointers not monotone");
-  for (int k = 0; k < nnz; ++k)
-    if (col_idx[k] < 0 || col_idx[k] >= n) return fail(h, XK_EINVAL, "CSR column index outside the state");
-  return congruence(h, row_ptr, col_idx, val, nnz, nullptr, 0, 0);
-}
-
-// Propagator::propagateCovarianceMatrices (propagator.cpp:166-205) on the resident covariance:
-//   P_ii <- F P_ii F^T + Q,  P_iv <- F P_iv,  P_vi <- P_vi F^T (computed on its own, as the reference insists),  P_vv kept
-extern "C" int xk_cov_propagate(xk_handle *h, const double *f_d, int ldf, const double *q_d, int ldq) {
-  if (!h || !f_d || !q_d || ldf < XK_CORE || ldq < XK_CORE) return XK_EINVAL;
-  const int n = h->n;
-  HIPCHK(h, hipSetDevice(h->device));
-  XkPropArgs a;
-  a.P = h->d_P; a.n = n;
-  for (int c = 0; c < XK_CORE; ++c)
-    for (int r = 0; r < XK_CORE; ++r) {
-      a.FQ[r + XK_CORE * c] = f_d[r + (size_t)c * ldf];
-      a.FQ[225 + r + XK_CORE * c] = q_d[r + (size_t)c * ldq];
-    }
-  hipLaunchKernelGGL(xk_cov_propagate_k, dim3(1 + (2 * (n - XK_CORE) + 255) / 256), dim3(256), 0, h->stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, XK_EDEVICE, "propagate launch", e);
-  h->have_rows = h->have_R = false;
-  return XK_OK;
-}
-
-extern "C" int xk_run_steps(xk_handle *h, double sigma_img, int steps) {
-  if (!h || steps < 0 || !(sigma_img > 0.0)) return XK_EINVAL;
-  HIPCHK(h, hipSetDevice(h->device));
-#ifdef XK_LAB
-  static const int use_graph = env_int("XK_GRAPH", 0);
-  if (use_graph && steps > 1) {
-    // experiment: the 30 launches of one update captured once and replayed
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = launch_build(h, sigma_img);
-    if (rc == XK_OK) rc = launch_compress(h);
-    if (rc == XK_OK) { UpdateSpec u = compressed_spec(h, nullptr, 1); rc = launch_update(h, u); }
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (rc != XK_OK) return rc;
-    if (e != hipSuccess) return fail(h, XK_EDEVICE, "graph capture", e);
-    HIPCHK(h, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    for (int it = 0; it < steps; ++it) HIPCHK(h, hipGraphLaunch(ge, h->stream));
-    rc = read_status(h);
-    hipGraphExecDestroy(ge);
-    hipGraphDestroy(g);
-    return rc;
-  }
-#endif
-  // (every step recomputes the same update from the resident prior, so a single-launch CAQR that gave up -- e.g. two
-  //  processes sharing one GPU, each with a grid that wants every CU -- costs one more pass with the multi-launch schedule)
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    for (int it = 0; it < steps; ++it) {
-      int rc = launch_build(h, sigma_img, attempt > 0 || it > 0);   // (staged range / sun rows: in every step)
-      if (rc != XK_OK) return rc;
-      UpdateSpec u = compressed_spec(h, nullptr, 1);
-      rc = launch_compress(h, nullptr, &u);
-      if (rc != XK_OK) return rc;
-      if (!h->last.fused) rc = launch_update(h, u);
-      if (rc != XK_OK) return rc;
-    }
-    const int rc = read_status(h, attempt == 0);
-    if (rc != XK_RETRY_CLASSIC) return rc;
-  }
-  return XK_EDEVICE;
-}
 
 // ---------------------------------------------------------------------------
 // fp64 ceiling probe (lab build only: include/xk_lab.h)

@@ -915,7 +915,7 @@ static int ci_round_apply(xk_handle *h, const CiRound &r, double *corrections, i
     else rc = read_status(h);
     if (rc != XK_OK) return rc;
     std::swap(h->d_P, h->d_Pout);
-    h->have_rows = h->have_R = false;
+    pending_drop(h);
   }
   *n_fused = fused;
   return XK_OK;

@@ -1,6 +1,7 @@
 // xk_compress.hip.h -- host side of the measurement compression (vio_updater.cpp:487-512): which schedule serves the staged stack and the
 // launches of each, the system they leave for the Kalman update (compressed_spec), the reading of the status words.  Included by
-// xk_api.hip only, behind launch_build; the two small kernels here keep their place among the __global__ functions of that file.
+// xk_update_api.hip.h only (xk_api.hip's translation unit), behind launch_build; the two small kernels here keep their place among the
+// __global__ functions of that translation unit.
 #pragma once
 #include <type_traits>
 
@@ -481,11 +482,7 @@ static int compress_multi(xk_handle *h, int ntiles, hipEvent_t mid, XkOutcome &o
 // fuse: (optional) the Kalman update that follows this compression.  If the single launch takes it along (narrow geometry,
 // correction_total = 0, covariance update, no external S), h->last.fused says so and the caller must NOT queue launch_update.
 static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateSpec *fuse = nullptr) {
-  // A compression that xk_build_compress_async left for xk_apply_update is no longer pending once ANY compression runs (xk_apply_update
-  // takes the flag down before it comes here; an xk_qr_compress in between does the work now, and xk_apply_update then applies d_R as
-  // it stands instead of compressing rows the multi-launch schedule has already reduced in place).
-  h->compress_deferred = false;
-  if (!h->have_rows) return fail(h, XK_EINVAL, "xk_msckf_build has not run on the staged inputs");
+  if (h->upd.stage == XK_UPD_STAGED) return fail(h, XK_EINVAL, "xk_msckf_build has not run on the staged inputs");
   const int slam_tiles = (2 * h->M + h->DB - 1) / h->DB;
   const int ntiles = h->K + h->K2 + slam_tiles;
   const int mode = h->want_full_T ? 0 : h->plan;   // (latched at the build: what compressed_spec saw; xk_qr_compress: the whole stack)
@@ -508,7 +505,10 @@ static int launch_compress(xk_handle *h, hipEvent_t mid = nullptr, const UpdateS
   }
   if (rc != XK_OK) return rc;
   h->last = o;
-  h->have_R = true;
+  // A compression that xk_build_compress_async left for xk_apply_update is no longer deferred once ANY compression has run: an
+  // xk_qr_compress in between does the work now, and xk_apply_update then applies d_R as it stands instead of compressing rows the
+  // multi-launch schedule has already reduced in place.  (A queued pass stays queued.)
+  if (h->upd.stage < XK_UPD_COMPRESSED) h->upd.stage = XK_UPD_COMPRESSED;
   return XK_OK;
 }
 
@@ -521,7 +521,7 @@ static UpdateSpec compressed_spec_base(xk_handle *h, const double *d_ct, int cov
   u.str = h->C1P; u.stc = 1; u.kdim = h->na; u.col0 = XK_CORE; u.sz = h->C1P;   // rows of C1P doubles over the active columns, the residual at column na
   u.rdiag = nullptr; u.rscalar = h->sigma_img * h->sigma_img;    // vio_updater.cpp:508-509; the SLAM rows carry sigma_img^2 too (slam_update.cpp: r = var_img I)
   u.Pin = h->d_P; u.Pout = h->d_Pout; u.ct = d_ct; u.cov_update = cov_update;
-  if (const int mode = h->have_R ? outcome_R2_mode(h->last) : h->plan) {
+  if (const int mode = h->upd.stage >= XK_UPD_COMPRESSED ? outcome_R2_mode(h->last) : h->plan) {
     // the split form (d_R2): 6 N rows of R1 over the pose columns, then the 2 M rows of the SLAM features as built; mode 2: those rows alone
     const int r0 = mode == 2 ? 6 * h->N : 0;
     u.T = h->d_R2 + (size_t)r0 * h->C1P;
@@ -551,7 +551,7 @@ static UpdateSpec compressed_spec(xk_handle *h, const double *d_ct, int cov_upda
 static int give_up(xk_handle *h, int pst, bool allow_retry) {
   h->fast_giveups++; h->fast_reason = pst;
   h->xsync_dirty = true;
-  h->have_rows = h->have_R = false;
+  pending_drop(h);
   return allow_retry ? XK_RETRY_CLASSIC : XK_EDEVICE;
 }
 static int eval_status(xk_handle *h, int st, int pst, bool allow_retry) {

@@ -1,4 +1,4 @@
-// xk_handle.hip.h -- the engine's handle and the small helpers every part of xk_api.hip uses on it.  Included by xk_api.hip only.
+// xk_handle.hip.h -- the engine's handle and the small helpers every part of xk_api.hip's translation unit uses on it.  Included by xk_api.hip only.
 #pragma once
 
 #define XK_STAGE_SLOTS 8
@@ -37,6 +37,28 @@ static inline bool outcome_single(const XkOutcome &o) { return o.schedule == XK_
 static inline int outcome_status(const XkOutcome &o) {
   return o.schedule == XK_SCHED_NONE || o.schedule == XK_SCHED_MULTI ? 0 : outcome_single(o) ? 2 : o.schedule == XK_SCHED_MULTI_TAIL ? 3 : 4;
 }
+
+// How far the update of the staged inputs has got, and what of it is still owed to xk_apply_update.  One record: the entries of
+// xk_update_api.hip.h raise the stage as they queue work, and pending_drop (below) takes the whole record back to "staged" -- the stage
+// is lowered nowhere else.  Plain data: the handle is calloc'ed.
+enum XkUpdateStage {
+  XK_UPD_STAGED = 0,       // inputs staged, or none yet: no rows of theirs on the device
+  XK_UPD_ROWS,             // launch_build has queued the rows
+  XK_UPD_ROWS_DEFERRED,    // ... and xk_build_compress_async has left the compression to xk_apply_update, where the Kalman role can ride
+                           // along on the covariance the applyCI entries in between have left (MULTI_UAV order)
+  XK_UPD_COMPRESSED,       // launch_compress has queued [T_H | z]: xk_handle::last says where it is
+  XK_UPD_QUEUED,           // ... and the Kalman update is queued behind it (xk_build_compress_update[_pass]_async): xk_apply_update only waits
+};
+struct XkPending {
+  XkUpdateStage stage;
+  bool unread;             // the status words of the queued launches have yet to be read: whoever reads them (settle_async,
+                           // xk_apply_update) owns the retry if the single-launch CAQR gave up
+  // XK_UPD_QUEUED: what the queued pass was asked for -- xk_apply_update must ask the same -- and its completion marker
+  int cov_update;
+  bool ct_zero;            // correction_total NULL or all zero
+  double *ct;              // ... else its n doubles (allocated by xk_create)
+  unsigned long long seq;  // the marker xk_apply_update waits for (0: for the stream)
+};
 
 struct xk_handle {
   int device;
@@ -114,15 +136,8 @@ struct xk_handle {
   // calls no getenv); xk_set_option changes them on a live handle (tests do)
   int opt_resident, opt_poison, opt_test_stall, opt_tall26;
   int opt_kalman;          // the Kalman update inside the single launch (xk_pipe_kalman) where the geometry allows it
-  bool compress_deferred;  // xk_build_compress_async queued the rows only: the compression waits for xk_apply_update, where the Kalman
-                           // role can ride along on the covariance the applyCI entries in between have left (MULTI_UAV order)
-  int fused_cov_update;    // what the queued pass was asked for (xk_build_compress_update[_pass]_async): xk_apply_update must ask the same
-  bool fused_ct_zero;
-  std::vector<double> *fused_ct;
-  bool fused_pending;      // xk_build_compress_update_async ran: xk_apply_update only has to wait
-  unsigned long long fused_seq;   // ... for this completion marker (0: for the stream)
+  XkPending upd;           // the staged update: how far it has got, what xk_apply_update has to collect
   bool xsync_dirty;     // a pipelined launch gave up: its counters are mid-count, clear both sets before the next one
-  bool have_rows, have_R;
   double sigma_img;
   // update workspace
   int CM, LDA;
@@ -176,7 +191,6 @@ struct xk_handle {
   double *h_flag_d;
   char *trk_slot;          // xk_stage_tracks_begin .. _end: the staging slot being filled
   int trk_slot_K, trk_slot_nobs;
-  bool async_pending;      // xk_build_compress_async ran: xk_apply_update owns the retry if the single-launch CAQR gave up
   // range-facet / sun-angle rows (xk_stage_range / xk_stage_sun_angle, xk_aux.hip.h).  Staged measurements wait in aux_in until the next
   // build, which consumes them (the reference uses a measurement once: timestamp = -1, vio_updater.cpp:380,402) and fixes the plan of that
   // update in aux_mask / naux: which rows, how many, and which variances they carry.  A replay of the same update (a retry after a single
@@ -193,6 +207,15 @@ struct xk_handle {
   int *h_pin_i;
   char err[256];
 };
+
+// Back to "staged", whole: the stage, a deferred compression, a queued pass and what it was asked for, status words nobody has read.
+// Everything that invalidates the rows or the compressed system calls this -- staging, a rewritten covariance (congruence, propagation,
+// the device CI round), a give-up, a new build, the end of an update -- and nothing else lowers the stage.
+static inline void pending_drop(xk_handle *h) {
+  double *ct = h->upd.ct;
+  memset(&h->upd, 0, sizeof(h->upd));
+  h->upd.ct = ct;
+}
 
 static int fail(xk_handle *h, int code, const char *what, hipError_t e = hipSuccess) {
   if (h) {
