@@ -72,8 +72,11 @@ void *xk_stream(xk_handle *h);
  *   P [n x n], ldp                                  prior covariance
  *       (Matrix P = state.getCovariance(), vio_updater.cpp:284);
  *   SLAM (M may be 0): feat [3M] inverse-depth states, anchor_idxs [M],
- *       track_sizes [M] (only used for the chi-square dof,
- *       slam_update.cpp:196), z_last [M x 2] newest observation. */
+ *       track_sizes [M] >= 1 (only used for the chi-square dof 2 * size,
+ *       slam_update.cpp:196; no upper limit -- a persistent feature's track
+ *       grows every frame: the 0.9 quantile comes from a table below dof 513
+ *       and is computed on the host past it), z_last [M x 2] newest
+ *       observation. */
 int xk_stage_window(xk_handle *h, const double *C_q_G, const double *G_p_C, int n_poses);
 int xk_stage_tracks(xk_handle *h, const int *trk_off, const double *obs_xy, int K);
 /* The same in two halves for a host that builds the CSR lists anyway: *trk_off (K+1 ints) and *obs_xy (2 n_obs doubles)
@@ -84,6 +87,9 @@ int xk_stage_tracks_begin(xk_handle *h, int K, int n_obs, int **trk_off, double 
 int xk_stage_tracks_end(xk_handle *h);
 int xk_stage_slam(xk_handle *h, const double *feat, const int *anchor_idxs, const int *track_sizes,
                   const double *z_last, int M);
+/* boost::math::quantile(chi_squared(dof), p) as xk_stage_slam computes it past its table (0 < p < 1, dof >= 1); no handle, no
+ * device. */
+int xk_chi2_quantile(double p, int dof, double *out);
 int xk_upload_P(xk_handle *h, const double *P, int ldp, int n);
 int xk_download_P(xk_handle *h, double *P, int ldp, int n);
 

@@ -42,6 +42,14 @@ int xk_debug_persist_stamps(xk_handle *h, long long *out, int n_out);
  * taken.  K = the staged track count.  Waits for the handle's stream.  tests/test_gpu_feature_geometry.py compares both per track. */
 int xk_debug_feature_points(xk_handle *h, double *gpf, int *gn_iters, int K);
 
+/* The rows [H | res] AS BUILT by the last xk_msckf_build, before any compression: nrows rows from the first row of slot `slot` of the
+ * stack (slots [0, K) the MSCKF tracks -- valid only when the build left tiles, not factor records --, [K, K + K2) the MSCKF-SLAM
+ * tracks, from K + K2 the SLAM features' rows, feature j at rows 2 j, 2 j + 1; slots are consecutive, so nrows may run over several).
+ * out [nrows][n - 15 + 1] row-major: the active columns, then the residual.  xk_qr_compress always compresses the whole stack, so
+ * the rows themselves leave the device nowhere else.  Waits for the handle's stream.  tests/test_gpu_slam_rows.py compares them
+ * per feature. */
+int xk_debug_stack_rows(xk_handle *h, int slot, int nrows, double *out);
+
 /* Micro-benchmark of the fp64 ceiling this path is priced against: a grid of waves issuing independent
  * v_mfma_f64_16x16x4_f64 (use_mfma=1) or v_fma_f64 (use_mfma=0) chains.  Reports sustained TFLOP/s. */
 int xk_probe_fp64_peak(xk_handle *h, int use_mfma, double *tflops);

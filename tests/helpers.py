@@ -65,6 +65,7 @@ def check_visual(got, exp, tol=TOL_TIGHT):
     if "inlier_slam" in exp:
         assert np.array_equal(np.asarray(got["inlier_slam"]).astype(int), exp["inlier_slam"].astype(int))
         assert rel(got["gamma_slam"], exp["gamma_slam"]) <= 1e-8
+        check_gamma_per_track(got["gamma_slam"], got["inlier_slam"], exp["gamma_slam"])      # (feature by feature as well)
     rp, rc = rel(got["P"], exp["P"]), rel(got["correction"], exp["correction"])
     assert rp <= tol, f"posterior covariance rel error {rp}"
     assert rc <= max(tol, 1e-8), f"correction rel error {rc}"

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import GOLDEN_DIR, rel
+from helpers import GOLDEN_DIR, check_gamma_per_track, rel
 from oracle import ref_np
 from x_multi_agent_amd import synth
 
@@ -35,6 +35,7 @@ def test_update_with_msckf_slam_rows_and_feature_init(xk):
     ms = eng.msckf_slam_results()
     assert np.array_equal(ms["inlier"], g["exp_inlier_ms"])
     assert rel(ms["gamma"], g["exp_gamma_ms"]) <= 1e-8
+    check_gamma_per_track(ms["gamma"], ms["inlier"], g["exp_gamma_ms"])         # (track by track as well)
     assert rel(ms["features"], g["exp_features"]) <= 1e-9
     # what initMsckfSlamFeatures consumes is independent of the column-space basis
     H2i = np.linalg.inv(ms["H2"])

@@ -34,6 +34,35 @@ def test_chi2_table_of_the_product_matches_independent_quantile(oracle_c):
             assert abs(vals[dof] - oracle_c.chi2inv(p, dof)) <= 5e-12 * vals[dof], (name, dof)
 
 
+def test_host_quantile_of_the_product_matches_the_table_and_the_reference():
+    """Past the table the product computes the SLAM gate's 0.9 quantile on the host (xk_chi2_quantile; csrc/xk_chi2_quantile.h): it
+    continues the table -- the same numbers at every tabulated dof -- and agrees with ref_np.chi2inv where no table reaches."""
+    import ctypes as C
+    import os
+    import re
+    from x_multi_agent_amd import engine
+    L = engine.lib()
+
+    def quantile(p, dof):
+        out = C.c_double()
+        assert L.xk_chi2_quantile(C.c_double(p), C.c_int(dof), C.byref(out)) == 0
+        return out.value
+    path = os.path.join(os.path.dirname(__file__), "..", "x_multi_agent_amd", "csrc", "xk_chi2_table.h")
+    txt = open(path).read()
+    for name, p in (("XK_CHI2_095", 0.95), ("XK_CHI2_090", 0.90)):
+        body = txt.split(name + "[XK_CHI2_LEN] = {")[1].split("};")[0]
+        vals = [float(v) for v in re.findall(r"[-+0-9.eE]+", body)]
+        assert len(vals) == 513
+        for dof in range(1, 513):
+            assert abs(quantile(p, dof) - vals[dof]) <= 5e-12 * vals[dof], (name, dof)
+    for dof in (514, 2000, 20000):
+        ref = ref_np.chi2inv(0.9, dof)
+        assert abs(quantile(0.9, dof) - ref) <= 5e-12 * ref, (dof, quantile(0.9, dof), ref)
+    out = C.c_double()
+    for p, dof in ((0.0, 4), (1.0, 4), (0.9, 0), (float("nan"), 4)):
+        assert L.xk_chi2_quantile(C.c_double(p), C.c_int(dof), C.byref(out)) == 1
+
+
 @pytest.fixture(scope="module")
 def case():
     sc = synth.make_scenario(8, 24, 0, seed=123)

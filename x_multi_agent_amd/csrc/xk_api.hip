@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "xk_chi2_table.h"
+#include "xk_chi2_quantile.h"
 #include "xk_feature.hip.h"
 #include "xk_slaminit.hip.h"
 #include "xk_linalg.hip.h"
@@ -106,14 +108,12 @@ static int create_impl(int device, int n_poses_max, int n_feat_max, int k_max, x
   HIPCHK(h, dalloc(&h->d_feat, 3 * (size_t)n_feat_max));
   HIPCHK(h, dalloc(&h->d_zlast, 2 * (size_t)n_feat_max));
   HIPCHK(h, dalloc(&h->d_anchor, (size_t)n_feat_max));
-  HIPCHK(h, dalloc(&h->d_tsz, (size_t)n_feat_max));
+  HIPCHK(h, dalloc(&h->d_chi_s, (size_t)n_feat_max));
   HIPCHK(h, dalloc(&h->d_P, nn));
   HIPCHK(h, dalloc(&h->d_Pout, nn));
   HIPCHK(h, dalloc(&h->d_fq, (size_t)450));
   HIPCHK(h, dalloc(&h->d_chi95, (size_t)XK_CHI2_LEN));
-  HIPCHK(h, dalloc(&h->d_chi90, (size_t)XK_CHI2_LEN));
   HIPCHK(h, hipMemcpy(h->d_chi95, XK_CHI2_095, sizeof(double) * XK_CHI2_LEN, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_chi90, XK_CHI2_090, sizeof(double) * XK_CHI2_LEN, hipMemcpyHostToDevice));
   // (+ 256 rows behind the slots: where the first of two tail launches leaves its R for the second one, XkCaqrPipeArgs::extra_row0 --
   //  zero outside the trapezoid the launch writes, like d_R)
   HIPCHK(h, dalloc(&h->d_A, ((size_t)h->ntiles_max * h->DB + 256) * h->C1P));
@@ -267,8 +267,8 @@ extern "C" int xk_destroy(xk_handle *h) {
   if (!h) return XK_OK;
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
-  void *ptrs[] = {h->d_q, h->d_obs, h->d_feat, h->d_zlast, h->d_anchor, h->d_tsz,
-                  h->d_P, h->d_Pout, h->d_chi95, h->d_chi90, h->d_A, h->d_tile_rows, h->d_panel[0], h->d_panel[1], h->d_inl, h->d_inl_s,
+  void *ptrs[] = {h->d_q, h->d_obs, h->d_feat, h->d_zlast, h->d_anchor, h->d_chi_s,
+                  h->d_P, h->d_Pout, h->d_chi95, h->d_A, h->d_tile_rows, h->d_panel[0], h->d_panel[1], h->d_inl, h->d_inl_s,
                   h->d_gn, h->d_gam, h->d_gam_s, h->d_gpf, h->d_R, h->d_Maug, h->d_X, h->d_corr,
                   h->d_ct, h->d_tmpH, h->d_tmpS, h->d_tmpP, h->d_rdiag, h->d_tmpz, h->d_payload,
                   h->d_ci};
@@ -455,30 +455,51 @@ extern "C" int xk_stage_tracks(xk_handle *h, const int *trk_off, const double *o
   return xk_stage_tracks_end(h);
 }
 
+extern "C" int xk_chi2_quantile(double p, int dof, double *out) {
+  if (!out || !(p > 0.0 && p < 1.0) || dof < 1) return XK_EINVAL;
+  *out = xk_chi2_quantile_host(p, dof);
+  return XK_OK;
+}
+
+// The gate of a persistent feature (slam_update.cpp:196-199): the 0.9 quantile at dof = 2 * track size, for EVERY track size -- a
+// feature's track grows for as long as the feature lives.  From the table where it reaches, computed on the host past it; the handle
+// remembers the last few computed ones (the features of one frame share a handful of sizes, and next frame's are one larger).
+static double slam_gate_threshold(xk_handle *h, int track_size) {
+  const int dof = 2 * track_size;
+  if (dof < XK_CHI2_LEN) return XK_CHI2_090[dof];
+  for (int i = 0; i < 8; ++i)
+    if (h->chi_far_dof[i] == dof) return h->chi_far_val[i];
+  const double v = xk_chi2_quantile_host(0.9, dof);
+  h->chi_far_dof[h->chi_far_next] = dof;
+  h->chi_far_val[h->chi_far_next] = v;
+  h->chi_far_next = (h->chi_far_next + 1) % 8;
+  return v;
+}
+
 extern "C" int xk_stage_slam(xk_handle *h, const double *feat, const int *anchor_idxs, const int *track_sizes,
                              const double *z_last, int M) {
   if (!h || M < 0 || (M > 0 && (!feat || !anchor_idxs || !track_sizes || !z_last))) return XK_EINVAL;
   if (M > h->Mmax) return fail(h, XK_ECAPACITY, "M > n_feat_max");
   h->anchor_max = -1;
-  for (int j = 0; j < M; ++j) {   // a stale anchor (-1 in StateManager's unused slots) or size would index the window / chi-square table out of bounds
+  for (int j = 0; j < M; ++j) {   // a stale anchor (-1 in StateManager's unused slots) would index the window out of bounds, a size < 1 has no quantile
     if (anchor_idxs[j] < 0 || anchor_idxs[j] >= h->N) return fail(h, XK_EINVAL, "SLAM anchor index outside [0, n_poses_max)");
-    if (track_sizes[j] < 1) return fail(h, XK_EINVAL, "SLAM track size < 1");
+    if (track_sizes[j] < 1 || track_sizes[j] > INT_MAX / 2) return fail(h, XK_EINVAL, "SLAM track size outside [1, INT_MAX / 2]");
     h->anchor_max = std::max(h->anchor_max, anchor_idxs[j]);
   }
   if (M > 0) {
     HIPCHK(h, hipSetDevice(h->device));
-    char *st = stage_slot(h, sizeof(double) * 6 * M);
+    char *st = stage_slot(h, sizeof(double) * 6 * M + sizeof(int) * M);
     if (!st) return fail(h, XK_ECAPACITY, "staging slot too small");
     double *sd = (double *)st;
-    int *si = (int *)(sd + 5 * M);
+    int *si = (int *)(sd + 6 * M);
     memcpy(sd, feat, sizeof(double) * 3 * M);
     memcpy(sd + 3 * M, z_last, sizeof(double) * 2 * M);
+    for (int j = 0; j < M; ++j) sd[5 * M + j] = slam_gate_threshold(h, track_sizes[j]);
     memcpy(si, anchor_idxs, sizeof(int) * M);
-    memcpy(si + M, track_sizes, sizeof(int) * M);
     HIPCHK(h, hipMemcpyAsync(h->d_feat, sd, sizeof(double) * 3 * M, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_zlast, sd + 3 * M, sizeof(double) * 2 * M, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_anchor, si, sizeof(int) * M, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_tsz, si + M, sizeof(int) * M, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_chi_s, sd + 5 * M, sizeof(double) * M, hipMemcpyHostToDevice, h->stream));
   }
   h->M = M;
   pending_drop(h);
@@ -888,6 +909,16 @@ extern "C" int xk_debug_feature_points(xk_handle *h, double *gpf, int *gn_iters,
   if (K == 0) return XK_OK;
   HIPCHK(h, hipMemcpy(gpf, h->d_gpf, sizeof(double) * 3 * (size_t)K, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(gn_iters, h->d_gn, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost));
+  return XK_OK;
+}
+
+extern "C" int xk_debug_stack_rows(xk_handle *h, int slot, int nrows, double *out) {
+  if (!h || !out || slot < 0 || nrows < 0 || (long)slot * h->DB + nrows > (long)h->ntiles_max * h->DB) return XK_EINVAL;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (nrows == 0) return XK_OK;
+  HIPCHK(h, hipMemcpy2D(out, sizeof(double) * (h->na + 1), h->d_A + (size_t)slot * h->DB * h->C1P, sizeof(double) * h->C1P,
+                        sizeof(double) * (h->na + 1), (size_t)nrows, hipMemcpyDeviceToHost));
   return XK_OK;
 }
 #endif   // XK_LAB

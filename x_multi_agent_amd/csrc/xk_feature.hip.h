@@ -1253,14 +1253,12 @@ struct XkSlamArgs {
   int n_poses, n_poses_max;
   const double *feat;      // [3M]
   const int *anchor_idxs;  // [M]
-  const int *track_sizes;  // [M]
   const double *z_last;    // [M][2]
   int M;
   const double *P;
   int n;
   double var_img;
-  const double *chi90;  // chi-square 0.9 quantile by dof
-  int chi_len;
+  const double *chi;  // [M] gate threshold of each feature: the chi-square 0.9 quantile at dof = 2 * track size (host: xk_stage_slam)
   double *A;  // tile base of the FIRST slam tile
   int DB, C1P, na;
   int *inlier;
@@ -1335,9 +1333,7 @@ __device__ __forceinline__ void xk_slam_rows_body(const XkSlamArgs &a, const int
     const double det = S[0][0] * S[1][1] - S[0][1] * S[1][0];
     const double i00 = S[1][1] / det, i01 = -S[0][1] / det, i10 = -S[1][0] / det, i11 = S[0][0] / det;
     const double g = rs[0] * (i00 * rs[0] + i01 * rs[1]) + rs[1] * (i10 * rs[0] + i11 * rs[1]);
-    const int dof = 2 * a.track_sizes[j];
-    const double chi = (dof < a.chi_len) ? a.chi90[dof] : INFINITY;
-    ok = (g < chi) ? 1 : 0;
+    ok = (g < a.chi[j]) ? 1 : 0;
     a.gamma[j] = g;
     a.inlier[j] = ok;
   }

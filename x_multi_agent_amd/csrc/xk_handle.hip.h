@@ -72,12 +72,16 @@ struct xk_handle {
   int n_poses, K, M;
   size_t obs_cap;
   double *d_q, *d_p, *d_obs, *d_feat, *d_zlast;
-  int *d_trk_off, *d_anchor, *d_tsz;
+  int *d_trk_off, *d_anchor;
+  double *d_chi_s;        // [Mmax] chi-square threshold of each staged SLAM feature (xk_stage_slam)
+  int chi_far_dof[8];     // the thresholds past the table that xk_stage_slam computed last (a feature's dof grows by 2 per frame)
+  double chi_far_val[8];
+  int chi_far_next;
   double *d_P, *d_Pout;
   double *d_Psnap;        // xk_snapshot_P (slot of the caller)
   double *d_Psnap2;       // ... slot of the filter loop (x::Ekf saves the prior of an update the IMU thread may lap)
   double *d_fq;           // f_d, q_d of xk_cov_propagate
-  double *d_chi95, *d_chi90;
+  double *d_chi95;
   double *d_A;
   double *d_Hc;            // factor records of the MSCKF tracks (xk_feature.hip.h: XkFeatArgs::Hc), hc_stride doubles each, 64-row slots only
   int hc_stride;

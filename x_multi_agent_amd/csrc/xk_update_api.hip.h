@@ -99,8 +99,8 @@ static int launch_build(xk_handle *h, double sigma_img, bool replay = false) {
     if (h->anchor_max >= h->n_poses) return fail(h, XK_EINVAL, "SLAM anchor outside the staged window");
     XkSlamArgs s;
     s.q = h->d_q; s.p = h->d_p; s.n_poses = h->n_poses; s.n_poses_max = h->N;
-    s.feat = h->d_feat; s.anchor_idxs = h->d_anchor; s.track_sizes = h->d_tsz; s.z_last = h->d_zlast; s.M = h->M;
-    s.P = h->d_P; s.n = h->n; s.var_img = sigma_img * sigma_img; s.chi90 = h->d_chi90; s.chi_len = XK_CHI2_LEN;
+    s.feat = h->d_feat; s.anchor_idxs = h->d_anchor; s.z_last = h->d_zlast; s.M = h->M;
+    s.P = h->d_P; s.n = h->n; s.var_img = sigma_img * sigma_img; s.chi = h->d_chi_s;
     s.A = h->d_A + (size_t)(h->K + h->K2) * h->DB * h->C1P; s.DB = h->DB; s.C1P = h->C1P; s.na = h->na;
     s.inlier = h->d_inl_s; s.gamma = h->d_gam_s;
     if (h->K > 0 && !h->feat_dbg && !xk_feature_packed(h->n_poses)) hipLaunchKernelGGL(xk_build_rows, dim3(h->K + h->M), dim3(XK_FEAT_THREADS), feat_lds, h->stream, fa, s);

@@ -25,7 +25,7 @@ STATUS = {0: "XK_OK", 1: "XK_EINVAL", 2: "XK_ESINGULAR", 3: "XK_ENAN", 4: "XK_ED
 # every symbol include/xk.h declares (tests check the library exports them all)
 SYMBOLS = [
     "xk_create", "xk_destroy", "xk_strerror", "xk_last_error", "xk_version", "xk_stream",
-    "xk_stage_window", "xk_stage_tracks", "xk_stage_tracks_begin", "xk_stage_tracks_end", "xk_stage_slam", "xk_upload_P", "xk_download_P",
+    "xk_stage_window", "xk_stage_tracks", "xk_stage_tracks_begin", "xk_stage_tracks_end", "xk_stage_slam", "xk_chi2_quantile", "xk_upload_P", "xk_download_P",
     "xk_msckf_build", "xk_qr_compress", "xk_apply_update", "xk_visual_update_staged", "xk_visual_update",
     "xk_apply_update_dense", "xk_apply_ci", "xk_fuse_ci_msckf", "xk_fuse_ci_slam", "xk_multi_slam_match", "xk_msckf_ci_track",
     "xk_ci_round_device", "xk_ci_round_weights", "xk_ci_solve_weights", "xk_ci_last_weights", "xk_cov_congruence", "xk_cov_propagate",
@@ -53,7 +53,7 @@ SYMBOLS = [
 
 
 # what include/xk_lab.h adds (lab build only; the release library must NOT export them)
-LAB_SYMBOLS = ["xk_is_lab", "xk_probe_fp64_peak", "xk_debug_persist_stamps", "xk_debug_feature_points"]
+LAB_SYMBOLS = ["xk_is_lab", "xk_probe_fp64_peak", "xk_debug_persist_stamps", "xk_debug_feature_points", "xk_debug_stack_rows"]
 
 
 class XkTiming(C.Structure):
@@ -509,6 +509,13 @@ class Engine:
         self._chk(self.L.xk_debug_feature_points(self.h, gpf.ctypes.data_as(c_dp), it.ctypes.data_as(c_ip), C.c_int(self._K)),
                   "xk_debug_feature_points")
         return gpf[:self._K], it[:self._K]
+
+    def debug_stack_rows(self, slot, nrows):
+        """xk_debug_stack_rows (lab build): nrows rows [H | res] of the last msckf_build as built, from the first row of slot `slot`
+        (slots [0, K) tracks, [K, K + K2) MSCKF-SLAM tracks, then the SLAM features' rows) -> [nrows, n - 15 + 1]."""
+        out = np.zeros((max(nrows, 1), self.n - 15 + 1))
+        self._chk(self.L.xk_debug_stack_rows(self.h, C.c_int(slot), C.c_int(nrows), out.ctypes.data_as(c_dp)), "xk_debug_stack_rows")
+        return out[:nrows]
 
     def payload_doubles(self):
         return int(self.L.xk_payload_doubles(C.c_int(self.N), C.c_int(self.M)))
