@@ -229,7 +229,7 @@ void VioUpdater::buildMsckfCiLists(const State &state, const TrackList &tracks, 
       for (const Attitude &a : ss.getCameraAttitudesList()) { mq[i].push_back(a.ax); mq[i].push_back(a.ay); mq[i].push_back(a.az); mq[i].push_back(a.aw); }
       for (const Translation &t : ss.getCameraPositionsList()) { mp[i].push_back(t.tx); mp[i].push_back(t.ty); mp[i].push_back(t.tz); }
       mL[i] = (int)mine[i].received_track_ptr->size();
-      mnp[i] = ss.nPosesMax();
+      mnp[i] = ss.nPosesMax();   // a SimpleState's lists are as long as its window: list length and window size are one number
       mn[i] = ss.getErrorStateSize();
       po[i] = mo[i].data(); pq[i] = mq[i].data(); pp[i] = mp[i].data(); pP[i] = ss.covariance().data();
     }
@@ -238,7 +238,7 @@ void VioUpdater::buildMsckfCiLists(const State &state, const TrackList &tracks, 
     int self_inl = 0, has_ci = 0;
     double self_gamma = 0, ci_gamma = 0;
     const int rc = xk_msckf_ci_track(xk_, obs.data(), (int)track.size(), q.data(), p.data(), np, P->data(), n, n, n_poses_max_,
-                                     sigma_img_, k, po.data(), mL.data(), pq.data(), pp.data(), mnp.data(), pP.data(), mn.data(),
+                                     sigma_img_, k, po.data(), mL.data(), pq.data(), pp.data(), mnp.data(), mnp.data(), pP.data(), mn.data(),
                                      ci_msckf_w_, &self_inl, &self_gamma, &has_ci, &ci_gamma, H->data(), 3 * k, res->data(),
                                      S->data(), 3 * k, Pj->data(), n);
     if (rc == XK_EINVAL) throw std::runtime_error(xk_last_error(xk_));   // the places the reference throws (ci.cpp:59-62)

@@ -139,7 +139,12 @@ int xk_apply_update_dense(xk_handle *h, double *P, int ldp, int n, const double 
                           int cov_update, double *correction);
 
 /* Updater::applyCI(state, ci_P, H, res, S) (updater.cpp:144-161):
- * K = ci_P H^T S^-1, corr = K res, P_out = sym((I-KH) ci_P). */
+ * K = ci_P H^T S^-1, corr = K res, P_out = sym((I-KH) ci_P).
+ * S and ci_P are taken as symmetric, S positive definite (what the CI entries produce from a
+ * covariance): S is factored by Cholesky, ONE of its triangles is read, and an S that is not
+ * positive definite is XK_ESINGULAR.  The reference inverts S as a general matrix; on an S whose
+ * two triangles differ by 4e-8 (relative) the two disagree by 4e-7 on P_out
+ * (tests/test_ci_entry_cases.py). */
 int xk_apply_ci(xk_handle *h, double *P_out, int ldp, const double *ci_P, int ldc, int n,
                 const double *H, int ldh, int m, const double *res, const double *S, int lds,
                 double *correction);
@@ -216,16 +221,22 @@ int xk_multi_slam_match(xk_handle *h, const double *C_q_G, const double *G_p_C, 
  * fuseCI (:252-255) and the block scaling of P_j (:256-267).
  *   obs [L x 2], own window lists / P as in xk_stage_*;
  *   per matched agent i: m_obs[i] [m_L[i] x 2], m_q[i] [m_nposes[i] x 4], m_p[i]
- *   [m_nposes[i] x 3] (its full window lists; its track sees the LAST m_L[i] poses),
- *   m_P[i] [m_n[i] x m_n[i]] dense column-major, m_n[i] = 15 + 6*m_nposes[i] + 3*M_i.
+ *   [m_nposes[i] x 3] (the lists of its VALID window poses, as for the own agent; its track sees
+ *   the LAST m_L[i] of them), m_nposes_max[i] the window size its covariance is laid out for
+ *   (m_nposes[i] <= m_nposes_max[i] <= 64: the attitude block of pose p starts at column
+ *   15 + 3*m_nposes_max[i] + 3*p, whatever m_nposes[i] is),
+ *   m_P[i] [m_n[i] x m_n[i]] dense column-major, m_n[i] = 15 + 6*m_nposes_max[i] + 3*M_i.
+ * The joint gate's threshold comes from the table up to 512 degrees of freedom and from the same quantile function
+ * beyond (eight agents with windows of 33 and more).
  * Outputs: *self_inlier, *self_gamma; *has_ci; if *has_ci: H (3k x n, ldh), res (3k),
  * S (3k x 3k, lds), P_j (n x n, ldpj), feed them to xk_apply_ci.  H/res/S are defined up to
  * a common orthogonal factor (basis of the null space), H^T S^-1 H and H^T S^-1 res are not. */
 int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const double *C_q_G, const double *G_p_C,
                       int n_poses, const double *P, int ldp, int n, int n_poses_max, double sigma_img, int k,
                       const double *const *m_obs, const int *m_L, const double *const *m_q,
-                      const double *const *m_p, const int *m_nposes, const double *const *m_P,
-                      const int *m_n, double ci_msckf_w, int *self_inlier, double *self_gamma, int *has_ci,
+                      const double *const *m_p, const int *m_nposes, const int *m_nposes_max,
+                      const double *const *m_P, const int *m_n, double ci_msckf_w, int *self_inlier,
+                      double *self_gamma, int *has_ci,
                       double *ci_gamma, double *H, int ldh, double *res, double *S, int lds, double *P_j,
                       int ldpj);
 

@@ -34,6 +34,9 @@ def lib(path=None):
         if not os.path.exists(p):
             build()
         _LIB = C.CDLL(p)
+        if not hasattr(_LIB, "xo_msckf_ci_track_win"):    # a library from before the entry existed: an error, not a wrong call
+            _LIB = None
+            raise RuntimeError(f"{p} is older than oracle/xk_oracle.c: run oracle.c_oracle.build(force=True)")
         _LIB.xo_gemm_probe.restype = C.c_double
     return _LIB
 
@@ -334,6 +337,7 @@ def msckf_ci_track(trk, C_q_G, G_p_C, P, n_poses_max, sigma_img, matches, ci_msc
     arr = lambda xs: (c_dp * max(k, 1))(*[x[1] for x in xs])
     mL, mLp = _i([len(m["obs"]) for m in matches] or [0])
     mnp, mnpp = _i([len(m["p_list"]) for m in matches] or [0])
+    mnm, mnmp = _i([m["n_poses_max"] for m in matches] or [0])
     mn, mnp_ = _i([m["P"].shape[0] for m in matches] or [0])
     si, sg, hc, cg = C.c_int(), C.c_double(), C.c_int(), C.c_double()
     m3 = max(3 * k, 1)
@@ -342,14 +346,14 @@ def msckf_ci_track(trk, C_q_G, G_p_C, P, n_poses_max, sigma_img, matches, ci_msc
     S = np.zeros((m3, m3), order="F")
     Pj = np.zeros((n, n), order="F")
     gpf = np.zeros(3)
-    rc = lib().xo_msckf_ci_track(base[0][1], C.c_int(len(trk)), base[1][1], base[2][1], C.c_int(len(G_p_C)),
+    rc = lib().xo_msckf_ci_track_win(base[0][1], C.c_int(len(trk)), base[1][1], base[2][1], C.c_int(len(G_p_C)),
                                  base[3][1], C.c_int(n), C.c_int(n_poses_max), C.c_double(sigma_img), C.c_int(k),
-                                 arr(mo), mLp, arr(mq), arr(mp), mnpp, arr(mP), mnp_, C.c_double(ci_msckf_w),
+                                 arr(mo), mLp, arr(mq), arr(mp), mnpp, mnmp, arr(mP), mnp_, C.c_double(ci_msckf_w),
                                  C.byref(si), C.byref(sg), C.byref(hc), C.byref(cg), H.ctypes.data_as(c_dp),
                                  res.ctypes.data_as(c_dp), S.ctypes.data_as(c_dp), Pj.ctypes.data_as(c_dp),
                                  gpf.ctypes.data_as(c_dp))
     if rc != 0:
-        raise RuntimeError(f"xo_msckf_ci_track status {rc}")
+        raise RuntimeError(f"xo_msckf_ci_track_win status {rc}")
     out = dict(self_inlier=bool(si.value), self_gamma=sg.value, gpf=gpf, ci=None, ci_gamma=cg.value)
     if hc.value:
         out["ci"] = dict(S=np.ascontiguousarray(S), P_j=np.ascontiguousarray(Pj), H=np.ascontiguousarray(H), res=res)

@@ -1163,16 +1163,17 @@ int xo_multi_slam_match(const double *C_q_G, const double *G_p_C, const double *
 /* MSCKF-MSCKF CI block of preProcessOneTrack, msckf_update.cpp:96-279, for
  * ONE track with k matched agents (ground-truth association).
  * m_* arrays describe the matched agents; their tracks are concatenated
- * FIRST for triangulation, self last (:113-149).
+ * FIRST for triangulation, self last (:113-149).  m_q / m_p hold an agent's
+ * m_nposes VALID poses; its covariance is laid out for m_nposes_max.
  * Outputs: self_inlier/self_gamma (own single-agent gate), has_ci, and if
  * has_ci: H (3k x n, ld 3k), res (3k), S (3k x 3k), P_j (n x n). */
-int xo_msckf_ci_track(const double *obs, int L, const double *C_q_G, const double *G_p_C, int n_poses,
-                      const double *P, int n, int n_poses_max, double sigma_img, int k,
-                      const double *const *m_obs, const int *m_L, const double *const *m_q,
-                      const double *const *m_p, const int *m_nposes, const double *const *m_P,
-                      const int *m_n, double ci_msckf_w, int *self_inlier, double *self_gamma,
-                      int *has_ci, double *ci_gamma, double *H, double *res, double *S, double *P_j,
-                      double *gpf_out) {
+int xo_msckf_ci_track_win(const double *obs, int L, const double *C_q_G, const double *G_p_C, int n_poses,
+                          const double *P, int n, int n_poses_max, double sigma_img, int k,
+                          const double *const *m_obs, const int *m_L, const double *const *m_q,
+                          const double *const *m_p, const int *m_nposes, const int *m_nposes_max,
+                          const double *const *m_P, const int *m_n, double ci_msckf_w, int *self_inlier, double *self_gamma,
+                          int *has_ci, double *ci_gamma, double *H, double *res, double *S, double *P_j,
+                          double *gpf_out) {
   double var_img = sigma_img * sigma_img;
   int Ltot = L;
   for (int i = 0; i < k; ++i) Ltot += m_L[i];
@@ -1215,7 +1216,7 @@ int xo_msckf_ci_track(const double *obs, int L, const double *C_q_G, const doubl
   int col = n;
   for (int i = 0; i < k; ++i) {
     track_out_t o;
-    rc = process_one_track(m_obs[i], m_L[i], m_P[i], m_n[i], m_q[i], m_p[i], m_nposes[i], m_nposes[i], var_img,
+    rc = process_one_track(m_obs[i], m_L[i], m_P[i], m_n[i], m_q[i], m_p[i], m_nposes[i], m_nposes_max[i], var_img,
                            gpf, 1, &o);
     if (rc != XO_OK) { free(jx); free(jf); free(rp); return rc; }
     if (o.valid) {
@@ -1285,6 +1286,20 @@ int xo_msckf_ci_track(const double *obs, int L, const double *C_q_G, const doubl
   }
   free(Hs); free(Sc); free(Si); free(T); free(hx); free(Q); free(jx); free(jf); free(rp);
   return rc;
+}
+
+/* The entry as it was before matched windows could be short: every matched agent's lists are as long as its window
+ * (m_nposes_max = m_nposes), which is what the reference's SimpleState sends.  Kept with its argument list, so a binding
+ * written for it keeps working on this library. */
+int xo_msckf_ci_track(const double *obs, int L, const double *C_q_G, const double *G_p_C, int n_poses,
+                      const double *P, int n, int n_poses_max, double sigma_img, int k,
+                      const double *const *m_obs, const int *m_L, const double *const *m_q,
+                      const double *const *m_p, const int *m_nposes, const double *const *m_P,
+                      const int *m_n, double ci_msckf_w, int *self_inlier, double *self_gamma,
+                      int *has_ci, double *ci_gamma, double *H, double *res, double *S, double *P_j,
+                      double *gpf_out) {
+  return xo_msckf_ci_track_win(obs, L, C_q_G, G_p_C, n_poses, P, n, n_poses_max, sigma_img, k, m_obs, m_L, m_q, m_p, m_nposes,
+                               m_nposes, m_P, m_n, ci_msckf_w, self_inlier, self_gamma, has_ci, ci_gamma, H, res, S, P_j, gpf_out);
 }
 
 /* achieved-rate probe used by bench.py to report the baseline's dgemm GF/s */

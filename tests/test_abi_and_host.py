@@ -63,6 +63,21 @@ def test_null_and_bad_arguments_are_status_codes_not_crashes():
     assert L.xk_run_steps(None, C.c_double(1e-3), 1) == 1
 
 
+def test_ci_track_prototype_carries_the_matched_window_size():
+    """xk_msckf_ci_track takes a matched agent's list length (m_nposes) and the window size its covariance is laid out for
+    (m_nposes_max) apart; the header's prototype and the definition have one parameter list."""
+    params = []
+    for path in (("include", "xk.h"), ("x_multi_agent_amd", "csrc", "xk_ci_api.hip.h")):
+        src = open(os.path.join(ROOT, *path)).read()
+        m = re.search(r"int xk_msckf_ci_track\(([^)]*)\)", src)
+        assert m, path
+        params.append([re.sub(r"\s+", " ", x).strip() for x in m.group(1).split(",")])
+    assert params[0] == params[1]
+    names = [x.split()[-1].lstrip("*") for x in params[0]]
+    assert names.index("m_nposes_max") == names.index("m_nposes") + 1 and names.index("m_P") == names.index("m_nposes_max") + 1
+    assert "const int *m_nposes_max" in params[0]
+
+
 def test_synth_is_deterministic_and_platform_independent():
     r = synth.SplitMix(0x5EED0000)
     u = r.u64(3)

@@ -306,24 +306,31 @@ extern "C" int xk_multi_slam_match(xk_handle *h, const double *C_q_G, const doub
 // ---------------------------------------------------------------------------
 // MSCKF-MSCKF CI block (msckf_update.cpp:96-279) for one track
 // ---------------------------------------------------------------------------
+// The joint gate's threshold chi2(0.95, dof) (:245-247), compared on the host in both routes: from the table, and past its 512
+// degrees of freedom (eight agents with windows of 33 and more) from the quantile function (as slam_gate_threshold at 0.9).
+static double ci_gate_threshold(int dof) { return dof < XK_CHI2_LEN ? XK_CHI2_095[dof] : xk_chi2_quantile_host(0.95, dof); }
+
 extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const double *C_q_G, const double *G_p_C,
                                  int n_poses, const double *P, int ldp, int n, int n_poses_max, double sigma_img,
                                  int k, const double *const *m_obs, const int *m_L, const double *const *m_q,
-                                 const double *const *m_p, const int *m_nposes, const double *const *m_P,
-                                 const int *m_n, double ci_msckf_w, int *self_inlier, double *self_gamma,
-                                 int *has_ci, double *ci_gamma, double *H, int ldh, double *res, double *S, int lds,
-                                 double *P_j, int ldpj) {
+                                 const double *const *m_p, const int *m_nposes, const int *m_nposes_max,
+                                 const double *const *m_P, const int *m_n, double ci_msckf_w, int *self_inlier,
+                                 double *self_gamma, int *has_ci, double *ci_gamma, double *H, int ldh, double *res, double *S,
+                                 int lds, double *P_j, int ldpj) {
   if (!h || !obs || !C_q_G || !G_p_C || !P || !self_inlier || !self_gamma || !has_ci || k < 0) return XK_EINVAL;
   if (k > XK_CI_MAXK) return fail(h, XK_ECAPACITY, "more than 7 matched agents");
   if (n != h->n || ldp < n || L < 2 || L > n_poses || n_poses > h->N || n_poses_max != h->N) return XK_EINVAL;
-  if (k > 0 && (!m_obs || !m_L || !m_q || !m_p || !m_nposes || !m_P || !m_n || !H || !res || !S || !P_j || !ci_gamma ||
+  if (k > 0 && (!m_obs || !m_L || !m_q || !m_p || !m_nposes || !m_nposes_max || !m_P || !m_n || !H || !res || !S || !P_j || !ci_gamma ||
                 ldh < 3 * k || lds < 3 * k || ldpj < n))
     return XK_EINVAL;
   const int srch = k > 0 ? check_w(h, ci_msckf_w) : 0;
   if (srch < 0) return fail(h, XK_EINVAL, "The CI weights must be lower than 1.0 and larger 0.0");
   int Ltot = L, nmax = n;
   for (int i = 0; i < k; ++i) {
-    if (m_L[i] < 2 || m_L[i] > m_nposes[i] || m_nposes[i] > 64 || m_n[i] < XK_CORE + 6 * m_nposes[i]) return XK_EINVAL;
+    // a matched agent's lists hold its VALID poses; its covariance is laid out for its own window size (include/xk.h)
+    if (m_L[i] < 2 || m_L[i] > m_nposes[i] || m_nposes[i] > m_nposes_max[i] || m_nposes_max[i] > 64 ||
+        m_n[i] < XK_CORE + 6 * m_nposes_max[i])
+      return XK_EINVAL;
     Ltot += m_L[i];
     nmax = std::max(nmax, m_n[i]);
   }
@@ -362,7 +369,7 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
     const double *hq = self ? C_q_G : m_q[i - 1], *hp = self ? G_p_C : m_p[i - 1], *hobs = self ? obs : m_obs[i - 1];
     const double *hP = self ? P : m_P[i - 1];
     const int np_i = self ? n_poses : m_nposes[i - 1], L_i = self ? L : m_L[i - 1], n_i = self ? n : m_n[i - 1];
-    const int ld_i = self ? ldp : n_i, npm_i = self ? n_poses_max : m_nposes[i - 1];
+    const int ld_i = self ? ldp : n_i, npm_i = self ? n_poses_max : m_nposes_max[i - 1];
     HIPCHK(h, hipStreamSynchronize(h->stream));  // scratch reuse across agents
     HIPCHK(h, hipMemcpyAsync(aq, hq, sizeof(double) * 4 * np_i, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(ap, hp, sizeof(double) * 3 * np_i, hipMemcpyHostToDevice, h->stream));
@@ -427,9 +434,7 @@ extern "C" int xk_msckf_ci_track(xk_handle *h, const double *obs, int L, const d
   if (srch)
     if (int rc = ciw_chol_status(h)) return rc;
   *ci_gamma = g_ci;
-  const int dof = 2 * Ltot - 3;
-  if (dof >= XK_CHI2_LEN) return fail(h, XK_ECAPACITY, "chi-square table too short");
-  if (!(g_ci < XK_CHI2_095[dof])) return XK_OK;   // :243-250
+  if (!(g_ci < ci_gate_threshold(2 * Ltot - 3))) return XK_OK;   // :243-250
   // the CI-weighted S (ci.cpp:78-85 + :255): the weights sit in the entry's device slots, the host's constants or the searched ones
   if (!srch) {
     double v[XK_CIW_MAXK1] = {w0};
@@ -598,7 +603,7 @@ static CiwrLayout ciwr_layout(int n) {
 // What the stages of one round share.
 //   srch: the weights are searched (ci_msckf_w < 0), else fixed: w0 own, w_oth every other agent (searched: xk_ci_combine runs with
 //   unit weights); ci_seq: what the gate markers of this round hold; side: track j >= 1 runs its chain on ci_stream[j]; per track
-//   its stream, the length of the own track and the degrees of freedom of the joint gate; ws: a track's region laid out for this
+//   its stream, the length of the own track and the threshold of the joint gate; ws: a track's region laid out for this
 //   round's k1, region: the regions' spacing in d_ciws; as / fin: searched, filled track by track while the chains are prepared
 struct CiRound {
   int world, self_rank, n_tracks, k, k1, m, n, N, srch;
@@ -609,7 +614,8 @@ struct CiRound {
   unsigned long long ci_seq;
   bool side;
   hipStream_t stream[8];
-  int L0[8], dof[8];
+  int L0[8];
+  double chi[8];
   CiTrackWs ws;
   size_t region;
   CiwrLayout wr;
@@ -621,7 +627,7 @@ static double *ci_round_ws(const xk_handle *h, const CiRound &r, int j) { return
 // this track passed both gates: the own chi-square test (:180) and the joint one (:243-250)
 static bool ci_round_passed(const xk_handle *h, const CiRound &r, int j) {
   const double *g = xk_cip_gate(h->h_ci_w, j);
-  return g[0] != 0.0 && g[1] < XK_CHI2_095[r.dof[j]];
+  return g[0] != 0.0 && g[1] < r.chi[j];
 }
 
 // The agents of shared track j where their data lie on the device: index 0 = self (the staged problem), 1.. = the others by rank
@@ -647,7 +653,7 @@ static void ci_round_agents(const xk_handle *h, const CiRound &r, int j, CiTrack
 }
 
 // Everything is validated BEFORE anything is queued or forked: an early return later would leave side streams running into
-// workspace and pinned words the next call reuses.  Leaves every track's own length and degrees of freedom in the record.
+// workspace and pinned words the next call reuses.  Leaves every track's own length and joint-gate threshold in the record.
 static int ci_round_validate(xk_handle *h, CiRound &r) {
   if (r.k > XK_CI_MAXK) return fail(h, XK_ECAPACITY, "more than 7 matched agents");
   if (r.self_rank < 0 || r.self_rank >= r.world || r.n_tracks < 0 || r.n_tracks > 8) return XK_EINVAL;
@@ -666,8 +672,7 @@ static int ci_round_validate(xk_handle *h, CiRound &r) {
     for (int i = 1; i < r.k1; ++i)
       if (ag.L[i] < 2 || ag.L[i] > ag.np[i] || ag.np[i] > r.N) return fail(h, XK_EINVAL, "received track / window lengths inconsistent");
     r.L0[j] = ag.L[0];
-    r.dof[j] = 2 * ag.Ltot - 3;
-    if (r.dof[j] >= XK_CHI2_LEN) return fail(h, XK_ECAPACITY, "chi-square table too short");
+    r.chi[j] = ci_gate_threshold(2 * ag.Ltot - 3);
   }
   return XK_OK;
 }

@@ -366,6 +366,8 @@ class Engine:
         return out
 
     def msckf_ci_track(self, trk, C_q_G, G_p_C, P, n_poses_max, sigma_img, matches, ci_msckf_w):
+        """matches: per matched agent dict(obs, q_list, p_list, P, n_poses_max) -- the lists hold the agent's VALID poses, its
+        covariance is laid out for its own n_poses_max (oracle/ref_np.msckf_ci_track takes the same dicts)."""
         k = len(matches)
         n = P.shape[0]
         base = [_d(trk), _d(C_q_G), _d(G_p_C), _f(P)]
@@ -376,6 +378,7 @@ class Engine:
         arr = lambda xs: (c_dp * max(k, 1))(*[x[1] for x in xs])
         mL, mLp = _i([len(m["obs"]) for m in matches] or [0])
         mnp, mnpp = _i([len(m["p_list"]) for m in matches] or [0])
+        mnm, mnmp = _i([m["n_poses_max"] for m in matches] or [0])
         mn, mnp_ = _i([m["P"].shape[0] for m in matches] or [0])
         si, sg, hc, cg = C.c_int(), C.c_double(), C.c_int(), C.c_double()
         m3 = max(3 * k, 1)
@@ -386,7 +389,7 @@ class Engine:
         self._chk(self.L.xk_msckf_ci_track(
             self.h, base[0][1], C.c_int(len(trk)), base[1][1], base[2][1], C.c_int(len(G_p_C)), base[3][1],
             C.c_int(n), C.c_int(n), C.c_int(n_poses_max), C.c_double(sigma_img), C.c_int(k), arr(mo), mLp, arr(mq),
-            arr(mp), mnpp, arr(mP), mnp_, C.c_double(ci_msckf_w), C.byref(si), C.byref(sg), C.byref(hc), C.byref(cg),
+            arr(mp), mnpp, mnmp, arr(mP), mnp_, C.c_double(ci_msckf_w), C.byref(si), C.byref(sg), C.byref(hc), C.byref(cg),
             H.ctypes.data_as(c_dp), C.c_int(m3), res.ctypes.data_as(c_dp), S.ctypes.data_as(c_dp), C.c_int(m3),
             Pj.ctypes.data_as(c_dp), C.c_int(n)), "xk_msckf_ci_track")
         out = dict(self_inlier=bool(si.value), self_gamma=sg.value, ci=None, ci_gamma=cg.value)
