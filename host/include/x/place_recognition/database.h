@@ -8,6 +8,11 @@
 // Every bit operation -- the vocabulary descent, the XOR / OR aggregation, the Hamming norms, the 2-NN search --
 // runs on the GPU behind the xk_pr_* entry points (include/xk.h); keyframes (SimpleState payload, tracks,
 // descriptors, VLAD) stay in device memory.  There is no CPU fallback.
+//
+// findCorrespondences exists twice: Database::findCorrespondences is the reference's function as one device call (match,
+// ratio test, essential-matrix filter, mask, duplicate removal, classification; the lists never visit the host in
+// between), and knnMatch / essentialInliers with the free functions ratioTestMatches / goodMatches / classifyMatches are
+// the same thing stage by stage, with the list work on the host.  Both give the same lists.
 #pragma once
 #include <memory>
 #include <string>
@@ -55,6 +60,18 @@ struct Candidate {                 // what VIO::processOtherRequests sends back 
   int n_descriptors = 0;
 };
 
+// What findCorrespondences hands to the CI update, before the bookkeeping of :518-577.
+struct GoodMatch { int queryIdx, trainIdx; };
+enum class MatchKind { MSCKF_OPP, SLAM_SLAM, SLAM_OPP, OPP_OPP };
+struct ClassifiedMatch { MatchKind kind; int current, received; };
+struct Correspondences {
+  int status = 0;                  // xk_pr_corr_out::status: 0 matched, 1...5 the reference's early returns
+  int n_candidates = 0, n_inliers = 0;
+  std::vector<GoodMatch> good;     // after the mask and the duplicate removal (:275-302)
+  std::vector<ClassifiedMatch> classified;   // :311-383
+  double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 class Database {                   // database.h / database.cpp
  public:
   // payload_doubles / tracks_doubles: sizes of the per-keyframe device buffers the store copies
@@ -79,6 +96,17 @@ class Database {                   // database.h / database.cpp
   std::vector<unsigned char> essentialInliers(const std::vector<float> &current_points, const std::vector<float> &received_points,
                                               double fx, double fy, double cx, double cy, double threshold = 1.0,
                                               int n_hyp = 1024, unsigned long seed = 0);
+
+  // PlaceRecognition::findCorrespondences (place_recognition.cpp:137-385, the non-GT branch) in one call
+  // (xk_pr_find_correspondences): 2-NN match, distance + ratio test, essential-matrix filter, mask, duplicate removal and
+  // classification on the device, one copy in, one result block out, one wait.  Descriptors and pixels ([rows][2], x then
+  // y) of both sides in MSCKF | SLAM | OPP order.  The same lists as knnMatch -> ratioTestMatches -> essentialInliers ->
+  // goodMatches -> classifyMatches.
+  Correspondences findCorrespondences(const Descriptors &received, const std::vector<float> &received_points,
+                                      const Descriptors &current, const std::vector<float> &current_points, int n_cur_msckf,
+                                      int n_cur_slam, int n_rec_msckf, int n_rec_slam, double pr_min_distance,
+                                      double pr_ratio_thr, double fx, double fy, double cx, double cy, double threshold = 1.0,
+                                      int n_hyp = 1024, unsigned long seed = 0);
 
  private:
   xk_handle *xk_;
@@ -111,7 +139,7 @@ class VocabularyTrainer {
 
 // The rest of findCorrespondences' non-GT branch on the 2-NN result: distance + ratio test (:252-263), optional
 // RANSAC inlier mask (:268-281; Database::essentialInliers estimates it on the device), duplicate removal (:283-301).
-struct GoodMatch { int queryIdx, trainIdx; };
+// The stage-by-stage path: Database::findCorrespondences computes the same lists in one call.
 // The survivors of the distance + ratio test alone (:252-263), before the mask and the duplicate removal: the matches whose
 // pixel positions the reference collects for findEssentialMat (:264-267), and the list an inlier mask is indexed by.
 std::vector<GoodMatch> ratioTestMatches(const std::vector<int> &idx, const std::vector<int> &dist, double pr_min_distance,
@@ -120,8 +148,6 @@ std::vector<GoodMatch> goodMatches(const std::vector<int> &idx, const std::vecto
                                    double pr_ratio_thr, const std::vector<unsigned char> *inlier_mask = nullptr);
 
 // Classification of place_recognition.cpp:311-388.
-enum class MatchKind { MSCKF_OPP, SLAM_SLAM, SLAM_OPP, OPP_OPP };
-struct ClassifiedMatch { MatchKind kind; int current, received; };
 std::vector<ClassifiedMatch> classifyMatches(const std::vector<GoodMatch> &good, int n_cur_msckf, int n_cur_slam,
                                              int n_rec_msckf, int n_rec_slam);
 }  // namespace x

@@ -73,6 +73,26 @@ std::vector<unsigned char> Database::essentialInliers(const std::vector<float> &
   return mask;
 }
 
+Correspondences Database::findCorrespondences(const Descriptors &rec, const std::vector<float> &rec_px, const Descriptors &cur,
+                                              const std::vector<float> &cur_px, int n_cur_msckf, int n_cur_slam, int n_rec_msckf,
+                                              int n_rec_slam, double pr_min_distance, double pr_ratio_thr, double fx, double fy,
+                                              double cx, double cy, double threshold, int n_hyp, unsigned long seed) {
+  if (rec_px.size() != 2 * (size_t)rec.rows || cur_px.size() != 2 * (size_t)cur.rows)
+    throw std::runtime_error("findCorrespondences: a side's points do not match its descriptors");
+  xk_pr_corr_out out;
+  std::vector<int> good(2 * (size_t)rec.rows + 2), cls(3 * (size_t)rec.rows + 3);   // (never a null pointer)
+  check(xk_, xk_pr_find_correspondences(pr_, rec.ptr(), rec_px.data(), rec.rows, cur.ptr(), cur_px.data(), cur.rows, n_cur_msckf,
+                                        n_cur_slam, n_rec_msckf, n_rec_slam, pr_min_distance, pr_ratio_thr, fx, fy, cx, cy,
+                                        threshold, n_hyp, seed, &out, good.data(), cls.data()),
+        "xk_pr_find_correspondences");
+  Correspondences c;
+  c.status = out.status; c.n_candidates = out.n_candidates; c.n_inliers = out.n_inliers;
+  for (int i = 0; i < out.n_good; ++i) c.good.push_back({good[2 * i], good[2 * i + 1]});
+  for (int i = 0; i < out.n_classified; ++i) c.classified.push_back({(MatchKind)cls[3 * i], cls[3 * i + 1], cls[3 * i + 2]});
+  for (int i = 0; i < 9; ++i) c.E[i] = out.E[i];
+  return c;
+}
+
 VocabularyTrainer::VocabularyTrainer(xk_handle *xk, int k, int L, int desc_bytes, int max_descriptors)
     : xk_(xk), k_(k), L_(L), desc_bytes_(desc_bytes) {
   check(xk_, xk_voc_create(xk_, k, L, desc_bytes, max_descriptors, &voc_), "xk_voc_create");

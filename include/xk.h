@@ -389,6 +389,51 @@ int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, i
 int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n_cand, double *E /* [count][10][9] */,
                                int *inliers /* [count][10] */);
 
+/* PlaceRecognition::findCorrespondences (place_recognition.cpp:137-385, the non-GT_DEBUG branch) in ONE call: what
+ * xk_pr_knn_match -> ratio test -> xk_pr_essential_ransac -> mask and duplicate removal -> classification compute as a
+ * chain of stage calls and host list work, with nothing returning to the host in between.  One pinned block and one copy
+ * in (descriptors and pixels of both sides), six launches on the handle's stream (xk_desc_knn2, xk_corr_candidates,
+ * xk_ess_solve, xk_ess_score, xk_ess_mask, xk_corr_finish) with the candidate count in device memory, one result block
+ * out, one synchronisation.
+ *   2-NN with query = received, train = current; a query passes when its second neighbour exists and
+ *   (double)d0 < pr_min_distance && (double)d0 < (double)d1 * pr_ratio_thr (:254-255).  The candidates' pixels, in query
+ *   order, go through the essential filter exactly as xk_pr_essential_ransac takes them (same sampler, solver, key and
+ *   tie rule: mask and E are bit-equal to that entry on the same pairs).  Then the mask (:275-281), the duplicate search
+ *   and the erase loop with its running offset (:283-302; NOT a clean de-duplication, and reproduced as it is), and the
+ *   classification (:311-383). */
+typedef struct xk_pr_corr_out {
+  int status;        /* 0 matched; 1 no current features (:209); 2 no received features (:244); 3 no match passes the
+                        distance + ratio test (:265); 4 fewer than 5 candidates or no hypothesis produced a candidate
+                        (F_1.empty(), :274); 5 nothing left after mask + duplicate removal (:304) */
+  int n_candidates;  /* survivors of the ratio test = pairs given to the RANSAC */
+  int n_inliers, winner;
+  int n_good;        /* after mask and duplicate removal; 0 unless status == 0 */
+  int n_classified;  /* <= n_good (a good match falls in at most one class); 0 unless status == 0 */
+  int launches;      /* kernels queued by this call: 6, or 0 for status 1 and 2 (decided on the host) */
+  double E[9];       /* as xk_pr_essential_ransac; zero for status 1..4 */
+} xk_pr_corr_out;
+
+/* rec_* the received keyframe (query side), cur_* the current features (train side), each HOST in MSCKF | SLAM | OPP
+ * order: desc [n][desc_bytes], xy [n][2] float32 pixels.  good HOST [n_rec][2] (queryIdx, trainIdx), classified HOST
+ * [n_rec][3] (kind in the numbering of x::MatchKind: 0 MSCKF x OPP, 1 SLAM x SLAM, 2 SLAM x OPP, 3 OPP x OPP; index in
+ * the current list of its class; index in the received list of its class); the first n_good / n_classified rows are
+ * written; either may be NULL.  For every non-zero status the lists are empty (the reference returns before committing
+ * anything).  xk_pr_essential_hypotheses works after this call as after xk_pr_essential_ransac.
+ * XK_EINVAL: null pointers, negative counts, class counts beyond their side, fx / fy <= 0, non-finite intrinsics,
+ * threshold_px < 0, n_hyp outside 1...4096.  XK_ECAPACITY: n_rec or n_cur above max_desc. */
+int xk_pr_find_correspondences(xk_pr *p, const unsigned char *rec_desc, const float *rec_xy, int n_rec,
+                               const unsigned char *cur_desc, const float *cur_xy, int n_cur, int n_cur_msckf,
+                               int n_cur_slam, int n_rec_msckf, int n_rec_slam, double pr_min_distance, double pr_ratio_thr,
+                               double fx, double fy, double cx, double cy, double threshold_px, int n_hyp, unsigned long seed,
+                               xk_pr_corr_out *out, int *good /* [n_rec][2], may be NULL */,
+                               int *classified /* [n_rec][3], may be NULL */);
+
+/* Inspection of the last xk_pr_find_correspondences: candidates HOST [n_rec][2] (query, train; n_candidates rows written),
+ * mask HOST [n_rec] (the essential filter's, zero past the candidates), remove_ids HOST [n_rec] (*n_remove written: the
+ * list of :283-296).  Any output may be NULL.  No device work: the rows came back in the call's result block.  XK_EINVAL
+ * before a completed call. */
+int xk_pr_find_correspondences_stage(xk_pr *p, int *candidates, unsigned char *mask, int *remove_ids, int *n_remove);
+
 /* ---- training a vocabulary (DBoW3::Vocabulary::create, third_party/DBow3/src/Vocabulary.cpp:157-186) -------------
  * Hierarchical k-means of binary descriptors on the device: HKmeansStep (Vocabulary.cpp:233-394) with k-means++ seeding
  * (initiateClustersKMpp, :409-491), Hamming distances, bit-majority means (DescManip::meanValue, DescManip.cpp:26-75) and

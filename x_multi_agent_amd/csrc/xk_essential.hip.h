@@ -10,6 +10,9 @@
 //                   and a packed 64-bit atomicMax key (count << 32 | ~hypothesis) -- order-independent
 //   xk_ess_mask     the winner's inlier set, its E and count
 //
+// The pair count is a value (the stage entry, xk_pr_essential_ransac) or, with XkEssArgs::n_dev, what an earlier launch on the
+// stream left in device memory (xk_pr_find_correspondences, xk_correspond.hip.h): then n only bounds grids and buffers.
+//
 // All n_hyp hypotheses are evaluated.  The CPU estimator's adaptive stop (prob = 0.99) only truncates a sequential loop,
 // and the best of all hypotheses is at least the best of any prefix: `prob` is therefore not a parameter.
 //
@@ -245,6 +248,7 @@ XK_RANSAC_HD double xk_ess_sampson(const double *E, double cx, double cy, double
 struct XkEssArgs {
   const float *cur_xy, *rec_xy;     // [n][2] pixels
   int n, n_hyp;
+  const int *n_dev;                 // NULL: n pairs.  Else n is the bound the grids are sized by, *n_dev the count (xk_dev_count)
   double fx, fy, cx, cy, t2;
   unsigned long long seed;
   XkRansacScratch s;                // XK_ESS_MAX_HYP hypotheses of XK_ESS_MAXC candidates
@@ -259,14 +263,20 @@ __global__ __launch_bounds__(XK_ESS_SOLVE_T) void xk_ess_solve(XkEssArgs a) {
   const int h = blockIdx.x * XK_ESS_SOLVE_T + threadIdx.x;
   if (h == 0) *a.s.key = 0ull;
   if (h >= a.n_hyp) return;
+  const int n = xk_dev_count(a.n_dev, a.n);
+  double *E = a.s.cand + (size_t)h * (XK_ESS_MAXC * 9);
+  if (n < 5) {                      // (the sampler has no rejection loop: below five pairs its indices leave the list)
+    for (int i = 0; i < XK_ESS_MAXC * 9; ++i) E[i] = 0.0;
+    a.s.ncand[h] = 0;
+    return;
+  }
   int pick[5];
-  xk_ransac_sample<5>(a.seed, h, a.n, pick);
+  xk_ransac_sample<5>(a.seed, h, n, pick);
   double cur[5][2], rec[5][2];
   for (int k = 0; k < 5; ++k) {
     cur[k][0] = ((double)a.cur_xy[2 * pick[k]] - a.cx) / a.fx; cur[k][1] = ((double)a.cur_xy[2 * pick[k] + 1] - a.cy) / a.fy;
     rec[k][0] = ((double)a.rec_xy[2 * pick[k]] - a.cx) / a.fx; rec[k][1] = ((double)a.rec_xy[2 * pick[k] + 1] - a.cy) / a.fy;
   }
-  double *E = a.s.cand + (size_t)h * (XK_ESS_MAXC * 9);
   const int nc = xk_ess_solve5(cur, rec, ws + threadIdx.x * XK_ESS_WS, E);
   for (int i = nc * 9; i < XK_ESS_MAXC * 9; ++i) E[i] = 0.0;
   a.s.ncand[h] = nc;
@@ -279,21 +289,21 @@ __device__ __forceinline__ double xk_ess_error_at(const XkEssArgs &a, const doub
 }
 
 __global__ __launch_bounds__(256) void xk_ess_score(XkEssArgs a) {
-  xk_ransac_score<XK_ESS_MAXC>(a.s, a.n, a.t2, [&](const double *E, int i) { return xk_ess_error_at(a, E, i); });
+  xk_ransac_score<XK_ESS_MAXC>(a.s, xk_dev_count(a.n_dev, a.n), a.t2, [&](const double *E, int i) { return xk_ess_error_at(a, E, i); });
 }
 
 __global__ __launch_bounds__(256) void xk_ess_mask(XkEssArgs a) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.x * 256 + threadIdx.x, n = xk_dev_count(a.n_dev, a.n);
   const XkRansacWinner w = xk_ransac_winner(*a.s.key);
   if (!w.valid) {
-    if (i < a.n) a.mask[i] = 0;
+    if (i < n) a.mask[i] = 0;
     if (i < 9) a.E[i] = 0.0;
     if (i == 0) { a.res[0] = 0; a.res[1] = -1; }
     return;
   }
   const double *Ep = a.s.cand + ((size_t)w.h * XK_ESS_MAXC + a.s.bestc[w.h]) * 9;
   const double E[9] = {Ep[0], Ep[1], Ep[2], Ep[3], Ep[4], Ep[5], Ep[6], Ep[7], Ep[8]};
-  if (i < a.n) a.mask[i] = xk_ess_error_at(a, E, i) <= a.t2 ? 1 : 0;
+  if (i < n) a.mask[i] = xk_ess_error_at(a, E, i) <= a.t2 ? 1 : 0;
   if (i < 9) a.E[i] = Ep[i];
   if (i == 0) { a.res[0] = w.count; a.res[1] = w.h; }
 }

@@ -6,6 +6,7 @@
 #pragma once
 #include "xk_place.hip.h"
 #include "xk_essential.hip.h"
+#include "xk_correspond.hip.h"
 #include "xk_vocab.hip.h"
 
 #define XK_PR_MAX_KEYFRAMES 15   // database.h:70
@@ -35,6 +36,11 @@ struct xk_pr {
   unsigned char *d_ess;       // XkRansacScratch | E [9] | res [2] | pixel pairs [4 max_desc] floats | mask [max_desc]
   unsigned char *h_ess;       // pinned: pixel pairs in, E / n_inliers / winner / mask out
   int ess_n_hyp;              // hypotheses of the last call (0: none yet)
+  // findCorrespondences in one call (xk_correspond.hip.h): allocated by the first xk_pr_find_correspondences
+  unsigned char *d_corr;      // input block | G, first_j, alive, count | result block, each sized by max_desc
+  unsigned char *h_corr;      // pinned: input block | result block of the last call
+  int corr_n_rec;             // bound the last call's result block is laid out by (-1 after a failed call); corr_called: any call yet
+  bool corr_called;
 };
 
 extern "C" void xk_pr_destroy(xk_pr *p) {
@@ -46,6 +52,8 @@ extern "C" void xk_pr_destroy(xk_pr *p) {
   if (p->h_words) hipHostFree(p->h_words);
   hipFree(p->d_ess);
   if (p->h_ess) hipHostFree(p->h_ess);
+  hipFree(p->d_corr);
+  if (p->h_corr) hipHostFree(p->h_corr);
   for (auto &u : p->uav_ids) delete u;
   free(p);
 }
@@ -265,6 +273,22 @@ static XkEssArgs ess_args(xk_pr *p) {
   return a;
 }
 
+static size_t ess_xy_bytes(const xk_pr *p) { return sizeof(float) * 4 * (size_t)p->max_desc; }
+static size_t ess_out_bytes(const xk_pr *p) { return 9 * sizeof(double) + 2 * sizeof(int) + (size_t)p->max_desc; }
+
+// the essential block and its pinned mirror, on first use
+static int ess_reserve(xk_pr *p) {
+  if (p->d_ess) return XK_OK;
+  xk_handle *h = p->h;
+  void *d = nullptr, *hp = nullptr;
+  if (hipMalloc(&d, xk_ransac_scratch_bytes<XK_ESS_MAXC>(XK_ESS_MAX_HYP) + ess_xy_bytes(p) + ess_out_bytes(p)) != hipSuccess)
+    return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: scratch block");
+  if (hipHostMalloc(&hp, ess_xy_bytes(p) + ess_out_bytes(p)) != hipSuccess) { hipFree(d); return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: pinned block"); }
+  p->d_ess = (unsigned char *)d;
+  p->h_ess = (unsigned char *)hp;
+  return XK_OK;
+}
+
 extern "C" int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float *rec_xy, int n, double fx, double fy, double cx,
                                       double cy, double threshold_px, int n_hyp, unsigned long seed, unsigned char *mask,
                                       double *E, int *n_inliers) {
@@ -282,15 +306,9 @@ extern "C" int xk_pr_essential_ransac(xk_pr *p, const float *cur_xy, const float
   if (E) memset(E, 0, 9 * sizeof(double));
   if (n < 5) return XK_OK;                                   // F_1.empty() -> return false
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t xy_bytes = sizeof(float) * 4 * (size_t)p->max_desc, out_bytes = 9 * sizeof(double) + 2 * sizeof(int) + (size_t)p->max_desc;
-  if (!p->d_ess) {
-    void *d = nullptr, *hp = nullptr;
-    if (hipMalloc(&d, xk_ransac_scratch_bytes<XK_ESS_MAXC>(XK_ESS_MAX_HYP) + xy_bytes + out_bytes) != hipSuccess)
-      return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: scratch block");
-    if (hipHostMalloc(&hp, xy_bytes + out_bytes) != hipSuccess) { hipFree(d); return fail(h, XK_ENOMEM, "xk_pr_essential_ransac: pinned block"); }
-    p->d_ess = (unsigned char *)d;
-    p->h_ess = (unsigned char *)hp;
-  }
+  const size_t xy_bytes = ess_xy_bytes(p), out_bytes = ess_out_bytes(p);
+  const int rc = ess_reserve(p);
+  if (rc != XK_OK) return rc;
   XkEssArgs a = ess_args(p);
   a.n = n; a.n_hyp = n_hyp;
   a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
@@ -324,6 +342,135 @@ extern "C" int xk_pr_essential_hypotheses(xk_pr *p, int first, int count, int *n
   if (!p) return XK_EINVAL;
   return ransac_hypotheses(p->h, "xk_pr_essential_hypotheses", "xk_pr_essential_ransac", p->d_ess ? p->ess_n_hyp : -1,
                            p->d_ess ? ess_args(p).s : XkRansacScratch{}, XK_ESS_MAXC, first, count, n_cand, E, inliers);
+}
+
+// ---------------------------------------------------------------------------
+// findCorrespondences in one call (place_recognition.cpp:137-385, the non-GT branch), xk_correspond.hip.h: one copy in, six
+// launches with the candidate count in device memory, one result block out, one wait
+// ---------------------------------------------------------------------------
+// The result block for the bound n: head | E [9] | good [n][2] | classified [n][3] | candidates [n][2] | remove_ids [n] | mask [n]
+struct XkCorrResult {
+  XkCorrHead *head;
+  double *E;
+  int *good, *classified, *cand, *remove_ids;
+  unsigned char *mask;
+};
+static size_t corr_result_bytes(size_t n) { return sizeof(XkCorrHead) + 9 * sizeof(double) + sizeof(int) * 8 * n + n; }
+static XkCorrResult corr_result(unsigned char *at, size_t n) {   // at: 8-byte aligned
+  XkCorrResult r;
+  r.head = (XkCorrHead *)at;
+  r.E = (double *)(r.head + 1);
+  r.good = (int *)(r.E + 9); r.classified = r.good + 2 * n; r.cand = r.classified + 3 * n; r.remove_ids = r.cand + 2 * n;
+  r.mask = (unsigned char *)(r.remove_ids + n);
+  return r;
+}
+// the device block: input (descriptors and pixels of both sides, packed by the call's counts) | alive | G | first_j | count | result
+static size_t corr_in_bytes(const xk_pr *p) { return (size_t)p->max_desc * (8 * (size_t)p->W + 16); }   // (a multiple of 8)
+static size_t corr_work_bytes(const xk_pr *p) {
+  const size_t M = (size_t)p->max_desc;
+  return (8 * ((M + 63) / 64) + sizeof(int) * (3 * M + 2) + 7) / 8 * 8;
+}
+
+extern "C" int xk_pr_find_correspondences(xk_pr *p, const unsigned char *rec_desc, const float *rec_xy, int n_rec,
+                                          const unsigned char *cur_desc, const float *cur_xy, int n_cur, int n_cur_msckf,
+                                          int n_cur_slam, int n_rec_msckf, int n_rec_slam, double pr_min_distance,
+                                          double pr_ratio_thr, double fx, double fy, double cx, double cy, double threshold_px,
+                                          int n_hyp, unsigned long seed, xk_pr_corr_out *out, int *good, int *classified) {
+  if (!p) return XK_EINVAL;
+  xk_handle *h = p->h;
+  if (!out || n_rec < 0 || n_cur < 0 || (n_rec > 0 && (!rec_desc || !rec_xy)) || (n_cur > 0 && (!cur_desc || !cur_xy)))
+    return fail(h, XK_EINVAL, "xk_pr_find_correspondences: null argument or negative count");
+  if (n_cur_msckf < 0 || n_cur_slam < 0 || n_rec_msckf < 0 || n_rec_slam < 0 || (long)n_cur_msckf + n_cur_slam > n_cur ||
+      (long)n_rec_msckf + n_rec_slam > n_rec)
+    return fail(h, XK_EINVAL, "xk_pr_find_correspondences: class counts negative or beyond their side");
+  if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+    return fail(h, XK_EINVAL, "xk_pr_find_correspondences: focal lengths must be positive and the intrinsics finite");
+  if (!(threshold_px >= 0.0) || !std::isfinite(threshold_px)) return fail(h, XK_EINVAL, "xk_pr_find_correspondences: threshold_px < 0");
+  if (n_hyp < 1 || n_hyp > XK_ESS_MAX_HYP) return fail(h, XK_EINVAL, "xk_pr_find_correspondences: n_hyp outside 1...4096");
+  if (n_rec > p->max_desc || n_cur > p->max_desc) return fail(h, XK_ECAPACITY, "xk_pr_find_correspondences: more descriptors than max_desc");
+  memset(out, 0, sizeof(*out));
+  out->winner = -1;
+  p->corr_called = true;
+  p->corr_n_rec = -1;
+  if (n_cur == 0 || n_rec == 0) {                            // :209, :244 -- decided here, nothing queued
+    out->status = n_cur == 0 ? 1 : 2;
+    p->corr_n_rec = 0;
+    return XK_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = ess_reserve(p);
+  if (rc != XK_OK) return rc;
+  const size_t in_cap = corr_in_bytes(p), work = corr_work_bytes(p), res_cap = corr_result_bytes((size_t)p->max_desc);
+  if (!p->d_corr) {
+    void *d = nullptr, *hp = nullptr;
+    if (hipMalloc(&d, in_cap + work + res_cap) != hipSuccess) return fail(h, XK_ENOMEM, "xk_pr_find_correspondences: device block");
+    if (hipHostMalloc(&hp, in_cap + res_cap) != hipSuccess) { hipFree(d); return fail(h, XK_ENOMEM, "xk_pr_find_correspondences: pinned block"); }
+    p->d_corr = (unsigned char *)d;
+    p->h_corr = (unsigned char *)hp;
+  }
+  // one pinned block, one copy: received descriptors | current descriptors | received pixels | current pixels
+  const size_t W = (size_t)p->W, rdb = (size_t)n_rec * W * 4, cdb = (size_t)n_cur * W * 4, rxb = sizeof(float) * 2 * (size_t)n_rec,
+               cxb = sizeof(float) * 2 * (size_t)n_cur;
+  memcpy(p->h_corr, rec_desc, rdb);
+  memcpy(p->h_corr + rdb, cur_desc, cdb);
+  memcpy(p->h_corr + rdb + cdb, rec_xy, rxb);
+  memcpy(p->h_corr + rdb + cdb + rxb, cur_xy, cxb);
+  HIPCHK(h, hipMemcpyAsync(p->d_corr, p->h_corr, rdb + cdb + rxb + cxb, hipMemcpyHostToDevice, h->stream));
+  const unsigned int *d_rec_desc = (const unsigned int *)p->d_corr, *d_cur_desc = (const unsigned int *)(p->d_corr + rdb);
+  const float *d_rec_xy = (const float *)(p->d_corr + rdb + cdb), *d_cur_xy = (const float *)(p->d_corr + rdb + cdb + rxb);
+  unsigned long long *d_alive = (unsigned long long *)(p->d_corr + in_cap);
+  int *d_G = (int *)(d_alive + ((size_t)p->max_desc + 63) / 64), *d_fj = d_G + 2 * (size_t)p->max_desc, *d_count = d_fj + p->max_desc;
+  const XkCorrResult R = corr_result(p->d_corr + in_cap + work, (size_t)n_rec);
+
+  XkKnnArgs ka{d_rec_desc, d_cur_desc, n_rec, n_cur, p->W, p->d_knn, p->d_knn + 2 * (size_t)p->max_desc};
+  hipLaunchKernelGGL(xk_desc_knn2, dim3((n_rec + XK_KNN_Q - 1) / XK_KNN_Q), dim3(256), 0, h->stream, ka);
+  XkEssArgs a = ess_args(p);
+  a.rec_xy = a.cur_xy + 2 * (size_t)p->max_desc;             // (the stage entry packs it 2 n behind; here n is on the device)
+  a.n = n_rec; a.n_dev = d_count; a.n_hyp = n_hyp;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+  const double t = threshold_px / ((fx + fy) / 2.0);
+  a.t2 = t * t;
+  a.seed = (unsigned long long)seed;
+  XkCorrCandArgs ca{ka.idx, ka.dist, n_rec, pr_min_distance, pr_ratio_thr, d_rec_xy, d_cur_xy, (float *)a.cur_xy, (float *)a.rec_xy,
+                    R.cand, d_count};
+  hipLaunchKernelGGL(xk_corr_candidates, dim3(1), dim3(256), 0, h->stream, ca);
+  p->ess_n_hyp = 0;
+  hipLaunchKernelGGL(xk_ess_solve, dim3((n_hyp + XK_ESS_SOLVE_T - 1) / XK_ESS_SOLVE_T), dim3(XK_ESS_SOLVE_T), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ess_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ess_mask, dim3((n_rec + 255) / 256), dim3(256), 0, h->stream, a);
+  XkCorrFinishArgs fa{n_rec, d_count, R.cand, a.mask, a.E, a.res, n_cur_msckf, n_cur_slam, n_rec_msckf, n_rec_slam, d_G, d_fj, d_alive,
+                      R.head, R.E, R.good, R.classified, R.remove_ids, R.mask};
+  hipLaunchKernelGGL(xk_corr_finish, dim3(1), dim3(256), 0, h->stream, fa);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, XK_EDEVICE, "xk_pr_find_correspondences launch", e);
+  unsigned char *h_res = p->h_corr + in_cap;
+  HIPCHK(h, hipMemcpyAsync(h_res, R.head, corr_result_bytes((size_t)n_rec), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  p->ess_n_hyp = n_hyp;
+  p->corr_n_rec = n_rec;
+  const XkCorrResult H = corr_result(h_res, (size_t)n_rec);
+  out->status = H.head->status; out->n_candidates = H.head->n_candidates; out->n_inliers = H.head->n_inliers;
+  out->winner = H.head->winner; out->n_good = H.head->n_good; out->n_classified = H.head->n_classified;
+  out->launches = 6;
+  memcpy(out->E, H.E, 9 * sizeof(double));
+  if (good) memcpy(good, H.good, sizeof(int) * 2 * (size_t)out->n_good);
+  if (classified) memcpy(classified, H.classified, sizeof(int) * 3 * (size_t)out->n_classified);
+  return XK_OK;
+}
+
+extern "C" int xk_pr_find_correspondences_stage(xk_pr *p, int *candidates, unsigned char *mask, int *remove_ids, int *n_remove) {
+  if (!p) return XK_EINVAL;
+  xk_handle *h = p->h;
+  if (!p->corr_called || p->corr_n_rec < 0) return fail(h, XK_EINVAL, "xk_pr_find_correspondences_stage: no completed xk_pr_find_correspondences");
+  if (n_remove) *n_remove = 0;
+  if (p->corr_n_rec == 0) return XK_OK;                      // (statuses 1 and 2: nothing was queued)
+  const size_t n = (size_t)p->corr_n_rec;
+  const XkCorrResult H = corr_result(p->h_corr + corr_in_bytes(p), n);
+  if (candidates) memcpy(candidates, H.cand, sizeof(int) * 2 * (size_t)H.head->n_candidates);
+  if (mask) memcpy(mask, H.mask, n);
+  if (remove_ids) memcpy(remove_ids, H.remove_ids, sizeof(int) * (size_t)H.head->n_remove);
+  if (n_remove) *n_remove = H.head->n_remove;
+  return XK_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -35,7 +35,7 @@ SYMBOLS = [
     "xk_stage_range", "xk_stage_sun_angle", "xk_fetch_aux_flags", "xk_aux_rows",
     "xk_pr_create", "xk_pr_destroy", "xk_pr_vlad_bytes", "xk_pr_size", "xk_pr_compute_vlad", "xk_pr_add_keyframe",
     "xk_pr_find_candidate", "xk_pr_keyframe", "xk_pr_copy_keyframe", "xk_pr_knn_match",
-    "xk_pr_essential_ransac", "xk_pr_essential_hypotheses",
+    "xk_pr_essential_ransac", "xk_pr_essential_hypotheses", "xk_pr_find_correspondences", "xk_pr_find_correspondences_stage",
     "xk_voc_create", "xk_voc_destroy", "xk_voc_add", "xk_voc_count", "xk_voc_clear", "xk_voc_train", "xk_voc_get",
     "xk_trk_create", "xk_trk_destroy", "xk_trk_undistort", "xk_trk_fundamental_ransac", "xk_trk_fundamental_hypotheses",
     "xk_trk_filter_matches",

@@ -4,7 +4,8 @@ points (include/xk.h), and the training of the vocabulary they consume (xk_voc_*
 `PlaceRecognition::findCorrespondences` (place_recognition.cpp:137-390).
 
 No fallback: everything numeric runs in libxk.so's HIP kernels; the host part here is the same bookkeeping the
-reference does on the host (ratio test, duplicate removal, MSCKF / SLAM / OPP classification)."""
+reference does on the host (ratio test, duplicate removal, MSCKF / SLAM / OPP classification) -- the stage-by-stage
+path.  Database.find_correspondences is findCorrespondences as one device call, list work included."""
 import ctypes as C
 import os
 
@@ -35,6 +36,12 @@ class XkVocOutcome(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("n_words", C.c_int), ("levels", C.c_int), ("level_nodes", C.c_int * XK_VOC_MAX_LEVELS),
                 ("level_passes", C.c_int * XK_VOC_MAX_LEVELS), ("capped_nodes", C.c_int), ("launches", C.c_int),
                 ("host_waits", C.c_int)]
+
+
+class XkPrCorrOut(C.Structure):
+    """xk_pr_corr_out of include/xk.h."""
+    _fields_ = [("status", C.c_int), ("n_candidates", C.c_int), ("n_inliers", C.c_int), ("winner", C.c_int), ("n_good", C.c_int),
+                ("n_classified", C.c_int), ("launches", C.c_int), ("E", C.c_double * 9)]
 
 
 def _u8(a):
@@ -164,6 +171,48 @@ class Database:
         self._chk(self.L.xk_pr_essential_hypotheses(self.p, C.c_int(first), C.c_int(count), nc.ctypes.data_as(c_ip), E.ctypes.data_as(c_dp),
                                                     inl.ctypes.data_as(c_ip)), "xk_pr_essential_hypotheses")
         return nc[:count], E[:count], inl[:count]
+
+    def find_correspondences(self, rec_desc, rec_xy, cur_desc, cur_xy, counts, min_distance, ratio_thr, K, threshold_px=1.0,
+                             n_hyp=1024, seed=0):
+        """PlaceRecognition::findCorrespondences (place_recognition.cpp:137-385, non-GT branch) in one call
+        (xk_pr_find_correspondences): rec_* the received keyframe (query side), cur_* the current features (train side),
+        descriptors [n, desc_bytes] and float32 pixels [n, 2] in MSCKF | SLAM | OPP order; counts = (n_cur_msckf,
+        n_cur_slam, n_rec_msckf, n_rec_slam); K as for essential_ransac.  -> dict(status, n_candidates, n_inliers, winner,
+        E [3, 3], good [n_good, 2] (query, train), classified [n_classified, 3] (kind 0...3 as x::MatchKind, current,
+        received), launches).  The lists are empty for every non-zero status."""
+        K = np.asarray(K, np.float64)
+        fx, fy, cx, cy = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.ravel()
+        rd, rdp = _u8(np.asarray(rec_desc, np.uint8).reshape(-1, self.desc_bytes))
+        cd, cdp = _u8(np.asarray(cur_desc, np.uint8).reshape(-1, self.desc_bytes))
+        rx = np.ascontiguousarray(rec_xy, np.float32).reshape(-1, 2)
+        cx_ = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
+        if len(rx) != len(rd) or len(cx_) != len(cd):
+            raise ValueError("descriptors and pixels of a side differ in length")
+        n_rec, n_cur = len(rd), len(cd)
+        ncm, ncs, nrm, nrs = (int(c) for c in counts)
+        out = XkPrCorrOut()
+        good = np.zeros((max(n_rec, 1), 2), np.int32)
+        cls = np.zeros((max(n_rec, 1), 3), np.int32)
+        c_fp = C.POINTER(C.c_float)
+        self._chk(self.L.xk_pr_find_correspondences(
+            self.p, rdp, rx.ctypes.data_as(c_fp), C.c_int(n_rec), cdp, cx_.ctypes.data_as(c_fp), C.c_int(n_cur), C.c_int(ncm),
+            C.c_int(ncs), C.c_int(nrm), C.c_int(nrs), C.c_double(min_distance), C.c_double(ratio_thr), C.c_double(fx), C.c_double(fy),
+            C.c_double(cx), C.c_double(cy), C.c_double(threshold_px), C.c_int(n_hyp), C.c_ulong(seed), C.byref(out),
+            good.ctypes.data_as(c_ip), cls.ctypes.data_as(c_ip)), "xk_pr_find_correspondences")
+        self._corr_last = (n_rec, out.n_candidates)       # what find_correspondences_stage sizes and cuts its arrays by
+        return dict(status=out.status, n_candidates=out.n_candidates, n_inliers=out.n_inliers, winner=out.winner,
+                    E=np.array(out.E, np.float64).reshape(3, 3), good=good[:out.n_good].copy(),
+                    classified=cls[:out.n_classified].copy(), launches=out.launches)
+
+    def find_correspondences_stage(self):
+        """What the last find_correspondences passed between its stages -> dict(candidates [n_candidates, 2] (query, train),
+        mask uint8 [n_rec] (the essential filter's, zero past the candidates), remove_ids [n_remove])."""
+        n_rec, n_cand = getattr(self, "_corr_last", (0, 0))
+        n = max(n_rec, 1)
+        cand, mask, rem, nrem = np.zeros((n, 2), np.int32), np.zeros(n, np.uint8), np.zeros(n, np.int32), C.c_int(0)
+        self._chk(self.L.xk_pr_find_correspondences_stage(self.p, cand.ctypes.data_as(c_ip), mask.ctypes.data_as(c_ub),
+                                                          rem.ctypes.data_as(c_ip), C.byref(nrem)), "xk_pr_find_correspondences_stage")
+        return dict(candidates=cand[:n_cand].copy(), mask=mask[:n_rec].copy(), remove_ids=rem[:nrem.value].copy())
 
 
 def good_matches(idx, dist, min_distance, ratio_thr, inlier_mask=None):
