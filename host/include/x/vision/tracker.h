@@ -15,8 +15,9 @@
 namespace x {
 class Tracker {
  public:
-  // The reference's parameters (tracker.h:75-79, :234-261): outlier_method is cv::RANSAC there and RANSAC here whatever it says;
-  // outlier_param1 is the threshold in pixels; outlier_param2, the confidence, has no counterpart: all n_hyp hypotheses are
+  // The reference's parameters (tracker.h:75-79, :234-261): outlier_method 4 (cv::LMEDS) is least median of squares, which ignores
+  // outlier_param1; every other value is RANSAC (8 is cv::RANSAC; cv::FM_7POINT and FM_8POINT are out of scope: DESIGN 3.10).
+  // outlier_param1 is the RANSAC threshold in pixels; outlier_param2, the confidence, has no counterpart: all n_hyp hypotheses are
   // evaluated.  max_features bounds every list of a frame.  term_crit_ is (COUNT + EPS, 30, 0.01) as there.
   Tracker(xk_handle *xk, const Camera &cam, int fast_detection_delta, bool non_max_supp, unsigned int block_half_length,
           unsigned int margin, unsigned int n_feat_min, int outlier_method, double outlier_param1, double outlier_param2,
@@ -67,6 +68,9 @@ class Tracker {
   const xk_trk_frame_out &counts() const { return out_; }
   const std::vector<int> &origins() const { return origin_v_; }
   int getImgId() const { return img_id_; }
+  // the winner's median and scale of the last frame's outlier removal under outlier_method 4 (zeros: no candidate, nothing kept); false
+  // under RANSAC and after a first image
+  bool lastLmeds(double *median, double *sigma);
 
  private:
   void apply();               // the setups behind the parameters, made (again) before the next frame
@@ -74,7 +78,7 @@ class Tracker {
   xk_handle *xk_;
   xk_trk *trk_ = nullptr;
   int width_, height_, max_features_;
-  int threshold_, nms_, b_, margin_, n_feat_min_, win_w_, win_h_, max_level_, n_hyp_;
+  int threshold_, nms_, b_, margin_, n_feat_min_, win_w_, win_h_, max_level_, n_hyp_, outlier_method_;
   double threshold_px_, min_eig_thr_;
   unsigned int tiles_h_ = 1, tiles_w_ = 1, max_per_tile_ = 1u << 30;
   bool described_ = false, centroid_ = false, own_pattern_ = false, dirty_ = true;

@@ -10,13 +10,33 @@ static void check(xk_handle *h, int rc, const char *what) {
   if (rc != XK_OK) throw std::runtime_error(std::string(what) + ": " + xk_strerror(rc) + " (" + (h ? xk_last_error(h) : "") + ")");
 }
 
-MatchFilter::MatchFilter(xk_handle *xk, const Camera &camera, int max_matches, double outlier_param1, int n_hyp, unsigned long seed)
+MatchFilter::MatchFilter(xk_handle *xk, const Camera &camera, int max_matches, double outlier_param1, int n_hyp, unsigned long seed,
+                         int outlier_method)
     : xk_(xk), threshold_(outlier_param1), n_hyp_(n_hyp), seed_(seed) {
   check(xk_, xk_trk_create(xk_, max_matches, camera.getFx(), camera.getFy(), camera.getCx(), camera.getCy(), camera.getS(), &trk_),
         "xk_trk_create");
   const size_t m = (size_t)max_matches;                       // (>= 1 here: xk_trk_create refused anything else)
   prev_in_.resize(2 * m); cur_in_.resize(2 * m); prev_out_.resize(2 * m); cur_out_.resize(2 * m);
   mask_.resize(m); keep_.resize(m);
+  if (outlier_method == XK_TRK_LMEDS) {
+    const int rc = xk_trk_outlier_method(trk_, XK_TRK_LMEDS);
+    if (rc != XK_OK) {
+      xk_trk_destroy(trk_);
+      check(xk_, rc, "xk_trk_outlier_method");
+    }
+  }
+}
+
+void MatchFilter::setOutlierMethod(int outlier_method) {
+  check(xk_, xk_trk_outlier_method(trk_, outlier_method == XK_TRK_LMEDS ? XK_TRK_LMEDS : XK_TRK_RANSAC), "xk_trk_outlier_method");
+}
+
+bool MatchFilter::lastLmeds(double *median, double *sigma) {
+  double last[2] = {0.0, 0.0};
+  if (xk_trk_fundamental_medians(trk_, 0, 0, nullptr, last) != XK_OK) return false;
+  if (median) *median = last[0];
+  if (sigma) *sigma = last[1];
+  return true;
 }
 
 MatchFilter::~MatchFilter() { xk_trk_destroy(trk_); }

@@ -14,11 +14,12 @@ static void check(xk_handle *h, int rc, const char *what) {
 }
 
 Tracker::Tracker(xk_handle *xk, const Camera &cam, int fast_detection_delta, bool non_max_supp, unsigned int block_half_length,
-                 unsigned int margin, unsigned int n_feat_min, int /*outlier_method*/, double outlier_param1, double /*outlier_param2*/,
+                 unsigned int margin, unsigned int n_feat_min, int outlier_method, double outlier_param1, double /*outlier_param2*/,
                  int win_size_w, int win_size_h, int max_level, double min_eig_thr, int max_features, int n_hyp)
     : xk_(xk), width_((int)cam.getWidth()), height_((int)cam.getHeight()), max_features_(max_features), threshold_(fast_detection_delta),
       nms_(non_max_supp ? 1 : 0), b_((int)block_half_length), margin_((int)margin), n_feat_min_((int)n_feat_min), win_w_(win_size_w),
-      win_h_(win_size_h), max_level_(max_level), n_hyp_(n_hyp), threshold_px_(outlier_param1), min_eig_thr_(min_eig_thr) {
+      win_h_(win_size_h), max_level_(max_level), n_hyp_(n_hyp), outlier_method_(outlier_method == XK_TRK_LMEDS ? XK_TRK_LMEDS : XK_TRK_RANSAC),
+      threshold_px_(outlier_param1), min_eig_thr_(min_eig_thr) {
   if (max_features < 1) throw std::runtime_error("Tracker: max_features < 1");
   const size_t m = (size_t)max_features;                      // (the staging first: nothing below can throw once the handle exists)
   prev_xy_.resize(2 * m); cur_xy_.resize(2 * m); prev_dist_.resize(2 * m); cur_dist_.resize(2 * m);
@@ -61,6 +62,14 @@ void Tracker::setSpatialCalibration(int div, double thr, int max_rows) {
   dirty_ = true;
 }
 
+bool Tracker::lastLmeds(double *median, double *sigma) {
+  double last[2] = {0.0, 0.0};
+  if (xk_trk_fundamental_medians(trk_, 0, 0, nullptr, last) != XK_OK) return false;
+  if (median) *median = last[0];
+  if (sigma) *sigma = last[1];
+  return true;
+}
+
 void Tracker::reset() {
   img_id_ = 0;
   matches_.clear();
@@ -69,6 +78,7 @@ void Tracker::reset() {
 
 // detection, description and frame setups, in the order each needs the one before; a new one starts the tracker over
 void Tracker::apply() {
+  check(xk_, xk_trk_outlier_method(trk_, outlier_method_), "xk_trk_outlier_method");
   check(xk_, xk_trk_detect_setup(trk_, threshold_, nms_, b_, described_ ? std::max(margin_, edge_) : margin_, 32768), "xk_trk_detect_setup");
   if (described_)
     check(xk_, xk_trk_describe_setup(trk_, centroid_ ? 1 : 0, angle_deg_, edge_, own_pattern_ ? pattern_ : nullptr, max_features_),

@@ -523,6 +523,39 @@ int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *c
                           int n_hyp, unsigned long seed, unsigned char *mask, int *keep_idx, double *prev_xy, double *cur_xy,
                           int *n_inliers);
 
+/* Tracker's outlier_method_ (tracker.h:56, :256), the method argument of cv::findFundamentalMat: XK_TRK_RANSAC (cv::RANSAC, the
+ * default at creation) or XK_TRK_LMEDS (cv::LMEDS); anything else is XK_EINVAL and changes nothing.  Sticky on the object: it
+ * governs xk_trk_filter_matches, xk_trk_frame and xk_trk_photo_frame from the next call on.  Under XK_TRK_LMEDS those calls ignore
+ * their threshold_px (as OpenCV ignores param1) and keep nothing for n < 8.  It drops no setup and allocates nothing. */
+#define XK_TRK_LMEDS 4
+#define XK_TRK_RANSAC 8
+int xk_trk_outlier_method(xk_trk *t, int method);
+
+/* cv::findFundamentalMat(pts1, pts2, cv::LMEDS, ., 0.99, mask), the stage entry beside xk_trk_fundamental_ransac (which stays RANSAC
+ * whatever the sticky method is, as this one is LMedS whatever it is): the same inputs, sampler, solver and error, all n_hyp
+ * hypotheses evaluated.  Per candidate med = 0.5 (e[(n-1)/2] + e[n/2]) of its ascending errors e, in fp64, a NaN error counting as
+ * +inf; a candidate whose median is not finite is not a candidate.  The winner has the smallest median, then the lowest hypothesis,
+ * then the lowest candidate.  sigma = 2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(med), at least 0.001; an inlier has error <= sigma^2.
+ * No refit.  *median and *sigma (may be NULL): the winner's.  Three launches, one synchronisation.  n < 8: XK_OK, nothing kept, mask,
+ * F, *median and *sigma zeroed.  For 8 <= n <= 13 both middle errors belong to the seven sample points, which every candidate fits
+ * exactly: the medians are round-off and the selection arbitrary (in OpenCV too).  Status codes as xk_trk_fundamental_ransac. */
+int xk_trk_fundamental_lmeds(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, int n_hyp, unsigned long seed,
+                             unsigned char *mask, double *F /* 9, row-major, may be NULL */, int *n_inliers, double *median,
+                             double *sigma);
+
+/* What the last call left if it ran LMedS (xk_trk_fundamental_lmeds, or xk_trk_filter_matches or a frame past its first under
+ * XK_TRK_LMEDS): median HOST [count][3] of hypotheses first ... first+count-1 (+inf: not a candidate), last HOST [2]: the winner's
+ * median and sigma (zeros: no winner).  Either may be NULL.  XK_EINVAL outside that call's range and after any other call that
+ * used the scratch.  After an LMedS stage call xk_trk_fundamental_hypotheses returns n_cand and F as usual and zero inliers. */
+int xk_trk_fundamental_medians(xk_trk *t, int first, int count, double *median /* [count][3] */, double *last /* [2] */);
+
+/* Caller-supplied models under both criteria: F HOST [m][9] row-major in pixel coordinates, used as given (m = 1...4096), prev_xy /
+ * cur_xy HOST [n][2] float32 as above (1 <= n <= max_matches) -> inliers HOST [m] (errors <= threshold_px^2) and median HOST [m]
+ * (as defined above; +inf where it is not finite).  For a caller that carries a model over from the previous frame.  It uses the
+ * scratch: xk_trk_fundamental_hypotheses and _medians then ask for a filter call first. */
+int xk_trk_fundamental_score(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, const double *F /* [m][9] */, int m,
+                             double threshold_px, int *inliers /* [m] */, double *median /* [m] */);
+
 /* ---- feature tracking in front of that filter (Tracker::featureTracking, tracker.cpp:623-690) --------------------
  * Every frame the reference runs cv::calcOpticalFlowPyrLK(previous image, current image, pts1, ..., win_size_, max_level_,
  * term_crit_, cv::OPTFLOW_LK_GET_MIN_EIGENVALS, min_eig_thr_) on the previous features' distorted pixels and drops every

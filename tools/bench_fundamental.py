@@ -2,7 +2,9 @@
 xk_trk_filter_matches call (host buffers in and out, four launches, one synchronisation) at n = 100 and 400 and at
 n_hyp = 256 and 1024, timed with HIP events on the handle's stream over >= 500 calls after warm-up (repeated three times:
 the spread is printed), and one core's time for the NumPy restatement beside it:
-    python tools/bench_fundamental.py [--calls 500]
+    python tools/bench_fundamental.py [--calls 500] [--method ransac|lmeds]
+--method lmeds times the same call under xk_trk_outlier_method(4): xk_fund_median and xk_fund_mask_lmeds in the place of xk_fund_score
+and xk_fund_mask.
 The per-kernel split comes from a run of its own under the profiler (tracing slows the host, so the times above are taken
 without it):
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k -- python tools/bench_fundamental.py --calls 50 --no-cpu
@@ -15,6 +17,8 @@ sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=500)
+ap.add_argument("--method", choices=("ransac", "lmeds"), default="ransac", help="the outlier_method of the timed calls")
+ap.add_argument("--lib", default=None, help="the libxk.so to load instead of this tree's (the parent commit's, as the yardstick)")
 ap.add_argument("--no-cpu", action="store_true", help="skip the NumPy restatement (profiler runs)")
 ap.add_argument("--kernel-stats", metavar="DIR", help="print the xk_fund_* rows of a rocprofv3 --kernel-trace --stats run and exit")
 args = ap.parse_args()
@@ -30,13 +34,16 @@ if args.kernel_stats:
 
 import torch
 import fundamental_np as fnp
+import lmeds_np as lnp
 from x_multi_agent_amd import engine, tracker
 
 if not torch.cuda.is_available():
     sys.exit("bench_fundamental: no GPU -- a time measured anywhere else says nothing")
 K, S, THR = fnp.K_DEFAULT, 0.95, 0.3
-eng = engine.Engine(4, 0, 4)
+eng = engine.Engine(4, 0, 4, lib_path=args.lib)
 mf = tracker.MatchFilter(eng, 512, K, S)
+if args.method == "lmeds":
+    mf.outlier_method(4)
 stream = torch.cuda.ExternalStream(eng.L.xk_stream(eng.h))
 for n in (100, 400):
     prev, cur, _ = fnp.make_pair(n, 0.2, 0.05, 50 + n, "general", S)
@@ -54,11 +61,14 @@ for n in (100, 400):
             ev1.synchronize()
             wall = (time.perf_counter() - t0) / args.calls
             per_call.append((ev0.elapsed_time(ev1) / args.calls, 1e3 * wall))
-        line = (f"n = {n:3d}, n_hyp = {n_hyp:4d}: " + " / ".join(f"{e:6.3f}" for e, _ in per_call) + " ms per call (HIP events, three repeats), "
+        line = (f"{args.method}: n = {n:3d}, n_hyp = {n_hyp:4d}: " + " / ".join(f"{e:6.3f}" for e, _ in per_call) + " ms per call (HIP events, three repeats), "
                 + " / ".join(f"{w:6.3f}" for _, w in per_call) + f" ms host wall, {len(keep)} kept")
         if not args.no_cpu:
             t0 = time.perf_counter()
-            ref = fnp.filter_matches(prev, cur, K, S, THR, n_hyp, args.calls - 1)
+            if args.method == "lmeds":
+                ref = lnp.filter_matches(prev, cur, K, S, n_hyp, args.calls - 1)
+            else:
+                ref = fnp.filter_matches(prev, cur, K, S, THR, n_hyp, args.calls - 1)
             cpu = time.perf_counter() - t0
             line += (f";  NumPy restatement, one core: {1e3 * cpu:8.1f} ms, same mask: {np.array_equal(ref['mask'], mask)}"
                      f" (margin {ref['margin']:.1e})")

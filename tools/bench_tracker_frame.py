@@ -10,7 +10,8 @@ bench_fundamental.py); about 200 and about 400 features (block_half_length 26 an
     steady, queued + skipped   n_feat_min = 1: its launches are issued on every frame and return at the flag
     re-detecting               n_feat_min = 100000: every frame detects on the previous image and tracks what it accepts
 
-    python tools/bench_tracker_frame.py [--frames 300]
+    python tools/bench_tracker_frame.py [--frames 300] [--method ransac|lmeds]
+--method lmeds: both sides under xk_trk_outlier_method(4).
 The frame entry of another build of the library (the parent commit's, as the yardstick of a change to the host code):
     python tools/bench_tracker_frame.py --only-frame --lib /path/to/the/parent's/libxk.so
 One profiler run of its own lists the HIP calls of a frame (the single hipStreamSynchronize, the two hipMemcpyAsync):
@@ -25,6 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=300)
 ap.add_argument("--only-frame", action="store_true", help="the frame entry alone, steady and queued (profiler runs)")
 ap.add_argument("--lib", default=None, help="the libxk.so to load instead of this tree's")
+ap.add_argument("--method", choices=("ransac", "lmeds"), default="ransac", help="the outlier_method of both sides")
 args = ap.parse_args()
 
 import torch
@@ -58,6 +60,8 @@ eng = engine.Engine(4, 0, 4, lib_path=args.lib)
 def make(b, n_feat_min, frame):
     mf = tracker.MatchFilter(eng, MAX_FEATURES, K, 0.0)
     k = tracker.Klt(eng, 0, W, H, WIN, MAX_LEVEL, match_filter=mf)
+    if args.method == "lmeds":
+        mf.outlier_method(4)
     k.detect_setup(9, 1, b, 20, 32768)
     if frame:
         k.frame_setup(n_feat_min, 1, 1, 100000, 0.3, N_HYP)

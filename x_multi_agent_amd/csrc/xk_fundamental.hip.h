@@ -1,4 +1,4 @@
-// xk_fundamental.hip.h -- fundamental-matrix RANSAC filter of the tracker's matches, Tracker::track (gfx950).
+// xk_fundamental.hip.h -- fundamental-matrix RANSAC / LMedS filter of the tracker's matches, Tracker::track (gfx950).
 //
 //   camera_.undistort(current_features); camera_.undistort(previous_features_);           (tracker.cpp:233-237, camera.cpp:62-87)
 //   cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask); keep the masked pairs (tracker.cpp:243-293)
@@ -15,6 +15,15 @@
 //   xk_fund_mask       one workgroup: the winner's mask, F and count (counted here, with the mask), and the ORDERED
 //                      compaction (workgroup scan) of the kept indices and of the kept pairs' undistorted fp64 pixels
 //                      (tracker.cpp:262-271 pushes them in order)
+//
+// Under outlier_method = cv::LMEDS (xk_trk_outlier_method, xk_trk_fundamental_lmeds) the last two launches are instead
+//   xk_fund_median     the same grid as xk_fund_score: per candidate the median 0.5 (e[(n-1)/2] + e[n/2]) of the pairs' errors by
+//                      radix select in LDS (xk_ransac_median), the hypothesis' candidate of smallest median
+//   xk_fund_mask_lmeds one workgroup: the argmin over the hypotheses (smallest median, lowest hypothesis, lowest candidate),
+//                      sigma = 2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median), at least 0.001, the mask error <= sigma^2 and the
+//                      same compaction; the winner's median and sigma go behind the result block
+// n < 8 keeps nothing there.  For 8 <= n <= 13 both middle errors belong to the seven sample points, which every candidate fits
+// exactly: the medians are round-off and the selection is arbitrary (in OpenCV too); the formula is kept.
 //
 // All n_hyp hypotheses are evaluated, so there is no `prob` (xk_essential.hip.h says why).  No refit.
 //
@@ -169,6 +178,8 @@ struct XkFundArgs {
   double *F;                        // [9]
   XkKeptPairs kept;                 // res: n_inliers, winner hypothesis
   unsigned char *mask;              // [n]
+  double *lmeds;                    // [2] the winner's median and sigma (xk_fund_mask_lmeds only)
+  int min_n;                        // fewer pairs than this leave no candidate: 7, least median of squares 8
   const int *n_dev;                 // NULL: n pairs.  Else n is the bound every list is laid out by (the current list starts 2 n doubles behind
                                     //   the previous one), *n_dev the count (xk_dev_count); xk_fund_undistort then takes n_pts = 2 n
 };
@@ -188,7 +199,7 @@ __global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {
   if (h == 0) *a.sc.key = 0ull;
   if (h >= a.n_hyp) return;
   const int n = xk_dev_count(a.n_dev, a.n);
-  if (n < 7) {                                  // (only with a device count: the stage entries return before the launch.  No candidate, so
+  if (n < a.min_n) {                            // (only with a device count: the stage entries return before the launch.  No candidate, so
     a.sc.ncand[h] = 0;                          //  the key stays zero and xk_fund_mask keeps nothing)
     return;
   }
@@ -214,17 +225,15 @@ __global__ __launch_bounds__(256) void xk_fund_score(XkFundArgs a) {
   });
 }
 
-__global__ __launch_bounds__(256) void xk_fund_mask(XkFundArgs a) {
-  const XkRansacWinner w = xk_ransac_winner(*a.sc.key);
-  const int h = w.valid ? w.h : 0;
-  const double *Fp = a.sc.cand + ((size_t)h * XK_FUND_MAXC + (w.valid ? a.sc.bestc[h] : 0)) * 9;
+// The winner's mask, F and count, and the ordered compaction of the kept pairs: valid = false keeps nothing.  Fp: the winner's candidate.
+__device__ __forceinline__ void xk_fund_keep(const XkFundArgs &a, bool valid, int h, const double *Fp, double t2) {
   const double F[9] = {Fp[0], Fp[1], Fp[2], Fp[3], Fp[4], Fp[5], Fp[6], Fp[7], Fp[8]};
   const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
   const double *U1 = a.und, *U2 = a.und + 2 * (size_t)a.n;
   const int kept = xk_ransac_compact(
       xk_dev_count(a.n_dev, a.n),
       [&](int i) {
-        const bool keep = w.valid && xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]) <= a.t2;
+        const bool keep = valid && xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]) <= t2;
         a.mask[i] = keep ? 1 : 0;
         return keep;
       },
@@ -233,7 +242,37 @@ __global__ __launch_bounds__(256) void xk_fund_mask(XkFundArgs a) {
         a.kept.kept_prev[2 * pos] = U1[2 * i]; a.kept.kept_prev[2 * pos + 1] = U1[2 * i + 1];
         a.kept.kept_cur[2 * pos] = U2[2 * i]; a.kept.kept_cur[2 * pos + 1] = U2[2 * i + 1];
       });
-  if (threadIdx.x < 9) a.F[threadIdx.x] = w.valid ? Fp[threadIdx.x] : 0.0;
+  if (threadIdx.x < 9) a.F[threadIdx.x] = valid ? Fp[threadIdx.x] : 0.0;
   // (the count is this kernel's own: the length of what it compacted, whatever the scoring kernel's rounding made of the same pairs)
-  if (threadIdx.x == 0) { a.kept.res[0] = kept; a.kept.res[1] = w.valid ? h : -1; }
+  if (threadIdx.x == 0) { a.kept.res[0] = kept; a.kept.res[1] = valid ? h : -1; }
+}
+
+__global__ __launch_bounds__(256) void xk_fund_mask(XkFundArgs a) {
+  const XkRansacWinner w = xk_ransac_winner(*a.sc.key);
+  const int h = w.valid ? w.h : 0;
+  xk_fund_keep(a, w.valid, h, a.sc.cand + ((size_t)h * XK_FUND_MAXC + (w.valid ? a.sc.bestc[h] : 0)) * 9, a.t2);
+}
+
+// Least median of squares (cv::LMEDS): xk_fund_median takes the place of xk_fund_score, xk_fund_mask_lmeds that of xk_fund_mask.
+// A count below a.min_n = 8 leaves no candidate (the scale needs n - 7 > 0; xk_fund_solve has left ncand = 0 then).
+__global__ __launch_bounds__(256) void xk_fund_median(XkFundArgs a) {
+  const double *P1 = a.pts, *P2 = a.pts + 2 * (size_t)a.n;
+  xk_ransac_median<XK_FUND_MAXC>(a.sc, max(xk_dev_count(a.n_dev, a.n), 1), [&](const double *F, int i) {
+    return xk_fund_error(F, P1[2 * i], P1[2 * i + 1], P2[2 * i], P2[2 * i + 1]);
+  });
+}
+
+// sigma = 2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(med), at least 0.001, evaluated in this order (OpenCV's LMeDSPointSetRegistrator);
+// there is no multiply-add in it to contract.  An inlier has error <= sigma^2.
+__global__ __launch_bounds__(256) void xk_fund_mask_lmeds(XkFundArgs a) {
+  const int n = xk_dev_count(a.n_dev, a.n);
+  const XkMedianWinner w = xk_ransac_median_winner(a.sc, a.n_hyp, XK_FUND_MAXC);
+  const bool valid = w.valid && n >= a.min_n;
+  double sigma = 0.0;
+  if (valid) {
+    sigma = 2.5 * 1.4826 * (1.0 + 5.0 / (double)(n - 7)) * sqrt(w.med);
+    sigma = fmax(sigma, 0.001);
+  }
+  xk_fund_keep(a, valid, w.h, a.sc.cand + ((size_t)w.h * XK_FUND_MAXC + (valid ? a.sc.bestc[w.h] : 0)) * 9, sigma * sigma);
+  if (threadIdx.x == 0) { a.lmeds[0] = valid ? w.med : 0.0; a.lmeds[1] = sigma; }
 }

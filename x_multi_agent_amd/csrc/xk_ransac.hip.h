@@ -7,6 +7,7 @@
 //   polynomials         Horner, the safeguarded bracket root, real roots by derivative bracketing
 //   score               per candidate inlier count + summed error, the hypothesis' best candidate, the packed atomicMax key
 //   winner              the key decoded
+//   median              per candidate the median of the errors by radix select in LDS (least median of squares), the argmin
 //   ordered compaction  ballot + popcount per wavefront, wave totals through LDS, a running base over chunks of 256
 //   XkRansacScratch     the per-hypothesis scratch block; XkKeptPairs, the "kept pairs" tail of a result block
 //
@@ -231,6 +232,148 @@ __device__ __forceinline__ void xk_ransac_score(const XkRansacScratch &s, int n,
     // count in the high word, inverted hypothesis index in the low word: the maximum is the highest count, then the lowest h
     if (best_c >= 0) atomicMax(s.key, ((unsigned long long)best_cnt << 32) | (unsigned long long)(0xffffffffu - (unsigned int)h));
   }
+}
+
+// Errors of a candidate that the median body keeps in LDS: n at most this many are computed once and staged, more are recomputed in
+// every pass.  4096 keys are 32 KiB; with the histogram a workgroup holds 33 KiB, so four of them (one per SIMD) still fit the 160 KiB
+// of a CU.  Both paths see the same keys, so they give the same bits.
+#define XK_RANSAC_MED_STAGE 4096
+
+// The order key of a squared error d >= +0: its bit pattern, which orders as the value does; a NaN counts as +inf.
+__device__ __forceinline__ unsigned long long xk_ransac_med_key(double d) {
+  return d != d ? 0x7ff0000000000000ull : (unsigned long long)__double_as_longlong(d);
+}
+
+// The body of a median kernel (least median of squares): the same grid as xk_ransac_score, workgroup blockIdx.x of 256 takes hypothesis
+// blockIdx.x, lanes over the n >= 1 points, candidates in turn.  Per candidate med = 0.5 (e[(n-1)/2] + e[n/2]) of the ascending errors
+// e, to s.sum; a candidate whose median is not finite is not a candidate (s.sum = +inf, as for the slots past ncand).  s.cnt = 0.
+// The hypothesis' best candidate (smallest median, then the lower index; -1: none) to s.bestc.  No key: the medians are doubles, the
+// winner is an argmin over s.sum (xk_ransac_median_winner).
+//
+// e[(n-1)/2] by radix select on the keys, most significant byte first: per pass a 256-bin histogram in LDS by integer atomics (counts
+// do not depend on the order of the adds), scanned by wavefront 0 (four bins per lane, named scalars), the rank narrowed into the bin
+// that holds it.  After eight passes the key is known, and with it the number of keys below it and equal to it.  e[n/2] is the same key
+// if more than n/2 keys are <= it, else the smallest key above it: one min-reduction pass.
+template <int MAXC, class Err>
+__device__ __forceinline__ void xk_ransac_median(const XkRansacScratch &s, int n, Err err) {
+  __shared__ unsigned long long s_key[XK_RANSAC_MED_STAGE];
+  __shared__ unsigned long long s_min[4];
+  __shared__ int s_hist[256];
+  __shared__ int s_sel[4];                     // the chosen bin, the rank inside it, the pass' keys below it, the keys in it
+  const int h = blockIdx.x, nc = s.ncand[h];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const bool staged = n <= XK_RANSAC_MED_STAGE;
+  int best_c = -1;
+  double best_med = 0.0;
+  for (int c = 0; c < MAXC; ++c) {
+    double med = INFINITY;
+    if (c < nc) {
+      const double *Cp = s.cand + ((size_t)h * MAXC + c) * 9;
+      const double C[9] = {Cp[0], Cp[1], Cp[2], Cp[3], Cp[4], Cp[5], Cp[6], Cp[7], Cp[8]};
+      auto key_at = [&](int i) { return staged ? s_key[i] : xk_ransac_med_key(err(C, i)); };
+      if (staged)
+        for (int i = threadIdx.x; i < n; i += 256) s_key[i] = xk_ransac_med_key(err(C, i));
+      unsigned long long pre = 0ull;           // the bytes chosen so far, in place
+      int rank = (n - 1) / 2, below = 0, equal = 0;
+      for (int p = 0; p < 8; ++p) {
+        const int shift = 56 - 8 * p;
+        s_hist[threadIdx.x] = 0;
+        __syncthreads();                       // (also: s_key is written, and s_sel of the pass before has been read)
+        for (int i = threadIdx.x; i < n; i += 256) {
+          const unsigned long long k = key_at(i);
+          if (p == 0 || ((k ^ pre) >> (shift + 8)) == 0ull) atomicAdd(&s_hist[(int)((k >> shift) & 255ull)], 1);
+        }
+        __syncthreads();
+        if (w == 0) {
+          const int a0 = s_hist[4 * lane], a1 = s_hist[4 * lane + 1], a2 = s_hist[4 * lane + 2], a3 = s_hist[4 * lane + 3];
+          const int tot = a0 + a1 + a2 + a3;
+          int inc = tot;
+#pragma unroll
+          for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += up;
+          }
+          const int exc = inc - tot;           // keys of this pass in the bins below this lane's four
+          if (exc <= rank && rank < inc) {     // exactly one lane: the counts of a pass sum to more than the rank
+            int r = rank - exc, b = 0, in_bin = a0;
+            if (r >= a0) { r -= a0; b = 1; in_bin = a1;
+              if (r >= a1) { r -= a1; b = 2; in_bin = a2;
+                if (r >= a2) { r -= a2; b = 3; in_bin = a3; } } }
+            s_sel[0] = 4 * lane + b;
+            s_sel[1] = r;
+            s_sel[2] = rank - r;
+            s_sel[3] = in_bin;
+          }
+        }
+        __syncthreads();
+        const int bin = s_sel[0];
+        below += s_sel[2];
+        rank = s_sel[1];
+        equal = s_sel[3];                      // (not s_hist[bin]: the next pass is already zeroing it)
+        pre |= (unsigned long long)bin << shift;
+      }
+      // pre = e[(n-1)/2]; `below` keys are smaller, `equal` keys equal it
+      unsigned long long hi = pre;
+      if (below + equal <= n / 2) {            // (uniform: every thread holds the same counts)
+        unsigned long long m = ~0ull;
+        for (int i = threadIdx.x; i < n; i += 256) {
+          const unsigned long long k = key_at(i);
+          if (k > pre && k < m) m = k;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const unsigned long long v = __shfl_down(m, o, 64);
+          if (v < m) m = v;
+        }
+        if (lane == 0) s_min[w] = m;
+        __syncthreads();
+        hi = s_min[0];
+        if (s_min[1] < hi) hi = s_min[1];
+        if (s_min[2] < hi) hi = s_min[2];
+        if (s_min[3] < hi) hi = s_min[3];
+      }
+      __syncthreads();                         // (s_key, s_hist and s_min are free for the next candidate)
+      med = 0.5 * (__longlong_as_double((long long)pre) + __longlong_as_double((long long)hi));
+      if (!(med < INFINITY)) med = INFINITY;
+      else if (best_c < 0 || med < best_med) { best_med = med; best_c = c; }
+    }
+    if (threadIdx.x == 0) { s.cnt[h * MAXC + c] = 0; s.sum[h * MAXC + c] = med; }
+  }
+  if (threadIdx.x == 0) s.bestc[h] = best_c;
+}
+
+// The winner of the medians by ONE workgroup of 256: smallest median, then the lowest hypothesis (its candidate is s.bestc: the
+// smallest median, then the lowest candidate).  (median, hypothesis) is a total order, so the reduction's shape does not matter.
+struct XkMedianWinner { bool valid; int h; double med; };
+__device__ __forceinline__ XkMedianWinner xk_ransac_median_winner(const XkRansacScratch &s, int n_hyp, int maxc) {
+  __shared__ double s_med[4];
+  __shared__ int s_h[4];
+  double med = INFINITY;
+  int hb = 0x7fffffff;
+  for (int h = threadIdx.x; h < n_hyp; h += 256) {
+    const int c = s.bestc[h];
+    if (c < 0) continue;
+    const double m = s.sum[(size_t)h * maxc + c];
+    if (m < med) { med = m; hb = h; }          // (ascending h per thread: a tie keeps the lower one)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double m = __shfl_down(med, o, 64);
+    const int h = __shfl_down(hb, o, 64);
+    if (m < med || (m == med && h < hb)) { med = m; hb = h; }
+  }
+  if ((threadIdx.x & 63) == 0) { s_med[threadIdx.x >> 6] = med; s_h[threadIdx.x >> 6] = hb; }
+  __syncthreads();
+  med = s_med[0]; hb = s_h[0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j)
+    if (s_med[j] < med || (s_med[j] == med && s_h[j] < hb)) { med = s_med[j]; hb = s_h[j]; }
+  __syncthreads();
+  XkMedianWinner wn;
+  wn.valid = hb != 0x7fffffff;
+  wn.h = wn.valid ? hb : 0;
+  wn.med = wn.valid ? med : 0.0;
+  return wn;
 }
 
 // The key decoded.  valid = false: no hypothesis produced a candidate (the solve kernel's thread 0 zeroes the key).

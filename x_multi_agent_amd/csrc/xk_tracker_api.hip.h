@@ -208,13 +208,19 @@ struct xk_trk {
   XkRansacScratch sc;
   unsigned char *d_res;       // the result block: F | XkKeptPairs | mask, packed per call
   unsigned char *h_res;       // pinned: points in (4 max_matches doubles), then the result block out, at h_res
-  int n_hyp;                  // hypotheses of the last RANSAC (0: none yet)
+  int n_hyp;                  // hypotheses of the last RANSAC or LMedS stage call (0: none yet)
+  int method;                 // XK_TRK_RANSAC or XK_TRK_LMEDS: what xk_trk_filter_matches and the frames run (xk_trk_outlier_method)
+  int lmeds_hyp;              // hypotheses of the last call if it was LMedS, stage entry or frame (0: it was not): their medians are in sc.sum
+  const double *lmeds_last;   // device: that call's winner's median and sigma
   struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
   struct xk_bl *bl;           // the baseline check of the track manager's candidates (xk_trk_baseline_setup); NULL before
 };
 
 // the result blocks for n pairs: F [9] | kept pairs | mask [n], and cur_xy [n][2] | min_eig [n] | kept pairs | status [n]
 static size_t trk_res_bytes(int n) { return sizeof(double) * 9 + xk_kept_pairs_bytes(n) + (size_t)n; }
+// LMedS adds its winner's median and sigma behind that block, at the next multiple of 8: nothing in front of them moves
+static size_t trk_lmeds_off(int n) { return (trk_res_bytes(n) + 7) & ~(size_t)7; }
+static size_t trk_res_total(int n) { return trk_lmeds_off(n) + 2 * sizeof(double); }
 static size_t klt_res_bytes(int n) { return sizeof(double) * 3 * (size_t)n + xk_kept_pairs_bytes(n) + (size_t)n; }
 
 // The count at `at` in a result block's pinned copy: 0 <= count <= n, or XK_EDEVICE.
@@ -348,7 +354,7 @@ extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy
   t->s_term = s != 0.0 ? 1.0 / (2.0 * std::tan(s / 2.0)) : 0.0;        // camera.cpp:39
   const size_t pts = sizeof(double) * 4 * (size_t)max_matches;
   const size_t head = 3 * pts + xk_ransac_scratch_bytes<XK_FUND_MAXC>(XK_FUND_MAX_HYP);
-  const int rc = blk_alloc(h, t->blk, head + trk_res_bytes(max_matches), pts + trk_res_bytes(max_matches), "xk_trk_create");
+  const int rc = blk_alloc(h, t->blk, head + trk_res_total(max_matches), pts + trk_res_total(max_matches), "xk_trk_create");
   if (rc != XK_OK) {
     free(t);
     return rc;
@@ -358,11 +364,12 @@ extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy
   t->sc = xk_ransac_scratch<XK_FUND_MAXC>(t->blk.d + off, XK_FUND_MAX_HYP);
   t->d_res = t->blk.d + head;                                            // (a multiple of 8: doubles first, and the scratch is not padded)
   t->h_res = t->blk.h + pts;
+  t->method = XK_TRK_RANSAC;
   *out = t;
   return XK_OK;
 }
 
-// The outlier removal of n pairs whose result block (trk_res_bytes(n)) starts at d_res: the stage entries' t->d_res or a frame's.  With
+// The outlier removal of n pairs whose result block (trk_res_total(n)) starts at d_res: the stage entries' t->d_res or a frame's.  With
 // n_dev the count is the device's and n the bound the block is laid out by.
 static XkFundArgs trk_args(xk_trk *t, unsigned char *d_res, int n, const int *n_dev = nullptr) {
   XkFundArgs a{};
@@ -370,21 +377,37 @@ static XkFundArgs trk_args(xk_trk *t, unsigned char *d_res, int n, const int *n_
   a.F = (double *)d_res;
   a.kept = xk_kept_pairs(a.F + 9, n);
   a.mask = xk_kept_pairs_end(a.kept, n);
+  a.lmeds = (double *)(d_res + trk_lmeds_off(n));
   a.n = n; a.n_pts = 2 * n; a.n_dev = n_dev;
   a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.s = t->s; a.s_term = t->s_term;
   return a;
 }
 
-// The RANSAC of a's pairs, queued: Camera::undistort of both lists first (undistort = true), then solve, score and mask.
-static int trk_queue_ransac(xk_handle *h, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
+// The outlier removal of a's pairs by `method`, queued: Camera::undistort of both lists first (undistort = true), then solve, score and
+// mask (RANSAC) or solve, median and mask (LMedS, which ignores threshold_px).  Three launches either way, four with the undistortion.
+static int trk_queue_ransac(xk_handle *h, XkFundArgs &a, int method, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
+  const bool lmeds = method == XK_TRK_LMEDS;
   a.n_hyp = n_hyp;
   a.t2 = threshold_px * threshold_px;
   a.seed = (unsigned long long)seed;
+  a.min_n = lmeds ? 8 : 7;
   if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.n + 255) / 256), dim3(256), 0, h->stream, a);
   hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
-  return launched(h, "fundamental RANSAC launch");
+  if (lmeds) {
+    hipLaunchKernelGGL(xk_fund_median, dim3(n_hyp), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(xk_fund_mask_lmeds, dim3(1), dim3(256), 0, h->stream, a);
+  } else {
+    hipLaunchKernelGGL(xk_fund_score, dim3(n_hyp), dim3(256), 0, h->stream, a);
+    hipLaunchKernelGGL(xk_fund_mask, dim3(1), dim3(256), 0, h->stream, a);
+  }
+  return launched(h, lmeds ? "fundamental LMedS launch" : "fundamental RANSAC launch");
+}
+
+// What xk_trk_fundamental_medians reads after the call that `method` ran with n_hyp hypotheses on the result block at d_res for n pairs
+// (n_hyp = 0: nothing ran).
+static void trk_note_call(xk_trk *t, int method, int n_hyp, const unsigned char *d_res, int n) {
+  t->lmeds_hyp = method == XK_TRK_LMEDS ? n_hyp : 0;
+  t->lmeds_last = (const double *)(d_res + trk_lmeds_off(n));
 }
 
 /* Camera::undistort (camera.cpp:62-87) */
@@ -409,16 +432,18 @@ extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double 
 
 // The launches behind both RANSAC entries: the points are in the pinned block (4n doubles: previous, then current), distorted
 // (undistort = true: they go through xk_fund_undistort) or already what the RANSAC sees.  One copy in, one copy out, one wait.
-static int trk_run(xk_trk *t, XkFundArgs &a, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
+static int trk_run(xk_trk *t, XkFundArgs &a, int method, bool undistort, double threshold_px, int n_hyp, unsigned long seed) {
   xk_handle *h = t->h;
   const int n = a.n;
   if (!undistort) a.und = a.pts;
   t->n_hyp = 0;
+  trk_note_call(t, method, 0, t->d_res, n);
   HIPCHK(h, hipMemcpyAsync((void *)(undistort ? a.dist : a.pts), t->blk.h, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  XKCHK(trk_queue_ransac(h, a, undistort, threshold_px, n_hyp, seed));
-  HIPCHK(h, hipMemcpyAsync(t->h_res, t->d_res, trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
+  XKCHK(trk_queue_ransac(h, a, method, undistort, threshold_px, n_hyp, seed));
+  HIPCHK(h, hipMemcpyAsync(t->h_res, t->d_res, method == XK_TRK_LMEDS ? trk_res_total(n) : trk_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   t->n_hyp = n_hyp;
+  trk_note_call(t, method, n_hyp, t->d_res, n);
   return XK_OK;
 }
 
@@ -441,16 +466,104 @@ extern "C" int xk_trk_fundamental_ransac(xk_trk *t, const float *prev_xy, const 
   *n_inliers = 0;
   memset(mask, 0, (size_t)n);
   if (F) memset(F, 0, 9 * sizeof(double));
-  if (n < 7) { t->n_hyp = 0; return XK_OK; }                 // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
+  if (n < 7) { t->n_hyp = t->lmeds_hyp = 0; return XK_OK; }  // (OpenCV returns an empty mask: the loop of :263-268 keeps nothing; no hypotheses)
   HIPCHK(h, hipSetDevice(h->device));
   XkFundArgs a = trk_args(t, t->d_res, n);
   double *h_pts = (double *)t->blk.h;
   for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
-  XKCHK(trk_run(t, a, false, threshold_px, n_hyp, seed));
+  XKCHK(trk_run(t, a, XK_TRK_RANSAC, false, threshold_px, n_hyp, seed));
   const unsigned char *r = t->h_res;
   if (F) memcpy(F, r, 9 * sizeof(double));
   memcpy(n_inliers, r + ((unsigned char *)a.kept.res - t->d_res), sizeof(int));
   memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
+  return XK_OK;
+}
+
+/* cv::findFundamentalMat(pts1, pts2, cv::LMEDS, ., 0.99, mask): the outlier_method a configuration may name (tracker.h:256) */
+extern "C" int xk_trk_outlier_method(xk_trk *t, int method) {
+  if (!t) return XK_EINVAL;
+  if (method != XK_TRK_RANSAC && method != XK_TRK_LMEDS) return fail(t->h, XK_EINVAL, "xk_trk_outlier_method: method is 8 (RANSAC) or 4 (LMedS)");
+  t->method = method;
+  return XK_OK;
+}
+
+extern "C" int xk_trk_fundamental_lmeds(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, int n_hyp, unsigned long seed,
+                                        unsigned char *mask, double *F, int *n_inliers, double *median, double *sigma) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  XKCHK(trk_check(t, "xk_trk_fundamental_lmeds", n, 0.0, n_hyp, !mask || !n_inliers || (n > 0 && (!prev_xy || !cur_xy))));
+  *n_inliers = 0;
+  memset(mask, 0, (size_t)n);
+  if (F) memset(F, 0, 9 * sizeof(double));
+  if (median) *median = 0.0;
+  if (sigma) *sigma = 0.0;
+  if (n < 8) { t->n_hyp = t->lmeds_hyp = 0; return XK_OK; }  // (the scale needs n - 7 > 0)
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, t->d_res, n);
+  double *h_pts = (double *)t->blk.h;
+  for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
+  XKCHK(trk_run(t, a, XK_TRK_LMEDS, false, 0.0, n_hyp, seed));
+  const unsigned char *r = t->h_res;
+  if (F) memcpy(F, r, 9 * sizeof(double));
+  memcpy(n_inliers, r + ((unsigned char *)a.kept.res - t->d_res), sizeof(int));
+  memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
+  if (median) memcpy(median, r + trk_lmeds_off(n), sizeof(double));
+  if (sigma) memcpy(sigma, r + trk_lmeds_off(n) + sizeof(double), sizeof(double));
+  return XK_OK;
+}
+
+/* The medians of hypotheses first ... first+count-1 of the last call if it was LMedS (+inf: not a candidate), and its winner's median and sigma */
+extern "C" int xk_trk_fundamental_medians(xk_trk *t, int first, int count, double *median, double *last) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (first < 0 || count < 0) return fail(h, XK_EINVAL, "xk_trk_fundamental_medians: negative range");
+  if (t->lmeds_hyp < 1 || first + (long)count > t->lmeds_hyp)
+    return fail(h, XK_EINVAL, "xk_trk_fundamental_medians: range outside the hypotheses of the last call, or that call was not LMedS");
+  if ((count == 0 || !median) && !last) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (median && count > 0)
+    HIPCHK(h, hipMemcpyAsync(median, t->sc.sum + (size_t)first * XK_FUND_MAXC, sizeof(double) * XK_FUND_MAXC * (size_t)count, hipMemcpyDeviceToHost,
+                             h->stream));
+  if (last) HIPCHK(h, hipMemcpyAsync(last, t->lmeds_last, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// One model per hypothesis slot, as its only candidate: what xk_fund_score and xk_fund_median then score.  (The models are in place:
+// the copy put model j at cand[j][0].)
+__global__ __launch_bounds__(256) void xk_fund_models(XkFundArgs a) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j == 0) *a.sc.key = 0ull;
+  if (j >= a.n_hyp) return;
+  double *F = a.sc.cand + (size_t)j * (XK_FUND_MAXC * 9);
+  for (int i = 9; i < XK_FUND_MAXC * 9; ++i) F[i] = 0.0;
+  a.sc.ncand[j] = 1;
+}
+
+/* The m models F, as given, under both criteria: the inlier count at threshold_px and the median of the errors of the n pairs */
+extern "C" int xk_trk_fundamental_score(xk_trk *t, const float *prev_xy, const float *cur_xy, int n, const double *F, int m, double threshold_px,
+                                        int *inliers, double *median) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  XKCHK(trk_check(t, "xk_trk_fundamental_score", n, threshold_px, m, !prev_xy || !cur_xy || !F || !inliers || !median));
+  if (n < 1) return fail(h, XK_EINVAL, "xk_trk_fundamental_score: n < 1");
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, t->d_res, n);
+  a.n_hyp = m; a.t2 = threshold_px * threshold_px; a.min_n = 1;
+  t->n_hyp = t->lmeds_hyp = 0;                                // (the scratch no longer holds a filter's hypotheses)
+  double *h_pts = (double *)t->blk.h;
+  for (size_t i = 0; i < 2 * (size_t)n; ++i) { h_pts[i] = (double)prev_xy[i]; h_pts[2 * (size_t)n + i] = (double)cur_xy[i]; }
+  const size_t slot = sizeof(double) * XK_FUND_MAXC * 9, row = sizeof(double) * XK_FUND_MAXC, irow = sizeof(int) * XK_FUND_MAXC;
+  HIPCHK(h, hipMemcpyAsync((void *)a.pts, t->blk.h, sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpy2DAsync(a.sc.cand, slot, F, sizeof(double) * 9, sizeof(double) * 9, (size_t)m, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_fund_models, dim3((m + 255) / 256), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_fund_score, dim3(m), dim3(256), 0, h->stream, a);
+  XKCHK(launched(h, "fundamental score launch"));
+  HIPCHK(h, hipMemcpy2DAsync(inliers, sizeof(int), a.sc.cnt, irow, sizeof(int), (size_t)m, hipMemcpyDeviceToHost, h->stream));
+  hipLaunchKernelGGL(xk_fund_median, dim3(m), dim3(256), 0, h->stream, a);      // (it zeroes sc.cnt: the counts are on their way out)
+  XKCHK(launched(h, "fundamental median launch"));
+  HIPCHK(h, hipMemcpy2DAsync(median, sizeof(double), a.sc.sum, row, sizeof(double), (size_t)m, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return XK_OK;
 }
 
@@ -471,12 +584,12 @@ extern "C" int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, cons
                      !mask || !keep_idx || !prev_xy || !cur_xy || !n_inliers || (n > 0 && (!prev_dist_xy || !cur_dist_xy))));
   *n_inliers = 0;
   memset(mask, 0, (size_t)n);
-  if (n < 7) { t->n_hyp = 0; return XK_OK; }
+  if (n < (t->method == XK_TRK_LMEDS ? 8 : 7)) { t->n_hyp = t->lmeds_hyp = 0; return XK_OK; }
   HIPCHK(h, hipSetDevice(h->device));
   XkFundArgs a = trk_args(t, t->d_res, n);
   memcpy(t->blk.h, prev_dist_xy, sizeof(double) * 2 * (size_t)n);
   memcpy(t->blk.h + sizeof(double) * 2 * (size_t)n, cur_dist_xy, sizeof(double) * 2 * (size_t)n);
-  XKCHK(trk_run(t, a, true, threshold_px, n_hyp, seed));
+  XKCHK(trk_run(t, a, t->method, true, threshold_px, n_hyp, seed));
   const unsigned char *r = t->h_res;
   XKCHK(kept_pairs_out(h, "xk_trk_filter_matches", a.kept, t->d_res, r, n, keep_idx, prev_xy, cur_xy, n_inliers));
   memcpy(mask, r + (a.mask - t->d_res), (size_t)n);
@@ -1715,7 +1828,7 @@ extern "C" int xk_trk_frame_setup(xk_trk *t, int n_feat_min, int n_tiles_h, int 
   f->cap_new = o ? std::min(f->cap_det, o->max_desc) : f->cap_det;
   const size_t N = (size_t)f->cap_new;
   const size_t klt_bytes = up16(klt_res_bytes(t->max_matches)), det_bytes = up16(det_res_bytes(t->max_matches));
-  const size_t orb_bytes = o ? up16(xk_orb_res_bytes(N)) : 0, fund_bytes = up16(trk_res_bytes(t->max_matches));
+  const size_t orb_bytes = o ? up16(xk_orb_res_bytes(N)) : 0, fund_bytes = up16(trk_res_total(t->max_matches));
   const size_t out_bytes = up16(xk_frame_out_bytes(M, o != nullptr)), desc_bytes = o ? up16(32 * M) : 0;
   const size_t d_bytes = up16(sizeof(int) * XK_FC_N) + up16(16 * M) + up16(8 * M) + up16(4 * M) + desc_bytes       // counts, resident list
                          + 2 * up16(4 * M) + 2 * up16(16 * M) + desc_bytes + up16(8 * N)                             // pair lists, new points
@@ -1927,6 +2040,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
   const int M = t->max_matches, R = first ? 0 : f->n_res;
   const int n_hyp_photo = ph ? std::max(1, std::min(R, pf->n_hyp)) : 0;
   f->n_res = -1;                                                    // (whatever fails below: the next frame is a first frame)
+  t->lmeds_hyp = 0;                                                 // (and this one has run no LMedS yet)
   XKCHK(trk_push(t, img, stride));
   XkFrameArgs a = f->a;
   a.first = first ? 1 : 0;
@@ -1964,6 +2078,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
     XkFundArgs fa = trk_args(t, f->fund_res, a.B, c + XK_FC_TOTAL);
     a.kept3 = fa.kept;
     t->n_hyp = 0;                                                   // (the scratch no longer holds the last xk_trk_filter_matches)
+    trk_note_call(t, t->method, 0, f->fund_res, a.B);
     // 3. the resident list from the previous image to the current one, its post-filter; 4. the overflow pass (both intensities move with their pair)
     if (R > 0) XKCHK(frame_queue_track(t, f, pf, 0, a.res_pts, R, nullptr));
     hipLaunchKernelGGL(xk_frame_overflow, dim3(1), dim3(256), sizeof(int) * (size_t)f->tiles_h * f->tiles_w, h->stream, a);
@@ -1975,7 +2090,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
     }
     hipLaunchKernelGGL(xk_frame_concat, dim3(1), dim3(256), 0, h->stream, a);
     // 6. the outlier removal; 7. the result block (the calibration's outcome in its head) and the new resident list
-    XKCHK(trk_queue_ransac(h, fa, true, f->threshold_px, f->n_hyp, seed));
+    XKCHK(trk_queue_ransac(h, fa, t->method, true, f->threshold_px, f->n_hyp, seed));
     hipLaunchKernelGGL(xk_frame_pack, dim3((a.B + 255) / 256), dim3(256), 0, h->stream, a);
     out_bytes = ph ? xk_frame_photo_out_bytes(B, desc) : xk_frame_out_bytes(B, desc);
   }
@@ -2006,6 +2121,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
     f->n_res = head[XK_FC_NEW];
     return XK_OK;
   }
+  trk_note_call(t, t->method, f->n_hyp, f->fund_res, a.B);
   out->n_matches = m;
   memcpy(out->prev_xy, r + xk_frame_out_xy(B, 0), sizeof(double) * 2 * (size_t)m);
   memcpy(out->cur_xy, r + xk_frame_out_xy(B, 1), sizeof(double) * 2 * (size_t)m);

@@ -1,5 +1,5 @@
 """Outlier removal of the tracker's matches on the device -- ctypes binding of the xk_trk_* entry points
-(include/xk.h).  Mirrors the undistortion and the fundamental-matrix RANSAC of `Tracker::track`
+(include/xk.h).  Mirrors the undistortion and the fundamental-matrix filter (RANSAC, or LMedS under `outlier_method(4)`) of `Tracker::track`
 (src/x/vision/tracker.cpp:233-293, camera.cpp:62-87): what every frame's match list passes through before the track
 manager sees it.
 
@@ -44,6 +44,11 @@ class _Trk:
     def _chk(self, rc, what):
         if rc != 0:
             raise self._error(rc, what)
+
+    def outlier_method(self, method):
+        """Tracker's outlier_method_ (tracker.h:256): 8 = cv::RANSAC (the default), 4 = cv::LMEDS.  Sticky on the xk_trk: filter_matches,
+        Klt.frame and Klt.photo_frame follow it from the next call on."""
+        self._chk(self.L.xk_trk_outlier_method(self.p, C.c_int(method)), "xk_trk_outlier_method")
 
     def close(self):
         if self.owner is None and self.p:
@@ -99,6 +104,44 @@ class MatchFilter(_Trk):
         self._chk(self.L.xk_trk_fundamental_hypotheses(self.p, C.c_int(first), C.c_int(count), nc.ctypes.data_as(c_ip), F.ctypes.data_as(c_dp),
                                                        inl.ctypes.data_as(c_ip)), "xk_trk_fundamental_hypotheses")
         return nc[:count], F[:count], inl[:count]
+
+    def fundamental_lmeds(self, prev_xy, cur_xy, n_hyp=1024, seed=0):
+        """cv::findFundamentalMat(pts1, pts2, LMEDS, ., 0.99, mask) on undistorted pixels [n, 2] (cast to float32) -> (mask uint8 [n],
+        F [3, 3], n_inliers, median, sigma): the winner has the smallest median of the pairs' errors, an inlier has error <= sigma^2 with
+        sigma = 2.5 * 1.4826 * (1 + 5 / (n - 7)) * sqrt(median), at least 0.001.  All n_hyp hypotheses are evaluated."""
+        prev = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+        cur = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
+        if len(prev) != len(cur):
+            raise ValueError("prev_xy and cur_xy differ in length")
+        n = len(prev)
+        mask, F, ninl, med, sig = np.zeros(max(n, 1), np.uint8), np.zeros(9), C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        self._chk(self.L.xk_trk_fundamental_lmeds(self.p, prev.ctypes.data_as(c_fp), cur.ctypes.data_as(c_fp), C.c_int(n), C.c_int(n_hyp),
+                                                  C.c_ulong(seed), mask.ctypes.data_as(c_ub), F.ctypes.data_as(c_dp), C.byref(ninl),
+                                                  C.byref(med), C.byref(sig)), "xk_trk_fundamental_lmeds")
+        return mask[:n], F.reshape(3, 3), ninl.value, med.value, sig.value
+
+    def fundamental_medians(self, first, count):
+        """What the last call left if it ran LMedS -> (median [count, 3] of hypotheses first ... first+count-1, +inf where there is no
+        candidate, and (median, sigma) of its winner)."""
+        med, last = np.zeros((max(count, 1), 3)), np.zeros(2)
+        self._chk(self.L.xk_trk_fundamental_medians(self.p, C.c_int(first), C.c_int(count), med.ctypes.data_as(c_dp), last.ctypes.data_as(c_dp)),
+                  "xk_trk_fundamental_medians")
+        return med[:count], (float(last[0]), float(last[1]))
+
+    def fundamental_score(self, prev_xy, cur_xy, F, threshold_px=0.3):
+        """The models F [m, 3, 3] (pixel coordinates, used as given) on the pairs [n, 2] -> (inliers int32 [m]: errors <= threshold_px^2,
+        median fp64 [m]: 0.5 (e[(n-1)/2] + e[n/2]) of the ascending errors, +inf where that is not finite)."""
+        prev = np.ascontiguousarray(prev_xy, np.float32).reshape(-1, 2)
+        cur = np.ascontiguousarray(cur_xy, np.float32).reshape(-1, 2)
+        if len(prev) != len(cur):
+            raise ValueError("prev_xy and cur_xy differ in length")
+        Fm = np.ascontiguousarray(F, np.float64).reshape(-1, 9)
+        m = len(Fm)
+        inl, med = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1))
+        self._chk(self.L.xk_trk_fundamental_score(self.p, prev.ctypes.data_as(c_fp), cur.ctypes.data_as(c_fp), C.c_int(len(prev)),
+                                                  Fm.ctypes.data_as(c_dp), C.c_int(m), C.c_double(threshold_px), inl.ctypes.data_as(c_ip),
+                                                  med.ctypes.data_as(c_dp)), "xk_trk_fundamental_score")
+        return inl[:m], med[:m]
 
     def filter_matches(self, prev_dist_xy, cur_dist_xy, threshold_px=0.3, n_hyp=1024, seed=0):
         """tracker.cpp:233-293: distorted pixels [n, 2] of the tracked pairs -> (mask uint8 [n], keep_idx [m] ascending,
