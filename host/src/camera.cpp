@@ -3,6 +3,9 @@
 #include "x/vision/camera.h"
 
 #include <cmath>
+#include <stdexcept>
+
+#include "../../x_multi_agent_amd/csrc/xk_camera.h"   // the radial-tangential and the equidistant model: the text the device compiles
 
 namespace x {
 
@@ -16,11 +19,71 @@ double Camera::radialGain(double r_d) const {
   return std::tan(r_d * fov_) * half_cot_ / r_d;
 }
 
+void Camera::setDistortion(int model, const std::vector<double> &coeffs) {
+  const size_t n = coeffs.size();
+  const bool count_ok = model == XK_CAM_MODEL_FOV ? n == 1 : model == XK_CAM_MODEL_RADTAN ? (n == 4 || n == 5) :
+                        model == XK_CAM_MODEL_EQUIDISTANT ? n == 4 : false;
+  if (!count_ok) throw std::invalid_argument("Camera::setDistortion: model is 0 (1 coefficient), 1 (4 or 5) or 2 (4)");
+  for (double c : coeffs)
+    if (!std::isfinite(c)) throw std::invalid_argument("Camera::setDistortion: coefficient not finite");
+  model_ = model; n_coeffs_ = (int)n;
+  for (double &c : k_) c = 0.0;
+  if (model == XK_CAM_MODEL_FOV) {
+    fov_ = coeffs[0];
+    half_cot_ = fov_ != 0.0 ? 0.5 / std::tan(0.5 * fov_) : 0.0;
+  } else {
+    for (size_t i = 0; i < n; ++i) k_[i] = coeffs[i];
+  }
+}
+
+std::vector<double> Camera::getCoeffs() const {
+  if (model_ == XK_CAM_MODEL_FOV) return {fov_};
+  return std::vector<double>(k_, k_ + n_coeffs_);
+}
+
+bool Camera::undistort(double u_dist, double v_dist, double *u, double *v, int *steps) const {
+  const double xd = toPlane(u_dist, 0), yd = toPlane(v_dist, 1);
+  double x, y;
+  int it = 0;
+  bool ok = true;
+  if (model_ == XK_CAM_MODEL_FOV) {
+    const double gain = radialGain(std::sqrt(xd * xd + yd * yd));
+    x = gain * xd; y = gain * yd;
+  } else {
+    ok = xk_cam_inverse(model_, k_, xd, yd, &x, &y, &it);
+  }
+  *u = ok ? toPixel(x, 0) : u_dist;                            // an invalid point keeps its distorted pixel
+  *v = ok ? toPixel(y, 1) : v_dist;
+  if (steps) *steps = it;
+  return ok;
+}
+
 void Camera::undistort(TrackedFeature &feature) const {
-  const double x = toPlane(feature.getXDist(), 0), y = toPlane(feature.getYDist(), 1);
-  const double gain = radialGain(std::sqrt(x * x + y * y));
-  feature.setX(toPixel(gain * x, 0));
-  feature.setY(toPixel(gain * y, 1));
+  double u, v;
+  undistort(feature.getXDist(), feature.getYDist(), &u, &v);
+  feature.setX(u);
+  feature.setY(v);
+}
+
+void Camera::distort(double u, double v, double *u_dist, double *v_dist) const {
+  const double x = toPlane(u, 0), y = toPlane(v, 1);
+  double xd = x, yd = y;
+  if (model_ != XK_CAM_MODEL_FOV) {
+    xk_cam_forward(model_, k_, x, y, &xd, &yd);
+  } else if (fov_ != 0.0) {                                     // r_d = atan(2 r tan(s/2)) / s, the identity where undistort is
+    const double r = std::sqrt(x * x + y * y);
+    const double rd = std::atan(r / half_cot_) / fov_;
+    if (rd > 0.01) { xd = x * (rd / r); yd = y * (rd / r); }
+  }
+  *u_dist = toPixel(xd, 0);
+  *v_dist = toPixel(yd, 1);
+}
+
+void Camera::distort(TrackedFeature &feature) const {
+  double u, v;
+  distort(feature.getX(), feature.getY(), &u, &v);
+  feature.setXDist(u);
+  feature.setYDist(v);
 }
 
 void Camera::undistort(FeatureList &features) const {

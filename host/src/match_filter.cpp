@@ -18,6 +18,14 @@ MatchFilter::MatchFilter(xk_handle *xk, const Camera &camera, int max_matches, d
   const size_t m = (size_t)max_matches;                       // (>= 1 here: xk_trk_create refused anything else)
   prev_in_.resize(2 * m); cur_in_.resize(2 * m); prev_out_.resize(2 * m); cur_out_.resize(2 * m);
   mask_.resize(m); keep_.resize(m);
+  if (camera.getModel() != XK_CAM_FOV) {                        // the camera's lens (Camera::setDistortion)
+    const std::vector<double> k = camera.getCoeffs();
+    const int rc = xk_trk_camera_model(trk_, camera.getModel(), k.data(), (int)k.size());
+    if (rc != XK_OK) {
+      xk_trk_destroy(trk_);
+      check(xk_, rc, "xk_trk_camera_model");
+    }
+  }
   if (outlier_method == XK_TRK_LMEDS) {
     const int rc = xk_trk_outlier_method(trk_, XK_TRK_LMEDS);
     if (rc != XK_OK) {

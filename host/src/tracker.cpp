@@ -27,7 +27,16 @@ Tracker::Tracker(xk_handle *xk, const Camera &cam, int fast_detection_delta, boo
   out_.prev_xy = prev_xy_.data(); out_.cur_xy = cur_xy_.data(); out_.prev_dist_xy = prev_dist_.data(); out_.cur_dist_xy = cur_dist_.data();
   out_.score = score_.data(); out_.origin = origin_.data(); out_.tiles = tiles_.data(); out_.desc = desc_.data();
   check(xk_, xk_trk_create(xk_, max_features, cam.getFx(), cam.getFy(), cam.getCx(), cam.getCy(), cam.getS(), &trk_), "xk_trk_create");
-  const int rc = xk_trk_klt_setup(trk_, width_, height_, win_w_, win_h_, max_level_, 30, 0.01, min_eig_thr_);   // term_crit_, tracker.cpp:47
+  int rc = XK_OK;
+  if (cam.getModel() != XK_CAM_FOV) {                           // the camera's lens (Camera::setDistortion)
+    const std::vector<double> k = cam.getCoeffs();
+    rc = xk_trk_camera_model(trk_, cam.getModel(), k.data(), (int)k.size());
+    if (rc != XK_OK) {
+      xk_trk_destroy(trk_);
+      check(xk_, rc, "xk_trk_camera_model");
+    }
+  }
+  rc = xk_trk_klt_setup(trk_, width_, height_, win_w_, win_h_, max_level_, 30, 0.01, min_eig_thr_);   // term_crit_, tracker.cpp:47
   if (rc != XK_OK) {
     xk_trk_destroy(trk_);
     check(xk_, rc, "xk_trk_klt_setup");

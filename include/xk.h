@@ -479,7 +479,7 @@ int xk_voc_get(const xk_voc *v, unsigned char *node_desc, int *children, int *wo
  * (camera.cpp:62-87,163-168), runs cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask) on their float casts
  * and keeps the masked pairs as the frame's matches.  An xk_trk does that on the device of its handle; it needs no
  * vocabulary and no xk_pr.  Intrinsics in pixels (Camera's fx_ ... cy_, camera.cpp:30-33) and the FOV parameter s are
- * fixed at creation; max_matches: most pairs per call. */
+ * fixed at creation (xk_trk_camera_model below gives it another lens); max_matches: most pairs per call. */
 typedef struct xk_trk xk_trk;
 
 /* Camera::Camera (camera.cpp:27-48).  max_matches < 1, fx / fy <= 0, non-finite intrinsics: XK_EINVAL. */
@@ -530,6 +530,31 @@ int xk_trk_filter_matches(xk_trk *t, const double *prev_dist_xy, const double *c
 #define XK_TRK_LMEDS 4
 #define XK_TRK_RANSAC 8
 int xk_trk_outlier_method(xk_trk *t, int method);
+
+/* The lens of the camera, for calibrations the FOV model does not cover (DESIGN 3.10.2 defines the models; they are this project's,
+ * not the reference's).  XK_CAM_FOV: 1 coefficient, s -- the same camera as xk_trk_create with that s, bit for bit.  XK_CAM_RADTAN:
+ * k1 k2 p1 p2 [k3] (4 or 5 coefficients, k3 = 0 with 4), Kalibr's radtan / OpenCV's plumb-bob model.  XK_CAM_EQUIDISTANT: k1 ... k4,
+ * Kannala-Brandt.  All fp64 on conditioned coordinates x = (u - cx)/fx, y = (v - cy)/fy.  Sticky on the object: xk_trk_undistort,
+ * xk_trk_distort, xk_trk_filter_matches, xk_trk_frame and xk_trk_photo_frame follow it from the next call on.  It drops no setup and
+ * allocates nothing.  An unknown model, a count the model does not take, a non-finite coefficient or a null pointer: XK_EINVAL, and
+ * the camera stays what it was.
+ * The inverses of the two new models are Newton iterations of at most 20 steps.  A point where the model folds (det J not > 0, or
+ * d theta_d / d theta not > 0), whose angle leaves (0, pi/2), or that has not converged after 20 steps is INVALID: its undistorted
+ * pixel is its distorted pixel, bit for bit -- finite and inert, never a NaN -- and it is counted (xk_trk_undistort_status). */
+#define XK_CAM_FOV 0
+#define XK_CAM_RADTAN 1
+#define XK_CAM_EQUIDISTANT 2
+int xk_trk_camera_model(xk_trk *t, int model, const double *coeffs, int n_coeffs);
+
+/* The forward map of the camera model: xy HOST [n][2] undistorted pixels -> dist_xy HOST [n][2] distorted pixels, fp64.  Capacity and
+ * status codes as xk_trk_undistort.  (FOV: r_d = atan(2 r tan(s/2)) / s, the identity where that is not above 0.01.) */
+int xk_trk_distort(xk_trk *t, const double *xy, int n, double *dist_xy);
+
+/* What the last xk_trk_undistort, xk_trk_filter_matches, xk_trk_frame or xk_trk_photo_frame (past its first frame, which undistorts
+ * nothing) left: *n_invalid, the number of invalid points, and *max_steps, the most Newton steps any point took.  Either may be NULL.
+ * Both are 0 under XK_CAM_FOV, and after xk_trk_camera_model.  An inspection path: one small copy and one wait of its own, so a
+ * frame's copies and waits are what they were. */
+int xk_trk_undistort_status(xk_trk *t, int *n_invalid, int *max_steps);
 
 /* cv::findFundamentalMat(pts1, pts2, cv::LMEDS, ., 0.99, mask), the stage entry beside xk_trk_fundamental_ransac (which stays RANSAC
  * whatever the sticky method is, as this one is LMedS whatever it is): the same inputs, sampler, solver and error, all n_hyp

@@ -12,6 +12,8 @@ bench_fundamental.py); about 200 and about 400 features (block_half_length 26 an
 
     python tools/bench_tracker_frame.py [--frames 300] [--method ransac|lmeds]
 --method lmeds: both sides under xk_trk_outlier_method(4).
+--model euroc: both sides under a radial-tangential lens (xk_trk_camera_model); the scene is rendered without one, so
+the feature counts are the scene's, the times are those of the launches.
 The frame entry of another build of the library (the parent commit's, as the yardstick of a change to the host code):
     python tools/bench_tracker_frame.py --only-frame --lib /path/to/the/parent's/libxk.so
 One profiler run of its own lists the HIP calls of a frame (the single hipStreamSynchronize, the two hipMemcpyAsync):
@@ -27,6 +29,7 @@ ap.add_argument("--frames", type=int, default=300)
 ap.add_argument("--only-frame", action="store_true", help="the frame entry alone, steady and queued (profiler runs)")
 ap.add_argument("--lib", default=None, help="the libxk.so to load instead of this tree's")
 ap.add_argument("--method", choices=("ransac", "lmeds"), default="ransac", help="the outlier_method of both sides")
+ap.add_argument("--model", choices=("fov", "euroc"), default="fov", help="euroc: both sides under xk_trk_camera_model(1, EuRoC's radtan coefficients)")
 args = ap.parse_args()
 
 import torch
@@ -62,6 +65,8 @@ def make(b, n_feat_min, frame):
     k = tracker.Klt(eng, 0, W, H, WIN, MAX_LEVEL, match_filter=mf)
     if args.method == "lmeds":
         mf.outlier_method(4)
+    if args.model == "euroc":
+        mf.camera_model(tracker.CAM_RADTAN, (-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05, 0.0))
     k.detect_setup(9, 1, b, 20, 32768)
     if frame:
         k.frame_setup(n_feat_min, 1, 1, 100000, 0.3, N_HYP)

@@ -4,7 +4,9 @@
 //   cv::findFundamentalMat(pts1, pts2, cv::RANSAC, 0.3, 0.99, mask); keep the masked pairs (tracker.cpp:243-293)
 //
 // Four launches on the handle's stream, no host round trip between them:
-//   xk_fund_undistort  one thread per point, both lists: the FOV model's inverse (camera.cpp:69-87), the fp64 undistorted
+//   xk_fund_undistort  one thread per point, both lists: the FOV model's inverse (camera.cpp:69-87) -- or, after xk_trk_camera_model,
+//                      the Newton inverse of the radial-tangential or the equidistant model (xk_camera.h), one branch per thread,
+//                      invalid points and the largest step count into two counters -- the fp64 undistorted
 //                      pixels (what the matches carry) and their float cast widened back to fp64 (what the RANSAC sees: the
 //                      reference casts to cv::Point2f, tracker.cpp:251-256)
 //   xk_fund_solve      one thread per hypothesis: seven distinct pairs from the counter-based splitmix64 sampler, the
@@ -53,6 +55,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "xk_camera.h"
 #include "xk_ransac.hip.h"
 
 #define XK_FUND_MAXC 3             // candidates per hypothesis
@@ -165,6 +168,42 @@ XK_RANSAC_HD void xk_fund_undistort1(double ud, double vd, double fx, double fy,
   *v = f * y * fy + cy;
 }
 
+// The camera models of xk_trk_camera_model: the FOV model above, or one of xk_camera.h's two, between the pinhole
+// arithmetic of xk_fund_undistort1.  k[5]: the model's coefficients (unused under the FOV model).
+// One distorted pixel through the inverse of `model`: false where the point is INVALID (xk_cam_inverse says when); an invalid point
+// keeps its distorted pixel, bit for bit.  *steps: Newton steps taken (0 under the FOV model, which has a closed form).
+XK_RANSAC_HD bool xk_cam_undistort1(int model, const double *k, double ud, double vd, double fx, double fy, double cx, double cy, double s,
+                                 double s_term, double *u, double *v, int *steps) {
+  if (model == XK_CAM_MODEL_FOV) {
+    *steps = 0;
+    xk_fund_undistort1(ud, vd, fx, fy, cx, cy, s, s_term, u, v);
+    return true;
+  }
+  double x, y;
+  const bool ok = xk_cam_inverse(model, k, (ud - cx) / fx, (vd - cy) / fy, &x, &y, steps);
+  *u = ok ? x * fx + cx : ud;
+  *v = ok ? y * fy + cy : vd;
+  return ok;
+}
+
+// One undistorted pixel through the forward map of `model`.  FOV: r_d = atan(2 r tan(s/2)) / s = atan(r / s_term) / s, and the identity
+// where that r_d is not above the 0.01 below which xk_fund_undistort1 is the identity too.
+XK_RANSAC_HD void xk_cam_distort1(int model, const double *k, double u, double v, double fx, double fy, double cx, double cy, double s,
+                               double s_term, double *ud, double *vd) {
+  const double x = (u - cx) / fx, y = (v - cy) / fy;
+  double xd = x, yd = y;
+  if (model != XK_CAM_MODEL_FOV) {
+    xk_cam_forward(model, k, x, y, &xd, &yd);
+  } else if (s != 0.0) {
+    const double r = sqrt(x * x + y * y);
+    const double rd = atan(r / s_term) / s;
+    if (rd > 0.01) { xd = x * (rd / r); yd = y * (rd / r); }
+  }
+  *ud = xd * fx + cx;
+  *vd = yd * fy + cy;
+}
+
+
 struct XkFundArgs {
   const double *dist;               // [n_pts][2] distorted pixels (xk_fund_undistort only)
   double *und;                      // [n_pts][2] undistorted pixels, fp64: previous list, then the current one behind it
@@ -182,6 +221,9 @@ struct XkFundArgs {
   int min_n;                        // fewer pairs than this leave no candidate: 7, least median of squares 8
   const int *n_dev;                 // NULL: n pairs.  Else n is the bound every list is laid out by (the current list starts 2 n doubles behind
                                     //   the previous one), *n_dev the count (xk_dev_count); xk_fund_undistort then takes n_pts = 2 n
+  int model;                        // XK_CAM_MODEL_*: what xk_fund_undistort and xk_cam_distort apply (xk_trk_camera_model)
+  double cam_k[5];                  // its coefficients; unused under the FOV model, which has s and s_term
+  int *cam_cnt;                     // [2] invalid points, largest step count: cleared in front of xk_fund_undistort.  NULL under the FOV model
 };
 
 __global__ __launch_bounds__(256) void xk_fund_undistort(XkFundArgs a) {
@@ -189,9 +231,25 @@ __global__ __launch_bounds__(256) void xk_fund_undistort(XkFundArgs a) {
   if (i >= a.n_pts) return;
   if (a.n_dev && (i >= a.n ? i - a.n : i) >= xk_dev_count(a.n_dev, a.n)) return;   // (past the count of its list)
   double u, v;
-  xk_fund_undistort1(a.dist[2 * i], a.dist[2 * i + 1], a.fx, a.fy, a.cx, a.cy, a.s, a.s_term, &u, &v);
+  if (a.model == XK_CAM_MODEL_FOV) {
+    xk_fund_undistort1(a.dist[2 * i], a.dist[2 * i + 1], a.fx, a.fy, a.cx, a.cy, a.s, a.s_term, &u, &v);
+  } else {
+    int steps;
+    const bool ok = xk_cam_undistort1(a.model, a.cam_k, a.dist[2 * i], a.dist[2 * i + 1], a.fx, a.fy, a.cx, a.cy, a.s, a.s_term, &u, &v, &steps);
+    if (!ok) atomicAdd(a.cam_cnt, 1);
+    if (steps > 0) atomicMax(a.cam_cnt + 1, steps);
+  }
   a.und[2 * i] = u; a.und[2 * i + 1] = v;
   a.pts[2 * i] = (double)(float)u; a.pts[2 * i + 1] = (double)(float)v;
+}
+
+// The forward map of a list: und [n_pts][2] undistorted pixels -> pts [n_pts][2] distorted pixels, one thread per point.
+__global__ __launch_bounds__(256) void xk_cam_distort(XkFundArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_pts) return;
+  double ud, vd;
+  xk_cam_distort1(a.model, a.cam_k, a.und[2 * i], a.und[2 * i + 1], a.fx, a.fy, a.cx, a.cy, a.s, a.s_term, &ud, &vd);
+  a.pts[2 * i] = ud; a.pts[2 * i + 1] = vd;
 }
 
 __global__ __launch_bounds__(XK_FUND_SOLVE_T) void xk_fund_solve(XkFundArgs a) {

@@ -212,6 +212,9 @@ struct xk_trk {
   int method;                 // XK_TRK_RANSAC or XK_TRK_LMEDS: what xk_trk_filter_matches and the frames run (xk_trk_outlier_method)
   int lmeds_hyp;              // hypotheses of the last call if it was LMedS, stage entry or frame (0: it was not): their medians are in sc.sum
   const double *lmeds_last;   // device: that call's winner's median and sigma
+  int model;                  // XK_CAM_FOV, XK_CAM_RADTAN or XK_CAM_EQUIDISTANT: what every undistortion applies (xk_trk_camera_model)
+  double cam_k[5];            // that model's coefficients (unused under XK_CAM_FOV: s and s_term above)
+  int *cam_cnt;               // device [2]: invalid points and the largest step count of the last undistortion under another model than FOV
   struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
   struct xk_bl *bl;           // the baseline check of the track manager's candidates (xk_trk_baseline_setup); NULL before
 };
@@ -354,7 +357,8 @@ extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy
   t->s_term = s != 0.0 ? 1.0 / (2.0 * std::tan(s / 2.0)) : 0.0;        // camera.cpp:39
   const size_t pts = sizeof(double) * 4 * (size_t)max_matches;
   const size_t head = 3 * pts + xk_ransac_scratch_bytes<XK_FUND_MAXC>(XK_FUND_MAX_HYP);
-  const int rc = blk_alloc(h, t->blk, head + trk_res_total(max_matches), pts + trk_res_total(max_matches), "xk_trk_create");
+  const size_t cnt_off = (head + trk_res_total(max_matches) + 7) & ~(size_t)7;          // the two counters, behind everything else
+  const int rc = blk_alloc(h, t->blk, cnt_off + 2 * sizeof(int), pts + trk_res_total(max_matches), "xk_trk_create");
   if (rc != XK_OK) {
     free(t);
     return rc;
@@ -364,13 +368,19 @@ extern "C" int xk_trk_create(xk_handle *h, int max_matches, double fx, double fy
   t->sc = xk_ransac_scratch<XK_FUND_MAXC>(t->blk.d + off, XK_FUND_MAX_HYP);
   t->d_res = t->blk.d + head;                                            // (a multiple of 8: doubles first, and the scratch is not padded)
   t->h_res = t->blk.h + pts;
+  t->cam_cnt = (int *)(t->blk.d + cnt_off);
   t->method = XK_TRK_RANSAC;
+  t->model = XK_CAM_FOV;
   *out = t;
   return XK_OK;
 }
 
+static_assert(XK_CAM_FOV == XK_CAM_MODEL_FOV && XK_CAM_RADTAN == XK_CAM_MODEL_RADTAN && XK_CAM_EQUIDISTANT == XK_CAM_MODEL_EQUIDISTANT,
+              "include/xk.h and xk_camera.h number the camera models alike");
+
 // The outlier removal of n pairs whose result block (trk_res_total(n)) starts at d_res: the stage entries' t->d_res or a frame's.  With
-// n_dev the count is the device's and n the bound the block is laid out by.
+// n_dev the count is the device's and n the bound the block is laid out by.  The camera model goes with it: this is the one place every
+// undistortion, stage entry or frame, takes it from.
 static XkFundArgs trk_args(xk_trk *t, unsigned char *d_res, int n, const int *n_dev = nullptr) {
   XkFundArgs a{};
   a.dist = t->dist; a.und = t->und; a.pts = t->pts; a.sc = t->sc;
@@ -380,7 +390,18 @@ static XkFundArgs trk_args(xk_trk *t, unsigned char *d_res, int n, const int *n_
   a.lmeds = (double *)(d_res + trk_lmeds_off(n));
   a.n = n; a.n_pts = 2 * n; a.n_dev = n_dev;
   a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.s = t->s; a.s_term = t->s_term;
+  a.model = t->model;
+  if (t->model != XK_CAM_FOV) {
+    memcpy(a.cam_k, t->cam_k, sizeof a.cam_k);
+    a.cam_cnt = t->cam_cnt;
+  }
   return a;
+}
+
+// Camera::undistort of a.n_pts points, queued.  Under another model than FOV the two counters are cleared in front of the kernel.
+static void trk_queue_undistort(xk_handle *h, const XkFundArgs &a) {
+  if (a.cam_cnt) hipMemsetAsync(a.cam_cnt, 0, 2 * sizeof(int), h->stream);
+  hipLaunchKernelGGL(xk_fund_undistort, dim3((a.n_pts + 255) / 256), dim3(256), 0, h->stream, a);
 }
 
 // The outlier removal of a's pairs by `method`, queued: Camera::undistort of both lists first (undistort = true), then solve, score and
@@ -391,7 +412,7 @@ static int trk_queue_ransac(xk_handle *h, XkFundArgs &a, int method, bool undist
   a.t2 = threshold_px * threshold_px;
   a.seed = (unsigned long long)seed;
   a.min_n = lmeds ? 8 : 7;
-  if (undistort) hipLaunchKernelGGL(xk_fund_undistort, dim3((2 * a.n + 255) / 256), dim3(256), 0, h->stream, a);
+  if (undistort) trk_queue_undistort(h, a);
   hipLaunchKernelGGL(xk_fund_solve, dim3((n_hyp + XK_FUND_SOLVE_T - 1) / XK_FUND_SOLVE_T), dim3(XK_FUND_SOLVE_T), 0, h->stream, a);
   if (lmeds) {
     hipLaunchKernelGGL(xk_fund_median, dim3(n_hyp), dim3(256), 0, h->stream, a);
@@ -422,11 +443,69 @@ extern "C" int xk_trk_undistort(xk_trk *t, const double *dist_xy, int n, double 
   a.n_pts = n;
   memcpy(t->blk.h, dist_xy, sizeof(double) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync((void *)a.dist, t->blk.h, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(xk_fund_undistort, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
+  trk_queue_undistort(h, a);
   XKCHK(launched(h, "undistort launch"));
   HIPCHK(h, hipMemcpyAsync(t->blk.h, a.und, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   memcpy(xy, t->blk.h, sizeof(double) * 2 * (size_t)n);
+  return XK_OK;
+}
+
+/* The camera model of every undistortion from the next call on */
+extern "C" int xk_trk_camera_model(xk_trk *t, int model, const double *coeffs, int n_coeffs) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  const bool count_ok = model == XK_CAM_FOV ? n_coeffs == 1 : model == XK_CAM_RADTAN ? (n_coeffs == 4 || n_coeffs == 5) :
+                        model == XK_CAM_EQUIDISTANT ? n_coeffs == 4 : false;
+  if (!coeffs || !count_ok)
+    return fail(h, XK_EINVAL, "xk_trk_camera_model: model is 0 (FOV, 1 coefficient), 1 (radial-tangential, 4 or 5) or 2 (equidistant, 4)");
+  for (int i = 0; i < n_coeffs; ++i)
+    if (!std::isfinite(coeffs[i])) return fail(h, XK_EINVAL, "xk_trk_camera_model: coefficient not finite");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemsetAsync(t->cam_cnt, 0, 2 * sizeof(int), h->stream));   // (what xk_trk_undistort_status reports until the next undistortion)
+  t->model = model;
+  memset(t->cam_k, 0, sizeof t->cam_k);
+  if (model == XK_CAM_FOV) {
+    t->s = coeffs[0];
+    t->s_term = t->s != 0.0 ? 1.0 / (2.0 * std::tan(t->s / 2.0)) : 0.0;  // camera.cpp:39, as xk_trk_create
+  } else {
+    memcpy(t->cam_k, coeffs, sizeof(double) * (size_t)n_coeffs);
+  }
+  return XK_OK;
+}
+
+/* The forward map of the camera model: undistorted pixels -> distorted pixels */
+extern "C" int xk_trk_distort(xk_trk *t, const double *xy, int n, double *dist_xy) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  if (n < 0 || (n > 0 && (!xy || !dist_xy))) return fail(h, XK_EINVAL, "xk_trk_distort: null argument or negative n");
+  if (n > t->max_matches) return fail(h, XK_ECAPACITY, "xk_trk_distort: more points than max_matches");
+  if (n == 0) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkFundArgs a = trk_args(t, t->d_res, 0);
+  a.n_pts = n;
+  memcpy(t->blk.h, xy, sizeof(double) * 2 * (size_t)n);
+  HIPCHK(h, hipMemcpyAsync((void *)a.und, t->blk.h, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_cam_distort, dim3((n + 255) / 256), dim3(256), 0, h->stream, a);
+  XKCHK(launched(h, "distort launch"));
+  HIPCHK(h, hipMemcpyAsync(t->blk.h, a.pts, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  memcpy(dist_xy, t->blk.h, sizeof(double) * 2 * (size_t)n);
+  return XK_OK;
+}
+
+/* The counters of the last undistortion: an inspection path with a copy and a wait of its own */
+extern "C" int xk_trk_undistort_status(xk_trk *t, int *n_invalid, int *max_steps) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  int cnt[2] = {0, 0};
+  if (t->model != XK_CAM_FOV && (n_invalid || max_steps)) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(cnt, t->cam_cnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  if (n_invalid) *n_invalid = cnt[0];
+  if (max_steps) *max_steps = cnt[1];
   return XK_OK;
 }
 

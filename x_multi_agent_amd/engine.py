@@ -39,6 +39,7 @@ SYMBOLS = [
     "xk_voc_create", "xk_voc_destroy", "xk_voc_add", "xk_voc_count", "xk_voc_clear", "xk_voc_train", "xk_voc_get",
     "xk_trk_create", "xk_trk_destroy", "xk_trk_undistort", "xk_trk_fundamental_ransac", "xk_trk_fundamental_hypotheses",
     "xk_trk_filter_matches", "xk_trk_outlier_method", "xk_trk_fundamental_lmeds", "xk_trk_fundamental_medians", "xk_trk_fundamental_score",
+    "xk_trk_camera_model", "xk_trk_distort", "xk_trk_undistort_status",
     "xk_trk_klt_setup", "xk_trk_klt_levels", "xk_trk_push_image", "xk_trk_track", "xk_trk_klt_level",
     "xk_trk_detect_setup", "xk_trk_detect", "xk_trk_detect_stage",
     "xk_trk_describe_setup", "xk_trk_describe", "xk_trk_describe_stage",

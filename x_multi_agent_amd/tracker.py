@@ -28,6 +28,7 @@ c_ub = C.POINTER(C.c_ubyte)
 c_fp = C.POINTER(C.c_float)
 c_sp = C.POINTER(C.c_short)
 c_sb = C.POINTER(C.c_byte)
+CAM_FOV, CAM_RADTAN, CAM_EQUIDISTANT = 0, 1, 2      # XK_CAM_*: MatchFilter(model=...), MatchFilter.camera_model
 
 
 class _Trk:
@@ -66,12 +67,25 @@ class MatchFilter(_Trk):
     """The camera model and the RANSAC of x::Tracker on one agent's GPU.  K = (fx, fy, cx, cy) in pixels or a 3 x 3 camera
     matrix, s = the FOV distortion parameter (0: none)."""
 
-    def __init__(self, eng, max_matches, K, s=0.0):
+    def __init__(self, eng, max_matches, K, s=0.0, model=None, coeffs=None):
         K = np.asarray(K, np.float64)
         self.K = tuple(float(v) for v in ((K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.ravel()))
         self.s = float(s)
         self.max_matches = int(max_matches)
         self._create(eng, self.max_matches, self.K, self.s)
+        if model is not None:
+            try:
+                self.camera_model(model, coeffs)
+            except Exception:
+                self.close()
+                raise
+
+    def camera_model(self, model, coeffs):
+        """xk_trk_camera_model: CAM_FOV (s), CAM_RADTAN (k1 k2 p1 p2 [k3]) or CAM_EQUIDISTANT (k1 ... k4), DESIGN 3.10.2.  Sticky:
+        undistort, distort, filter_matches, Klt.frame and Klt.photo_frame follow it from the next call on."""
+        k = np.ascontiguousarray(() if coeffs is None else coeffs, np.float64).ravel()
+        self._chk(self.L.xk_trk_camera_model(self.p, C.c_int(model), k.ctypes.data_as(c_dp) if len(k) else None, C.c_int(len(k))),
+                  "xk_trk_camera_model")
 
     def undistort(self, dist_xy):
         """Camera::undistort (camera.cpp:62-87): distorted pixels [n, 2] -> undistorted pixels [n, 2], fp64."""
@@ -79,6 +93,19 @@ class MatchFilter(_Trk):
         out = np.zeros((max(len(d), 1), 2))
         self._chk(self.L.xk_trk_undistort(self.p, d.ctypes.data_as(c_dp), C.c_int(len(d)), out.ctypes.data_as(c_dp)), "xk_trk_undistort")
         return out[:len(d)]
+
+    def distort(self, xy):
+        """The forward map of the camera model: undistorted pixels [n, 2] -> distorted pixels [n, 2], fp64."""
+        u = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        out = np.zeros((max(len(u), 1), 2))
+        self._chk(self.L.xk_trk_distort(self.p, u.ctypes.data_as(c_dp), C.c_int(len(u)), out.ctypes.data_as(c_dp)), "xk_trk_distort")
+        return out[:len(u)]
+
+    def undistort_status(self):
+        """-> (invalid points, most Newton steps) of the last undistortion: undistort, filter_matches or a frame.  (0, 0) under the FOV model."""
+        bad, steps = C.c_int(0), C.c_int(0)
+        self._chk(self.L.xk_trk_undistort_status(self.p, C.byref(bad), C.byref(steps)), "xk_trk_undistort_status")
+        return bad.value, steps.value
 
     def fundamental_ransac(self, prev_xy, cur_xy, threshold_px=0.3, n_hyp=1024, seed=0):
         """cv::findFundamentalMat(pts1, pts2, RANSAC, threshold_px, 0.99, mask) (tracker.cpp:243-260) on undistorted
