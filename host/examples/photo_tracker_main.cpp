@@ -1,7 +1,9 @@
 // Tracker::track of a PHOTOMETRIC_CALI build (tracker.cpp:134-306 with calibrateImage at :186-190) on the mirror: a case file and raw
 // images from files (written by tests/test_gpu_photo_frame_host.py), every image through the photometric x::Tracker, one block of
 // lines per frame.
-//   usage  : xk_photo_tracker_example case.txt image0.raw image1.raw ...
+//   usage  : xk_photo_tracker_example [--second win_w win_h max_level min_eig_thr] case.txt image0.raw image1.raw ...
+//            --second: the second Lucas-Kanade parameter set (Tracker::setSecondKlt), which the frames switch to once the
+//            calibration is done
 //   case   : fx fy cx cy s width height stride win_w win_h max_level min_eig_thr fast_threshold non_max_supp block_half_length margin
 //            n_feat_min n_tiles_h n_tiles_w max_feat_per_tile threshold_px n_hyp seed max_features describe centroid edge
 //            kernel_size epsilon_gap epsilon_base n_hyp_photo fast_threshold_photo seed_photo
@@ -11,10 +13,12 @@
 //            G <kept> <estimated> <done> <support> <a_rel> <b_rel> <frame_ab x 4>     the frame's calibration, %.17g
 //            O <origin ...>                              where each match's feature was in the previous frame's match list
 //            I <previous current ...>                    getIntensity() of both features of each match, %.17g
+//            K <set>                                     with --second only: the set the frame's feature trackings ran with
 //            X <checksum>                                FNV-1a (64 bits, hex) over the bytes of every match in order: the previous
 //                                                        feature's x y x_dist y_dist, the current one's, both intensities (fp64), the
 //                                                        FAST score, the four tile indices (int32) and the descriptor
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -41,7 +45,15 @@ struct Fnv {
 };
 
 int main(int argc, char **argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s case.txt image0.raw image1.raw ...\n", argv[0]); return 2; }
+  bool second = false;
+  int win_w2 = 0, win_h2 = 0, max_level2 = 0;
+  double min_eig_thr2 = 0.0;
+  if (argc >= 6 && std::strcmp(argv[1], "--second") == 0) {
+    second = true;
+    win_w2 = std::atoi(argv[2]); win_h2 = std::atoi(argv[3]); max_level2 = std::atoi(argv[4]); min_eig_thr2 = std::atof(argv[5]);
+    argc -= 5; argv += 5;
+  }
+  if (argc < 3) { std::fprintf(stderr, "usage: %s [--second win_w win_h max_level min_eig_thr] case.txt image0.raw image1.raw ...\n", argv[0]); return 2; }
   std::ifstream in(argv[1]);
   double fx, fy, cx, cy, s, min_eig_thr, threshold_px, eps_gap, eps_base;
   unsigned int width, height, block_half_length, margin, n_feat_min, n_tiles_h, n_tiles_w, max_feat_per_tile;
@@ -61,6 +73,7 @@ int main(int argc, char **argv) {
                     max_level, min_eig_thr, max_features, n_hyp);
     tracker.setTiles(n_tiles_h, n_tiles_w, max_feat_per_tile);
     if (describe) tracker.setDescription(centroid != 0, -1.0, edge);
+    if (second) tracker.setSecondKlt(win_w2, win_h2, max_level2, min_eig_thr2);
     tracker.setPhotometric(kernel_size, eps_gap, eps_base, n_hyp_photo, fast_threshold_photo);
     tracker.setSeed(seed);
     tracker.setPhotoSeed(seed_photo);
@@ -85,6 +98,7 @@ int main(int argc, char **argv) {
         sum.i32(m.previous.getTileRow()); sum.i32(m.previous.getTileCol()); sum.i32(m.current.getTileRow()); sum.i32(m.current.getTileCol());
         if (m.current.hasDescriptor()) sum.bytes(m.current.getDescriptor().data(), m.current.getDescriptor().size());
       }
+      if (second) std::printf("\nK %d", tracker.lastKltSet());
       std::printf("\nX %016llx\n", sum.h);
     }
   } catch (const std::exception &e) {

@@ -58,6 +58,15 @@ class FeatureTracker {
   // the undistortion).  kept_indices (optional): their positions in the input list, ascending.
   std::pair<FeatureList, FeatureList> track(const FeatureList &previous, std::vector<int> *kept_indices = nullptr);
   int levels() const { return xk_trk_klt_levels(trk_); }
+  // The second parameter set of a PHOTOMETRIC_CALI build (win_size_photo_, max_level_photo_, min_eig_thr_photo_; xk_trk_klt_second).
+  // A setup: the pushed images are forgotten and setDetection, setDescription, setPhotometric and setSpatialCalibration have to be
+  // called again.  After setPhotometric track() picks the set from this object's own calibration, as tracker.cpp:641 does: the second
+  // set once a calibrate() has estimated gains, the first before; calibrate() itself always tracks with the first (:784-787).
+  void setSecondKlt(int win_w, int win_h, int max_level, double min_eig_thr);
+  // the set track() uses without a photometric calibration (xk_trk_klt_select): 0, or 1 after setSecondKlt
+  void selectKlt(int set);
+  int selectedKlt() const { return xk_trk_klt_selected(trk_); }   // the set the last track() used
+  int levelsOf(int set) const { return xk_trk_klt_levels_of(trk_, set); }
 
   // the parameters of the detection (tracker.h:245-255: 9, true, 20, 20) and the most candidates one image may have
   void setDetection(int threshold = 9, bool non_max_supp = true, int block_half_length = 20, int margin = 20, int max_candidates = 8192);
@@ -138,6 +147,7 @@ class FeatureTracker {
   std::vector<int> desc_xy_, desc_keep_, desc_dir_, desc_mom_;
   std::vector<unsigned char> desc_out_;
   int photo_hyp_ = 0;                         // 0: no photometric calibration set up
+  bool second_klt_ = false, photo_done_ = false;   // setSecondKlt was called; a calibrate() has estimated gains (CALIBRATION_DONE)
   std::vector<double> photo_val_, photo_in_;
   std::vector<int> photo_xy_, photo_sum_, photo_cnt_;
   bool spatial_set_ = false, spatial_done_ = false;

@@ -37,9 +37,15 @@ class Tracker {
   // PHOTOMETRIC_CALI: calibrateImage on every image after the first (tracker.cpp:186-190).  kernel_size is intensities_kernel_size_
   // (tracker.h:366), epsilon_gap and epsilon_base the drift parameters of IRPhotoCalib, n_hyp_photo the most hypotheses of a frame's
   // gain estimate, fast_detection_delta_photo the FAST threshold once gains were estimated (tracker.cpp:848; < 0: no switch).  From
-  // then on track() goes through xk_trk_photo_frame and every TrackedFeature of a match carries its getIntensity().  The frame tracks
-  // with the one Lucas-Kanade parameter set of the constructor (the reference's second set, tracker.cpp:641-645, is out of scope).
+  // then on track() goes through xk_trk_photo_frame and every TrackedFeature of a match carries its getIntensity().
   void setPhotometric(int kernel_size, double epsilon_gap, double epsilon_base, int n_hyp_photo, int fast_detection_delta_photo = -1);
+  // The second Lucas-Kanade parameter set of a PHOTOMETRIC_CALI build (win_size_photo_, max_level_photo_, min_eig_thr_photo_,
+  // tracker.cpp:641-651; xk_trk_klt_second).  It is forwarded before the photometric setups; the photometric frames then switch to it
+  // on the device from the frame of the first gain estimate on, with no further call.  Without setPhotometric the frames stay on the
+  // first set.
+  void setSecondKlt(int win_size_w, int win_size_h, int max_level, double min_eig_thr);
+  // the set the last frame's feature trackings ran with: 1 iff a second set is declared and the calibration was done by then
+  int lastKltSet() const { return second_ && photo_ && calibration_.done ? 1 : 0; }
   // IRPhotoCalib's spatial map, as FeatureTracker::setSpatialCalibration, after setPhotometric: every frame accumulates its rows on the
   // device; after a frame that estimated gains track() reads the status and, once the coverage passes thr, runs the estimate and
   // installs the map (synchronous, on the caller's thread)
@@ -87,6 +93,9 @@ class Tracker {
   signed char pattern_[1024];
   unsigned long seed_ = 0, seed_photo_ = 0;
   bool photo_ = false, spatial_ = false, spatial_done_ = false;
+  bool second_ = false, second_pending_ = false;
+  int win_w2_ = 31, win_h2_ = 31, max_level2_ = 2;
+  double min_eig_thr2_ = 0.003;
   int photo_kernel_ = 30, photo_hyp_ = 0, photo_threshold_ = -1, spatial_div_ = 16, spatial_rows_ = 0;
   double eps_gap_ = 0.0, eps_base_ = 0.0, spatial_thr_ = 0.9;
   Calibration calibration_;

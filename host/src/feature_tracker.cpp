@@ -40,6 +40,7 @@ std::pair<FeatureList, FeatureList> FeatureTracker::track(const FeatureList &pre
     prev_in_[2 * i] = (float)previous[i].getXDist(); prev_in_[2 * i + 1] = (float)previous[i].getYDist();
   }
   int n_kept = 0;
+  if (second_klt_ && photo_hyp_ > 0) check(xk_, xk_trk_klt_select(trk_, photo_done_ ? 1 : 0), "xk_trk_klt_select");   // tracker.cpp:641
   check(xk_, xk_trk_track(trk_, prev_in_.data(), (int)n, cur_.data(), status_.data(), min_eig_.data(), keep_.data(), kept_prev_.data(),
                           kept_cur_.data(), &n_kept),
         "xk_trk_track");
@@ -57,9 +58,19 @@ std::pair<FeatureList, FeatureList> FeatureTracker::track(const FeatureList &pre
   return out;
 }
 
+void FeatureTracker::setSecondKlt(int win_w, int win_h, int max_level, double min_eig_thr) {
+  check(xk_, xk_trk_klt_second(trk_, win_w, win_h, max_level, min_eig_thr), "xk_trk_klt_second");
+  second_klt_ = true;
+  detection_set_ = false; desc_edge_ = 0; max_descriptors_ = 0; photo_hyp_ = 0;   // (every setup behind the KLT setup went with it)
+  spatial_set_ = spatial_done_ = photo_done_ = false;
+}
+
+void FeatureTracker::selectKlt(int set) { check(xk_, xk_trk_klt_select(trk_, set), "xk_trk_klt_select"); }
+
 void FeatureTracker::setPhotometric(int kernel_size, double epsilon_gap, double epsilon_base, int n_hyp) {
   check(xk_, xk_trk_photo_setup(trk_, kernel_size, epsilon_gap, epsilon_base, n_hyp), "xk_trk_photo_setup");
   photo_hyp_ = n_hyp;
+  photo_done_ = false;                                           // (a new photo setup starts the ring over)
   spatial_set_ = spatial_done_ = false;                          // (a new photo setup drops the spatial one)
   const size_t m = (size_t)max_features_;
   photo_val_.resize(m); photo_in_.resize(m); photo_xy_.resize(2 * m); photo_sum_.resize(m); photo_cnt_.resize(m);
@@ -91,6 +102,7 @@ FeatureTracker::Calibration FeatureTracker::calibrate(const FeatureList &previou
                                     photo_sum_.data(), photo_cnt_.data(), &c.kept, &c.a_rel, &c.b_rel, &c.support, c.frame_ab, &estimated),
         "xk_trk_photo_calibrate");
   c.estimated = estimated != 0;
+  photo_done_ = photo_done_ || c.estimated;                       // tracker.cpp:849
   if (spatial_set_ && !spatial_done_ && c.estimated && spatialStatus().ready) {   // irPhotoCalib.cpp:199-209, without the thread
     check(xk_, xk_trk_photo_spatial_estimate(trk_, 1, &spatial_outcome_), "xk_trk_photo_spatial_estimate");
     spatial_done_ = spatial_outcome_.converged != 0;

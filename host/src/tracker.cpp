@@ -65,6 +65,12 @@ void Tracker::setPhotometric(int kernel_size, double epsilon_gap, double epsilon
   dirty_ = true;
 }
 
+void Tracker::setSecondKlt(int win_size_w, int win_size_h, int max_level, double min_eig_thr) {
+  second_ = second_pending_ = true;
+  win_w2_ = win_size_w; win_h2_ = win_size_h; max_level2_ = max_level; min_eig_thr2_ = min_eig_thr;
+  dirty_ = true;
+}
+
 void Tracker::setSpatialCalibration(int div, double thr, int max_rows) {
   if (!photo_) throw std::runtime_error("Tracker::setSpatialCalibration: before setPhotometric");
   spatial_ = true; spatial_div_ = div; spatial_thr_ = thr; spatial_rows_ = max_rows;
@@ -88,6 +94,10 @@ void Tracker::reset() {
 // detection, description and frame setups, in the order each needs the one before; a new one starts the tracker over
 void Tracker::apply() {
   check(xk_, xk_trk_outlier_method(trk_, outlier_method_), "xk_trk_outlier_method");
+  if (second_pending_) {                                      // before every setup below: it drops them and forgets the images
+    check(xk_, xk_trk_klt_second(trk_, win_w2_, win_h2_, max_level2_, min_eig_thr2_), "xk_trk_klt_second");
+    second_pending_ = false;
+  }
   check(xk_, xk_trk_detect_setup(trk_, threshold_, nms_, b_, described_ ? std::max(margin_, edge_) : margin_, 32768), "xk_trk_detect_setup");
   if (described_)
     check(xk_, xk_trk_describe_setup(trk_, centroid_ ? 1 : 0, angle_deg_, edge_, own_pattern_ ? pattern_ : nullptr, max_features_),

@@ -598,8 +598,30 @@ int xk_trk_fundamental_score(xk_trk *t, const float *prev_xy, const float *cur_x
  * min_eig_thr < 0. */
 int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int win_h, int max_level, int max_iter, double eps,
                      double min_eig_thr);
-/* levels as above, or -1 before xk_trk_klt_setup. */
+/* levels of that (the first) set as above, or -1 before xk_trk_klt_setup. */
 int xk_trk_klt_levels(xk_trk *t);
+
+/* The second parameter set of a PHOTOMETRIC_CALI build (win_size_photo_, max_level_photo_, min_eig_thr_photo_, vio/types.h:98-106):
+ * Tracker::featureTracking uses it from the frame of the first gain estimate on (tracker.cpp:641-651).  Called after
+ * xk_trk_klt_setup, with its ranges; max_iter and eps are shared (the reference passes one term_crit_ to both calls).  Its
+ * levels follow the rule above with this window.  It is a setup-class call: both image slots are laid out again for the
+ * deeper of the two sets' levels (so are the raw slots of a later xk_trk_photo_setup), and every push builds every level up to
+ * there; the images are forgotten, every dependent setup is DROPPED and the selection returns to 0, exactly as after a
+ * repeated xk_trk_klt_setup.  A call that fails (XK_EINVAL: before xk_trk_klt_setup, a value out of range, a window that does
+ * not fit level 0; XK_ENOMEM) leaves the earlier setup, its images and its dependent setups as they were.  A later
+ * xk_trk_klt_setup forgets the second set.  An xk_trk that never calls this is, bit for bit and launch for launch, what it
+ * was without the entry. */
+int xk_trk_klt_second(xk_trk *t, int win_w, int win_h, int max_level, double min_eig_thr);
+
+/* The set that xk_trk_track and both trackings of xk_trk_frame use from now on: sticky, as xk_trk_outlier_method.  It
+ * allocates nothing, drops nothing and queues nothing.  The tracking inside xk_trk_photo_calibrate never follows it: it
+ * always uses set 0 (tracker.cpp:784-787); xk_trk_photo_frame ignores it and leaves it unchanged (see there).  XK_EINVAL, and
+ * the selection as it was: before xk_trk_klt_setup, set 1 without a second set, any value but 0 or 1. */
+int xk_trk_klt_select(xk_trk *t, int set);
+/* 0 or 1; -1 before xk_trk_klt_setup. */
+int xk_trk_klt_selected(xk_trk *t);
+/* levels of set 0 or 1; -1 before xk_trk_klt_setup, for a second set that was not declared, for any other value. */
+int xk_trk_klt_levels_of(xk_trk *t, int set);
 
 /* previous_img_ = current_img.clone() (tracker.cpp:302) and the new current image: img HOST [height][stride] uint8, stride
  * >= width.  The current slot becomes the previous one; the image is copied (through the pinned staging: the caller's
@@ -623,7 +645,7 @@ int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_xy, unsigne
 /* One pyramid level of the previous (which = 0) or the current (1) image as the device holds it (the pyramid that
  * cv::calcOpticalFlowPyrLK builds inside the call of tracker.cpp:648-651): img HOST [h][w] uint8, dIx / dIy HOST [h][w]
  * int16, *w, *h.  Any output may be NULL.  An inspection path, not part of a frame: straight copies.  XK_EINVAL: a level
- * above levels, an image that has not been pushed. */
+ * above the deeper of the two sets' levels, an image that has not been pushed. */
 int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *img, short *dIx, short *dIy, int *w, int *h);
 
 /* ---- detection of the features that are tracked (Tracker::featureDetection, tracker.cpp:390-590) -----------------
@@ -790,8 +812,9 @@ int xk_trk_frame_reset(xk_trk *t);
  * xk_trk_photo_frame is xk_trk_frame of a build that calibrates every image: the resident list also holds each feature's
  * intensity (Feature::getIntensity), the calibration is fed from it with nothing uploaded, and the frame still has one
  * image copied in, one result block out and one wait.  xk_trk_frame_reset and xk_trk_frame_features serve
- * both frames.  It tracks with the one Lucas-Kanade parameter set of xk_trk_klt_setup (the reference's second set,
- * tracker.cpp:641-645, is out of scope), and leaves refinePhotometricParams to the caller (xk_trk_photo_gains).
+ * both frames.  With a second Lucas-Kanade parameter set declared (xk_trk_klt_second) its feature trackings switch to it
+ * on the device once the calibration is done, as tracker.cpp:641-651 does (see xk_trk_photo_frame).  It leaves
+ * refinePhotometricParams to the caller (xk_trk_photo_gains).
  *
  * xk_trk_photo_frame_setup, after xk_trk_frame_setup AND xk_trk_photo_setup: n_hyp_photo in 1 ... max_hyp of the photo
  * setup caps the gain RANSAC -- a frame with R resident features evaluates max(1, min(R, n_hyp_photo)) hypotheses;
@@ -828,6 +851,13 @@ typedef struct {
  * selected on the device, the new features' intensities there, their description, tracking, and intensities in the raw
  * current plane; 7. undistortion and the fundamental RANSAC with `seed`; 8. the kept current features and their
  * intensities become the resident list.  Bit for bit what the stage entries return when chained through the host.
+ * With a second parameter set (xk_trk_klt_second) the feature trackings of steps 3 and 6 run with set 1 iff XkPhotoState's
+ * done flag -- the one the detection's threshold switch reads -- is set when their kernel runs, and with set 0 otherwise: every
+ * wavefront reads the flag once and takes one set for its whole feature.  The frame of the first estimate therefore already
+ * tracks with set 1 (calibrateImage sets CALIBRATION_DONE at tracker.cpp:849, before the tracking at :193), while the
+ * calibration's own tracking in step 2 runs with set 0 (:784-787).  The frame ignores xk_trk_klt_select's selection and leaves it
+ * unchanged; after xk_trk_photo_reset it is back on set 0 with no further action.  The switch adds no copy, wait or launch; the
+ * chain of stage entries states it as xk_trk_klt_select(done) between xk_trk_photo_calibrate and xk_trk_track.
  * Errors as xk_trk_frame, and XK_EINVAL without the photometric frame setup.  After XK_ECAPACITY the counts and the
  * calibration's outcome are returned (the ring has advanced), and the next frame is a first frame. */
 int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int stride, unsigned long seed, unsigned long seed_photo,
@@ -862,8 +892,9 @@ int xk_trk_photo_frame_intensities(xk_trk *t, double *intensity, int *n);
  *              C's sign rule; u = max(m, 0); out = u < 128 ? 2u : (u == 128 ? 255 : 512 - 2u) (the table of :42-51)
  * The spatial map PS is estimated on the device too, through the xk_trk_photo_spatial_* entries below; until
  * one is installed the correction takes the caller's map (zeros by default).
- * Out of scope: the second Lucas-Kanade parameter set and FAST threshold (tracker.cpp:641-645, :848; the caller re-runs the setups),
- * keyframe mode, the detached thread of refinePhotometricParams, pyramid levels above 0. */
+ * The second Lucas-Kanade parameter set (tracker.cpp:641-651) is xk_trk_klt_second; the calibration's own tracking always uses the
+ * first.  Out of scope: the second FAST threshold through the stage entries (tracker.cpp:848; the caller re-runs the setup --
+ * xk_trk_photo_frame switches it on the device), keyframe mode, the detached thread of refinePhotometricParams, pyramid levels above 0. */
 
 /* intensities_kernel_size_ (2...64; tracker.h:366: 30), epsilon_gap and epsilon_base of IRPhotoCalib (finite, in [0, 1]),
  * max_hyp (1...4096): the most hypotheses a gain estimate may evaluate.  Called after xk_trk_klt_setup, whose image size it

@@ -12,6 +12,13 @@ alternating in blocks of --frames frames, three repeats.
     python tools/bench_photo_frame.py [--frames 300]
 The chain uses only entries that exist without the photometric frame, so the yardstick is the chain ON A BUILD OF THE PARENT COMMIT:
     python tools/bench_photo_frame.py --only-chain --lib /path/to/the/parent's/libxk.so
+--second W H MAX_LEVEL MIN_EIG_THR declares the second Lucas-Kanade parameter set (xk_trk_klt_second) on both sides: the frame
+switches to it on the device once the calibration is done, the chain calls klt_select(done) between photo_calibrate and track.  Every
+line above is then a time AFTER the switch (the scene estimates gains from its second tracked image on).  A frame that tracks BEFORE
+the switch exists only at a start: after a uniform image the list is empty, the next image but one re-detects on its predecessor and
+tracks what it found with the first set, and the image after that estimates.  The option therefore adds, per feature count, cycles of
+photo_reset, frame_reset, a uniform image, the two images and --after further frames of a re-detecting tracker, and reports the
+re-detecting frame before the switch (no calibration yet: its list was empty) and the re-detecting frames after it separately.
 One profiler run of its own lists the HIP calls of a frame (the single hipStreamSynchronize, the two hipMemcpyAsync):
     rocprofv3 --hip-trace --stats --output-format csv -d DIR -o f -- python tools/bench_photo_frame.py --frames 50 --only-frame"""
 import argparse, os, sys, time
@@ -25,7 +32,11 @@ ap.add_argument("--frames", type=int, default=300)
 ap.add_argument("--only-frame", action="store_true", help="the frame entry alone, steady frames (profiler runs)")
 ap.add_argument("--only-chain", action="store_true", help="the chain alone (with --lib: on another build of the library)")
 ap.add_argument("--lib", default=None, help="the libxk.so to load instead of this tree's")
+ap.add_argument("--second", nargs=4, default=None, metavar=("W", "H", "MAX_LEVEL", "MIN_EIG_THR"), help="the second Lucas-Kanade parameter set")
+ap.add_argument("--after", type=int, default=20, help="with --second: frames after the switch per cycle")
 args = ap.parse_args()
+SECOND = None if args.second is None else dict(win=(int(args.second[0]), int(args.second[1])), max_level=int(args.second[2]),
+                                               min_eig_thr=float(args.second[3]))
 
 import torch
 from x_multi_agent_amd import engine, tracker
@@ -62,7 +73,7 @@ eng = engine.Engine(4, 0, 4, lib_path=args.lib)
 
 def make(b, n_feat_min, frame):
     mf = tracker.MatchFilter(eng, MAX_FEATURES, K, 0.0)
-    k = tracker.Klt(eng, 0, W, H, WIN, MAX_LEVEL, match_filter=mf)
+    k = tracker.Klt(eng, 0, W, H, WIN, MAX_LEVEL, match_filter=mf, **({} if SECOND is None else dict(second=SECOND)))
     k.detect_setup(9, 1, b, 20, 32768)
     k.photo_setup(KERNEL, EPS_GAP, EPS_BASE, PHOTO_HYP)
     if frame:
@@ -92,7 +103,7 @@ class Chain:
 
     def __init__(self, b, n_feat_min):
         self.mf, self.k = make(b, n_feat_min, False)
-        self.n_feat_min, self.i, self.xy, self.val = n_feat_min, 0, None, None
+        self.n_feat_min, self.i, self.xy, self.val, self.done = n_feat_min, 0, None, None, False
 
     def step(self):
         k, redetected = self.k, 0
@@ -103,6 +114,9 @@ class Chain:
             self.i += 1
             return len(self.xy), 0, 0
         c = k.photo_calibrate(self.xy.astype(np.float32), self.val, max(1, min(len(self.xy), PHOTO_HYP)), self.i)
+        if SECOND is not None:
+            self.done = self.done or bool(c["estimated"])
+            k.klt_select(1 if self.done else 0)
         r = k.track(self.xy.astype(np.float32))
         prev, cur = self.xy[r["keep_idx"]], r["kept_cur"]
         val = k.photo_intensity(np.trunc(cur).astype(np.int32), 1, 0)[0].copy()
@@ -153,4 +167,38 @@ for b in (26, 17):
         print(line, flush=True)
         for _, o in sides:
             o.close()
+
+def switch_cycles(b):
+    """Cycles from a start on a re-detecting tracker with the second set -> (ms of the frame that tracks before the switch, ms per frame
+    after it, features)."""
+    f = Frame(b, 100000)
+    blank = np.full((H, W), 64, np.uint8)
+    before, after, n = [], [], 0
+    cycles = max(3, args.frames // max(args.after, 1))
+    for c in range(cycles + 2):                                     # (two cycles of warm-up)
+        f.k.photo_reset()
+        f.k.frame_reset()
+        f.i = 0
+        f.k.photo_frame(blank)
+        f.step()
+        t0 = time.perf_counter()
+        r = f.k.photo_frame(pair[1], seed=1, seed_photo=1)
+        t1 = time.perf_counter()
+        assert not r["done"] and r["n_new_tracked"] > 0, "the frame before the switch tracked nothing"
+        f.i = 2
+        for _ in range(args.after):
+            n, red, est = f.step()
+        t2 = time.perf_counter()
+        if c >= 2:
+            before.append(1e3 * (t1 - t0))
+            after.append(1e3 * (t2 - t1) / args.after)
+    f.close()
+    return before, after, n
+
+
+if SECOND is not None and not args.only_chain and not args.only_frame:
+    for b in (26, 17):
+        before, after, n = switch_cycles(b)
+        print(f"b = {b:2d}  re-detecting frame BEFORE the switch (first set, no calibration): median {np.median(before):6.3f} min {min(before):6.3f} ms;  "
+              f"AFTER it (second set): median {np.median(after):6.3f} min {min(after):6.3f} ms per frame ({n} features, {len(before)} cycles)", flush=True)
 eng.close()

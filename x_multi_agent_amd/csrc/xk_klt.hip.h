@@ -45,10 +45,19 @@ struct XkKltLevel {
 };
 struct XkKltPyr { XkKltLevel lv[XK_KLT_MAX_LEVELS]; };
 
+// One Lucas-Kanade parameter set: what Tracker::featureTracking switches once the photometric calibration is done (tracker.cpp:641-651).
+struct XkKltSet {
+  int levels, win_w, win_h;
+  double min_eig_thr;
+};
+
 struct XkKltArgs {
-  XkKltPyr prev, cur;
-  int levels, n, win_w, win_h, max_iter;
-  double eps2, min_eig_thr;
+  XkKltPyr prev, cur;              // both built to the deeper set's levels
+  XkKltSet set[2];
+  const int *second_on;            // NULL: set[0], the host chose.  Else set[1] where *second_on is not 0 when the kernel runs (the
+                                   //   photometric frame: XkPhotoState::done), set[0] where it is 0
+  int n, max_iter;
+  double eps2;
   const float *pts;                // [n][2] previous points, cv::Point2f
   double *cur_xy;                  // [n][2]
   double *min_eig;                 // [n]
@@ -180,7 +189,11 @@ __global__ __launch_bounds__(64 * XK_KLT_WAVES) void xk_klt_track(XkKltArgs a) {
     if (lane == 0) { a.cur_xy[2 * f] = px; a.cur_xy[2 * f + 1] = py; a.status[f] = 0; a.min_eig[f] = 0.0; }
     return;
   }
-  const int win_w = a.win_w, win_h = a.win_h, npix = win_w * win_h;
+  // One set for the whole feature, read once: the address is the kernel argument's, so the load and the selects below are scalar.
+  const bool second = a.second_on && *a.second_on != 0;
+  const int levels = second ? a.set[1].levels : a.set[0].levels;
+  const int win_w = second ? a.set[1].win_w : a.set[0].win_w, win_h = second ? a.set[1].win_h : a.set[0].win_h, npix = win_w * win_h;
+  const double min_eig_thr = second ? a.set[1].min_eig_thr : a.set[0].min_eig_thr;
   const double hx = (double)(win_w - 1) * 0.5, hy = (double)(win_h - 1) * 0.5;
   const double scale20 = 1.0 / 1048576.0;
   int wx[XK_KLT_SLOTS], wy[XK_KLT_SLOTS], Iw[XK_KLT_SLOTS], gx[XK_KLT_SLOTS], gy[XK_KLT_SLOTS];
@@ -193,13 +206,13 @@ __global__ __launch_bounds__(64 * XK_KLT_WAVES) void xk_klt_track(XkKltArgs a) {
   }
   int status = 1;
   double min_eig_out = 0.0, nx = 0.0, ny = 0.0;
-  for (int l = a.levels; l >= 0; --l) {
+  for (int l = levels; l >= 0; --l) {
     const XkKltLevel P = a.prev.lv[l];
     const unsigned char *J = a.cur.lv[l].img;
     const int W = P.w, H = P.h, pitch = P.pitch;
     const double scale = 1.0 / (double)(1 << l);
     double qx = px * scale, qy = py * scale;
-    if (l == a.levels) { nx = qx; ny = qy; } else { nx = 2.0 * nx; ny = 2.0 * ny; }
+    if (l == levels) { nx = qx; ny = qy; } else { nx = 2.0 * nx; ny = 2.0 * ny; }
     qx -= hx; qy -= hy;
     double fx = floor(qx), fy = floor(qy);
     if (!xk_klt_corner_ok(fx, fy, W, H, win_w, win_h)) {
@@ -228,7 +241,7 @@ __global__ __launch_bounds__(64 * XK_KLT_WAVES) void xk_klt_track(XkKltArgs a) {
     const double dA = A11 - A22;
     const double min_eig = (A22 + A11 - sqrt(dA * dA + 4.0 * A12 * A12)) / (double)(2 * win_w * win_h);
     if (l == 0) min_eig_out = min_eig;
-    if (min_eig < a.min_eig_thr || D < 1.1920928955078125e-07) {  // 2^-23, FLT_EPSILON
+    if (min_eig < min_eig_thr || D < 1.1920928955078125e-07) {  // 2^-23, FLT_EPSILON
       if (l == 0) status = 0;
       continue;
     }

@@ -146,8 +146,12 @@ struct xk_psp {
 };
 
 struct xk_klt {
-  int width, height, win_w, win_h, max_level, max_iter, levels;
+  int width, height, win_w, win_h, max_level, max_iter, levels;    // the first parameter set (win_size_, max_level_, min_eig_thr_)
   double eps, min_eig_thr;
+  int has_second, sel;        // xk_trk_klt_second declared a second set; the set xk_trk_track and xk_trk_frame use (xk_trk_klt_select)
+  int win_w2, win_h2, max_level2, levels2;                         // the second set (win_size_photo_, ...); max_iter and eps are shared
+  double min_eig_thr2;
+  int deep;                   // max(levels, levels2): what the slots are laid out for and a push builds
   xk_block blk;                 // device: slot 0 | slot 1 | previous points (floats) | result block
   XkKltPyr slot[2];           // per slot and level: image, dIx, dIy at the level's pitch
   int cur, pushed;            // the slot of the current image; images pushed since the setup, counted to 2
@@ -695,6 +699,56 @@ static int klt_count_levels(int w, int h, int win_w, int win_h, int max_level) {
   return lv;
 }
 
+// One parameter set's checks for entry `who`: its levels by rule 1, or -1 after fail(XK_EINVAL).
+static int klt_set_levels(xk_handle *h, const char *who, int width, int height, int win_w, int win_h, int max_level, double min_eig_thr) {
+  const char *what = win_w < 3 || win_w > XK_KLT_MAX_WIN || win_h < 3 || win_h > XK_KLT_MAX_WIN ? "window outside 3...31" :
+                     max_level < 0 || max_level >= XK_KLT_MAX_LEVELS ? "max_level outside 0...4" :
+                     !(min_eig_thr >= 0.0) || !std::isfinite(min_eig_thr) ? "min_eig_thr < 0" : nullptr;
+  const int levels = what ? -1 : klt_count_levels(width, height, win_w, win_h, max_level);
+  if (!what && levels < 0) what = "the window does not fit the image";
+  if (what) fail_at(h, XK_EINVAL, who, what);
+  return levels;
+}
+
+// The setup behind xk_trk_klt_setup and xk_trk_klt_second: `par` holds the checked parameters (both sets' levels and `deep` included); the
+// buffers of two images are laid out for par.deep levels, and the new setup replaces the old one with everything that hangs on it.
+static int klt_make(xk_trk *t, const xk_klt &par, const char *who) {
+  xk_handle *h = t->h;
+  const int width = par.width, height = par.height, levels = par.deep;
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_klt *k = (xk_klt *)calloc(1, sizeof(xk_klt));
+  if (!k) return XK_ENOMEM;
+  k->width = width; k->height = height; k->win_w = par.win_w; k->win_h = par.win_h; k->max_level = par.max_level; k->max_iter = par.max_iter;
+  k->levels = par.levels; k->eps = par.eps; k->min_eig_thr = par.min_eig_thr;
+  k->has_second = par.has_second; k->sel = 0;
+  k->win_w2 = par.win_w2; k->win_h2 = par.win_h2; k->max_level2 = par.max_level2; k->levels2 = par.levels2; k->min_eig_thr2 = par.min_eig_thr2;
+  k->deep = levels;
+  k->cur = 0; k->pushed = 0;
+  XkKltPyr P{};                                                   // per level: pitch h bytes of image, then two planes of shorts
+  for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) {
+    P.lv[l].w = w; P.lv[l].h = hh; P.lv[l].pitch = round_up(w, 16);
+    k->slot_bytes += 5 * (size_t)P.lv[l].pitch * hh;
+  }
+  const size_t pts_bytes = up16(sizeof(float) * 2 * (size_t)t->max_matches), res_bytes = klt_res_bytes(t->max_matches);
+  const size_t img_bytes = (size_t)P.lv[0].pitch * height;
+  int rc = blk_alloc(h, k->blk, 2 * k->slot_bytes + pts_bytes + res_bytes, pts_bytes + res_bytes, who);
+  if (rc == XK_OK && (hipHostMalloc((void **)&k->h_img, img_bytes) != hipSuccess ||
+                      hipEventCreateWithFlags(&k->img_copied, hipEventDisableTiming) != hipSuccess))
+    rc = fail_at(h, XK_ENOMEM, who, "allocation failed");
+  if (rc == XK_OK) {
+    memset(k->h_img, 0, img_bytes);                               // (the staging's padding columns, as blk_alloc's)
+    size_t off = 0;
+    for (int s = 0; s < 2; ++s) {
+      k->slot[s] = P;
+      klt_place(k->slot[s], levels, carve<unsigned char>(k->blk.d, off, k->slot_bytes));
+    }
+    k->d_pts = carve<float>(k->blk.d, off, pts_bytes);
+    k->d_res = k->blk.d + off;
+    k->h_res = k->blk.h + pts_bytes;
+  }
+  return setup_install(h, rc, who, t->klt, k);                            // (the old setup's detection, description and photo setups go with it)
+}
+
 /* The parameters of cv::calcOpticalFlowPyrLK as Tracker holds them (tracker.h:234-261) and the device buffers of two images */
 extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int win_h, int max_level, int max_iter, double eps,
                                 double min_eig_thr) {
@@ -708,43 +762,55 @@ extern "C" int xk_trk_klt_setup(xk_trk *t, int width, int height, int win_w, int
   if (!(min_eig_thr >= 0.0) || !std::isfinite(min_eig_thr)) return fail(h, XK_EINVAL, "xk_trk_klt_setup: min_eig_thr < 0");
   const int levels = klt_count_levels(width, height, win_w, win_h, max_level);
   if (levels < 0) return fail(h, XK_EINVAL, "xk_trk_klt_setup: the window does not fit the image");
-  HIPCHK(h, hipSetDevice(h->device));
-  xk_klt *k = (xk_klt *)calloc(1, sizeof(xk_klt));
-  if (!k) return XK_ENOMEM;
-  k->width = width; k->height = height; k->win_w = win_w; k->win_h = win_h; k->max_level = max_level; k->max_iter = max_iter;
-  k->levels = levels; k->eps = eps; k->min_eig_thr = min_eig_thr;
-  k->cur = 0; k->pushed = 0;
-  XkKltPyr P{};                                                   // per level: pitch h bytes of image, then two planes of shorts
-  for (int l = 0, w = width, hh = height; l <= levels; ++l, w = (w + 1) / 2, hh = (hh + 1) / 2) {
-    P.lv[l].w = w; P.lv[l].h = hh; P.lv[l].pitch = round_up(w, 16);
-    k->slot_bytes += 5 * (size_t)P.lv[l].pitch * hh;
-  }
-  const size_t pts_bytes = up16(sizeof(float) * 2 * (size_t)t->max_matches), res_bytes = klt_res_bytes(t->max_matches);
-  const size_t img_bytes = (size_t)P.lv[0].pitch * height;
-  int rc = blk_alloc(h, k->blk, 2 * k->slot_bytes + pts_bytes + res_bytes, pts_bytes + res_bytes, "xk_trk_klt_setup");
-  if (rc == XK_OK && (hipHostMalloc((void **)&k->h_img, img_bytes) != hipSuccess ||
-                      hipEventCreateWithFlags(&k->img_copied, hipEventDisableTiming) != hipSuccess))
-    rc = fail(h, XK_ENOMEM, "xk_trk_klt_setup: allocation failed");
-  if (rc == XK_OK) {
-    memset(k->h_img, 0, img_bytes);                               // (the staging's padding columns, as blk_alloc's)
-    size_t off = 0;
-    for (int s = 0; s < 2; ++s) {
-      k->slot[s] = P;
-      klt_place(k->slot[s], levels, carve<unsigned char>(k->blk.d, off, k->slot_bytes));
-    }
-    k->d_pts = carve<float>(k->blk.d, off, pts_bytes);
-    k->d_res = k->blk.d + off;
-    k->h_res = k->blk.h + pts_bytes;
-  }
-  return setup_install(h, rc, "xk_trk_klt_setup", t->klt, k);             // (the old setup's detection, description and photo setups go with it)
+  xk_klt par{};
+  par.width = width; par.height = height; par.win_w = win_w; par.win_h = win_h; par.max_level = max_level; par.max_iter = max_iter;
+  par.levels = par.deep = levels; par.eps = eps; par.min_eig_thr = min_eig_thr;
+  return klt_make(t, par, "xk_trk_klt_setup");
 }
 
-/* levels of rule 1 (the pyramid has levels + 1 images), -1 before xk_trk_klt_setup */
+/* The second parameter set of a PHOTOMETRIC_CALI build (win_size_photo_, max_level_photo_, min_eig_thr_photo_; tracker.cpp:641-651).  A
+ * setup-class call: the slots are laid out again for the deeper of the two sets, the images are forgotten and the dependent setups go */
+extern "C" int xk_trk_klt_second(xk_trk *t, int win_w, int win_h, int max_level, double min_eig_thr) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  const xk_klt *k = t->klt;
+  if (!k) return fail(h, XK_EINVAL, "xk_trk_klt_second: before xk_trk_klt_setup");
+  const int levels2 = klt_set_levels(h, "xk_trk_klt_second", k->width, k->height, win_w, win_h, max_level, min_eig_thr);
+  if (levels2 < 0) return XK_EINVAL;
+  xk_klt par{};
+  par.width = k->width; par.height = k->height; par.win_w = k->win_w; par.win_h = k->win_h; par.max_level = k->max_level;
+  par.max_iter = k->max_iter; par.levels = k->levels; par.eps = k->eps; par.min_eig_thr = k->min_eig_thr;
+  par.has_second = 1; par.win_w2 = win_w; par.win_h2 = win_h; par.max_level2 = max_level; par.levels2 = levels2; par.min_eig_thr2 = min_eig_thr;
+  par.deep = std::max(k->levels, levels2);
+  return klt_make(t, par, "xk_trk_klt_second");
+}
+
+/* The set xk_trk_track and xk_trk_frame track with from now on: 0, or 1 once xk_trk_klt_second has declared it.  Nothing is queued */
+extern "C" int xk_trk_klt_select(xk_trk *t, int set) {
+  if (!t) return XK_EINVAL;
+  xk_klt *k = t->klt;
+  if (!k) return fail(t->h, XK_EINVAL, "xk_trk_klt_select: before xk_trk_klt_setup");
+  if (set != 0 && set != 1) return fail(t->h, XK_EINVAL, "xk_trk_klt_select: set is 0 or 1");
+  if (set == 1 && !k->has_second) return fail(t->h, XK_EINVAL, "xk_trk_klt_select: no second set (xk_trk_klt_second)");
+  k->sel = set;
+  return XK_OK;
+}
+
+/* the selected set, -1 before xk_trk_klt_setup */
+extern "C" int xk_trk_klt_selected(xk_trk *t) { return (t && t->klt) ? t->klt->sel : -1; }
+
+/* levels of rule 1 of the first set (the pyramid has levels + 1 images), -1 before xk_trk_klt_setup */
 extern "C" int xk_trk_klt_levels(xk_trk *t) { return (t && t->klt) ? t->klt->levels : -1; }
+
+/* levels of either set, -1 before xk_trk_klt_setup, for another value than 0 or 1 and for a second set that was not declared */
+extern "C" int xk_trk_klt_levels_of(xk_trk *t, int set) {
+  if (!t || !t->klt || (set != 0 && set != 1) || (set == 1 && !t->klt->has_second)) return -1;
+  return set ? t->klt->levels2 : t->klt->levels;
+}
 
 // Levels 1 ... of a slot from its level 0, and the Scharr derivatives of every level.
 static int klt_pyramid(xk_handle *h, const xk_klt *k, const XkKltPyr &P) {
-  for (int l = 0; l <= k->levels; ++l) {
+  for (int l = 0; l <= k->deep; ++l) {
     const XkKltLevel &L = P.lv[l];
     if (l > 0) {
       const XkKltLevel &S = P.lv[l - 1];
@@ -792,14 +858,22 @@ extern "C" int xk_trk_push_image(xk_trk *t, const unsigned char *img, int stride
 // The kept pairs in a tracking's result block for n points: cur_xy [n][2] | min_eig [n] | kept pairs | status [n].
 static XkKeptPairs klt_kept_at(unsigned char *d_res, int n) { return xk_kept_pairs((double *)d_res + 3 * (size_t)n, n); }
 
-// The tracking of the n points at d_pts from pyramid `prev` to `cur`, queued: the result block (klt_res_bytes(n)) goes to d_res.
-static int klt_queue_track(xk_handle *h, const xk_klt *k, const XkKltPyr &prev, const XkKltPyr &cur, const float *d_pts, unsigned char *d_res,
-                           int n, XkKltArgs &a, const int *n_dev = nullptr) {
+static XkKltSet klt_set(const xk_klt *k, int set) {
+  return set ? XkKltSet{k->levels2, k->win_w2, k->win_h2, k->min_eig_thr2} : XkKltSet{k->levels, k->win_w, k->win_h, k->min_eig_thr};
+}
+
+// The tracking of the n points at d_pts from pyramid `prev` to `cur`, queued: the result block (klt_res_bytes(n)) goes to d_res.  With
+// parameter set `set` (0 or 1) the host chose; with second_on (and a second set declared) the kernel takes set 1 where *second_on is not 0
+// when it runs and set 0 otherwise, whatever `set` says.
+static int klt_queue_track(xk_handle *h, const xk_klt *k, int set, const int *second_on, const XkKltPyr &prev, const XkKltPyr &cur,
+                           const float *d_pts, unsigned char *d_res, int n, XkKltArgs &a, const int *n_dev = nullptr) {
   a = XkKltArgs{};
   a.n_dev = n_dev;                                                // (then n is the bound the grid and the block are sized by)
   a.prev = prev; a.cur = cur;
-  a.levels = k->levels; a.n = n; a.win_w = k->win_w; a.win_h = k->win_h; a.max_iter = k->max_iter;
-  a.eps2 = k->eps * k->eps; a.min_eig_thr = k->min_eig_thr;
+  if (second_on && k->has_second) { a.set[0] = klt_set(k, 0); a.set[1] = klt_set(k, 1); a.second_on = second_on; }
+  else a.set[0] = a.set[1] = klt_set(k, set);
+  a.n = n; a.max_iter = k->max_iter;
+  a.eps2 = k->eps * k->eps;
   a.pts = d_pts;
   a.cur_xy = (double *)d_res; a.min_eig = a.cur_xy + 2 * (size_t)n;
   a.kept = klt_kept_at(d_res, n);
@@ -827,7 +901,7 @@ extern "C" int xk_trk_track(xk_trk *t, const float *prev_xy, int n, double *cur_
   memcpy(k->blk.h, prev_xy, sizeof(float) * 2 * (size_t)n);
   HIPCHK(h, hipMemcpyAsync(k->d_pts, k->blk.h, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   XkKltArgs a;
-  XKCHK(klt_queue_track(h, k, k->slot[k->cur ^ 1], k->slot[k->cur], k->d_pts, k->d_res, n, a));
+  XKCHK(klt_queue_track(h, k, k->sel, nullptr, k->slot[k->cur ^ 1], k->slot[k->cur], k->d_pts, k->d_res, n, a));
   const unsigned char *r = k->h_res;
   HIPCHK(h, hipMemcpyAsync(k->h_res, k->d_res, klt_res_bytes(n), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -844,7 +918,7 @@ extern "C" int xk_trk_klt_level(xk_trk *t, int which, int level, unsigned char *
   xk_handle *h = t->h;
   const int s = img_slot(t, "xk_trk_klt_level", which);
   if (s < 0) return XK_EINVAL;
-  if (level < 0 || level > t->klt->levels) return fail(h, XK_EINVAL, "xk_trk_klt_level: no such level");
+  if (level < 0 || level > t->klt->deep) return fail(h, XK_EINVAL, "xk_trk_klt_level: no such level");
   HIPCHK(h, hipSetDevice(h->device));
   const XkKltLevel &L = t->klt->slot[s].lv[level];
   if (w) *w = L.w;
@@ -1170,7 +1244,7 @@ extern "C" int xk_trk_photo_setup(xk_trk *t, int kernel_size, double epsilon_gap
     bool ok = true;
     for (int s = 0; s < 2; ++s) {
       p->raw[s] = k->slot[s];                                                           // the same layout at another base
-      klt_place(p->raw[s], k->levels, carve<unsigned char>(p->blk.d, off, k->slot_bytes));
+      klt_place(p->raw[s], k->deep, carve<unsigned char>(p->blk.d, off, k->slot_bytes));
       // images pushed before this call are raw and working at once
       ok = ok && hipMemcpyAsync(p->raw[s].lv[0].img, k->slot[s].lv[0].img, k->slot_bytes, hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
     }
@@ -1428,7 +1502,7 @@ static int photo_queue_calibrate(xk_trk *t, const float *d_pts, const double *pr
   xk_klt *k = t->klt;
   xk_photo *p = k->photo;
   XkKltArgs a;
-  XKCHK(klt_queue_track(h, k, p->raw[k->cur ^ 1], p->raw[k->cur], d_pts, p->klt_res, n, a));
+  XKCHK(klt_queue_track(h, k, 0, nullptr, p->raw[k->cur ^ 1], p->raw[k->cur], d_pts, p->klt_res, n, a));    // always the first set (tracker.cpp:784-787)
   kept = a.kept;
   XkPhotoGatherArgs ga{};
   ga.kept = kept; ga.prev_intensity = prev_int; ga.ixy = p->ixy; ga.o_hist = p->o_hist; ga.off = p->off; ga.frame_back = p->frame_back;
@@ -2087,7 +2161,8 @@ static int frame_queue_detect(xk_trk *t, const xk_frm *f, const XkFrameArgs &a, 
 static int frame_queue_track(xk_trk *t, const xk_frm *f, const xk_pfrm *pf, int which, const float *pts, int n, const int *n_dev) {
   xk_klt *k = t->klt;
   XkKltArgs ka;
-  XKCHK(klt_queue_track(t->h, k, k->slot[k->cur ^ 1], k->slot[k->cur], pts, f->klt_res[which], n, ka, n_dev));
+  XKCHK(klt_queue_track(t->h, k, pf ? 0 : k->sel, pf ? &k->photo->st->done : nullptr, k->slot[k->cur ^ 1], k->slot[k->cur], pts, f->klt_res[which],
+                        n, ka, n_dev));
   if (pf) photo_frame_queue_kept_intensity(t->h, k->photo, pf, k->photo->raw[k->cur], ka.kept, n, which ? pf->ixy2 : pf->ixy1,
                                            which ? pf->val2 : pf->val1);
   return XK_OK;

@@ -41,6 +41,7 @@ SYMBOLS = [
     "xk_trk_filter_matches", "xk_trk_outlier_method", "xk_trk_fundamental_lmeds", "xk_trk_fundamental_medians", "xk_trk_fundamental_score",
     "xk_trk_camera_model", "xk_trk_distort", "xk_trk_undistort_status",
     "xk_trk_klt_setup", "xk_trk_klt_levels", "xk_trk_push_image", "xk_trk_track", "xk_trk_klt_level",
+    "xk_trk_klt_second", "xk_trk_klt_select", "xk_trk_klt_selected", "xk_trk_klt_levels_of",
     "xk_trk_detect_setup", "xk_trk_detect", "xk_trk_detect_stage",
     "xk_trk_describe_setup", "xk_trk_describe", "xk_trk_describe_stage",
     "xk_trk_frame_setup", "xk_trk_frame", "xk_trk_frame_features", "xk_trk_frame_reset",

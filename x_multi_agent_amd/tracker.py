@@ -218,10 +218,12 @@ class Klt(_Trk):
     """cv::calcOpticalFlowPyrLK as x::Tracker calls it (tracker.cpp:642-651, parameters tracker.h:234-261) and the post-filter
     behind it (:658-686) on one agent's GPU: push_image per frame, track per frame.  match_filter: an existing MatchFilter
     whose xk_trk this object shares, so that one device object serves both steps of a frame (max_features is then its
-    max_matches); without one the object owns an xk_trk with placeholder intrinsics, which the tracking never reads."""
+    max_matches); without one the object owns an xk_trk with placeholder intrinsics, which the tracking never reads.  second: None,
+    or dict(win=(w, h), max_level=, min_eig_thr=) -- the second parameter set of a PHOTOMETRIC_CALI build (tracker.cpp:641-651), declared
+    right after the KLT setup (klt_second); klt_select chooses between the two for track and frame, photo_frame chooses on the device."""
 
     def __init__(self, eng, max_features, width, height, win=(31, 31), max_level=2, max_iter=30, eps=0.01, min_eig_thr=0.003,
-                 match_filter=None):
+                 match_filter=None, second=None):
         self.owner = match_filter
         if match_filter is not None:
             self.eng, self.L, self.p, self.max_features = eng, eng.L, match_filter.p, match_filter.max_matches
@@ -230,6 +232,8 @@ class Klt(_Trk):
             self._create(eng, self.max_features)
         try:
             self.setup(width, height, win, max_level, max_iter, eps, min_eig_thr)
+            if second is not None:
+                self.klt_second(**second)
         except XkError:
             self.close()
             raise
@@ -240,9 +244,28 @@ class Klt(_Trk):
                                           C.c_int(max_iter), C.c_double(eps), C.c_double(min_eig_thr)), "xk_trk_klt_setup")
         self.width, self.height, self.win = int(width), int(height), (int(win[0]), int(win[1]))
 
+    def klt_second(self, win=(31, 31), max_level=2, min_eig_thr=0.003):
+        """xk_trk_klt_second: the second parameter set (win_size_photo_, max_level_photo_, min_eig_thr_photo_), which photo_frame
+        switches to on the device once its calibration is done.  A setup-class call: the pushed images are forgotten and every
+        setup made after the KLT setup is dropped."""
+        self._chk(self.L.xk_trk_klt_second(self.p, C.c_int(win[0]), C.c_int(win[1]), C.c_int(max_level), C.c_double(min_eig_thr)),
+                  "xk_trk_klt_second")
+
+    def klt_select(self, which):
+        """xk_trk_klt_select: the set (0 or 1) that track and frame use from now on.  Sticky; photo_frame ignores it."""
+        self._chk(self.L.xk_trk_klt_select(self.p, C.c_int(which)), "xk_trk_klt_select")
+
+    @property
+    def klt_selected(self):
+        return int(self.L.xk_trk_klt_selected(self.p))
+
     def levels(self):
-        """The highest pyramid level in use (rule 1 of DESIGN 3.11)."""
+        """The highest pyramid level the first set uses (rule 1 of DESIGN 3.11)."""
         return int(self.L.xk_trk_klt_levels(self.p))
+
+    def levels_of(self, which):
+        """The highest pyramid level set `which` uses; -1 for a second set that was not declared."""
+        return int(self.L.xk_trk_klt_levels_of(self.p, C.c_int(which)))
 
     def push_image(self, img):
         """The next frame, uint8 [height, >= width]; a row stride beyond the width (a view of a wider array) is passed on."""
