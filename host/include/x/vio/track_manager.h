@@ -45,6 +45,11 @@ using TrackedTrackList = std::vector<TrackedTrack>;
 using OppIDList = std::vector<uniqueId>;
 using OppIDListPtr = std::shared_ptr<OppIDList>;
 
+// TrackManager::featureTriangleAtPoint on the persistent tracks' newest features (below): the search itself, shared with
+// x::ResidentTrackManager, whose tracks live on the device.
+std::vector<int> featureTriangleAtPoint(const std::vector<TrackedFeature> &newest, const TrackedFeature &lrf_img_pt, unsigned int width,
+                                        unsigned int height);
+
 class TrackManager {
  public:
   // max_tracks (1 ... 2^20): the most candidate tracks of one frame.  manageTracks refuses a frame, before it changes anything, whose

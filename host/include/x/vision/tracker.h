@@ -72,6 +72,10 @@ class Tracker {
   // the counts of the last frame, and for each match the position of its feature in the previous frame's match list (or -(k + 1)
   // for the k-th feature the frame's re-detection accepted)
   const xk_trk_frame_out &counts() const { return out_; }
+  // the device object behind this tracker: what xk_trk_tracks_manage_frame takes, so that the frame's matches stay on the device
+  // (x::ResidentTrackManager::manageFrame); owned by the tracker
+  xk_trk *handle() const { return trk_; }
+  int maxFeatures() const { return max_features_; }
   const std::vector<int> &origins() const { return origin_v_; }
   int getImgId() const { return img_id_; }
   // the winner's median and scale of the last frame's outlier removal under outlier_method 4 (zeros: no candidate, nothing kept); false

@@ -386,12 +386,20 @@ double inCircle(const P2 &a, const P2 &b, const P2 &c, const P2 &d) {
 }  // namespace
 
 std::vector<int> TrackManager::featureTriangleAtPoint(const TrackedFeature &lrf_img_pt, unsigned int width, unsigned int height) const {
-  const int n = (int)slam_trks_.size();
+  std::vector<TrackedFeature> newest;
+  newest.reserve(slam_trks_.size());
+  for (const TrackedTrack &trk : slam_trks_) newest.push_back(trk.back());
+  return x::featureTriangleAtPoint(newest, lrf_img_pt, width, height);
+}
+
+std::vector<int> x::featureTriangleAtPoint(const std::vector<TrackedFeature> &newest, const TrackedFeature &lrf_img_pt, unsigned int width,
+                                           unsigned int height) {
+  const int n = (int)newest.size();
   const P2 p{(double)(float)lrf_img_pt.getXDist(), (double)(float)lrf_img_pt.getYDist()};
   if (n < 3 || !(p.x >= -1.0 && p.x < (double)width + 1.0 && p.y >= -1.0 && p.y < (double)height + 1.0)) return {};
   std::vector<P2> pts;
   pts.reserve((size_t)n + 3);
-  for (const TrackedTrack &trk : slam_trks_) pts.push_back(P2{(double)(float)trk.back().getXDist(), (double)(float)trk.back().getYDist()});
+  for (const TrackedFeature &f : newest) pts.push_back(P2{(double)(float)f.getXDist(), (double)(float)f.getYDist()});
   const double big = 3.0 * (double)std::max(width + 2, height + 2);
   pts.push_back(P2{-1.0 + big, -1.0}); pts.push_back(P2{-1.0, -1.0 + big}); pts.push_back(P2{-1.0 - big, -1.0 - big});
   const int m = n + 3;

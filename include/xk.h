@@ -1085,6 +1085,108 @@ int xk_trk_baseline(xk_trk *t, const int *trk_off, const double *obs_xy, const u
                     const double *C_q_G, int n_quats, double min_baseline_x_n, double min_baseline_y_n, int *norm_off,
                     double *norm_xy, double *delta_xy, unsigned char *flag);
 
+/* ---- TrackManager::manageTracks on the device: the tracks stay there from frame to frame ----
+ * The whole of manageTracks (track_manager.cpp:115-436) in one call per frame: the association of the matches with the
+ * persistent tracks, the rebuild of the opportunistic ones, the baseline batch, the dead-track pass, the promotion walk
+ * with its tile rule and the MSCKF-SLAM / standard split (csrc/xk_track_store.hip.h).  The result equals
+ * x::TrackManager's (host/src/track_manager.cpp) and tests/track_manager_np.py's: ids, order, lengths, lost indices and
+ * every coordinate bit for bit.  Each of the max_tracks slots keeps a track's newest 64 observations, its true length
+ * and its id; the id counter starts at 1 and goes on across frames and across xk_trk_tracks_clear. */
+
+/* The five measurement lists of a call, in the order xk_trk_tracks_out::n_list counts them */
+#define XK_TRACKS_MSCKF 0          /* over-long opportunistic tracks whose baseline passes */
+#define XK_TRACKS_MSCKF_SHORT 1    /* dead opportunistic tracks */
+#define XK_TRACKS_NEW_SLAM_STD 2   /* new persistent tracks, standard initialisation */
+#define XK_TRACKS_NEW_MSCKF_SLAM 3 /* new persistent tracks, MSCKF-SLAM initialisation */
+#define XK_TRACKS_PERSISTENT 4     /* the persistent tracks cropped to their newest min(n_poses_max, 64) observations */
+/* xk_trk_tracks_out::status */
+#define XK_TRACKS_OUTSIDE_GRID 1   /* a match's current feature lies outside the tile grid: XK_EINVAL */
+#define XK_TRACKS_CAPACITY 2       /* more candidate or live tracks than max_tracks: XK_ECAPACITY */
+#define XK_TRACKS_BOOKKEEPING 3    /* the walk found the fullest tile without a track ("tile bookkeeping out of step"): XK_EDEVICE */
+
+/* What a manage call returns.  The caller sets the three capacities and the five pointers; the call fills the rest.
+ * lost_slam_idxs [cap_lost]: TrackManager::getLostSlamTrackIndexes, the lost persistent tracks' indices before the
+ * frame's deletions.  claimed: 1 where a persistent track took the match (manageTracks erases those from its list); it has no
+ * capacity field: it must hold n bytes for xk_trk_tracks_manage and, for xk_trk_tracks_manage_frame, the n_matches of the frame it
+ * is fed from (xk_trk_create's max_matches always suffices).
+ * The five lists lie behind one another in list order as one CSR: ids [cap_entries], off [cap_entries + 1] in
+ * observations, xy [cap_obs][2] the normalised coordinates (u - cx) / fx, (v - cy) / fy of Camera::normalize, oldest
+ * first; list l is the n_list[l] entries behind those of the lists before it.
+ * Capacities a call needs, with P persistent plus new persistent and O opportunistic tracks in the store before it:
+ * cap_lost >= P, cap_entries >= O + n + P, cap_obs >= (O + n) * n_quats + P * min(n_poses_max, 64). */
+typedef struct xk_trk_tracks_out {
+  int status;                    /* 0, XK_TRACKS_OUTSIDE_GRID, XK_TRACKS_CAPACITY, XK_TRACKS_BOOKKEEPING */
+  int n_persistent, n_new_persistent, n_opportunistic;   /* the store's own lists after the call */
+  int n_lost, n_claimed, n_candidates, n_candidate_obs;  /* candidates: tracks of the call's baseline batch */
+  long long next_id;             /* the id the next started track gets */
+  int n_list[5];
+  int cap_lost, cap_entries, cap_obs;
+  int *lost_slam_idxs;
+  unsigned char *claimed;
+  long long *ids;
+  int *off;
+  double *xy;
+} xk_trk_tracks_out;
+
+/* Allocates the store for max_tracks tracks, the result block and its pinned mirror.  The tile grid is TiledImage's of
+ * a width x height image (tiled_image.cpp:98-105); min_baseline_*_n and multi_uav as TrackManager's constructor takes
+ * them; the intrinsics are xk_trk_create's, the most matches of a call its max_matches.  A later successful setup
+ * replaces the store (empty, ids from 1); a failed one leaves the earlier one as it was.
+ * XK_EINVAL: max_tracks outside 1...2^20, tile counts below 1 or more than 4096 tiles, width or height below 1, a
+ * threshold that is NaN, multi_uav other than 0 or 1.  XK_ENOMEM: the allocation failed.
+ * Cost.  max_tracks is a capacity, not a working size: three steps of a manage call run in ONE workgroup or wavefront and grow with
+ * the lists, not with the device -- the stable sort of n opportunistic tracks (n^2 / 1024 comparisons per thread), the in-order
+ * resolve of a frame with contested claims (one step of three barriers per item) and the promotion walk (one step per opportunistic
+ * track).  They are measured at a few hundred tracks (0.31 ms at 400); at tens of thousands of live tracks a call
+ * takes seconds.  Every loop is bounded all the same. */
+int xk_trk_tracks_setup(xk_trk *t, int max_tracks, int n_tiles_h, int n_tiles_w, int width, int height,
+                        double min_baseline_x_n, double min_baseline_y_n, int multi_uav);
+
+/* manageTracks of n matches given as HOST columns in the layout of xk_trk_frame_out: prev_xy, cur_xy (undistorted
+ * pixels), prev_dist_xy, cur_dist_xy [n][2] fp64, score [n] (both features of a match carry it).  A feature's tile is
+ * computed from its distorted pixels.  C_q_G HOST [n_quats][4] (x,y,z,w), the window's camera attitudes oldest first.
+ * opp_ids / n_opp_ids: the caller's list of setOppUpgradesMSCKF (multi_uav: required, may be empty); the call consumes
+ * it: *n_opp_ids is 0 on XK_OK.  May be NULL single-agent.
+ * One copy in, four launches, one copy out, one wait.
+ * XK_EINVAL: before xk_trk_tracks_setup; n outside 0...max_matches; a null column with n > 0; C_q_G null or n_quats
+ * outside 3...64; n_poses_max < 3; n_slam_features_max < 0; min_track_length outside 1...n_poses_max; opp_ids null with
+ * *n_opp_ids > 0, *n_opp_ids outside 0...max_tracks, n_opp_ids null with multi_uav; a null output pointer or a capacity
+ * below the bound above; a match outside the tile grid (status XK_TRACKS_OUTSIDE_GRID).
+ * XK_ECAPACITY (status XK_TRACKS_CAPACITY): O + (min_track_length <= 2 ? n : 0) > max_tracks, or the frame starts
+ * more tracks than there are free slots (the frame's dead tracks hold theirs until the call ends).
+ * The two refusals with a status are decided on the device before anything changes and reported at the call's wait:
+ * the store, the id counter and *n_opp_ids are what they were.  The object stays usable after every one of these errors.
+ * XK_EDEVICE: a HIP error; status XK_TRACKS_BOOKKEEPING (which a consistent store cannot produce); or counts in the result block
+ * that fail the host's range checks.  Only after XK_EDEVICE has the store already been modified, and the host's copy of the list
+ * lengths (which bound later calls' capacities and the removal indices) is stale: call xk_trk_tracks_clear, or set the store up
+ * anew, before the next frame. */
+int xk_trk_tracks_manage(xk_trk *t, const double *prev_xy, const double *cur_xy, const double *prev_dist_xy,
+                         const double *cur_dist_xy, const int *score, int n, const double *C_q_G, int n_quats,
+                         int n_poses_max, int n_slam_features_max, int min_track_length, long long *opp_ids,
+                         int *n_opp_ids, xk_trk_tracks_out *out);
+
+/* The same on the matches the last xk_trk_frame / xk_trk_photo_frame of this xk_trk left in its result block on the
+ * device: only the attitudes and the ids go up.  A first frame is a valid empty match list.
+ * XK_EINVAL as xk_trk_tracks_manage, and: without a frame setup, before a frame, after xk_trk_frame_reset, after a
+ * frame that returned an error. */
+int xk_trk_tracks_manage_frame(xk_trk *t, const double *C_q_G, int n_quats, int n_poses_max, int n_slam_features_max,
+                               int min_track_length, long long *opp_ids, int *n_opp_ids, xk_trk_tracks_out *out);
+
+/* One of the store's own lists: which = 0 persistent, 1 new persistent, 2 opportunistic.  *n: its length; per track
+ * ids [*n], lengths [*n] (true lengths), obs [*n][64][4] (undistorted x, y, distorted x, y; the newest min(length, 64)
+ * observations oldest first, the rows behind them zero), score [*n][64], tiles [*n][64][2] (row, column).  Any array
+ * may be NULL.  An inspection path: a gather and straight copies.  XK_EINVAL: before xk_trk_tracks_setup, which outside
+ * 0...2, n null. */
+int xk_trk_tracks_lists(xk_trk *t, int which, long long *ids, int *lengths, double *obs, int *score, int *tiles, int *n);
+
+/* TrackManager::removePersistentTracksAtIndex, removeNewPersistentTracksAtIndexes (idxs HOST [n] in strictly increasing
+ * order) and clear (the id counter stays).  Tiny launches on the handle's stream with no wait of their own.
+ * XK_EINVAL: before xk_trk_tracks_setup; an index at or beyond the list's length as the last result block and the
+ * removals since give it; idxs null with n > 0, n < 0, indices not increasing.  Nothing is removed then. */
+int xk_trk_tracks_remove_persistent(xk_trk *t, unsigned int idx);
+int xk_trk_tracks_remove_new_persistent(xk_trk *t, const unsigned int *idxs, int n);
+int xk_trk_tracks_clear(xk_trk *t);
+
 /* xk_msckf_build + xk_qr_compress queued on the handle's stream with NO host synchronisation and no host outputs:
  * together with the non-blocking staging calls and xk_cov_congruence / xk_cov_propagate, a whole frame -- covariance
  * propagation, StateManager::manage, per-feature build, QR compression, Kalman update -- is queued back to back and

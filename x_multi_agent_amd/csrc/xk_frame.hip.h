@@ -121,16 +121,21 @@ __device__ __forceinline__ void xk_frame_cal_head(const XkFrameArgs &a, int *hea
 }
 
 // TiledImage::setTileForFeature (tiled_image.cpp:139-158): the loops as written, each bounded by its tile count (a feature inside the
-// image leaves them earlier).
-__device__ __forceinline__ void xk_frame_tile(const XkFrameArgs &a, double x, double y, int *row, int *col) {
+// image leaves them earlier).  The body is shared with the track store (xk_track_store.hip.h), which bins the same features.
+__device__ __forceinline__ void xk_tile_for_feature(double tile_w, double tile_h, double height, int tiles_h, int tiles_w, double x, double y,
+                                                    int *row, int *col) {
 #pragma clang fp contract(off)
-  double c = x - a.tile_w - 0.5;
+  double c = x - tile_w - 0.5;
   int cc = 0;
-  for (int it = 0; it <= a.tiles_w && c > 0; ++it) { cc += 1; c -= a.tile_w; }
-  double r = a.height - y - 0.5;
-  int rr = a.tiles_h - 1;
-  for (int it = 0; it <= a.tiles_h && r > a.tile_h; ++it) { rr -= 1; r -= a.tile_h; }
+  for (int it = 0; it <= tiles_w && c > 0; ++it) { cc += 1; c -= tile_w; }
+  double r = height - y - 0.5;
+  int rr = tiles_h - 1;
+  for (int it = 0; it <= tiles_h && r > tile_h; ++it) { rr -= 1; r -= tile_h; }
   *row = rr; *col = cc;
+}
+
+__device__ __forceinline__ void xk_frame_tile(const XkFrameArgs &a, double x, double y, int *row, int *col) {
+  xk_tile_for_feature(a.tile_w, a.tile_h, a.height, a.tiles_h, a.tiles_w, x, y, row, col);
 }
 
 // 32 bytes, both 8-byte aligned

@@ -5,7 +5,8 @@
 // all of them (tracker.cpp:761-877, irPhotoCalib.cpp; xk_photo.hip.h).  Behind them, the normalisation and baseline check of the
 // track manager's candidate tracks (track_manager.cpp:576-636, camera.cpp; xk_tracks.hip.h).  At the end, Tracker::track itself in
 // one call on a resident feature list (tracker.cpp:134-306; xk_frame.hip.h): xk_trk_frame, and xk_trk_photo_frame with calibrateImage,
-// which are one body (frame_run).  A stage's launches are queued in one place, by the function its stage entry and the frame both call
+// which are one body (frame_run).  Last, the whole of TrackManager::manageTracks on tracks that stay on the device
+// (track_manager.cpp:115-436; xk_track_store.hip.h): xk_trk_tracks_*, fed from the host or from the block the last frame left.  A stage's launches are queued in one place, by the function its stage entry and the frame both call
 // (klt_queue_track, det_queue, orb_queue, trk_queue_ransac, photo_queue_calibrate): it takes what differs as parameters.
 // Every stage keeps its buffers in one xk_block (a device block and its pinned mirror, carved once by the stage's setup, which stores
 // every pointer an entry needs) and reaches them through the same helpers: sub_of (the stage's setup or XK_EINVAL), img_slot (the
@@ -22,6 +23,7 @@
 #include "xk_orb.hip.h"
 #include "xk_photo.hip.h"
 #include "xk_photo_spatial.hip.h"
+#include "xk_track_store.hip.h"
 #include "xk_tracks.hip.h"
 
 #define XKCHK(call)                          \
@@ -182,6 +184,8 @@ struct xk_frm {
   unsigned char *fund_res;    // of the outlier removal (trk_res_bytes(max_matches))
   int *orb_res;               // of the description (xk_orb_res_bytes(cap_new)); NULL without one
   struct xk_pfrm *pf;         // xk_trk_photo_frame_setup; NULL before.  It goes with this setup, and with the photo setup it was made over
+  int last_m, last_B;         // the matches the last frame left in its result block on the device and the bound that block is laid out by;
+  const unsigned char *last_out;   //   last_m -1: no such block (before a frame, after a reset or an error), 0: a first frame's empty list
 };
 
 // The photometric frame setup (xk_trk_photo_frame_setup): what Tracker::track of a PHOTOMETRIC_CALI build needs beyond xk_frm.
@@ -203,6 +207,16 @@ struct xk_bl {
   size_t o_quat, o_trk_off, o_norm_off, o_drop, o_obs, o_delta, o_flag, o_norm;
 };
 
+// The track store (xk_trk_tracks_setup): TrackManager's lists on the device.  It belongs to the xk_trk, as the baseline setup.
+struct xk_ts {
+  int max_tracks, max_n;      // max_n: the xk_trk's max_matches, the most matches of a call
+  xk_block blk;                 // device: store | scratch | a call's inputs | result block | the lists entry's gather.  Pinned: inputs | result block
+  XkTsArgs a;                 // the store's and the scratch's device pointers, placed once
+  unsigned char *d_in, *d_out, *d_gather;
+  size_t in_bytes, out_bytes, gather_bytes;
+  int n_slam, n_new, n_opp;   // host mirrors of the list lengths, from the last result block and the removals since
+};
+
 struct xk_trk {
   xk_handle *h;
   int max_matches;
@@ -221,6 +235,7 @@ struct xk_trk {
   int *cam_cnt;               // device [2]: invalid points and the largest step count of the last undistortion under another model than FOV
   struct xk_klt *klt;         // the feature tracking in front of the filter (xk_trk_klt_setup); NULL before
   struct xk_bl *bl;           // the baseline check of the track manager's candidates (xk_trk_baseline_setup); NULL before
+  struct xk_ts *ts;           // the track manager's lists on the device (xk_trk_tracks_setup); NULL before
 };
 
 // the result blocks for n pairs: F [9] | kept pairs | mask [n], and cur_xy [n][2] | min_eig [n] | kept pairs | status [n]
@@ -341,9 +356,10 @@ static const XkKltPyr &photo_raw_slot(const xk_klt *k, int s) { return k->photo 
 // ---------------------------------------------------------------------------
 extern "C" void xk_trk_destroy(xk_trk *t) {
   if (!t) return;
-  if (t->klt || t->bl) hipStreamSynchronize(t->h->stream);
+  if (t->klt || t->bl || t->ts) hipStreamSynchronize(t->h->stream);
   setup_free(t->klt);
   setup_free(t->bl);
+  setup_free(t->ts);
   blk_free(t->blk);
   free(t);
 }
@@ -1975,7 +1991,7 @@ extern "C" int xk_trk_frame_setup(xk_trk *t, int n_feat_min, int n_tiles_h, int 
   if (!f) return XK_ENOMEM;
   f->n_feat_min = n_feat_min; f->tiles_h = n_tiles_h; f->tiles_w = n_tiles_w; f->max_per_tile = max_feat_per_tile;
   f->threshold_px = threshold_px; f->n_hyp = n_hyp;
-  f->det = d; f->orb = o; f->n_res = -1;
+  f->det = d; f->orb = o; f->n_res = -1; f->last_m = -1;
   const size_t M = (size_t)t->max_matches;
   f->cap_det = det_cap(t, d);
   f->cap_new = o ? std::min(f->cap_det, o->max_desc) : f->cap_det;
@@ -2025,7 +2041,7 @@ extern "C" int xk_trk_frame_reset(xk_trk *t) {
   if (!t) return XK_EINVAL;
   xk_frm *f = sub_of(t, &xk_klt::frm, "xk_trk_frame_reset", "xk_trk_frame_setup");
   if (!f) return XK_EINVAL;
-  f->n_res = -1;
+  f->n_res = -1; f->last_m = -1;
   return XK_OK;
 }
 
@@ -2194,6 +2210,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
   const int M = t->max_matches, R = first ? 0 : f->n_res;
   const int n_hyp_photo = ph ? std::max(1, std::min(R, pf->n_hyp)) : 0;
   f->n_res = -1;                                                    // (whatever fails below: the next frame is a first frame)
+  f->last_m = -1;
   t->lmeds_hyp = 0;                                                 // (and this one has run no LMedS yet)
   XKCHK(trk_push(t, img, stride));
   XkFrameArgs a = f->a;
@@ -2273,6 +2290,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
   if (status != 0) return fail_at(h, XK_ECAPACITY, who, frame_status_text(status));
   if (first) {
     f->n_res = head[XK_FC_NEW];
+    f->last_m = 0;
     return XK_OK;
   }
   trk_note_call(t, t->method, f->n_hyp, f->fund_res, a.B);
@@ -2290,6 +2308,7 @@ static int frame_run(xk_trk *t, xk_frm *f, const char *who, const unsigned char 
     memcpy(pout->cur_intensity, r + xk_frame_out_int(B, desc, 1), sizeof(double) * (size_t)m);
   }
   f->n_res = m;
+  f->last_m = m; f->last_B = a.B; f->last_out = a.out;
   return XK_OK;
 }
 
@@ -2316,4 +2335,295 @@ extern "C" int xk_trk_photo_frame(xk_trk *t, const unsigned char *img, int strid
   const int rc = frame_run(t, f, "xk_trk_photo_frame", img, stride, seed, out ? &o : nullptr, &ph);
   if (out) memcpy(out, &o, sizeof o);
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// TrackManager::manageTracks on tracks that stay on the device (track_manager.cpp:115-436), xk_track_store.hip.h
+// ---------------------------------------------------------------------------
+// The result block of one call, laid out by the host's bounds: head | lost [lost] | claimed [n] | entry starts, lengths [entries] each |
+// entry ids [entries] | normalised coordinates [obs][2].
+struct xk_ts_layout {
+  size_t o_lost, o_claimed, o_start, o_len, o_id, o_xy, bytes;
+};
+
+static xk_ts_layout ts_layout(size_t lost, size_t n, size_t entries, size_t obs) {
+  xk_ts_layout L{};
+  size_t off = up16(sizeof(int) * XK_TSR_N);
+  const auto piece = [&off](size_t bytes) { const size_t at = off; off += up16(bytes); return at; };
+  L.o_lost = piece(sizeof(int) * lost); L.o_claimed = piece(sizeof(int) * n);
+  L.o_start = piece(sizeof(int) * entries); L.o_len = piece(sizeof(int) * entries); L.o_id = piece(sizeof(long long) * entries);
+  L.o_xy = piece(sizeof(double) * 2 * obs);
+  L.bytes = off;
+  return L;
+}
+
+/* The store, its scratch, the staging of a call's inputs and the result block with its pinned mirror */
+extern "C" int xk_trk_tracks_setup(xk_trk *t, int max_tracks, int n_tiles_h, int n_tiles_w, int width, int height, double min_baseline_x_n,
+                                   double min_baseline_y_n, int multi_uav) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  const char *who = "xk_trk_tracks_setup";
+  if (max_tracks < 1 || max_tracks > (1 << 20)) return fail_at(h, XK_EINVAL, who, "max_tracks outside 1...2^20");
+  if (n_tiles_h < 1 || n_tiles_w < 1 || (long long)n_tiles_h * n_tiles_w > XK_TS_MAX_TILES) return fail_at(h, XK_EINVAL, who, "tile counts outside 1...4096 tiles");
+  if (width < 1 || height < 1) return fail_at(h, XK_EINVAL, who, "image size below 1 x 1");
+  if (min_baseline_x_n != min_baseline_x_n || min_baseline_y_n != min_baseline_y_n) return fail_at(h, XK_EINVAL, who, "a baseline threshold is not a number");
+  if (multi_uav < 0 || multi_uav > 1) return fail_at(h, XK_EINVAL, who, "multi_uav is 0 or 1");
+  HIPCHK(h, hipSetDevice(h->device));
+  xk_ts *s = (xk_ts *)calloc(1, sizeof(xk_ts));
+  if (!s) return XK_ENOMEM;
+  s->max_tracks = max_tracks; s->max_n = t->max_matches;
+  const size_t T = (size_t)max_tracks, M = (size_t)t->max_matches, R = XK_TS_RING;
+  s->in_bytes = up16(sizeof(double) * 4 * XK_TRACKS_MAX_QUATS) + up16(sizeof(long long) * T) + 4 * up16(sizeof(double) * 2 * M) + up16(sizeof(int) * M);
+  s->out_bytes = ts_layout(T, M, T + M, (T + M) * R).bytes;
+  s->gather_bytes = up16(8 * T) + up16(4 * T) + up16(32 * R * T) + up16(4 * R * T) + up16(8 * R * T);
+  const size_t store = up16(32 * R * T) + up16(4 * R * T) + up16(8 * R * T) + up16(4 * T) + up16(8 * T) + 4 * up16(4 * T) + 2 * 16;
+  const size_t scratch = up16(sizeof(int) * XK_TSC_N) + up16(16 * M) + 5 * up16(4 * M) + up16(16 * T) + 18 * up16(4 * T) + up16(4 * (T + 1)) * 2 +
+                         2 * up16(T) + up16(16 * T) + up16(16 * R * T);
+  const int rc = blk_alloc(h, s->blk, store + scratch + s->in_bytes + s->out_bytes + s->gather_bytes, s->in_bytes + s->out_bytes, who);
+  if (rc == XK_OK) {
+    XkTsArgs &a = s->a;
+    unsigned char *b = s->blk.d;
+    size_t off = 0;
+    a.obs = carve<double>(b, off, 32 * R * T); a.score = carve<int>(b, off, 4 * R * T); a.tile = carve<int>(b, off, 8 * R * T);
+    a.len = carve<int>(b, off, 4 * T); a.id = carve<long long>(b, off, 8 * T);
+    a.slam = carve<int>(b, off, 4 * T); a.newl = carve<int>(b, off, 4 * T); a.opp = carve<int>(b, off, 4 * T); a.free_ = carve<int>(b, off, 4 * T);
+    a.hdr = carve<int>(b, off, sizeof(int) * XK_TSH_N); a.next_id = carve<long long>(b, off, 8);
+    a.c = carve<int>(b, off, sizeof(int) * XK_TSC_N);
+    a.m_tile = carve<int>(b, off, 16 * M);
+    a.m_bin = carve<int>(b, off, 4 * M); a.m_owner = carve<int>(b, off, 4 * M); a.rm = carve<int>(b, off, 4 * M); a.mo = carve<int>(b, off, 4 * M);
+    a.newk = carve<int>(b, off, 4 * M);
+    a.last_xy = carve<double>(b, off, 16 * T);
+    int **per_track[] = {&a.pm, &a.kp, &a.lost_slot, &a.o_owner, &a.o_claimed, &a.comb, &a.cbin, &a.corig, &a.calive, &a.opp_tmp, &a.dead, &a.sorted,
+                         &a.lens, &a.act, &a.cand_of, &a.cand_slot, &a.l_msckf, &a.l_short};
+    for (int **p : per_track) *p = carve<int>(b, off, 4 * T);
+    a.trk_off = carve<int>(b, off, 4 * (T + 1)); a.norm_off = carve<int>(b, off, 4 * (T + 1));
+    a.drop = carve<unsigned char>(b, off, T); a.flag = carve<unsigned char>(b, off, T);
+    a.delta = carve<double>(b, off, 16 * T);
+    a.b_obs = carve<double>(b, off, 16 * R * T);
+    s->d_in = carve<unsigned char>(b, off, s->in_bytes);
+    s->d_out = carve<unsigned char>(b, off, s->out_bytes);
+    s->d_gather = carve<unsigned char>(b, off, s->gather_bytes);
+    a.max_tracks = max_tracks; a.multi_uav = multi_uav;
+    a.tiles_h = n_tiles_h; a.tiles_w = n_tiles_w;
+    a.height = (double)height; a.tile_h = (double)height / n_tiles_h; a.tile_w = (double)width / n_tiles_w;   // tiled_image.cpp:104-105
+    a.fx = t->fx; a.fy = t->fy; a.cx = t->cx; a.cy = t->cy; a.min_x = min_baseline_x_n; a.min_y = min_baseline_y_n;
+    hipLaunchKernelGGL(xk_ts_clear, dim3((max_tracks + 255) / 256), dim3(256), 0, h->stream, a, 1);
+  }
+  return setup_install(h, rc == XK_OK ? launched(h, "track store setup launch") : rc, who, t->ts, s);
+}
+
+static xk_ts *ts_of(xk_trk *t, const char *who) {
+  if (!t->ts) fail_at(t->h, XK_EINVAL, who, "before xk_trk_tracks_setup");
+  return t->ts;
+}
+
+// Both manage entries.  host: the match columns on the host (copied up with the attitudes), or dev: the same columns on the device.
+struct ts_matches {
+  const double *prev_xy, *cur_xy, *prev_dist_xy, *cur_dist_xy;
+  const int *score;
+};
+
+static int ts_manage(xk_trk *t, xk_ts *s, const char *who, const ts_matches *host, const ts_matches *dev, int n, const double *C_q_G, int n_quats,
+                     int n_poses_max, int n_slam_features_max, int min_track_length, long long *opp_ids, int *n_opp_ids, xk_trk_tracks_out *out) {
+  xk_handle *h = t->h;
+  const int n_ids = n_opp_ids ? *n_opp_ids : 0;
+  if (n < 0 || n > s->max_n) return fail_at(h, XK_EINVAL, who, "n outside 0...max_matches");
+  if (host && n > 0 && (!host->prev_xy || !host->cur_xy || !host->prev_dist_xy || !host->cur_dist_xy || !host->score))
+    return fail_at(h, XK_EINVAL, who, "null match column");
+  if (!C_q_G || n_quats < 3 || n_quats > XK_TRACKS_MAX_QUATS) return fail_at(h, XK_EINVAL, who, "3...64 camera attitudes");
+  if (n_poses_max < 3) return fail_at(h, XK_EINVAL, who, "n_poses_max < 3");
+  if (n_slam_features_max < 0) return fail_at(h, XK_EINVAL, who, "n_slam_features_max < 0");
+  if (min_track_length < 1 || min_track_length > n_poses_max) return fail_at(h, XK_EINVAL, who, "min_track_length outside 1...n_poses_max");
+  if (n_ids < 0 || n_ids > s->max_tracks || (n_ids > 0 && !opp_ids)) return fail_at(h, XK_EINVAL, who, "opp_ids: null, or their number outside 0...max_tracks");
+  if (s->a.multi_uav && !n_opp_ids) return fail_at(h, XK_EINVAL, who, "multi_uav without an id list");
+  const size_t P = (size_t)s->n_slam + s->n_new, O = (size_t)s->n_opp;
+  const size_t entries = O + n + P, obs = (O + n) * (size_t)n_quats + P * (size_t)std::min(n_poses_max, XK_TS_RING);
+  if (!out || !out->claimed || !out->lost_slam_idxs || !out->ids || !out->off || !out->xy) return fail_at(h, XK_EINVAL, who, "null output");
+  if ((size_t)std::max(out->cap_lost, 0) < P || (size_t)std::max(out->cap_entries, 0) < entries || (size_t)std::max(out->cap_obs, 0) < obs)
+    return fail_at(h, XK_EINVAL, who, "an output capacity is below the call's bound");
+  HIPCHK(h, hipSetDevice(h->device));
+  const xk_ts_layout L = ts_layout(P, (size_t)n, entries, obs);
+  XkTsArgs a = s->a;
+  a.n = n; a.n_quats = n_quats; a.n_poses_max = n_poses_max; a.n_slam_max = n_slam_features_max; a.min_track_length = min_track_length;
+  a.n_opp_ids = n_ids;
+  // the inputs: attitudes | ids | the match columns (host-fed), one copy
+  unsigned char *hi = s->blk.h;
+  size_t off = 0;
+  const auto put = [&](const void *src, size_t bytes) {
+    const size_t at = off;
+    if (bytes) memcpy(hi + at, src, bytes);
+    off += up16(bytes);
+    return s->d_in + at;
+  };
+  a.quat = (const double *)put(C_q_G, sizeof(double) * 4 * (size_t)n_quats);
+  a.opp_ids = (const long long *)put(opp_ids, sizeof(long long) * (size_t)n_ids);
+  if (host) {
+    a.m_prev = (const double *)put(host->prev_xy, 16 * (size_t)n); a.m_cur = (const double *)put(host->cur_xy, 16 * (size_t)n);
+    a.m_dprev = (const double *)put(host->prev_dist_xy, 16 * (size_t)n); a.m_dcur = (const double *)put(host->cur_dist_xy, 16 * (size_t)n);
+    a.m_score = (const int *)put(host->score, 4 * (size_t)n);
+  } else {
+    a.m_prev = dev->prev_xy; a.m_cur = dev->cur_xy; a.m_dprev = dev->prev_dist_xy; a.m_dcur = dev->cur_dist_xy; a.m_score = dev->score;
+  }
+  unsigned char *d = s->d_out, *r = s->blk.h + s->in_bytes;
+  a.head = (int *)d; a.lost = (int *)(d + L.o_lost); a.claimed = (int *)(d + L.o_claimed); a.e_start = (int *)(d + L.o_start);
+  a.e_len = (int *)(d + L.o_len); a.e_id = (long long *)(d + L.o_id); a.norm_xy = (double *)(d + L.o_xy);
+  // one copy in, four launches, one copy out, one wait
+  HIPCHK(h, hipMemcpyAsync(s->d_in, hi, off, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(xk_ts_associate, dim3(1), dim3(XK_TS_THREADS), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ts_candidates, dim3(1), dim3(XK_TS_THREADS), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ts_baseline, dim3((unsigned)((O + n + XK_TRACKS_WAVES) / XK_TRACKS_WAVES)), dim3(64 * XK_TRACKS_WAVES), 0, h->stream, a);
+  hipLaunchKernelGGL(xk_ts_walk, dim3(1), dim3(64), 0, h->stream, a);
+  XKCHK(launched(h, "track manager launch"));
+  HIPCHK(h, hipMemcpyAsync(r, d, L.bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int *head = (const int *)r;
+  const int status = head[XK_TSR_STATUS];
+  out->status = status;
+  out->n_persistent = head[XK_TSR_N_SLAM]; out->n_new_persistent = head[XK_TSR_N_NEW]; out->n_opportunistic = head[XK_TSR_N_OPP];
+  out->n_lost = head[XK_TSR_N_LOST]; out->n_claimed = head[XK_TSR_N_CLAIMED]; out->n_candidates = head[XK_TSR_N_CAND];
+  out->n_candidate_obs = head[XK_TSR_N_CAND_OBS];
+  out->next_id = (long long)(((unsigned long long)(unsigned int)head[XK_TSR_NEXT_ID_HI] << 32) | (unsigned int)head[XK_TSR_NEXT_ID_LO]);
+  for (int l = 0; l < 5; ++l) out->n_list[l] = 0;
+  if (status == XK_TS_EOUTSIDE) return fail_at(h, XK_EINVAL, who, "a match outside the tile grid");
+  if (status == XK_TS_ECAPACITY) return fail_at(h, XK_ECAPACITY, who, "the frame may have more candidate or live tracks than max_tracks");
+  if (status == XK_TS_EBOOKKEEPING) return fail_at(h, XK_EDEVICE, who, "tile bookkeeping out of step");
+  size_t n_entries = 0;
+  bool ok = status == 0 && head[XK_TSR_N_LOST] >= 0 && (size_t)head[XK_TSR_N_LOST] <= P && head[XK_TSR_N_NORM] >= 0 && head[XK_TSR_N_PER_OBS] >= 0 &&
+            (size_t)head[XK_TSR_N_NORM] + (size_t)head[XK_TSR_N_PER_OBS] <= obs && head[XK_TSR_N_SLAM] >= 0 && head[XK_TSR_N_NEW] >= 0 &&
+            head[XK_TSR_N_OPP] >= 0 && (long long)head[XK_TSR_N_SLAM] + head[XK_TSR_N_NEW] + head[XK_TSR_N_OPP] <= s->max_tracks;
+  for (int l = 0; l < 5 && ok; ++l) {
+    ok = head[XK_TSR_LIST0 + l] >= 0 && (size_t)head[XK_TSR_LIST0 + l] <= entries;
+    n_entries += (size_t)std::max(head[XK_TSR_LIST0 + l], 0);
+  }
+  if (!ok || n_entries > entries) return fail_at(h, XK_EDEVICE, who, "counts out of range");
+  s->n_slam = head[XK_TSR_N_SLAM]; s->n_new = head[XK_TSR_N_NEW]; s->n_opp = head[XK_TSR_N_OPP];
+  for (int l = 0; l < 5; ++l) out->n_list[l] = head[XK_TSR_LIST0 + l];
+  memcpy(out->lost_slam_idxs, r + L.o_lost, sizeof(int) * (size_t)out->n_lost);
+  const int *claimed = (const int *)(r + L.o_claimed);
+  for (int i = 0; i < n; ++i) out->claimed[i] = claimed[i] ? 1 : 0;
+  // the lists behind one another as one CSR: a list's coordinates are gathered in its order (a candidate's lie where the batch put them)
+  const int *e_start = (const int *)(r + L.o_start), *e_len = (const int *)(r + L.o_len);
+  const double *xy = (const double *)(r + L.o_xy);
+  memcpy(out->ids, r + L.o_id, sizeof(long long) * n_entries);
+  out->off[0] = 0;
+  for (size_t e = 0; e < n_entries; ++e) {
+    if (e_len[e] < 0 || e_start[e] < 0 || (size_t)e_start[e] + (size_t)e_len[e] > obs || (size_t)out->off[e] + (size_t)e_len[e] > obs)
+      return fail_at(h, XK_EDEVICE, who, "counts out of range");
+    memcpy(out->xy + 2 * (size_t)out->off[e], xy + 2 * (size_t)e_start[e], sizeof(double) * 2 * (size_t)e_len[e]);
+    out->off[e + 1] = out->off[e] + e_len[e];
+  }
+  if (n_opp_ids) *n_opp_ids = 0;                                    // the caller's list is consumed (track_manager.cpp:355)
+  return XK_OK;
+}
+
+/* manageTracks of a match list from the host */
+extern "C" int xk_trk_tracks_manage(xk_trk *t, const double *prev_xy, const double *cur_xy, const double *prev_dist_xy, const double *cur_dist_xy,
+                                    const int *score, int n, const double *C_q_G, int n_quats, int n_poses_max, int n_slam_features_max,
+                                    int min_track_length, long long *opp_ids, int *n_opp_ids, xk_trk_tracks_out *out) {
+  if (!t) return XK_EINVAL;
+  xk_ts *s = ts_of(t, "xk_trk_tracks_manage");
+  if (!s) return XK_EINVAL;
+  const ts_matches m{prev_xy, cur_xy, prev_dist_xy, cur_dist_xy, score};
+  return ts_manage(t, s, "xk_trk_tracks_manage", &m, nullptr, n, C_q_G, n_quats, n_poses_max, n_slam_features_max, min_track_length, opp_ids,
+                   n_opp_ids, out);
+}
+
+/* manageTracks of the matches the last frame left on the device */
+extern "C" int xk_trk_tracks_manage_frame(xk_trk *t, const double *C_q_G, int n_quats, int n_poses_max, int n_slam_features_max,
+                                          int min_track_length, long long *opp_ids, int *n_opp_ids, xk_trk_tracks_out *out) {
+  if (!t) return XK_EINVAL;
+  const char *who = "xk_trk_tracks_manage_frame";
+  xk_ts *s = ts_of(t, who);
+  if (!s) return XK_EINVAL;
+  xk_frm *f = sub_of(t, &xk_klt::frm, who, "xk_trk_frame_setup");
+  if (!f) return XK_EINVAL;
+  if (f->last_m < 0) return fail_at(t->h, XK_EINVAL, who, "no frame result on the device (before a frame, after xk_trk_frame_reset or a frame's error)");
+  const size_t B = (size_t)f->last_B;
+  const unsigned char *o = f->last_out;
+  ts_matches m{};
+  if (f->last_m > 0) {
+    m.prev_xy = (const double *)(o + xk_frame_out_xy(B, 0)); m.cur_xy = (const double *)(o + xk_frame_out_xy(B, 1));
+    m.prev_dist_xy = (const double *)(o + xk_frame_out_xy(B, 2)); m.cur_dist_xy = (const double *)(o + xk_frame_out_xy(B, 3));
+    m.score = (const int *)(o + xk_frame_out_score(B));
+  }
+  return ts_manage(t, s, who, nullptr, &m, f->last_m, C_q_G, n_quats, n_poses_max, n_slam_features_max, min_track_length, opp_ids, n_opp_ids, out);
+}
+
+/* One of the store's own lists */
+extern "C" int xk_trk_tracks_lists(xk_trk *t, int which, long long *ids, int *lengths, double *obs, int *score, int *tiles, int *n) {
+  if (!t) return XK_EINVAL;
+  xk_handle *h = t->h;
+  const char *who = "xk_trk_tracks_lists";
+  xk_ts *s = ts_of(t, who);
+  if (!s) return XK_EINVAL;
+  if (which < 0 || which > 2) return fail_at(h, XK_EINVAL, who, "which is 0, 1 or 2");
+  if (!n) return fail_at(h, XK_EINVAL, who, "null count");
+  const size_t N = (size_t)(which == 0 ? s->n_slam : which == 1 ? s->n_new : s->n_opp), T = (size_t)s->max_tracks, R = XK_TS_RING;
+  *n = (int)N;
+  if (N == 0 || (!ids && !lengths && !obs && !score && !tiles)) return XK_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  XkTsListOut o{};
+  size_t off = 0;
+  o.which = which; o.n = (int)N;
+  o.ids = carve<long long>(s->d_gather, off, 8 * T); o.lengths = carve<int>(s->d_gather, off, 4 * T); o.obs = carve<double>(s->d_gather, off, 32 * R * T);
+  o.score = carve<int>(s->d_gather, off, 4 * R * T); o.tiles = carve<int>(s->d_gather, off, 8 * R * T);
+  hipLaunchKernelGGL(xk_ts_gather, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, h->stream, s->a, o);
+  XKCHK(launched(h, "track list launch"));
+  if (ids) HIPCHK(h, hipMemcpyAsync(ids, o.ids, 8 * N, hipMemcpyDeviceToHost, h->stream));
+  if (lengths) HIPCHK(h, hipMemcpyAsync(lengths, o.lengths, 4 * N, hipMemcpyDeviceToHost, h->stream));
+  if (obs) HIPCHK(h, hipMemcpyAsync(obs, o.obs, 32 * R * N, hipMemcpyDeviceToHost, h->stream));
+  if (score) HIPCHK(h, hipMemcpyAsync(score, o.score, 4 * R * N, hipMemcpyDeviceToHost, h->stream));
+  if (tiles) HIPCHK(h, hipMemcpyAsync(tiles, o.tiles, 8 * R * N, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return XK_OK;
+}
+
+// erase of ascending list positions, the highest XK_TS_REMOVE_MAX first: a launch does not move what lies below its positions
+static int ts_remove(xk_trk *t, xk_ts *s, int which, const unsigned int *idxs, int n) {
+  HIPCHK(t->h, hipSetDevice(t->h->device));
+  for (int end = n; end > 0; end -= XK_TS_REMOVE_MAX) {
+    XkTsRemove r{};
+    const int first = std::max(end - XK_TS_REMOVE_MAX, 0);
+    r.which = which; r.n = end - first;
+    for (int j = 0; j < r.n; ++j) r.idx[j] = (int)idxs[first + j];
+    hipLaunchKernelGGL(xk_ts_remove, dim3(1), dim3(64), 0, t->h->stream, s->a, r);
+  }
+  XKCHK(launched(t->h, "track removal launch"));
+  (which == 0 ? s->n_slam : s->n_new) -= n;
+  return XK_OK;
+}
+
+/* removePersistentTracksAtIndex */
+extern "C" int xk_trk_tracks_remove_persistent(xk_trk *t, unsigned int idx) {
+  if (!t) return XK_EINVAL;
+  xk_ts *s = ts_of(t, "xk_trk_tracks_remove_persistent");
+  if (!s) return XK_EINVAL;
+  if (idx >= (unsigned int)s->n_slam) return fail_at(t->h, XK_EINVAL, "xk_trk_tracks_remove_persistent", "no such track");
+  return ts_remove(t, s, 0, &idx, 1);
+}
+
+/* removeNewPersistentTracksAtIndexes */
+extern "C" int xk_trk_tracks_remove_new_persistent(xk_trk *t, const unsigned int *idxs, int n) {
+  if (!t) return XK_EINVAL;
+  const char *who = "xk_trk_tracks_remove_new_persistent";
+  xk_ts *s = ts_of(t, who);
+  if (!s) return XK_EINVAL;
+  if (n < 0 || (n > 0 && !idxs)) return fail_at(t->h, XK_EINVAL, who, "null indices or negative n");
+  for (int i = 0; i < n; ++i) {
+    if (idxs[i] >= (unsigned int)s->n_new) return fail_at(t->h, XK_EINVAL, who, "no such track");
+    if (i > 0 && idxs[i] <= idxs[i - 1]) return fail_at(t->h, XK_EINVAL, who, "indices not in increasing order");
+  }
+  return n == 0 ? XK_OK : ts_remove(t, s, 1, idxs, n);
+}
+
+/* TrackManager::clear: the lists empty, the id counter as it was */
+extern "C" int xk_trk_tracks_clear(xk_trk *t) {
+  if (!t) return XK_EINVAL;
+  xk_ts *s = ts_of(t, "xk_trk_tracks_clear");
+  if (!s) return XK_EINVAL;
+  HIPCHK(t->h, hipSetDevice(t->h->device));
+  hipLaunchKernelGGL(xk_ts_clear, dim3((s->max_tracks + 255) / 256), dim3(256), 0, t->h->stream, s->a, 0);
+  XKCHK(launched(t->h, "track store clear launch"));
+  s->n_slam = s->n_new = s->n_opp = 0;
+  return XK_OK;
 }

@@ -48,7 +48,9 @@ __device__ __forceinline__ void xk_tracks_qmul(const double *a, const double *b,
   r[3] = a[0] * b[3] + a[3] * b[0] + a[1] * b[2] - a[2] * b[1];
 }
 
-__global__ __launch_bounds__(64 * XK_TRACKS_WAVES) void xk_tracks_baseline(XkTracksArgs a) {
+// The body of the launch for the first K tracks of a batch: xk_tracks_baseline takes K from its arguments, the track store's kernel
+// (xk_track_store.hip.h) from the count an earlier launch left on the device.  Every thread of the workgroup calls it (one barrier).
+__device__ __forceinline__ void xk_tracks_baseline_body(const XkTracksArgs &a, int K) {
 #pragma clang fp contract(off)
   __shared__ double q_n[XK_TRACKS_MAX_QUATS][4];                 // the normalised attitudes as (w, x, y, z)
   const int lane = threadIdx.x & 63;
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(64 * XK_TRACKS_WAVES) void xk_tracks_baseline(XkTra
   }
   __syncthreads();
   const int k = blockIdx.x * XK_TRACKS_WAVES + (threadIdx.x >> 6);
-  if (k >= a.K) return;                                          // (a whole wavefront, after the only barrier)
+  if (k >= K) return;                                             // (a whole wavefront, after the only barrier)
   const int o0 = a.trk_off[k], len_all = a.trk_off[k + 1] - o0;
   const int nq = a.n_quats - (int)a.drop_last[k];
   const int len = len_all < nq ? len_all : nq;                   // Camera::normalize(track, nq): the newest len observations
@@ -99,3 +101,5 @@ __global__ __launch_bounds__(64 * XK_TRACKS_WAVES) void xk_tracks_baseline(XkTra
     a.flag[k] = (dx > a.min_x || dy > a.min_y) ? 1 : 0;          // :632
   }
 }
+
+__global__ __launch_bounds__(64 * XK_TRACKS_WAVES) void xk_tracks_baseline(XkTracksArgs a) { xk_tracks_baseline_body(a, a.K); }

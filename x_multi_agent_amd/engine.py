@@ -51,6 +51,8 @@ SYMBOLS = [
     "xk_trk_photo_spatial_setup", "xk_trk_photo_spatial_add", "xk_trk_photo_spatial_status", "xk_trk_photo_spatial_rows",
     "xk_trk_photo_spatial_estimate", "xk_trk_photo_spatial_stage", "xk_trk_photo_spatial_reset",
     "xk_trk_baseline_setup", "xk_trk_baseline",
+    "xk_trk_tracks_setup", "xk_trk_tracks_manage", "xk_trk_tracks_manage_frame", "xk_trk_tracks_lists", "xk_trk_tracks_remove_persistent",
+    "xk_trk_tracks_remove_new_persistent", "xk_trk_tracks_clear",
 ]
 
 

@@ -16,8 +16,11 @@ calibration between the push and the tracking and the features' intensities resi
 `MatchFilter.baseline` is what the track manager behind them asks every frame (`TrackManager::checkBaseline`,
 track_manager.cpp:576-636, and `Camera::normalize`): the normalisation, crop and baseline check of all candidate tracks at once.
 
+`Klt.tracks_*` is `TrackManager::manageTracks` itself (track_manager.cpp:115-436) on tracks that stay on the device: `tracks_manage` takes
+a match list from the host, `tracks_manage_frame` the block the last `frame` / `photo_frame` left there (csrc/xk_track_store.hip.h).
+
 No fallback: everything numeric runs in libxk.so's HIP kernels (csrc/xk_fundamental.hip.h, csrc/xk_klt.hip.h, csrc/xk_fast.hip.h,
-csrc/xk_orb.hip.h, csrc/xk_photo.hip.h, csrc/xk_tracks.hip.h)."""
+csrc/xk_orb.hip.h, csrc/xk_photo.hip.h, csrc/xk_tracks.hip.h, csrc/xk_track_store.hip.h)."""
 import ctypes as C
 
 import numpy as np
@@ -28,6 +31,7 @@ c_ub = C.POINTER(C.c_ubyte)
 c_fp = C.POINTER(C.c_float)
 c_sp = C.POINTER(C.c_short)
 c_sb = C.POINTER(C.c_byte)
+c_lp = C.POINTER(C.c_longlong)
 CAM_FOV, CAM_RADTAN, CAM_EQUIDISTANT = 0, 1, 2      # XK_CAM_*: MatchFilter(model=...), MatchFilter.camera_model
 
 
@@ -642,6 +646,101 @@ class Klt(_Trk):
         self._chk(self.L.xk_trk_photo_spatial_reset(self.p), "xk_trk_photo_spatial_reset")
 
 
+    # ---- TrackManager::manageTracks on tracks that stay on the device (track_manager.cpp:115-436), csrc/xk_track_store.hip.h ----
+    _tracks = None
+
+    def tracks_setup(self, max_tracks, n_tiles_h=1, n_tiles_w=1, width=None, height=None, min_baseline_x_n=0.0, min_baseline_y_n=0.0,
+                     multi_uav=False):
+        """xk_trk_tracks_setup: the store of max_tracks tracks, empty, ids from 1.  The tile grid is TiledImage's of a width x height
+        image (default: the set-up size); the intrinsics are the xk_trk's (match_filter=...)."""
+        width, height = self.width if width is None else width, self.height if height is None else height
+        self._chk(self.L.xk_trk_tracks_setup(self.p, C.c_int(max_tracks), C.c_int(n_tiles_h), C.c_int(n_tiles_w), C.c_int(width), C.c_int(height),
+                                             C.c_double(min_baseline_x_n), C.c_double(min_baseline_y_n), C.c_int(1 if multi_uav else 0)),
+                  "xk_trk_tracks_setup")
+        self._tracks = dict(max_tracks=int(max_tracks), n=[0, 0, 0])
+
+    def _tracks_call(self, entry, head, n, C_q_G, n_poses_max, n_slam_features_max, min_track_length, opp_ids):
+        if self._tracks is None:
+            raise self._error(1, entry + ": before tracks_setup")
+        q = np.ascontiguousarray(C_q_G, np.float64).reshape(-1, 4)
+        slam, new, opp = self._tracks["n"]
+        per = slam + new
+        cap_lost, cap_entries = max(per, 1), max(opp + n + per, 1)
+        cap_obs = max((opp + n) * max(len(q), 1) + per * min(max(int(n_poses_max), 1), 64), 1)
+        o = TracksOut()
+        lost, claimed = np.zeros(cap_lost, np.int32), np.zeros(max(n, 1), np.uint8)
+        ids, off, xy = np.zeros(cap_entries, np.int64), np.zeros(cap_entries + 1, np.int32), np.zeros((cap_obs, 2))
+        o.cap_lost, o.cap_entries, o.cap_obs = cap_lost, cap_entries, cap_obs
+        o.lost_slam_idxs, o.claimed = lost.ctypes.data_as(c_ip), claimed.ctypes.data_as(c_ub)
+        o.ids, o.off, o.xy = ids.ctypes.data_as(c_lp), off.ctypes.data_as(c_ip), xy.ctypes.data_as(c_dp)
+        id_list = None if opp_ids is None else np.ascontiguousarray(list(opp_ids) + [0], np.int64)
+        n_ids = C.c_int(0 if opp_ids is None else len(opp_ids))
+        rc = getattr(self.L, entry)(self.p, *head, q.ctypes.data_as(c_dp), C.c_int(len(q)), C.c_int(n_poses_max), C.c_int(n_slam_features_max),
+                                    C.c_int(min_track_length), None if id_list is None else id_list.ctypes.data_as(c_lp),
+                                    None if opp_ids is None else C.byref(n_ids), C.byref(o))
+        if rc != 0:
+            err = self._error(rc, entry)
+            err.tracks_status = int(o.status)
+            raise err
+        if opp_ids is not None:
+            del opp_ids[:]                                        # the caller's list is consumed (track_manager.cpp:355)
+        self._tracks["n"] = [int(o.n_persistent), int(o.n_new_persistent), int(o.n_opportunistic)]
+        return TracksResult(o, lost, claimed[:n], ids, off, xy)
+
+    def tracks_manage(self, prev_xy, cur_xy, prev_dist_xy, cur_dist_xy, score, C_q_G, n_poses_max, n_slam_features_max, min_track_length,
+                      opp_ids=None):
+        """xk_trk_tracks_manage: manageTracks of a match list in the columns Klt.frame returns -> TracksResult.  opp_ids: a Python list
+        (setOppUpgradesMSCKF), required with multi_uav; it is emptied on success.  On a refusal the XkError carries the device's `tracks_status` (XK_TRACKS_OUTSIDE_GRID, XK_TRACKS_CAPACITY; 0 otherwise)."""
+        cols = [np.ascontiguousarray(v, np.float64).reshape(-1, 2) for v in (prev_xy, cur_xy, prev_dist_xy, cur_dist_xy)]
+        sc = np.ascontiguousarray(score, np.int32).ravel()
+        n = len(sc)
+        if any(len(c) != n for c in cols):
+            raise ValueError("tracks_manage: columns of one length")
+        head = [c.ctypes.data_as(c_dp) for c in cols] + [sc.ctypes.data_as(c_ip), C.c_int(n)]
+        return self._tracks_call("xk_trk_tracks_manage", head, n, C_q_G, n_poses_max, n_slam_features_max, min_track_length, opp_ids)
+
+    def tracks_manage_frame(self, C_q_G, n_poses_max, n_slam_features_max, min_track_length, opp_ids=None, n_matches=None):
+        """xk_trk_tracks_manage_frame: the same on the matches the last frame() / photo_frame() left on the device; only the attitudes
+        and the ids go up.  n_matches: that frame's count, for the output capacities (default: max_features)."""
+        n = self.max_features if n_matches is None else int(n_matches)
+        return self._tracks_call("xk_trk_tracks_manage_frame", [], n, C_q_G, n_poses_max, n_slam_features_max, min_track_length, opp_ids)
+
+    def tracks_lists(self, which):
+        """xk_trk_tracks_lists: which = 0 persistent, 1 new persistent, 2 opportunistic -> dict of ids int64 [n], lengths int32 [n] (true
+        lengths), obs fp64 [n, 64, 4] (undistorted x, y, distorted x, y; the newest min(length, 64) oldest first), score int32 [n, 64],
+        tiles int32 [n, 64, 2]."""
+        n = C.c_int(0)
+        self._chk(self.L.xk_trk_tracks_lists(self.p, C.c_int(which), None, None, None, None, None, C.byref(n)), "xk_trk_tracks_lists")
+        m = max(n.value, 1)
+        ids, lengths, obs = np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros((m, 64, 4))
+        score, tiles = np.zeros((m, 64), np.int32), np.zeros((m, 64, 2), np.int32)
+        self._chk(self.L.xk_trk_tracks_lists(self.p, C.c_int(which), ids.ctypes.data_as(c_lp), lengths.ctypes.data_as(c_ip), obs.ctypes.data_as(c_dp),
+                                             score.ctypes.data_as(c_ip), tiles.ctypes.data_as(c_ip), C.byref(n)), "xk_trk_tracks_lists")
+        k = n.value
+        return dict(ids=ids[:k], lengths=lengths[:k], obs=obs[:k], score=score[:k], tiles=tiles[:k])
+
+    def tracks_remove_persistent(self, idx):
+        """TrackManager::removePersistentTracksAtIndex."""
+        if idx < 0:
+            raise self._error(1, "xk_trk_tracks_remove_persistent: a negative index")
+        self._chk(self.L.xk_trk_tracks_remove_persistent(self.p, C.c_uint(idx)), "xk_trk_tracks_remove_persistent")
+        self._tracks["n"][0] -= 1
+
+    def tracks_remove_new_persistent(self, idxs):
+        """TrackManager::removeNewPersistentTracksAtIndexes: indices in increasing order."""
+        if any(i < 0 for i in idxs):
+            raise self._error(1, "xk_trk_tracks_remove_new_persistent: a negative index")
+        v = np.ascontiguousarray(list(idxs) + [0], np.uint32)
+        self._chk(self.L.xk_trk_tracks_remove_new_persistent(self.p, v.ctypes.data_as(C.POINTER(C.c_uint)), C.c_int(len(idxs))),
+                  "xk_trk_tracks_remove_new_persistent")
+        self._tracks["n"][1] -= len(idxs)
+
+    def tracks_clear(self):
+        """TrackManager::clear: the lists empty, the id counter as it was."""
+        self._chk(self.L.xk_trk_tracks_clear(self.p), "xk_trk_tracks_clear")
+        self._tracks["n"] = [0, 0, 0]
+
+
 class FrameOut(C.Structure):
     """xk_trk_frame_out (include/xk.h)"""
     COUNTS = ("n_tracked", "n_left", "redetected", "n_candidates", "n_accepted", "n_new_tracked", "n_matches", "winner")
@@ -660,3 +759,33 @@ class SpatialOutcome(C.Structure):
     """xk_photo_spatial_outcome (include/xk.h)"""
     _fields_ = [("n", C.c_int), ("converged", C.c_int), ("ls_iterations", C.c_int), ("gp_iterations", C.c_int),
                 ("ls_residual", C.c_double), ("gp_residual", C.c_double)]
+
+
+class TracksOut(C.Structure):
+    """xk_trk_tracks_out (include/xk.h)"""
+    COUNTS = ("status", "n_persistent", "n_new_persistent", "n_opportunistic", "n_lost", "n_claimed", "n_candidates", "n_candidate_obs")
+    _fields_ = [(k, C.c_int) for k in COUNTS] + [("next_id", C.c_longlong), ("n_list", C.c_int * 5)] + \
+               [(k, C.c_int) for k in ("cap_lost", "cap_entries", "cap_obs")] + \
+               [("lost_slam_idxs", c_ip), ("claimed", c_ub), ("ids", c_lp), ("off", c_ip), ("xy", c_dp)]
+
+
+class TracksResult:
+    """What Klt.tracks_manage and tracks_manage_frame return, as NumPy arrays: the counts of xk_trk_tracks_out as attributes, next_id,
+    lost_slam_idxs int32 [n_lost], claimed uint8 [n], and `lists`: per measurement list (XK_TRACKS_MSCKF, _MSCKF_SHORT, _NEW_SLAM_STD,
+    _NEW_MSCKF_SLAM, _PERSISTENT) a dict of ids int64 [k], off int32 [k + 1] and xy fp64 [off[k], 2], the normalised coordinates."""
+    NAMES = ("msckf", "msckf_short", "new_slam_std", "new_msckf_slam", "persistent")
+
+    def __init__(self, o, lost, claimed, ids, off, xy):
+        for k in TracksOut.COUNTS:
+            setattr(self, k, int(getattr(o, k)))
+        self.next_id = int(o.next_id)
+        self.lost_slam_idxs = lost[:self.n_lost].copy()
+        self.claimed = claimed.copy()
+        self.lists, e = [], 0
+        for l in range(5):
+            k = int(o.n_list[l])
+            first, last = int(off[e]), int(off[e + k])
+            self.lists.append(dict(ids=ids[e:e + k].copy(), off=(off[e:e + k + 1] - first).astype(np.int32), xy=xy[first:last].copy()))
+            e += k
+        for name, lst in zip(self.NAMES, self.lists):
+            setattr(self, name, lst)
